@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- FastDiff vocoder inference on MI355X: real-time factor of the N-step reverse sampler.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs1|config4|config5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs1|config4|config5] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set up, warm up W steps, time K steps, print the line (`value`, `ms_per_step` = the
+milliseconds of one timed step).  `--full` adds the objects listed under "Extra objects" below and the box state (rocm-smi).
+`--dump-outputs DIR` (configs1): after the timed steps, what the last timed step returned is written as DIR/<name>.npy in float32 --
+`pcm` (the host int16 PCM a caller receives) and `waveform` (the sampler's float32 output behind it; only this one with --no-host-io).
+Inputs and seeds depend on the arguments only, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 launches the N ranks itself (one process per GPU under torch.distributed.run, the reference's own
 one-process-per-GPU model: utils/trainer.py:94-107 mp.spawn) unless it already runs under a launcher (WORLD_SIZE set).  It refuses
@@ -22,7 +28,9 @@ Workloads
             300..864) -> the test-time loader and collater (dataset_utils.py:186-204, :100-160) -> one padded batch of 16 through
             fd_sample (N=4) + the int16 epilogue -> PCM on the host.  One step = the whole job from the files to host int16.
 
-Extra objects in the JSON line (rank 0, N=1 only where they need one GPU):
+Extra objects in the JSON line with --full (rank 0, N=1 only where they need one GPU; the --no-* options leave single ones out):
+  value_device_resident -- the same K steps again with the mel resident in HBM and the waveform left there;
+  b1 / stream    -- one utterance per call at the same length, and the short form of --workload stream;
   roofline       -- the dominant kernel of the step, timed live with HIP events on the launch stream (library option "profile"),
                     algorithmic bytes/flops per launch from DESIGN.md section 3;
   host_inclusive -- SURVEY.md 8(d)'s wall clock for the same batch: pinned host mel -> device -> fd_sample -> int16 epilogue ->
@@ -31,7 +39,8 @@ Extra objects in the JSON line (rank 0, N=1 only where they need one GPU):
                     what the default pipe (2-piece fp16 operands, fp32 accumulation) buys;
   parity         -- max |difference| of both pipes to the float64 CPU oracle on one utterance (B=1, T=864, N=4, injected x_T);
   cpu_baseline   -- the CPU restatement of the reference (kind "port": /root/reference does not exist on the GPU box) timed on
-                    this host on a bounded sample: one utterance (B=1, T=864), N=4.
+                    this host on a bounded sample: one utterance (B=1, T=864), N=4;
+  torch_eager_baseline -- the same sampling as plain PyTorch-ROCm eager ops on the same GPU.
 """
 import argparse
 import json
@@ -935,6 +944,23 @@ def project_sharded(args, model, items, t_full, dev):
             "not_included": "RCCL transport of <= 2.2 MB out / 3.5 MB back per peer over xGMI (the broadcast of names / ids / lengths is in, as timed on gloo)"}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6 - 4096      # --dump-outputs: array data of all files together (each .npy header adds ~128 B)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  When together they exceed DUMP_BUDGET_BYTES, each one is cut to a
+    fixed, seeded sample of its flattened elements (sorted indices from numpy default_rng(1234)): the same elements on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = a.size * DUMP_BUDGET_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(1234).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -967,7 +993,16 @@ def main():
                     help="config4: 'src' = the PCM of the whole job on rank 0's host (north_star's scatter / gather); 'none' = every rank keeps / "
                          "writes its own share, as the reference does (FastDiff.py:107-118)")
     ap.add_argument("--balance", default="time", choices=("time", "frames"), help="config4: what the LPT partition weighs (shard.utterance_cost | frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="configs1: also every extra object of the line (value_device_resident, host_inclusive, roofline + kernels, b1, stream, "
+                         "fp32_pipe, torch_eager_baseline, parity, cpu_baseline) and, for every workload, the box state.  Off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="configs1: after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.workload != "configs1":
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the configs1 workload only")
     if args.nsteps is None:
         args.nsteps = 6 if args.workload == "config4" else 4
     if args.batch is None:      # (config4 on one GPU: micro-batches of 16 take 64.0 ms per job, of 8 68.1 ms: profiles/r05/s9_config4_microbatch.txt)
@@ -1106,6 +1141,7 @@ def main():
                 host_settle(prev)
                 prev = cur
             host_settle(prev)
+            return None if prev is None else prev[1]      # the last call's waveform (its PCM is in pcm_h)
 
         def resident_loop(k0, n):
             out = None
@@ -1122,16 +1158,23 @@ def main():
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            timed(100, args.steps)
+            last = timed(100, args.steps)
             torch.cuda.synchronize()
             barrier()
             torch.cuda.synchronize()
             elapsed = time.perf_counter() - t0
             if child:
                 return
+            if args.dump_outputs is not None and rank == 0:
+                wave = last.cpu().numpy()[:, 0]
+                if use_lens is not None:      # behind an utterance's own samples the sampler leaves its row unspecified (FastDiff.sample)
+                    for b, t in enumerate(use_lens):
+                        wave[b, t * HOP:] = 0.0
+                dump_outputs(args.dump_outputs, {"waveform": wave, **({"pcm": pcm_h.numpy()} if host_metric else {})})
             resident = None
             if host_metric:
                 assert int(pcm_h.abs().max()) == 32767
+            if host_metric and args.full:
                 resident_loop(0, args.warmup)
                 torch.cuda.synchronize()
                 t1 = time.perf_counter()
@@ -1163,7 +1206,8 @@ def main():
                    "batch_per_gpu": B, "frames": T, "reverse_steps": N,
                    "sharding": ("utterances/rank, no data-path collective" if args.workload == "configs1" else
                                 "one GPU" if args.workload in ("config5", "stream") else "LPT partition, one packed p2p message per peer each way (RCCL)"),
-                   "value_is": (("host mel -> host int16 PCM (SURVEY 8d's definition); HBM-resident: value_device_resident" if not args.no_host_io
+                   "value_is": (("host mel -> host int16 PCM (SURVEY 8d's definition)" + ("; HBM-resident: value_device_resident" if args.full else "")
+                                 if not args.no_host_io
                                  else "HBM-resident mel -> HBM waveform (--no-host-io)") if args.workload == "configs1"
                                 else "files of a directory -> host int16 PCM" if args.workload == "config5"
                                 else "host mel -> host int16 PCM, last pass of the one-request-per-call leg" if args.workload == "stream" else "host mel -> host int16 PCM (rank 0)"),
@@ -1185,7 +1229,8 @@ def main():
                                  "of": "the last timed sample call (fd_get_counter); 0 / 0 = every piece ran on the default fp16x2 pipe"}
         line["config"]["parity_evidence"] = "all 1000 steps at T=864 vs the reference's float64 run, every 125th state (tests: test_config3_n1000_at_864_frames_against...)"
     if rank == 0:
-        line["box"] = box_state()
+        if args.full:
+            line["box"] = box_state()
         if args.workload == "config4" and projection is not None:
             line["projection" if world == 1 else "sharded_job_check"] = projection
         if args.workload == "config5":
@@ -1204,7 +1249,7 @@ def main():
         line["value_device_resident"] = round(audio_s / (resident / 1e3), 2)      # (world > 1: rank 0's loop standing for every rank)
         line["ms_per_step_device_resident"] = round(resident, 4)
         line["value_host_to_host"], line["ms_per_step_host_to_host"] = line["value"], line["ms_per_step"]
-    if rank == 0 and world == 1 and args.workload == "configs1":
+    if rank == 0 and world == 1 and args.workload == "configs1" and args.full:
         use_lens = None if args.no_lens else lens
         if not args.no_host_io:
             line["host_inclusive"] = host_inclusive(model, mel, rows, use_lens, audio_s, reps=args.steps)      # a second run of the same loop + the PCIe legs on their own

@@ -34,7 +34,7 @@ python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || { tail
 (rocm-smi --showclocks --showpower --showperflevel --showmaxpower 2>&1 | grep -v "^=\|^$" | head -30) > $O/box_state.txt
 echo "== pytest gpu"; timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider -k "not against_the_reference_trajectory" > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -6 $O/pytest_gpu.log
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-echo "== bench"; FD_BENCH_KEEP_STATS=$R/$O/bench_child_kernel_stats.csv timeout 900 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"; grep '^{' $O/bench.log | python -c "
+echo "== bench"; FD_BENCH_KEEP_STATS=$R/$O/bench_child_kernel_stats.csv timeout 900 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"; grep '^{' $O/bench.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps(d['summary'])); print(d['config']['value_is']); print({k:d['roofline'][k] for k in ('kernel','frac','avg_launch_us','traffic') if k in d['roofline']}); print(d.get('cpu_baseline',{}).get('value'), d['b1'].get('host_us_per_call_median'))"
 echo "== stream"; timeout 1500 python bench.py --workload stream --no-cpu-baseline > $O/bench_stream.log 2>&1; echo "stream rc=$?"
 grep '^{' $O/bench_stream.log | python -c "
@@ -113,7 +113,7 @@ s8)
 # round 6, session 8: the default bench line with its short stream object
 O=gpurun_out/r6s8; mkdir -p $O
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
-T0=$(date +%s); python bench.py > $O/bench.log 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); python bench.py --full > $O/bench.log 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"
 grep '^{' $O/bench.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps(d['summary'])); print(d['stream'])"
 ;;
