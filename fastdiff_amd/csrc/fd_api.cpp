@@ -174,7 +174,6 @@ int fd_create(const fd_config *cfg, int device, fd_handle *out)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
     }
-    for (int i = 0; i < ST_COUNT; ++i) c->fast[i] = true;
     // every resource of the handle lives in *c from the moment it exists, so one failure path (fd_destroy's own release code) frees
     // whatever was created before the failing call
     auto fail = [&](hipError_t err) {
@@ -222,12 +221,10 @@ static void reap_retired(fd_context *c, bool wait)
     }
 }
 
-// Drops every captured graph.  synced: the caller has just synchronised the device (workspace growth, fd_commit_weights, fd_destroy);
-// otherwise (an option that changes what a step launches) the device is synchronised here -- a replay may still be queued, and the
-// stream it is queued on may be gone by now, so there is nothing to record an event on.
-static void drop_graph(fd_context *c, bool synced = false)
+// Drops every captured graph.  The caller has just synchronised the device (workspace growth, fd_commit_weights, fd_destroy): no
+// replay is queued any more.  (An option does not drop graphs: the mode it changes is part of every graph's key.)
+static void drop_graph(fd_context *c)
 {
-    if (!synced && !(c->graphs.empty() && c->retired.empty())) hipDeviceSynchronize();
     for (auto &g : c->graphs) {
         if (g.exec) hipGraphExecDestroy(g.exec);
         if (g.graph) hipGraphDestroy(g.graph);
@@ -244,7 +241,7 @@ static void release_handle(fd_context *h)
     if (h->flags_done) hipEventDestroy(h->flags_done);
     if (h->flags_done2) hipEventDestroy(h->flags_done2);
     for (auto ev : h->event_pool) hipEventDestroy(ev);
-    drop_graph(h, true);
+    drop_graph(h);
     free_workspace(h);
     for (void *p : h->dev_allocs) hipFree(p);
     if (h->scratch) hipFree(h->scratch);
@@ -447,7 +444,7 @@ int fd_commit_weights(fd_handle h)
     for (void *p : h->dev_allocs) hipFree(p);
     h->dev_allocs.clear();
     h->w = DevWeights();
-    drop_graph(h, true);
+    drop_graph(h);
 
     std::map<std::string, Folded> f;
     for (const auto &s : param_specs(h->cfg)) {
@@ -759,7 +756,7 @@ static int ensure_workspace(fd_context *h, int B, int T, int pmult = 1)
     const int64_t frames = (int64_t)B * T, rows = (int64_t)B * gx_rows_host(T);
     if (workspace_fits(h, B, T, pmult)) return FD_OK;
     FD_HIP(h, hipDeviceSynchronize());
-    drop_graph(h, true);
+    drop_graph(h);
     // grow to the largest of each quantity seen so far, so that alternating shapes settle; if that does not fit, this call's own
     // needs alone are tried before giving up
     const int64_t own[6] = {B, frames, rows, frames * pmult, rows * pmult, (int64_t)B * pmult};
@@ -800,23 +797,23 @@ namespace fdk {
 
 hipError_t first_conv(const Launch &L, const StepIO &io, int B, int T)
 {
-    return L.ctx->fast[ST_FIRST] ? fast_first_conv(L, io, B, T) : naive_first_conv(L, io, B, T);
+    return L.mode->fast[ST_FIRST] ? fast_first_conv(L, io, B, T) : naive_first_conv(L, io, B, T);
 }
 hipError_t dblock(const Launch &L, const StepIO &io, int d, int B, int T)
 {
-    return L.ctx->fast[ST_DBLOCK] ? fast_dblock(L, d, B, T, io.x_in) : naive_dblock(L, d, B, T);
+    return L.mode->fast[ST_DBLOCK] ? fast_dblock(L, d, B, T, io.x_in) : naive_dblock(L, d, B, T);
 }
 hipError_t kp_front(const Launch &L, const StepIO &io, int B, int T)
 {
-    L.ctx->h_image_ready = false;      // only the fp16-pipe front writes the GEMM's h image itself
-    return L.ctx->fast[ST_KP_FRONT] ? fast_kp_front(L, io, B, T) : naive_kp_front(L, io, B, T);
+    return L.mode->fast[ST_KP_FRONT] ? fast_kp_front(L, io, B, T) : naive_kp_front(L, io, B, T);
 }
-hipError_t kp_gemm(const Launch &L, int B, int T) { return L.ctx->fast[ST_KP_GEMM] ? fast_kp_gemm(L, B, T) : naive_kp_gemm(L, B, T); }
+hipError_t kp_gemm(const Launch &L, int B, int T) { return L.mode->fast[ST_KP_GEMM] ? fast_kp_gemm(L, B, T) : naive_kp_gemm(L, B, T); }
 
 // One TimeAware_LVCBlock (modules.py:190-218) given the packed kernels of kp_gemm.  x_in: [B,32,Lin].
-static hipError_t lvc_block_run(const Launch &L, int n, const float *x_in, int B, int T, float **x_out)
+static hipError_t lvc_block_run(const Launch &L, const StepIO &io, int n, const float *x_in, int B, int T, float **x_out)
 {
     fd_context *c = L.ctx;
+    const StepMode &m = *L.mode;
     Workspace &ws = c->ws;
     const int Lin = T * (fd::hop(n) / fd::ratio(n));
     float *cur = (x_in == ws.xA) ? ws.xB : ws.xA;
@@ -824,26 +821,26 @@ static hipError_t lvc_block_run(const Launch &L, int n, const float *x_in, int B
     const float *skip = ws.a[2 - n];
     // blocks 1 and 2 (hop 64, 256) on the fp16x2 pipe with the range check on the host: the up-sampler runs inside the first layer
     // (k_lvc_h2<.., UP>), its output never goes to HBM and back; x_in is read by that layer, which writes the other buffer
-    const bool fuse_up = c->fuse_up && n >= 1 && c->fast[ST_CONVT] && c->fast[ST_LVC] &&
-                         fd_pipe(c, c->conv_f16 && c->w.convt_f16_ok, 16 + n) == PIPE_F16_ONLY &&
-                         fd_pipe(c, c->lvc_f16 && c->w.lvc_f16_ok, 1 + n * fd::LAYERS) == PIPE_F16_ONLY;
+    const bool fuse_up = m.fuse_up && n >= 1 && m.fast[ST_CONVT] && m.fast[ST_LVC] &&
+                         fd_pipe(m, m.conv_f16 && c->w.convt_f16_ok, 16 + n) == PIPE_F16_ONLY &&
+                         fd_pipe(m, m.lvc_f16 && c->w.lvc_f16_ok, 1 + n * fd::LAYERS) == PIPE_F16_ONLY;
     hipError_t e = hipSuccess;
     if (fuse_up) {
-        if ((e = fast_lvc_layer(L, n, 0, x_in, skip, cur, B, T, true)) != hipSuccess) return e;
+        if ((e = fast_lvc_layer(L, io, n, 0, x_in, skip, cur, B, T, true)) != hipSuccess) return e;
     } else {
-        e = c->fast[ST_CONVT] ? fast_convt(L, n, x_in, cur, B, Lin) : naive_convt(L, n, x_in, cur, B, Lin);
+        e = m.fast[ST_CONVT] ? fast_convt(L, n, x_in, cur, B, Lin) : naive_convt(L, n, x_in, cur, B, Lin);
         if (e != hipSuccess) return e;
     }
     for (int i = fuse_up ? 1 : 0; i < fd::LAYERS; ++i) {
-        if (c->fast[ST_LVC]) {
-            e = fast_lvc_layer(L, n, i, cur, skip, other, B, T);
+        if (m.fast[ST_LVC]) {
+            e = fast_lvc_layer(L, io, n, i, cur, skip, other, B, T);
             std::swap(cur, other);
         } else {
             e = naive_lvc_layer(L, n, i, cur, skip, other, B, T);
         }
         if (e != hipSuccess) return e;
     }
-    if (c->keep_taps) {
+    if (m.keep_taps) {
         e = hipMemcpyAsync(ws.xtap[n], cur, sizeof(float) * (size_t)B * fd::C * T * fd::hop(n), hipMemcpyDeviceToDevice, L.stream);
         if (e != hipSuccess) return e;
     }
@@ -853,13 +850,12 @@ static hipError_t lvc_block_run(const Launch &L, int n, const float *x_in, int B
 
 static hipError_t run_step(const Launch &L, const StepIO &io, int B, int T)
 {
-    fd_context *c = L.ctx;
-    Workspace &ws = c->ws;
+    Workspace &ws = L.ctx->ws;
     hipError_t e;
     // the reference's order of statements: down path (first conv, DBlocks), predictor (front + GEMM), the three LVC blocks.  With a
     // hoisted predictor (hoist_np > 1) front + GEMM of all N steps ran in front of the loop (sample_core).  Other orders and a second
     // stream were measured and did not pay (LABBOOK.md: overlap = gemm | paths, order = split | predictor).
-    const bool hoisted = c->hoist_np > 1;
+    const bool hoisted = L.mode->hoist_np > 1;
     // (round 6, measured and not kept: first_conv -- whose output a0 has no reader before the last block -- on a side branch of the
     // graph next to the DBlocks, joined in front of block 2, bit-identical: B=8 +0.5 %, B=1 +6 %; LABBOOK R6.7)
     if ((e = first_conv(L, io, B, T)) != hipSuccess) return e;
@@ -872,10 +868,10 @@ static hipError_t run_step(const Launch &L, const StepIO &io, int B, int T)
     float *x = ws.a[3];
     for (int n = 0; n < fd::NBLK; ++n) {
         float *xo = nullptr;
-        if ((e = lvc_block_run(L, n, x, B, T, &xo)) != hipSuccess) return e;
+        if ((e = lvc_block_run(L, io, n, x, B, T, &xo)) != hipSuccess) return e;
         x = xo;
     }
-    if (c->fast[ST_FINAL]) return fast_final(L, io, x, B, T);
+    if (L.mode->fast[ST_FINAL]) return fast_final(L, io, x, B, T);
     // naive tail: eps into the free ping-pong buffer (or the caller's), then the separate update kernel
     float *eps = io.sampler ? ((x == ws.xA) ? ws.xB : ws.xA) : io.eps_out;
     if ((e = naive_final_eps(L, x, eps, B, T)) != hipSuccess) return e;
@@ -950,11 +946,12 @@ static int follow_stream(fd_handle h, hipStream_t s)
     return FD_OK;
 }
 
-// `lens` (host, nullable): valid frames per utterance of a zero-padded batch, uploaded for the kernels from the pinned area `staged`.
+// `lens` (host, nullable): valid frames per utterance of a zero-padded batch, uploaded for the kernels from the pinned area `staged`;
+// *ragged: they were (some utterance is shorter than T).
 // reps: the hoisted predictor's batch holds every utterance once per reverse step (entry n * B + b): its lengths are staged that often
-static int set_lens(fd_handle h, const int *lens, int B, int T, hipStream_t stream, const char *who, int *staged, int reps = 1)
+static int set_lens(fd_handle h, const int *lens, int B, int T, hipStream_t stream, const char *who, int *staged, bool *ragged_out, int reps = 1)
 {
-    h->step_lens = nullptr;
+    *ragged_out = false;
     if (!lens) return FD_OK;
     bool ragged = false;
     for (int b = 0; b < B; ++b) {
@@ -963,12 +960,12 @@ static int set_lens(fd_handle h, const int *lens, int B, int T, hipStream_t stre
     }
     if (!ragged) return FD_OK;                       // every utterance fills the batch: same launches as without lens
     for (int i = ST_FIRST; i < ST_COUNT; ++i)      // (the step embedding has no time axis)
-        if (!h->fast[i])
+        if (!h->mode.fast[i])
             FD_FAIL(h, FD_ERR_UNSUPPORTED, "%s: a ragged batch (lens) needs the fast kernel set; the naive kernels (option kernels.<stage> = naive) "
                                            "compute the padded tensor and would silently ignore the lengths", who);
     for (int n = 0; n < reps; ++n) memcpy(staged + (size_t)n * B, lens, sizeof(int) * B);
     FD_HIP(h, hipMemcpyAsync(h->ws.lens_dev, staged, sizeof(int) * B * reps, hipMemcpyHostToDevice, stream));
-    h->step_lens = h->ws.lens_dev;
+    *ragged_out = true;
     return FD_OK;
 }
 
@@ -980,8 +977,6 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
     if (rc != FD_OK) return rc;
     if ((rc = fd_settle(h)) != FD_OK) return rc;
     if ((rc = follow_stream(h, (hipStream_t)stream)) != FD_OK) return rc;
-    h->inline_fallback = true; h->fp32_mask = 0;      // a single forward always carries its fallbacks inline
-    h->hoist_np = 1; h->hoist_step = 0; h->hoist_chunk = false;
     h->embed_valid = false;                      // fd_forward writes its own rows into the same table
     if (!x || !mel || !steps || !eps_out) FD_FAIL(h, FD_ERR_INVALID, "fd_forward: null pointer");
     if (x == eps_out) FD_FAIL(h, FD_ERR_INVALID, "fd_forward: eps_out must not alias x");
@@ -993,15 +988,14 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
         return mark_tail(h, (hipStream_t)stream);
     }
     if ((rc = ensure_workspace(h, B, T)) != FD_OK) return rc;
+    StepMode mode = h->mode;      // a single forward: its fallbacks inline, its own predictor (the per-call fields' defaults)
     if (lens) {
         fd_context::StageSlot *sl = nullptr;
         if ((rc = fd_stage_acquire(h, sizeof(int) * B, &sl)) != FD_OK) return rc;
-        if ((rc = set_lens(h, lens, B, T, (hipStream_t)stream, "fd_forward", reinterpret_cast<int *>(sl->host))) != FD_OK) return rc;
+        if ((rc = set_lens(h, lens, B, T, (hipStream_t)stream, "fd_forward", reinterpret_cast<int *>(sl->host), &mode.ragged)) != FD_OK) return rc;
         if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
-    } else {
-        h->step_lens = nullptr;
     }
-    fdk::Launch L = {h, (hipStream_t)stream, false};
+    fdk::Launch L = {h, (hipStream_t)stream, false, &mode};
     StepIO io = {x, mel, steps, eps_out, 0};
     hipError_t e = fdk::embed(L, io, B, 1);
     if (e == hipSuccess) e = fdk::clear_range_flags(L);
@@ -1009,14 +1003,6 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_forward: kernel launch failed: %s", hipGetErrorString(e));
     h->last_B = B; h->last_T = T;
     return mark_tail(h, (hipStream_t)stream);
-}
-
-static unsigned mode_signature(const fd_context *h)
-{
-    unsigned s = (h->keep_taps ? 1u : 0u) | (h->gemm_f16 ? 2u : 0u) | (h->lvc_f16 ? 4u : 0u) | (h->conv_f16 ? 8u : 0u) | (h->step_lens ? 16u : 0u) |
-                 (h->inline_fallback ? 32u : 0u) | (h->lvc_h8_mfma ? 64u : 0u) | ((unsigned)h->hoist_np << 11) | (h->hoist_chunk ? (1u << 21) : 0u) | (h->fuse_up ? (1u << 22) : 0u) | (h->fuse_advance ? (1u << 23) : 0u) | (h->gemm_wino ? (1u << 24) : 0u);
-    for (int i = 0; i < ST_COUNT; ++i) s = (s << 1) | (h->fast[i] ? 1u : 0u);
-    return s ^ (h->fp32_mask * 2654435761u);
 }
 
 static int resolve_pending(fd_handle h, unsigned *mask);
@@ -1030,110 +1016,99 @@ int fd_settle(fd_handle h)
 }
 
 // `count` consecutive denoiser steps of the current call on `stream`, starting at the device step counter: replayed from captured
-// graphs of up to 8 steps (kept per (B, T, mode): there are ~9 us between two graph launches, so a short schedule is one launch
+// graphs of up to 8 steps (kept per (B, T, steps, mode): there are ~9 us between two graph launches, so a short schedule is one launch
 // per call, a long one a series of 8-step launches and a shorter one for the remainder), or launched one by one (options graph = 0,
-// profile = 1).  fp32_mask / inline_fallback: fd_internal.h (fd_pipe).
-static int enqueue_steps(fd_handle h, int B, int T, int count, unsigned fp32_mask, bool inline_fallback, hipStream_t stream)
+// profile = 1).  mode: the call's (fd_internal.h: StepMode).
+static int enqueue_steps(fd_handle h, int B, int T, int count, const StepMode &mode, hipStream_t stream)
 {
     Workspace &ws = h->ws;
-    h->fp32_mask = fp32_mask;
-    h->inline_fallback = inline_fallback;
-    StepIO io = {ws.x, ws.mel, nullptr, nullptr, 1};
-    struct Restore { fd_handle h; ~Restore() { h->fp32_mask = 0; h->inline_fallback = true; h->hoist_step = 0; if (h->hoist_chunk) h->hoist_np = 1; } } restore{h};
     constexpr int CHUNK = 8;
-    // hoist_chunk: the predictor of an np-step piece in front of it, over np * B (step, utterance) entries; the steps then skip theirs
-    auto piece_predictor = [&](const fdk::Launch &L, int np) -> hipError_t {
-        h->hoist_np = np;
-        if (np < 2) return hipSuccess;
-        StepIO iop = {ws.x, ws.mel_rep, nullptr, nullptr, np};
-        hipError_t e = fdk::kp_front(L, iop, B * np, T);
-        return e == hipSuccess ? fdk::kp_gemm(L, B * np, T) : e;
+    // hoist_chunk: a piece of `steps` steps has the predictor of its own steps in front of it, over steps * B (step, utterance) entries
+    auto piece_mode = [&](int steps) {
+        StepMode m = mode;
+        if (m.hoist_chunk) m.hoist_np = steps;
+        return m;
     };
-    if (h->hoist_chunk) h->hoist_np = 1;          // (the signature below must not depend on the piece that ran last)
-    // between two steps of one sequence the bookkeeping rides in the next step's first kernel -- when that kernel is the fast one
-    const bool defer_advance = h->fuse_advance && h->fast[ST_FIRST];
-    h->advance_pending = false;
+    // between two steps of a piece the bookkeeping rides in the next step's first kernel -- when that kernel is the fast one.  (Not
+    // across pieces: a piece predictor's front reads the embedding rows through the device step counter, which must stand at the
+    // piece's first step.)
+    const bool defer_advance = mode.fuse_advance && mode.fast[ST_FIRST];
+    auto enqueue_piece = [&](const fdk::Launch &L, int steps) -> hipError_t {
+        const int np = L.mode->hoist_chunk ? L.mode->hoist_np : 1;
+        hipError_t e = hipSuccess;
+        if (np > 1) {
+            StepIO iop = {ws.x, ws.mel_rep, nullptr, nullptr, np};
+            e = fdk::kp_front(L, iop, B * np, T);
+            if (e == hipSuccess) e = fdk::kp_gemm(L, B * np, T);
+        }
+        for (int k = 0; k < steps && e == hipSuccess; ++k) {
+            StepIO io = {ws.x, ws.mel, nullptr, nullptr, 1};
+            io.hoist_step = L.mode->hoist_np > 1 ? k : 0;      // (hoisted: the piece is the whole call or one 8-step piece of it)
+            io.advance = k > 0 && defer_advance;
+            e = fdk::run_step(L, io, B, T);
+            if (e == hipSuccess && !(k + 1 < steps && defer_advance)) e = fdk::advance_step(L);
+        }
+        return e;
+    };
     if (!(h->use_graph && !h->profile)) {
-        fdk::Launch L = {h, stream, false};
-        for (int k = 0; k < count; ++k) {
-            if (h->hoist_chunk && k % CHUNK == 0) {
-                hipError_t e = piece_predictor(L, std::min(CHUNK, count - k));
-                if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: predictor launch failed: %s", hipGetErrorString(e));
-            }
-            h->hoist_step = h->hoist_np > 1 ? (h->hoist_chunk ? k % CHUNK : k) : 0;
-            hipError_t e = fdk::run_step(L, io, B, T);
-            if (e == hipSuccess) {
-                // the next step's first kernel does it -- unless a piece predictor runs in between: its front reads the embedding rows
-                // through the device step counter, which must already stand at the piece's first step
-                if (k + 1 < count && defer_advance && !(h->hoist_chunk && (k + 1) % CHUNK == 0)) h->advance_pending = true;
-                else e = fdk::advance_step(L);
-            }
-            if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: step %d failed: %s", k, hipGetErrorString(e));
+        const int piece = mode.hoist_chunk ? CHUNK : count;
+        for (int first = 0; first < count; first += piece) {
+            const int steps = std::min(piece, count - first);
+            const StepMode m = piece_mode(steps);
+            const hipError_t e = enqueue_piece({h, stream, false, &m}, steps);
+            if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: launch of steps %d.. failed: %s", first, hipGetErrorString(e));
         }
         return FD_OK;
     }
-    const unsigned sig = mode_signature(h);
-    auto graph_of = [&](int steps, hipGraphExec_t *out) -> int {
-        for (auto &g : h->graphs)
-            if (g.B == B && g.T == T && g.sig == sig && g.steps == steps) {
-                g.last_use = ++h->graph_clock;
-                *out = g.exec;
-                ++h->n_graph_hits;
-                return FD_OK;
-            }
-        reap_retired(h, false);
-        while (h->graphs.size() >= (size_t)std::max(1, h->max_graphs)) {
-            // evict the least recently used one.  It may still be running (or be queued behind the work on `stream`): retired with an
-            // event recorded here, destroyed by a later call once that event has completed -- no wait on this path
-            size_t lru = 0;
-            for (size_t i = 1; i < h->graphs.size(); ++i)
-                if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
-            fd_context::RetiredGraph r = {h->graphs[lru].graph, h->graphs[lru].exec, nullptr};
-            FD_HIP(h, hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-            FD_HIP(h, hipEventRecord(r.done, stream));
-            h->retired.push_back(r);
-            h->graphs.erase(h->graphs.begin() + lru);
-            ++h->n_graph_evictions;
-        }
-        ++h->n_graph_captures;
-        FD_HIP(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        fdk::Launch Lc = {h, h->cap_stream, true};
-        hipError_t ec = h->hoist_chunk ? piece_predictor(Lc, steps) : hipSuccess;
-        for (int k = 0; k < steps && ec == hipSuccess; ++k) {
-            h->hoist_step = h->hoist_np > 1 ? k : 0;      // (hoisted: the graph holds the whole call or piece, so k is its step)
-            ec = fdk::run_step(Lc, io, B, T);
-            if (ec == hipSuccess) {
-                if (k + 1 < steps && defer_advance) h->advance_pending = true;
-                else ec = fdk::advance_step(Lc);
-            }
-        }
-        hipGraph_t g = nullptr;
-        hipError_t e2 = hipStreamEndCapture(h->cap_stream, &g);
-        if (ec != hipSuccess || e2 != hipSuccess) {
-            if (g) hipGraphDestroy(g);
-            FD_FAIL(h, FD_ERR_HIP, "fd_sample: graph capture failed: %s", hipGetErrorString(ec != hipSuccess ? ec : e2));
-        }
+    // `reps` replays of the graph of a piece of `steps` steps, captured first if it is not cached.  Enqueued right away: a capture for
+    // the next piece that evicts this graph records the retire event behind them.
+    auto replay = [&](int steps, int reps) -> int {
+        const StepMode m = piece_mode(steps);
         hipGraphExec_t ex = nullptr;
-        hipError_t e3 = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        if (e3 != hipSuccess) {
-            hipGraphDestroy(g);
-            FD_FAIL(h, FD_ERR_HIP, "fd_sample: hipGraphInstantiate: %s", hipGetErrorString(e3));
+        for (auto &g : h->graphs)
+            if (g.B == B && g.T == T && g.steps == steps && g.mode == m) {
+                g.last_use = ++h->graph_clock;
+                ex = g.exec;
+                ++h->n_graph_hits;
+                break;
+            }
+        if (!ex) {
+            reap_retired(h, false);
+            while (h->graphs.size() >= (size_t)std::max(1, h->max_graphs)) {
+                // evict the least recently used one.  It may still be running (or be queued behind the work on `stream`): retired with
+                // an event recorded here, destroyed by a later call once that event has completed -- no wait on this path
+                size_t lru = 0;
+                for (size_t i = 1; i < h->graphs.size(); ++i)
+                    if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
+                fd_context::RetiredGraph r = {h->graphs[lru].graph, h->graphs[lru].exec, nullptr};
+                FD_HIP(h, hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
+                FD_HIP(h, hipEventRecord(r.done, stream));
+                h->retired.push_back(r);
+                h->graphs.erase(h->graphs.begin() + lru);
+                ++h->n_graph_evictions;
+            }
+            ++h->n_graph_captures;
+            FD_HIP(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+            const hipError_t ec = enqueue_piece({h, h->cap_stream, true, &m}, steps);
+            hipGraph_t g = nullptr;
+            const hipError_t e2 = hipStreamEndCapture(h->cap_stream, &g);
+            if (ec != hipSuccess || e2 != hipSuccess) {
+                if (g) hipGraphDestroy(g);
+                FD_FAIL(h, FD_ERR_HIP, "fd_sample: graph capture failed: %s", hipGetErrorString(ec != hipSuccess ? ec : e2));
+            }
+            const hipError_t e3 = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+            if (e3 != hipSuccess) {
+                hipGraphDestroy(g);
+                FD_FAIL(h, FD_ERR_HIP, "fd_sample: hipGraphInstantiate: %s", hipGetErrorString(e3));
+            }
+            h->graphs.push_back({B, T, steps, m, g, ex, ++h->graph_clock});
         }
-        h->graphs.push_back({B, T, steps, sig, g, ex, ++h->graph_clock});
-        *out = ex;
+        for (int r = 0; r < reps; ++r) FD_HIP(h, hipGraphLaunch(ex, stream));
         return FD_OK;
     };
-    int rc;
-    hipGraphExec_t g_chunk = nullptr, g_rest = nullptr;
-    if (count >= CHUNK && (rc = graph_of(CHUNK, &g_chunk)) != FD_OK) return rc;
-    if (count % CHUNK && (rc = graph_of(count % CHUNK, &g_rest)) != FD_OK) return rc;
-    if (count >= CHUNK && (count % CHUNK)) {      // the second capture may have evicted the first (full cache): look it up again
-        if ((rc = graph_of(CHUNK, &g_chunk)) != FD_OK) return rc;
-        if ((rc = graph_of(count % CHUNK, &g_rest)) != FD_OK) return rc;
-    }
-    for (int k = 0; k + CHUNK <= count; k += CHUNK) FD_HIP(h, hipGraphLaunch(g_chunk, stream));
-    if (count % CHUNK) FD_HIP(h, hipGraphLaunch(g_rest, stream));
-    return FD_OK;
+    int rc = count >= CHUNK ? replay(CHUNK, count / CHUNK) : FD_OK;
+    if (rc == FD_OK && count % CHUNK) rc = replay(count % CHUNK, 1);
+    return rc;
 }
 
 static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned force_mask, long long ticket);
@@ -1142,9 +1117,9 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
 // is replayed from graphs and every stage runs the kernel set that honours `lens`; T itself otherwise.
 static int bucket_frames(const fd_context *h, int T)
 {
-    if (h->t_bucket <= 1 || !h->use_graph || h->profile || h->keep_taps) return T;
+    if (h->t_bucket <= 1 || !h->use_graph || h->profile || h->mode.keep_taps) return T;
     for (int i = ST_FIRST; i < ST_COUNT; ++i)
-        if (!h->fast[i]) return T;
+        if (!h->mode.fast[i]) return T;
     const int64_t tp = ((int64_t)T + h->t_bucket - 1) / h->t_bucket * h->t_bucket;
     return tp > 0x3fffffff ? T : (int)tp;
 }
@@ -1153,8 +1128,8 @@ static int bucket_frames(const fd_context *h, int T)
 static int hoist_mult(const fd_context *h, int B, int T, int N)
 {
     if (h->hoist_mode == 0 || N < 2) return 1;
-    if (!(h->fast[ST_KP_FRONT] && h->fast[ST_KP_GEMM] && h->fast[ST_LVC]) || h->keep_taps) return 1;
-    const int np = std::min(N, 8);             // a longer schedule hoists per 8-step graph piece (fd_context::hoist_chunk)
+    if (!(h->mode.fast[ST_KP_FRONT] && h->mode.fast[ST_KP_GEMM] && h->mode.fast[ST_LVC]) || h->mode.keep_taps) return 1;
+    const int np = std::min(N, 8);             // a longer schedule hoists per 8-step graph piece (StepMode::hoist_chunk)
     if (h->hoist_mode == 2) return np;
     return (int64_t)B * T <= 4096 ? np : 1;        // measured at T = 864: B = 1 -7.8 %, 2 -6.2 %, 3 -4.1 %, 4 -1.9 %, 8 and 16 +-0 (profiles/r03/s20_*)
 }
@@ -1183,10 +1158,13 @@ static int resolve_call(fd_handle h, const fd_context::PendingCall &p, unsigned 
     Workspace &ws = h->ws;
     const size_t n_el = (size_t)p.B * p.T * fd::HOPT;
     FD_HIP(h, hipMemcpyAsync(ws.x, ws.xsave, sizeof(float) * n_el, hipMemcpyDeviceToDevice, p.stream));
-    fdk::Launch L = {h, p.stream, false};
+    StepMode mode = p.mode;
+    mode.fp32_mask = *mask;
+    mode.inline_fallback = true;
+    fdk::Launch L = {h, p.stream, false, &mode};
     hipError_t e = fdk::clear_range_flags(L, p.first);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample_check: %s", hipGetErrorString(e));
-    int rc = enqueue_steps(h, p.B, p.T, p.count, *mask, true, p.stream);
+    int rc = enqueue_steps(h, p.B, p.T, p.count, mode, p.stream);
     if (rc != FD_OK) return rc;
     if (p.first + p.count == p.N) {
         e = fdk::copy_rows(L, p.out, (int64_t)p.T_io * fd::HOPT, ws.x, (int64_t)p.T * fd::HOPT, p.T_io * fd::HOPT, p.B);
@@ -1214,6 +1192,15 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
     Workspace &ws = h->ws;
     const size_t n_el = (size_t)B * T * fd::HOPT;
     const std::vector<unsigned long long> &ids = a.ids;
+    constexpr int CHUNK = 8;
+    // this call's mode.  Hoisted predictor: one front + GEMM launch pair over the batch of np * B (step, utterance) entries -- in front
+    // of the loop (N <= 8), or in front of each 8-step piece (hoist_chunk).  force_mask != 0 (a redo): every fallback inline
+    StepMode mode = h->mode;
+    const int np = hoist_mult(h, B, T, N);
+    mode.hoist_np = np;
+    mode.hoist_chunk = np > 1 && N > CHUNK;
+    mode.fp32_mask = force_mask;
+    mode.inline_fallback = force_mask != 0 || !h->host_fallback;
     std::vector<int> own_lens;                  // a bucketed call without `lens`: every utterance is T_io of the T frames long
     const int *lens_eff = a.has_lens ? a.lens.data() : nullptr;
     if (!lens_eff && T != T_io) { own_lens.assign(B, T_io); lens_eff = own_lens.data(); }
@@ -1221,10 +1208,10 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
     // without waiting for the stream, so the host prepares the next call while this one runs.
     {
         fd_context::StageSlot *sl = nullptr;
-        const int np = hoist_mult(h, B, T, N);      // the hoisted predictor's batch: np reverse steps x B utterances (below)
         const size_t off_lens = sizeof(StepParams), off_ids = off_lens + ((sizeof(int) * B * np + 7) & ~(size_t)7);
         if ((rc = fd_stage_acquire(h, off_ids + sizeof(unsigned long long) * B, &sl)) != FD_OK) return rc;
-        if ((rc = set_lens(h, lens_eff, B, T, stream, "fd_sample", reinterpret_cast<int *>(sl->host + off_lens), np)) != FD_OK) return rc;
+        if ((rc = set_lens(h, lens_eff, B, T, stream, "fd_sample", reinterpret_cast<int *>(sl->host + off_lens), &mode.ragged, np)) != FD_OK)
+            return rc;
         if (!ids.empty()) {
             memcpy(sl->host + off_ids, ids.data(), sizeof(unsigned long long) * B);
             FD_HIP(h, hipMemcpyAsync(ws.uid_dev, sl->host + off_ids, sizeof(unsigned long long) * B, hipMemcpyHostToDevice, stream));
@@ -1242,7 +1229,7 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
                                  hipMemcpyHostToDevice, stream));
         if ((rc = fd_stage_commit(h, sl, stream)) != FD_OK) return rc;
     }
-    fdk::Launch L = {h, stream, false};
+    fdk::Launch L = {h, stream, false, &mode};
     hipError_t e = fdk::copy_rows(L, ws.mel, T, a.mel, T_io, T_io, B * fd::COND);
     if (e == hipSuccess && a.x_T) e = fdk::copy_rows(L, ws.x, Lp, a.x_T, L_io, (int)L_io, B);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: input copy failed: %s", hipGetErrorString(e));
@@ -1271,34 +1258,25 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
     }
     if ((e = fdk::clear_range_flags(L)) != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: %s", hipGetErrorString(e));
 
-    constexpr int CHUNK = 8;
-    // Hoisted predictor (fd_internal.h: hoist_np): one front + GEMM launch pair over the batch of N * B (step, utterance) entries
-    h->hoist_np = hoist_mult(h, B, T, N);
-    h->hoist_step = 0;
-    h->hoist_chunk = h->hoist_np > 1 && N > CHUNK;
-    if (h->hoist_np > 1) {      // the mel once per predicted step: ONE launch (the lengths were staged that often by set_lens)
+    if (np > 1) {      // the mel once per predicted step: ONE launch (the lengths were staged that often by set_lens)
         const int64_t mel_n = (int64_t)B * fd::COND * T;
-        if ((e = fdk::copy_rows(L, ws.mel_rep, T, ws.mel, T, T, B * fd::COND, h->hoist_np, mel_n)) != hipSuccess)
+        if ((e = fdk::copy_rows(L, ws.mel_rep, T, ws.mel, T, T, B * fd::COND, np, mel_n)) != hipSuccess)
             FD_FAIL(h, FD_ERR_HIP, "fd_sample: mel replication failed: %s", hipGetErrorString(e));
     }
-    if (h->hoist_chunk) h->hoist_np = 1;          // enqueue_steps sets it piece by piece
-    else if (h->hoist_np > 1) {
-        h->fp32_mask = force_mask;
-        h->inline_fallback = force_mask != 0 || !h->host_fallback;
+    if (np > 1 && !mode.hoist_chunk) {      // (hoist_chunk: enqueue_steps puts one in front of every piece)
         StepIO iop = {ws.x, ws.mel_rep, nullptr, nullptr, 0};      // "forward" addressing: batch entry n * B + b reads noise row n * B + b
         e = fdk::kp_front(L, iop, B * N, T);
         if (e == hipSuccess) e = fdk::kp_gemm(L, B * N, T);
-        h->fp32_mask = 0; h->inline_fallback = true;
         if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: predictor launch failed: %s", hipGetErrorString(e));
     }
     if (force_mask != 0) {
-        if ((rc = enqueue_steps(h, B, T, N, force_mask, true, stream)) != FD_OK) return rc;
+        if ((rc = enqueue_steps(h, B, T, N, mode, stream)) != FD_OK) return rc;
         if ((rc = copy_out()) != FD_OK) return rc;
     } else if (h->host_fallback && N <= CHUNK) {
         // fallback = host, one graph launch: no fp32 launch trails the fp16x2 kernels; their flags accumulate on the device and travel
         // to the host behind the work.  Looked at lazily: by the next fd_sample after it has enqueued itself, or by fd_sample_check /
         // fd_sample_settle; a flagged call is then run again as a whole.
-        if ((rc = enqueue_steps(h, B, T, N, 0u, /*inline_fallback=*/false, stream)) != FD_OK) return rc;
+        if ((rc = enqueue_steps(h, B, T, N, mode, stream)) != FD_OK) return rc;
         const int slot = (int)(ticket & 1);
         FD_HIP(h, hipMemcpyAsync(h->flags_host + 32 * slot, ws.range_flag + 64, sizeof(int) * 32, hipMemcpyDeviceToHost, stream));
         FD_HIP(h, hipEventRecord(slot ? h->flags_done2 : h->flags_done, stream));
@@ -1317,20 +1295,22 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
             ++h->n_pieces;
             if (mask != 0) ++h->n_pieces_fp32;
             if (first > 0 && mask == 0) FD_HIP(h, hipMemcpyAsync(ws.xsave, ws.x, sizeof(float) * n_el, hipMemcpyDeviceToDevice, stream));
-            if ((rc = enqueue_steps(h, B, T, count, mask, /*inline_fallback=*/mask != 0, stream)) != FD_OK) return rc;
+            mode.fp32_mask = mask;
+            mode.inline_fallback = mask != 0;
+            if ((rc = enqueue_steps(h, B, T, count, mode, stream)) != FD_OK) return rc;
             if (mask != 0) continue;              // already on the safe path: nothing to look at
             FD_HIP(h, hipMemcpyAsync(h->flags_host, ws.range_flag + 64, sizeof(int) * 32, hipMemcpyDeviceToHost, stream));
             FD_HIP(h, hipEventRecord(h->flags_done, stream));
             h->pending.active = true; h->pending.lazy = false; h->pending.slot = 0; h->pending.ticket = ticket;
             h->pending.B = B; h->pending.T = T; h->pending.T_io = T_io; h->pending.N = N; h->pending.first = first; h->pending.count = count; h->pending.out = a.out;
-            h->pending.stream = stream;
+            h->pending.stream = stream; h->pending.mode = mode;
             if (last) break;                      // the caller's fd_sample_check (or the next call on this handle) looks at it
             int redone = resolve_pending(h, &mask);
             if (redone < 0) return redone;
         }
         if ((rc = copy_out()) != FD_OK) return rc;      // (provisional while a check is pending)
     } else {
-        if ((rc = enqueue_steps(h, B, T, N, 0u, true, stream)) != FD_OK) return rc;
+        if ((rc = enqueue_steps(h, B, T, N, mode, stream)) != FD_OK) return rc;
         if ((rc = copy_out()) != FD_OK) return rc;
     }
     h->last_B = B; h->last_T = T;
@@ -1472,65 +1452,36 @@ int fd_set_option(fd_handle h, const char *key, const char *value)
         bool m = true;
         int rc = parse_mode(m);
         if (rc != FD_OK) return rc;
-        for (int i = 0; i < ST_COUNT; ++i) h->fast[i] = m;
+        for (int i = 0; i < ST_COUNT; ++i) h->mode.fast[i] = m;
         return FD_OK;
     }
     if (k.compare(0, 8, "kernels.") == 0) {
         for (int i = 0; i < ST_COUNT; ++i)
-            if (k.substr(8) == stage_names[i]) return parse_mode(h->fast[i]);
+            if (k.substr(8) == stage_names[i]) return parse_mode(h->mode.fast[i]);
         FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: unknown stage '%s'", key);
     }
+    // the options of two named values: set(h, value == a)
+    static const struct { const char *key, *a, *b; void (*set)(fd_context *, bool); } choices[] = {
+        {"gemm", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.gemm_f16 = a; }},
+        {"gemm_form", "winograd", "direct", [](fd_context *c, bool a) { c->mode.gemm_wino = a; }},   // how the fp16x2 GEMM does its 3 taps
+        {"lvc", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.lvc_f16 = a; }},
+        {"conv", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.conv_f16 = a; }},
+        {"lvc_h8", "mfma", "valu", [](fd_context *c, bool a) { c->mode.lvc_h8_mfma = a; }},
+        {"fallback", "graph", "host", [](fd_context *c, bool a) { c->host_fallback = !a; }},
+        // training operator, frames path: gather = dx reads the forward-order frames; copy = a reordered copy first
+        {"lvc_dx", "gather", "copy", [](fd_context *c, bool a) { c->lvc_dx_gather = a; }},
+        {"mel", "pwg", "tacotron", [](fd_context *c, bool a) { c->mel_variant = a ? MEL_PWG : MEL_TACOTRON; }},
+    };
+    for (const auto &ch : choices) {
+        if (k != ch.key) continue;
+        if (v != ch.a && v != ch.b) FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: %s expects %s|%s, got '%s'", key, ch.a, ch.b, value);
+        ch.set(h, v == ch.a);
+        return FD_OK;
+    }
     const bool on = (v == "1" || v == "true" || v == "on");
-    if (k == "gemm") {
-        if (v == "f16x2") h->gemm_f16 = true;
-        else if (v == "fp32") h->gemm_f16 = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: gemm expects f16x2|fp32, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "gemm_form") {      // how the fp16x2 predictor GEMM evaluates kernel_conv's three taps
-        if (v == "winograd") h->gemm_wino = true;
-        else if (v == "direct") h->gemm_wino = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: gemm_form expects winograd|direct, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "lvc") {
-        if (v == "f16x2") h->lvc_f16 = true;
-        else if (v == "fp32") h->lvc_f16 = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: lvc expects f16x2|fp32, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "conv") {
-        if (v == "f16x2") h->conv_f16 = true;
-        else if (v == "fp32") h->conv_f16 = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: conv expects f16x2|fp32, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "mel") {
-        if (v == "pwg") h->mel_variant = MEL_PWG;
-        else if (v == "tacotron") h->mel_variant = MEL_TACOTRON;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: mel expects pwg|tacotron, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "lvc_h8") {
-        if (v == "mfma") h->lvc_h8_mfma = true;
-        else if (v == "valu") h->lvc_h8_mfma = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: lvc_h8 expects mfma|valu, got '%s'", value);
-        drop_graph(h);
-        return FD_OK;
-    }
-    if (k == "fallback") {
-        if (v == "host") h->host_fallback = true;
-        else if (v == "graph") h->host_fallback = false;
-        else FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: fallback expects graph|host, got '%s'", value);
-        return FD_OK;
-    }
-    if (k == "fuse_final") { h->fuse_final = on; drop_graph(h); return FD_OK; }
-    if (k == "fuse_up") { h->fuse_up = on; drop_graph(h); return FD_OK; }
-    if (k == "fuse_advance") { h->fuse_advance = on; drop_graph(h); return FD_OK; }
-    if (k == "lvc_dx") {      // training operator, frames path: gather = dx reads the forward-order frames; copy = a reordered copy first
-        if (v != "gather" && v != "copy") FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: lvc_dx expects gather|copy, got '%s'", value);
-        h->lvc_dx_gather = (v == "gather"); return FD_OK;
-    }
+    if (k == "fuse_final") { h->mode.fuse_final = on; return FD_OK; }
+    if (k == "fuse_up") { h->mode.fuse_up = on; return FD_OK; }
+    if (k == "fuse_advance") { h->mode.fuse_advance = on; return FD_OK; }
     if (k == "embed_cache") { h->embed_cache = on; return FD_OK; }
     if (k == "hoist") {
         if (v == "auto") h->hoist_mode = 1;
@@ -1551,7 +1502,7 @@ int fd_set_option(fd_handle h, const char *key, const char *value)
         return FD_OK;
     }
     if (k == "profile") { h->profile = (v == "events") ? 2 : (on ? 1 : 0); return FD_OK; }
-    if (k == "taps") { h->keep_taps = on; return FD_OK; }
+    if (k == "taps") { h->mode.keep_taps = on; return FD_OK; }
     FD_FAIL(h, FD_ERR_INVALID, "fd_set_option: unknown option '%s'", key);
 }
 

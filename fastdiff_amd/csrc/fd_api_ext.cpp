@@ -213,7 +213,7 @@ int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capa
     } else if (k.size() == 5 && k.compare(0, 4, "kp_h") == 0 && k[4] >= '0' && k[4] <= '2') {
         n = (int64_t)B * fd::HID * T; src = w.kp_hB + (k[4] - '0') * n;
     } else if (k.size() == 2 && k[0] == 'x' && k[1] >= '0' && k[1] <= '2') {
-        if (!h->keep_taps) FD_FAIL(h, FD_ERR_STATE, "fd_read_tap: set option taps=1 before the forward to keep block outputs");
+        if (!h->mode.keep_taps) FD_FAIL(h, FD_ERR_STATE, "fd_read_tap: set option taps=1 before the forward to keep block outputs");
         const int blk = k[1] - '0';
         src = w.xtap[blk]; n = (int64_t)B * fd::C * T * fd::hop(blk);
     } else if (k == "range_flags") {       // 32 int32 (bit patterns): fp16-range flags of the last step, see Workspace::range_flag

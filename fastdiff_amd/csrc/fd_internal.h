@@ -119,6 +119,50 @@ struct StepParams {
 
 enum Stage { ST_EMBED = 0, ST_FIRST, ST_DBLOCK, ST_KP_FRONT, ST_KP_GEMM, ST_CONVT, ST_LVC, ST_FINAL, ST_COUNT };
 
+// Everything that decides which kernels a denoiser step (or a captured piece of steps) enqueues and with which arguments.  A captured
+// graph is keyed on (B, T, steps, StepMode).  fd_context::mode holds the option values; a call copies it and fills in its own fields.
+struct StepMode {
+    // options
+    bool fast[ST_COUNT] = {true, true, true, true, true, true, true, true};   // "kernels.<stage>" = fast | naive
+    bool gemm_f16 = true;        // kp_gemm on the fp16 matrix pipe with the 2-piece operand split
+    bool gemm_wino = true;       // option "gemm_form" = "winograd" | "direct": ... as Winograd F(2,3) over the frame axis (2/3 of the matrix work)
+    bool lvc_f16 = true;         // LVC layers (hop 64, 256) likewise
+    bool conv_f16 = true;        // DBlocks, ConvTranspose upsamplers and the predictor front likewise
+    bool lvc_h8_mfma = true;     // option "lvc_h8" = "mfma": the hop-8 layers on 16x16x32 fp16 tiles (k_lvc_h8m) | "valu" (k_lvc_h8)
+    bool fuse_final = true;      // option "fuse_final": final_conv inside the last LVC layer
+    bool fuse_up = true;         // option "fuse_up": the ConvTranspose of blocks 1 and 2 inside their first LVC layer (when both stages run
+                                 // fp16x2-only, i.e. under fallback = host or a forced mask without them).  Same bits, one launch and one
+                                 // round trip of x less per block: B=1 -5.2 %, B=8 -2.6 %
+    bool fuse_advance = true;    // option "fuse_advance": between two steps of one graph / launch sequence the end-of-step bookkeeping
+                                 // (k_advance) rides in the next step's first kernel instead of a launch of its own
+    bool keep_taps = false;      // option "taps"
+    // per call.  How a stage that has an fp16x2 kernel is launched (fd_pipe below):
+    //   inline_fallback  the fp32 kernel is enqueued right behind the fp16x2 one and exits at once unless that one raised its flag
+    //                    (fully asynchronous, works inside a captured graph; ~2 us per stage and step)
+    //   !inline_fallback only the fp16x2 kernel; flags accumulate in range_flag[64..95] and the HOST redoes the work with
+    //                    fp32_mask set (option fallback = host: fd_sample_check)
+    //   fp32_mask        bit i set: the stage whose flag word is i runs its fp32 kernel outright
+    unsigned fp32_mask = 0;
+    bool inline_fallback = true;
+    bool ragged = false;         // the call's `lens` are in Workspace::lens_dev (a ragged batch)
+    // hoisted predictor (fd_context::hoist_mode): the kernels of hoist_np reverse steps are predicted by ONE front + GEMM launch pair
+    // (batch entry n * B + b = step n of utterance b), in front of the call's steps -- or, hoist_chunk (a schedule of more than 8 steps),
+    // in front of each captured piece of up to 8 steps, over the piece's own steps (rows step_idx .. step_idx + 7 of the embedding
+    // table, read through the device step counter).  hoist_np = 1: each step runs its own predictor
+    int hoist_np = 1;
+    bool hoist_chunk = false;
+
+    bool operator==(const StepMode &o) const
+    {
+        for (int i = 0; i < ST_COUNT; ++i)
+            if (fast[i] != o.fast[i]) return false;
+        return gemm_f16 == o.gemm_f16 && gemm_wino == o.gemm_wino && lvc_f16 == o.lvc_f16 && conv_f16 == o.conv_f16 &&
+               lvc_h8_mfma == o.lvc_h8_mfma && fuse_final == o.fuse_final && fuse_up == o.fuse_up && fuse_advance == o.fuse_advance &&
+               keep_taps == o.keep_taps && fp32_mask == o.fp32_mask && inline_fallback == o.inline_fallback && ragged == o.ragged &&
+               hoist_np == o.hoist_np && hoist_chunk == o.hoist_chunk;
+    }
+};
+
 struct Workspace {
     int B = 0;                  // capacity: utterances (per-utterance arrays),
     int64_t frames = 0;         //           B*T frames (activations, predicted kernels),
@@ -139,7 +183,7 @@ struct Workspace {
     float *xA = nullptr, *xB = nullptr;                           // [B][32][L] ping-pong
     float *xtap[fd::NBLK] = {}; // block outputs kept for fd_read_tap
     int64_t pframes = 0, prows = 0, plens = 0;   // capacity of the predictor's buffers (kp_h*, kpack, mel_rep / h_f16 / lens_dev): frames, image
-                                                 // rows and utterances x the reverse steps predicted at once (fd_context::hoist_np), tracked on
+                                                 // rows and utterances x the reverse steps predicted at once (StepMode::hoist_np), tracked on
                                                  // their own so that a large batch and a hoisted small one do not multiply
     float *mel_rep = nullptr;   // [N][B][80][T] the mel once per reverse step: the hoisted predictor's batch
     float *mel = nullptr;       // [B][80][T] library-owned copy used by the sampler graph
@@ -183,40 +227,16 @@ struct fd_context {
     int num_cus = 256;
     std::string err;
     bool committed = false;
-    bool fast[ST_COUNT];
+    StepMode mode;                            // the options among the mode's fields; the per-call ones stay at their defaults here
     bool use_graph = true;
     int profile = 0;                          // option "profile": 0 off | 1 the kernels' own begin / end timestamps | 2 ("events") stream events around each launch
-    bool keep_taps = false;
-    bool gemm_f16 = true;                     // kp_gemm on the fp16 matrix pipe with the 2-piece operand split
-    bool gemm_wino = true;                    // option "gemm_form" = "winograd" | "direct": ... as Winograd F(2,3) over the frame axis (2/3 of the matrix work)
-    bool lvc_f16 = true;                      // LVC layers (hop 64, 256) likewise
-    bool conv_f16 = true;                     // DBlocks, ConvTranspose upsamplers and the predictor front likewise
-    const int *step_lens = nullptr;           // device copy of the caller's `lens` for this call (ragged batch), or null
     std::vector<unsigned long long> noise_ids; // fd_set_noise_streams: consumed by the next fd_sample
-    // How a stage that has an fp16x2 kernel is launched (fd_pipe below):
-    //   inline_fallback  the fp32 kernel is enqueued right behind the fp16x2 one and exits at once unless that one raised its flag
-    //                    (fully asynchronous, works inside a captured graph; ~2 us per stage and step)
-    //   !inline_fallback only the fp16x2 kernel; flags accumulate in range_flag[64..95] and the HOST redoes the work with
-    //                    fp32_mask set (option fallback = host: fd_sample_check)
-    //   fp32_mask        bit i set: the stage whose flag word is i runs its fp32 kernel outright
-    bool lvc_h8_mfma = true;                  // option "lvc_h8" = "mfma": the hop-8 layers on 16x16x32 fp16 tiles (k_lvc_h8m) | "valu" (k_lvc_h8)
     bool host_fallback = true;                // option "fallback" = "host" (default; settled inside fd_sample unless defer_check) | "graph"
-    bool inline_fallback = true;
-    unsigned fp32_mask = 0;
-    bool h_image_ready = false;               // set by fast_kp_front when it wrote the GEMM's fp16 image of h for this step
     std::map<std::string, std::pair<std::vector<int64_t>, std::vector<float>>> raw;   // host copies from fd_set_weight
     std::vector<void *> dev_allocs;          // weight arena pieces
     DevWeights w;
     Workspace ws;
-    bool fuse_final = true;                  // option "fuse_final": final_conv inside the last LVC layer
-    bool fuse_up = true;                     // option "fuse_up": the ConvTranspose of blocks 1 and 2 inside their first LVC layer (when both
-                                             // stages run fp16x2-only, i.e. under fallback = host or a forced mask without them).  Same
-                                             // bits, one launch and one round trip of x less per block: B=1 -5.2 %, B=8 -2.6 %
-    bool final_fused = false;                // set by the last LVC layer's launch, consumed by fast_final
-    bool fuse_advance = true;                // option "fuse_advance": between two steps of one graph / launch sequence the end-of-step
-                                             // bookkeeping (k_advance) rides in the next step's first kernel instead of a launch of its own
     bool lvc_dx_gather = true;               // option lvc_dx = gather | copy: the frames path's dx kernel reads kernel_conv's frames (fd_kernels_train.hip)
-    bool advance_pending = false;            // set by enqueue_steps after a step whose bookkeeping the next first_conv will do
     // the step embedding and the three fc_t rows of every reverse step depend on the schedule's t values and the weights only: kept from
     // the previous fd_sample when those are unchanged (two launches per call)
     std::vector<float> embed_t;
@@ -238,17 +258,12 @@ struct fd_context {
     hipEvent_t ev_switch = nullptr;          // the tail of the handle's last compute call (fd_api.cpp: mark_tail / follow_stream)
     bool tail_marked = false;
     // The predictor (front + GEMM) sees the mel and the step embedding only -- never x -- so for a short schedule on a small batch all N
-    // steps' kernels are predicted by ONE pair of launches in front of the loop (batch entry n * B + b = step n of utterance b): at
-    // B = 1 the front's seven-layer latency chain and the GEMM's fill are paid once per call instead of once per step.  hoist_np = N
-    // while such a call is enqueued (1 otherwise), hoist_step = the step being enqueued: the LVC layers read kpack at that offset.
-    // A longer schedule does the same per captured piece of 8 steps (hoist_chunk): the piece's graph starts with the predictor of its
-    // own steps (rows step_idx .. step_idx + 7 of the embedding table, read through the device step counter).
+    // steps' kernels are predicted by ONE pair of launches in front of the loop (StepMode::hoist_np): at B = 1 the front's seven-layer
+    // latency chain and the GEMM's fill are paid once per call instead of once per step.
     // option "hoist" = auto (B * T <= 4096 frames, N >= 2) | on | off
     int hoist_mode = 1;                       // 0 off, 1 auto, 2 on
-    int hoist_np = 1, hoist_step = 0;
-    bool hoist_chunk = false;                 // a long schedule (N > 8): the predictor of each 8-step graph piece is hoisted to the piece's front
-    // captured denoiser steps, one per (B, T, mode): micro-batches of different padded length alternate without re-capturing
-    struct StepGraph { int B, T, steps; unsigned sig; hipGraph_t graph; hipGraphExec_t exec; unsigned long long last_use; };   // `steps` denoiser steps per launch
+    // captured denoiser steps, one per (B, T, steps, mode): micro-batches of different padded length alternate without re-capturing
+    struct StepGraph { int B, T, steps; StepMode mode; hipGraph_t graph; hipGraphExec_t exec; unsigned long long last_use; };   // `steps` denoiser steps per launch
     std::vector<StepGraph> graphs;           // at most max_graphs, least recently used evicted
     unsigned long long graph_clock = 0;
     // An evicted graph may still be running: it is parked here with an event recorded behind everything enqueued so far and destroyed
@@ -297,6 +312,7 @@ struct fd_context {
         int T_io = 0;                                       // library's buffers (bucketed), T_io: the caller's
         float *out = nullptr;
         hipStream_t stream = nullptr;
+        StepMode mode;                                      // a piece of a long schedule: the mode it was enqueued with
         SampleArgs args;
     } pending;
     long long ticket_counter = 0;            // one per fd_sample
@@ -321,10 +337,23 @@ struct fd_context {
 };
 
 enum Pipe { PIPE_F16_THEN_F32, PIPE_F16_ONLY, PIPE_F32_ONLY };
-inline Pipe fd_pipe(const fd_context *c, bool f16_possible, int flag_word)
+inline Pipe fd_pipe(const StepMode &m, bool f16_possible, int flag_word)
 {
-    if (!f16_possible || ((c->fp32_mask >> flag_word) & 1u)) return PIPE_F32_ONLY;
-    return c->inline_fallback ? PIPE_F16_THEN_F32 : PIPE_F16_ONLY;
+    if (!f16_possible || ((m.fp32_mask >> flag_word) & 1u)) return PIPE_F32_ONLY;
+    return m.inline_fallback ? PIPE_F16_THEN_F32 : PIPE_F16_ONLY;
+}
+// What one launch leaves for another, as a function of the mode: producer and consumer both ask, so they agree by construction.
+// The fp16-pipe predictor front writes the direct fp16x2 GEMM's piece image of h itself (k_h_split is then not launched).
+inline bool front_writes_h_image(const StepMode &m, const DevWeights &w)
+{
+    return m.fast[ST_KP_FRONT] && fd_pipe(m, m.conv_f16 && w.kpf_f16_ok, 19) != PIPE_F32_ONLY &&
+           fd_pipe(m, m.gemm_f16 && w.gemm_f16_ok, 0) != PIPE_F32_ONLY && !(m.gemm_wino && w.gemm_w_ok);
+}
+// The last LVC layer (block 2, layer 3, flag word 12) leaves the final_conv sums in eps_acc; fast_final then adds the bias and updates x.
+inline bool last_lvc_fuses_final(const StepMode &m, const DevWeights &w)
+{
+    return m.fast[ST_LVC] && m.fast[ST_FINAL] && !m.keep_taps && m.fuse_final &&
+           fd_pipe(m, m.lvc_f16 && w.lvc_f16_ok, 1 + 2 * fd::LAYERS + 3) != PIPE_F32_ONLY;
 }
 
 // Arguments of one denoiser step (all device pointers)
@@ -334,6 +363,8 @@ struct StepIO {
     const float *steps;    // [B] (forward mode) -- ignored in sampler mode (table[step_idx].t)
     float *eps_out;        // forward mode: eps destination; sampler mode: null (x updated in place)
     int sampler;           // 0 = fd_forward, 1 = fd_sample step
+    int hoist_step = 0;    // hoisted predictor (StepMode::hoist_np > 1): which B entries of its kpack batch this step reads
+    bool advance = false;  // the first kernel does the previous step's end-of-step bookkeeping (StepMode::fuse_advance)
 };
 
 // kernels (fd_kernels_*.hip) -- each returns hipError from launch
@@ -342,6 +373,7 @@ struct Launch {
     fd_context *ctx;
     hipStream_t stream;
     bool capturing;
+    const StepMode *mode = nullptr;   // what the denoiser step's launchers read; left out (null) by the paths that launch no step
 };
 hipError_t embed(const Launch &L, const StepIO &io, int B, int n_steps);
 hipError_t first_conv(const Launch &L, const StepIO &io, int B, int T);

@@ -139,31 +139,32 @@ hipError_t fast_first_conv(const Launch &L, const StepIO &io, int B, int T)
     const DevWeights &w = L.ctx->w;
     const int Lf = T * fd::HOPT;
     fd_context *c = L.ctx;
-    const bool adv = io.sampler && c->advance_pending;      // the previous step of this sequence left its bookkeeping to us
-    FD_LAUNCH(L, "first_conv", k_first_conv, dim3((Lf + 1023) / 1024, B), dim3(256), 0, io.x_in, w.first.w, w.first.b, c->ws.a[0], Lf, c->step_lens,
+    const int *lens = L.mode->ragged ? c->ws.lens_dev : nullptr;
+    const bool adv = io.sampler && io.advance;      // the previous step of this sequence left its bookkeeping to us
+    FD_LAUNCH(L, "first_conv", k_first_conv, dim3((Lf + 1023) / 1024, B), dim3(256), 0, io.x_in, w.first.w, w.first.b, c->ws.a[0], Lf, lens,
               adv ? c->ws.params : (StepParams *)nullptr, c->ws.range_flag);
-    if (adv) c->advance_pending = false;
     return hipSuccess;
 }
 
 hipError_t fast_final(const Launch &L, const StepIO &io, const float *x32, int B, int T)
 {
     fd_context *c = L.ctx;
+    const StepMode &m = *L.mode;
     const DevWeights &w = c->w;
     const int Lf = T * fd::HOPT;
+    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
     const int *run_if = nullptr;
     const char *name = "final_conv_update";
-    if (c->final_fused) {       // the last LVC layer already left the conv sums in eps_acc
+    if (last_lvc_fuses_final(m, w)) {       // the last LVC layer already left the conv sums in eps_acc
         const int *flag = c->ws.range_flag + 1 + 2 * fd::LAYERS + 3;
         FD_LAUNCH(L, "final_update", k_final_acc, dim3((Lf + 1023) / 1024, B), dim3(256), 0, c->ws.eps_acc, w.final_.b, io.eps_out, c->ws.x,
-                  (const StepParams *)c->ws.params, io.sampler, Lf, c->step_lens, flag);
+                  (const StepParams *)c->ws.params, io.sampler, Lf, lens, flag);
         run_if = flag;
         name = "final_conv_fallback";
-        c->final_fused = false;
-        if (!c->inline_fallback) return hipSuccess;      // fallback = host: a flagged last layer is redone from the host
+        if (!m.inline_fallback) return hipSuccess;      // fallback = host: a flagged last layer is redone from the host
     }
     FD_LAUNCH(L, name, k_final, dim3((Lf + 1023) / 1024, B), dim3(256), 0, x32, w.final_.w, w.final_.b, io.eps_out,
-              c->ws.x, (const StepParams *)c->ws.params, io.sampler, Lf, c->step_lens, run_if);
+              c->ws.x, (const StepParams *)c->ws.params, io.sampler, Lf, lens, run_if);
     return hipSuccess;
 }
 

@@ -987,10 +987,11 @@ hipError_t fast_kp_front(const Launch &L, const StepIO &io, int B, int T)
     fd_context *c = L.ctx;
     const DevWeights &w = c->w;
     const dim3 grid((T + KPF_VALID - 1) / KPF_VALID, B, fd::NBLK);
+    const StepMode &m = *L.mode;
+    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
     const int *run_if = nullptr;
     const char *name = "kp_front";
-    c->h_image_ready = false;
-    const Pipe pipe = fd_pipe(c, c->conv_f16 && w.kpf_f16_ok, 19);
+    const Pipe pipe = fd_pipe(m, m.conv_f16 && w.kpf_f16_ok, 19);
     if (pipe != PIPE_F32_ONLY) {
         KpFrontW2 k2;
         for (int n = 0; n < fd::NBLK; ++n) {
@@ -999,10 +1000,9 @@ hipError_t fast_kp_front(const Launch &L, const StepIO &io, int B, int T)
         }
         // the direct fp16x2 GEMM reads the piece image this kernel can write on its way out; the Winograd form builds its own (k_h_wino)
         // and the fp32 GEMM reads hout
-        const bool image = fd_pipe(c, c->gemm_f16 && w.gemm_f16_ok, 0) != PIPE_F32_ONLY && !(c->gemm_wino && w.gemm_w_ok);
+        const bool image = front_writes_h_image(m, w);
         FD_LAUNCH(L, name, k_kp_front_h2, grid, dim3(256), 0, io.mel, c->ws.kp_hB, image ? reinterpret_cast<char *>(c->ws.h_f16) : (char *)nullptr, k2,
-                  (const float *)c->ws.noise, (const StepParams *)c->ws.params, io.sampler, B, T, gx_rows(T), c->ws.range_flag, c->step_lens);
-        c->h_image_ready = image;      // the GEMM's fp16 image of h is written (k_h_split not needed)
+                  (const float *)c->ws.noise, (const StepParams *)c->ws.params, io.sampler, B, T, gx_rows(T), c->ws.range_flag, lens);
         run_if = c->ws.range_flag + 19;
         name = "kp_front_fp32_fallback";
         if (pipe == PIPE_F16_ONLY) return hipSuccess;
@@ -1013,7 +1013,7 @@ hipError_t fast_kp_front(const Launch &L, const StepIO &io, int B, int T)
         for (int l = 0; l < 6; ++l) { kw.res_pack[n][l] = w.kp_res_pack[n][l]; kw.res_b[n][l] = w.blk[n].kp_res[l].b; }
     }
     FD_LAUNCH(L, name, k_kp_front, grid, dim3(256), 0, io.mel, c->ws.kp_hB, kw, (const float *)c->ws.noise,
-              (const StepParams *)c->ws.params, io.sampler, B, T, run_if, c->step_lens);
+              (const StepParams *)c->ws.params, io.sampler, B, T, run_if, lens);
     return hipSuccess;
 }
 
@@ -1028,37 +1028,39 @@ hipError_t fast_kp_gemm(const Launch &L, int B, int T)
     const int chunk_tiles = (tiles_per_utt + chunks_per_utt - 1) / chunks_per_utt;     // balanced, <= GEMM_CT
     const int n_items = fd::NBLK * (fd::KREC / 128) * B * chunks_per_utt;
     const int grid = n_items < 2 * c->num_cus ? n_items : 2 * c->num_cus;              // persistent: 2 workgroups per CU
-    const Pipe pipe = fd_pipe(c, c->gemm_f16 && w.gemm_f16_ok, 0);
+    const StepMode &m = *L.mode;
+    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
+    const Pipe pipe = fd_pipe(m, m.gemm_f16 && w.gemm_f16_ok, 0);
     const bool f16 = pipe != PIPE_F32_ONLY;
-    if (f16 && c->gemm_wino && w.gemm_w_ok) {
+    if (f16 && m.gemm_wino && w.gemm_w_ok) {
         // Winograd F(2,3) over the frame axis: the transformed piece image from the front's fp32 h, then 2/3 of the direct form's matrix work
         const int P = gw_pairs(T), chunks = P / GW_PAIRS, items = fd::NBLK * (fd::KREC / 128) * B * chunks;
         const int grid2 = items < 2 * c->num_cus ? items : 2 * c->num_cus;
         FD_LAUNCH(L, "h_wino", k_h_wino, dim3((8 * P + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
-                  reinterpret_cast<char *>(c->ws.h_f16), c->ws.range_flag, B, T, P, c->step_lens);
+                  reinterpret_cast<char *>(c->ws.h_f16), c->ws.range_flag, B, T, P, lens);
         FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_w, dim3(grid2), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[0]), reinterpret_cast<const float4 *>(w.gemm_w_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, P, chunks, items, c->step_lens);
+                  (const int *)c->ws.range_flag, B, T, P, chunks, items, lens);
         if (pipe == PIPE_F16_ONLY) return hipSuccess;
     } else if (f16) {
         const int R = gx_rows(T);
         const int chunks = (T + GX_CT * 32 - 1) / (GX_CT * 32), items = fd::NBLK * (fd::KREC / 128) * B * chunks;
         const int grid2 = items < 2 * c->num_cus ? items : 2 * c->num_cus;
-        if (!c->h_image_ready)      // the fp16-pipe predictor front writes the image itself
+        if (!front_writes_h_image(m, w))      // (else the fp16-pipe predictor front wrote the image)
             FD_LAUNCH(L, "h_split", k_h_split, dim3((32 * R + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
-                      reinterpret_cast<unsigned *>(c->ws.h_f16), c->ws.range_flag, B, T, R, c->step_lens);
+                      reinterpret_cast<unsigned *>(c->ws.h_f16), c->ws.range_flag, B, T, R, lens);
         FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_h2, dim3(grid2), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[0]), reinterpret_cast<const float4 *>(w.gemm_h2_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, R, chunks, items, c->step_lens, 0, fd::NBLK);
+                  (const int *)c->ws.range_flag, B, T, R, chunks, items, lens, 0, fd::NBLK);
         if (pipe == PIPE_F16_ONLY) return hipSuccess;
     }
     // fp32 matrix pipe: the whole job when the fp16 form is off, otherwise an early-exit launch that only works when
     // k_h_split found operands outside the fp16 range
     FD_LAUNCH(L, f16 ? "kp_gemm_fp32_fallback" : "kp_gemm", k_kp_gemm, dim3(grid), dim3(256), 0, (const float *)c->ws.kp_hB, c->ws.kpack,
               w.gemm_pack[0], w.gemm_pack[1], w.gemm_pack[2], w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2], B, T, chunks_per_utt,
-              chunk_tiles, n_items, f16 ? (const int *)c->ws.range_flag : (const int *)nullptr, c->step_lens);
+              chunk_tiles, n_items, f16 ? (const int *)c->ws.range_flag : (const int *)nullptr, lens);
     return hipSuccess;
 }
 

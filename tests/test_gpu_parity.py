@@ -813,6 +813,61 @@ def test_graph_cache_evicts_without_waiting_and_keeps_results(gc, sched):
         torch.cuda.synchronize()
         m.sample(mels[70], rows, seed=70)
     assert m.counter("graphs_retired") <= 2
+    # a cache of ONE graph under a long schedule (N = 19: two replays of the 8-step graph, then the 3-step one), the whole schedule in one
+    # sequence of graph launches (fallback = graph): each graph is launched as soon as it is obtained, so the capture of the remainder evicts
+    # the 8-step graph behind its replays, and neither graph is captured twice in a call.  Synchronous calls.
+    rows19 = [{"t": 190.0 - 9.5 * k, "c_eps": 0.02, "c_div": 0.99, "sigma": 0.05, "c1": 1.0, "c2": 0.0, "c3": 0.0, "add_noise": int(k < 18)}
+              for k in range(19)]
+    with torch.no_grad():
+        fresh = {}
+        for T in (20, 70):
+            f = gc.make_model()
+            f.set_option("fallback", "graph")
+            fresh[T] = f.sample(mels[T], rows19, seed=T)
+        m1 = gc.make_model()
+        m1.set_option("graph_cache", "1")
+        m1.set_option("fallback", "graph")
+        for i, T in enumerate((70, 20, 70, 20)):
+            if i > 0:
+                caps, evs = m1.counter("graph_captures"), m1.counter("graph_evictions")
+            y = m1.sample(mels[T], rows19, seed=T)
+            torch.cuda.synchronize()
+            assert torch.isfinite(y).all() and torch.equal(y, fresh[T]), (i, T)
+            if i > 0:
+                assert (m1.counter("graph_captures") - caps, m1.counter("graph_evictions") - evs) == (2, 2), i
+    assert m1.counter("graphs_resident") == 1
+
+
+def test_option_flips_on_a_warm_handle_replay_the_right_graph(gc, sched):
+    """Every option that changes what a denoiser step launches is part of a captured graph's key (fd_internal.h: StepMode), so no option
+    drops graphs.  Per option and value a fresh handle gives the reference; one warm handle then samples with v0, v1 and v0 again: each
+    result must be bit-equal to its reference, and the switch back must replay the graph of v0 (a hit, no capture).  hoist = off on every
+    handle, so the predictor is inside the captured steps; where the arithmetic differs, v0 and v1 must give different bits."""
+    import synth
+    B, T, N = 2, 100, 4
+    mel = torch.from_numpy(synth.synth_mel(41, B, T)).cuda()
+    rows, _ = gc.table_rows(sched, N)
+    flips = [("gemm_form", "winograd", "direct", True), ("lvc_h8", "mfma", "valu", True), ("gemm", "f16x2", "fp32", True),
+             ("fuse_final", "1", "0", False), ("fuse_up", "1", "0", False), ("fuse_advance", "1", "0", False)]
+    with torch.no_grad():
+        for key, v0, v1, differs in flips:
+            want = {}
+            for v in (v0, v1):
+                f = gc.make_model()
+                f.set_option("hoist", "off")
+                f.set_option(key, v)
+                want[v] = f.sample(mel, rows, seed=5)
+            assert torch.isfinite(want[v0]).all() and torch.isfinite(want[v1]).all(), key
+            if differs:
+                assert not torch.equal(want[v0], want[v1]), key
+            m = gc.make_model()
+            m.set_option("hoist", "off")
+            for i, v in enumerate((v0, v1, v0)):
+                m.set_option(key, v)
+                if i == 2:
+                    caps, hits = m.counter("graph_captures"), m.counter("graph_hits")
+                assert torch.equal(m.sample(mel, rows, seed=5), want[v]), (key, v, i)
+            assert m.counter("graph_captures") == caps and m.counter("graph_hits") > hits, key
 
 
 def test_consecutive_calls_may_change_streams(gc, sched):
