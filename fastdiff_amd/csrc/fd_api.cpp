@@ -1,6 +1,6 @@
-// fd_api.cpp -- host side of libfastdiff_hip.so, the inference boundary (include/fastdiff_hip.h): context, state_dict ingestion (weight-norm
-// fold + repack), workspace, the denoiser step sequence, the hipGraph-replayed reverse loop, options.  The rows next to the path and the
-// hooks: fd_api_ext.cpp (fastdiff_hip_ext.h); the training operators: fd_api_train.cpp (fastdiff_hip_train.h).
+// fd_api.cpp -- host side of libfastdiff_hip.so, the inference boundary (include/fastdiff_hip.h): context, workspace, the denoiser step
+// sequence, the hipGraph-replayed reverse loop, options.  The state_dict ingestion (weight-norm fold + repack): fd_weights.cpp; the rows
+// next to the path and the hooks: fd_api_ext.cpp (fastdiff_hip_ext.h); the training operators: fd_api_train.cpp (fastdiff_hip_train.h).
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -73,47 +73,6 @@ void fd_prof_drain(fd_context *c)
         c->event_pool.push_back(pe.e1);
     }
     c->prof_pending.clear();
-}
-
-// ------------------------------------------------------------------------------------------------
-// expected state_dict (FastDiff_model.py:13-72; modules.py:116-125,141-187,257-318)
-// ------------------------------------------------------------------------------------------------
-struct ParamSpec { std::string name; std::vector<int64_t> dims; bool weight_norm; bool transposed_conv; bool linear; };
-
-static const int KP_RES_IDX[6] = {1, 3, 6, 8, 11, 13};
-
-// the state_dict of FastDiff(**cfg): names, shapes and registration facts (weight-normed Conv1d, plain ConvTranspose1d / Linear)
-static std::vector<ParamSpec> param_specs(const fd_config &c)
-{
-    const int64_t C = c.inner_channels, COND = c.cond_channels, HID = c.kpnet_hidden_channels, KS = c.lvc_kernel_size, KK = c.kpnet_conv_size;
-    const int64_t LAYERS = c.lvc_layers_each_block, E_IN = c.diffusion_step_embed_dim_in, E_MID = c.diffusion_step_embed_dim_mid, E_OUT = c.diffusion_step_embed_dim_out;
-    std::vector<ParamSpec> s;
-    s.push_back({"first_audio_conv", {C, 1, 7}, true, false, false});
-    s.push_back({"fc_t1", {E_MID, E_IN}, false, false, true});
-    s.push_back({"fc_t2", {E_OUT, E_MID}, false, false, true});
-    for (int n = 0; n < c.n_upsample; ++n) {
-        const std::string p = "lvc_blocks." + std::to_string(n);
-        s.push_back({p + ".upsample", {C, C, 2 * (int64_t)c.upsample_ratios[n]}, false, true, false});
-        s.push_back({p + ".kernel_predictor.input_conv.0", {HID, COND, 5}, true, false, false});
-        for (int j = 0; j < 6; ++j)
-            s.push_back({p + ".kernel_predictor.residual_conv." + std::to_string(KP_RES_IDX[j]), {HID, HID, KK}, true, false, false});
-        s.push_back({p + ".kernel_predictor.kernel_conv", {LAYERS * C * 2 * C * KS, HID, KK}, true, false, false});
-        s.push_back({p + ".kernel_predictor.bias_conv", {LAYERS * 2 * C, HID, KK}, true, false, false});
-        s.push_back({p + ".fc_t", {COND, E_OUT}, false, false, true});
-        for (int i = 0; i < LAYERS; ++i) s.push_back({p + ".convs." + std::to_string(i), {C, C, KS}, true, false, false});
-        const std::string d = "downsample." + std::to_string(n);
-        s.push_back({d + ".residual_dense", {C, C, 1}, true, false, false});
-        for (int i = 0; i < 3; ++i) s.push_back({d + ".conv." + std::to_string(i), {C, C, 3}, true, false, false});
-    }
-    s.push_back({"final_conv.0", {c.audio_channels, C, 7}, true, false, false});
-    return s;
-}
-
-static int64_t numel(const std::vector<int64_t> &d)
-{
-    int64_t n = 1;
-    for (auto v : d) n *= v;
-    return n;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -223,7 +182,7 @@ static void reap_retired(fd_context *c, bool wait)
 
 // Drops every captured graph.  The caller has just synchronised the device (workspace growth, fd_commit_weights, fd_destroy): no
 // replay is queued any more.  (An option does not drop graphs: the mode it changes is part of every graph's key.)
-static void drop_graph(fd_context *c)
+void drop_graph(fd_context *c)
 {
     for (auto &g : c->graphs) {
         if (g.exec) hipGraphExecDestroy(g.exec);
@@ -243,7 +202,7 @@ static void release_handle(fd_context *h)
     for (auto ev : h->event_pool) hipEventDestroy(ev);
     drop_graph(h);
     free_workspace(h);
-    for (void *p : h->dev_allocs) hipFree(p);
+    if (h->weight_arena) hipFree(h->weight_arena);
     if (h->scratch) hipFree(h->scratch);
     if (h->lvc_scratch) hipFree(h->lvc_scratch);
     if (h->kconv_scratch) hipFree(h->kconv_scratch);
@@ -266,434 +225,6 @@ int fd_destroy(fd_handle h)
     hipDeviceSynchronize();
     fd_prof_drain(h);
     release_handle(h);
-    return FD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// weights
-// ------------------------------------------------------------------------------------------------
-int fd_set_weight(fd_handle h, const char *name, const float *host_data, const int64_t *dims, int ndim)
-{
-    if (!h || !name || !host_data || !dims || ndim <= 0 || ndim > 4) return FD_ERR_INVALID;
-    const std::string key(name);
-    // find the owning parameter and the expected shape of this tensor
-    const std::vector<ParamSpec> specs = param_specs(h->cfg);
-    std::vector<int64_t> expect;
-    for (const auto &s : specs) {
-        if (key.compare(0, s.name.size(), s.name) != 0 || key.size() <= s.name.size() || key[s.name.size()] != '.') continue;
-        const std::string suffix = key.substr(s.name.size() + 1);
-        if (suffix == "weight" || suffix == "weight_v") expect = s.dims;
-        else if (suffix == "weight_g") { expect = {s.dims[0], 1, 1}; }
-        else if (suffix == "bias") expect = {s.transposed_conv ? s.dims[1] : s.dims[0]};
-        else continue;
-        break;
-    }
-    if (expect.empty()) FD_FAIL(h, FD_ERR_INVALID, "fd_set_weight: unexpected key '%s' (not in the FastDiff state_dict)", name);
-    std::vector<int64_t> got(dims, dims + ndim);
-    if (got != expect) {
-        std::string a, b;
-        for (auto v : got) a += std::to_string(v) + ",";
-        for (auto v : expect) b += std::to_string(v) + ",";
-        FD_FAIL(h, FD_ERR_INVALID, "fd_set_weight: size mismatch for %s: got [%s] expected [%s]", name, a.c_str(), b.c_str());
-    }
-    auto &slot = h->raw[key];
-    slot.first = got;
-    slot.second.assign(host_data, host_data + numel(got));
-    h->committed = false;
-    return FD_OK;
-}
-
-namespace {
-
-typedef FoldedParam Folded;
-
-// w = v * (g / ||v||), norm over everything but dim 0 (torch._weight_norm(v, g, 0)); plain weights pass through
-int fold_param(fd_context *h, const ParamSpec &s, Folded &out)
-{
-    const auto itb = h->raw.find(s.name + ".bias");
-    if (itb == h->raw.end()) FD_FAIL(h, FD_ERR_MISSING, "fd_commit_weights: missing tensor %s.bias", s.name.c_str());
-    out.b = itb->second.second;
-    const auto itw = h->raw.find(s.name + ".weight");
-    const auto itv = h->raw.find(s.name + ".weight_v");
-    const auto itg = h->raw.find(s.name + ".weight_g");
-    if (itv != h->raw.end() && itg != h->raw.end()) {
-        const std::vector<float> &v = itv->second.second, &g = itg->second.second;
-        const int64_t cout = s.dims[0], per = numel(s.dims) / cout;
-        out.w.resize(v.size());
-        for (int64_t o = 0; o < cout; ++o) {
-            double ss = 0.0;
-            for (int64_t j = 0; j < per; ++j) ss += (double)v[o * per + j] * (double)v[o * per + j];
-            const float scale = g[o] / (float)sqrt(ss);
-            for (int64_t j = 0; j < per; ++j) out.w[o * per + j] = v[o * per + j] * scale;
-        }
-    } else if (itw != h->raw.end()) {
-        out.w = itw->second.second;
-    } else {
-        FD_FAIL(h, FD_ERR_MISSING, "fd_commit_weights: missing tensor %s.weight (or weight_g/weight_v)", s.name.c_str());
-    }
-    return FD_OK;
-}
-
-int upload(fd_context *h, const void *src, size_t bytes, const void **dst)
-{
-    void *d = nullptr;
-    FD_HIP(h, hipMalloc(&d, bytes));
-    h->dev_allocs.push_back(d);
-    FD_HIP(h, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    *dst = d;
-    return FD_OK;
-}
-
-int upload_f(fd_context *h, const std::vector<float> &v, const float **dst)
-{
-    return upload(h, v.data(), v.size() * sizeof(float), reinterpret_cast<const void **>(dst));
-}
-
-// Conv weight [cout][cin][ks] -> MFMA A-operand pack [mt][s4][lane][4], kk = tap*cin + ci = 2*(4*s4+r) + (lane>>5)
-std::vector<float> pack_A(const std::vector<float> &w, int cout, int cin, int ks)
-{
-    const int ns4 = cin * ks / 8, nmt = cout / 32;
-    std::vector<float> p((size_t)nmt * ns4 * 256);
-    for (int mt = 0; mt < nmt; ++mt)
-        for (int s4 = 0; s4 < ns4; ++s4)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int o = mt * 32 + (lane & 31), kk = 2 * (4 * s4 + r) + (lane >> 5);
-                    const int tap = kk / cin, ci = kk % cin;
-                    p[(((size_t)mt * ns4 + s4) * 64 + lane) * 4 + r] = w[((size_t)o * cin + ci) * ks + tap];
-                }
-    return p;
-}
-
-// IEEE binary16 <-> binary32 on the host (round to nearest even, subnormals kept): the weight pieces of the fp16x2 GEMM.
-static uint16_t f16_from_f32(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-    u &= 0x7FFFFFFFu;
-    if (u > 0x7F800000u) return sign | 0x7E00u;                  // NaN
-    if (u >= 0x477FF000u) return sign | 0x7C00u;                 // >= 65520 rounds to infinity
-    if (u < 0x38800000u) {                                       // below 2^-14: subnormal, a multiple of 2^-24
-        float ax;
-        memcpy(&ax, &u, 4);
-        return sign | (uint16_t)lrintf(ax * 16777216.0f);        // current rounding mode = nearest even; 1024 = smallest normal
-    }
-    uint32_t hbits = (((u >> 23) - 112u) << 10) | ((u & 0x7FFFFFu) >> 13);
-    const uint32_t rem = u & 0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (hbits & 1u))) ++hbits;   // a carry into the exponent is the correct result
-    return sign | (uint16_t)hbits;
-}
-static float f32_from_f16(uint16_t hb)
-{
-    const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, exp = (hb >> 10) & 0x1Fu, man = hb & 0x3FFu;
-    float v;
-    if (exp == 0) v = (float)man * (1.0f / 16777216.0f);
-    else if (exp == 31) { const uint32_t u = 0x7F800000u | (man << 13); memcpy(&v, &u, 4); }
-    else { const uint32_t u = ((exp + 112u) << 23) | (man << 13); memcpy(&v, &u, 4); }
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u |= sign;
-    memcpy(&v, &u, 4);
-    return v;
-}
-
-// fp16 pieces of a conv weight [cout][cin][ks] (cout a multiple of 32) in 32x32x16 A-operand order:
-// [mt = out/32][piece][kg][lane = out%32 + 32*g][8], k = 16*kg + 8*g + e = tap*cin + in.  *ok is cleared when a value does not
-// fit the fp16 range.
-static std::vector<uint16_t> pack_A_h2(const std::vector<float> &w, int cin, int ks, bool *ok, int cout = 32)
-{
-    const int nk = cin * ks, nkg = nk / 16, nmt = cout / 32;
-    std::vector<uint16_t> hp((size_t)nmt * 2 * nkg * 64 * 8);
-    for (int mt = 0; mt < nmt; ++mt)
-        for (int kg = 0; kg < nkg; ++kg)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int kk = kg * 16 + 8 * (lane >> 5) + e, tap = kk / cin, in = kk % cin, out = mt * 32 + (lane & 31);
-                    const float v = w[((size_t)out * cin + in) * ks + tap];
-                    if (!(fabsf(v) < 32768.0f)) *ok = false;
-                    const uint16_t p1 = f16_from_f32(v);
-                    hp[((((size_t)mt * 2 + 0) * nkg + kg) * 64 + lane) * 8 + e] = p1;
-                    hp[((((size_t)mt * 2 + 1) * nkg + kg) * 64 + lane) * 8 + e] = f16_from_f32((v - f32_from_f16(p1)) * 2048.0f);
-                }
-    return hp;
-}
-
-void unpack_kernel_index(int p, int &layer, int &in, int &out, int &tap)
-{
-    layer = p / fd::KLAYER;
-    const int q = p % fd::KLAYER, e = q & 7, lane = (q >> 3) & 63, mk = q >> 9;
-    const int mt = mk / 6, kg = mk % 6, kk = kg * 16 + 8 * (lane >> 5) + e, row = lane & 31;
-    tap = kk / fd::C; in = kk % fd::C;
-    out = 16 * mt + (row & 15) + 32 * (row >> 4);      // inverse of kernel_tile / kernel_row
-}
-
-}  // namespace
-
-int fd_commit_weights(fd_handle h)
-{
-    if (!h) return FD_ERR_INVALID;
-    FD_HIP(h, hipSetDevice(h->device));
-    {
-        const int rcs = fd_settle(h);      // a pending host check would otherwise run its call again on the NEW weights
-        if (rcs != FD_OK) return rcs;
-    }
-    h->embed_valid = false;
-    FD_HIP(h, hipDeviceSynchronize());
-    h->committed = false;            // until the new set is complete: a failed re-commit must not leave the old flag over freed weights
-    for (void *p : h->dev_allocs) hipFree(p);
-    h->dev_allocs.clear();
-    h->w = DevWeights();
-    drop_graph(h);
-
-    std::map<std::string, Folded> f;
-    for (const auto &s : param_specs(h->cfg)) {
-        int rc = fold_param(h, s, f[s.name]);
-        if (rc != FD_OK) return rc;
-    }
-    if (h->gen) {      // another architecture than base.yaml's: folded reference-layout weights, no operand packing
-        const int rcg = fdg::commit(h, f);
-        if (rcg == FD_OK) h->committed = true;
-        return rcg;
-    }
-    DevWeights &w = h->w;
-    int rc;
-#define UP(vec, dst) if ((rc = upload_f(h, vec, &(dst))) != FD_OK) return rc
-    auto up_conv = [&](const std::string &name, ConvW &cw) -> int {
-        int r1 = upload_f(h, f[name].w, &cw.w);
-        if (r1 != FD_OK) return r1;
-        return upload_f(h, f[name].b, &cw.b);
-    };
-    if ((rc = up_conv("first_audio_conv", w.first)) != FD_OK) return rc;
-    if ((rc = up_conv("final_conv.0", w.final_)) != FD_OK) return rc;
-    {   // the same weights in the order the last LVC layer holds its outputs: channel = 16 mt + 4 hi + (r & 3) + 8 (r >> 2)
-        const std::vector<float> &fw = f["final_conv.0"].w;
-        std::vector<float> ff(4 * 8 * 8, 0.0f);
-        for (int part = 0; part < 4; ++part)
-            for (int r = 0; r < 8; ++r)
-                for (int k = 0; k < 7; ++k) ff[(part * 8 + r) * 8 + k] = fw[(16 * (part >> 1) + 4 * (part & 1) + (r & 3) + 8 * (r >> 2)) * 7 + k];
-        UP(ff, w.final_fuse);
-    }
-    // embed MLP, transposed
-    auto transpose = [](const std::vector<float> &m, int rows, int cols) {
-        std::vector<float> t((size_t)rows * cols);
-        for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = m[(size_t)r * cols + c];
-        return t;
-    };
-    UP(transpose(f["fc_t1"].w, fd::E_MID, fd::E_IN), w.fc_t1_T);
-    UP(f["fc_t1"].b, w.fc_t1_b);
-    UP(transpose(f["fc_t2"].w, fd::E_OUT, fd::E_MID), w.fc_t2_T);
-    UP(f["fc_t2"].b, w.fc_t2_b);
-    {   // frequency table of calc_diffusion_step_embedding (util.py:425-427): fp32 product, fp32 exp
-        std::vector<float> table(64);
-        const float cst = (float)(-(log(10000.0) / 63.0));
-        for (int j = 0; j < 64; ++j) {
-            volatile float arg = (float)j * cst;
-            table[j] = expf(arg);
-        }
-        UP(table, w.embed_table);
-    }
-    bool f16_ok = true, w_ok = true, lvc_ok = true, dblock_ok = true, convt_ok = true, kpf_ok = true;
-    for (int n = 0; n < fd::NBLK; ++n) {
-        const std::string p = "lvc_blocks." + std::to_string(n), d = "downsample." + std::to_string(n);
-        if ((rc = up_conv(d + ".residual_dense", w.down[n].res)) != FD_OK) return rc;
-        for (int i = 0; i < 3; ++i) {
-            if ((rc = up_conv(d + ".conv." + std::to_string(i), w.down[n].conv[i])) != FD_OK) return rc;
-            UP(pack_A(f[d + ".conv." + std::to_string(i)].w, fd::C, fd::C, 3), w.down_pack[n][i]);
-        }
-        UP(pack_A(f[d + ".residual_dense"].w, fd::C, fd::C, 1), w.down_pack[n][3]);
-        for (int i = 0; i < 4; ++i) {      // the same four matrices as fp16 pieces (conv 0..2: K = 96, residual 1x1: K = 32)
-            const std::vector<uint16_t> hp = pack_A_h2(f[i < 3 ? d + ".conv." + std::to_string(i) : d + ".residual_dense"].w, fd::C, i < 3 ? 3 : 1, &dblock_ok);
-            if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.down_h2[n][i]))) != FD_OK) return rc;
-        }
-        if ((rc = up_conv(p + ".fc_t", w.blk[n].fc_t)) != FD_OK) return rc;
-        UP(transpose(f[p + ".fc_t"].w, fd::COND, fd::E_OUT), w.fc_t_T[n]);
-        w.fc_t_b[n] = w.blk[n].fc_t.b;
-        if ((rc = up_conv(p + ".upsample", w.blk[n].up)) != FD_OK) return rc;
-        {   // ConvTranspose1d weight [in][out][2r] -> per-phase MFMA A operands [ph][s4][lane][4], kk = sel*32 + i
-            const int r = fd::ratio(n), ks = 2 * r, pd = r / 2;
-            const std::vector<float> &uw = f[p + ".upsample"].w;
-            std::vector<float> up((size_t)r * 8 * 256);
-            for (int ph = 0; ph < r; ++ph)
-                for (int s4 = 0; s4 < 8; ++s4)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int q = 0; q < 4; ++q) {
-                            const int kk = 2 * (4 * s4 + q) + (lane >> 5), sel = kk >> 5, i = kk & 31, o = lane & 31;
-                            // sel 0: the nearer input position (jA), sel 1: the one before it (jB = jA - 1, tap + r)
-                            const int kA = (ph < pd) ? ph + pd : ph - pd, k = sel ? kA + r : kA;
-                            up[(((size_t)ph * 8 + s4) * 64 + lane) * 4 + q] = uw[((size_t)i * fd::C + o) * ks + k];
-                        }
-            UP(up, w.up_pack[n]);
-            // the same per-phase slices as fp16 pieces: [ph][piece][4 kg][64 lane = out + 32*g][8], k = 16*kg + 8*g + e = sel*32 + i
-            std::vector<uint16_t> hp((size_t)r * 2 * 4 * 64 * 8);
-            for (int ph = 0; ph < r; ++ph)
-                for (int kg = 0; kg < 4; ++kg)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int kk = kg * 16 + 8 * (lane >> 5) + e, sel = kk >> 5, i = kk & 31, o = lane & 31;
-                            const int kA = (ph < pd) ? ph + pd : ph - pd, k = sel ? kA + r : kA;
-                            const float v = uw[((size_t)i * fd::C + o) * ks + k];
-                            if (!(fabsf(v) < 32768.0f)) convt_ok = false;
-                            const uint16_t p1 = f16_from_f32(v);
-                            hp[((((size_t)ph * 2 + 0) * 4 + kg) * 64 + lane) * 8 + e] = p1;
-                            hp[((((size_t)ph * 2 + 1) * 4 + kg) * 64 + lane) * 8 + e] = f16_from_f32((v - f32_from_f16(p1)) * 2048.0f);
-                        }
-            if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.up_h2[n]))) != FD_OK) return rc;
-        }
-        if ((rc = up_conv(p + ".kernel_predictor.input_conv.0", w.blk[n].kp_in)) != FD_OK) return rc;
-        UP(pack_A(f[p + ".kernel_predictor.input_conv.0"].w, fd::HID, fd::COND, 5), w.kp_in_pack[n]);
-        {
-            const std::vector<uint16_t> hp = pack_A_h2(f[p + ".kernel_predictor.input_conv.0"].w, fd::COND, 5, &kpf_ok, fd::HID);
-            if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.kp_in_h2[n]))) != FD_OK) return rc;
-        }
-        for (int j = 0; j < 6; ++j) {
-            const std::string nm = p + ".kernel_predictor.residual_conv." + std::to_string(KP_RES_IDX[j]);
-            if ((rc = up_conv(nm, w.blk[n].kp_res[j])) != FD_OK) return rc;
-            UP(pack_A(f[nm].w, fd::HID, fd::HID, 3), w.kp_res_pack[n][j]);
-            const std::vector<uint16_t> hp = pack_A_h2(f[nm].w, fd::HID, 3, &kpf_ok, fd::HID);
-            if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.kp_res_h2[n][j]))) != FD_OK) return rc;
-        }
-        if ((rc = up_conv(p + ".kernel_predictor.kernel_conv", w.blk[n].kc)) != FD_OK) return rc;
-        if ((rc = up_conv(p + ".kernel_predictor.bias_conv", w.blk[n].bc)) != FD_OK) return rc;
-        for (int i = 0; i < fd::LAYERS; ++i) {
-            if ((rc = up_conv(p + ".convs." + std::to_string(i), w.blk[n].convs[i])) != FD_OK) return rc;
-            UP(pack_A(f[p + ".convs." + std::to_string(i)].w, fd::C, fd::C, 3), w.lvc_conv_pack[n][i]);
-            if (n == 0) {      // hop 8: 16x16x32 tiles: lane = out%16 + 16*g holds k = tap*32 + 8g + e, i.e. input channels 8g .. 8g+7 of one tap
-                const std::vector<float> &cw = f[p + ".convs." + std::to_string(i)].w;
-                std::vector<uint16_t> hp((size_t)2 * 3 * 2 * 64 * 8);
-                for (int rt = 0; rt < 2; ++rt)
-                    for (int tap = 0; tap < 3; ++tap)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int out = 16 * rt + (lane & 15), in = 8 * (lane >> 4) + e;
-                                const float v = cw[((size_t)out * fd::C + in) * 3 + tap];
-                                if (!(fabsf(v) < 32768.0f)) lvc_ok = false;
-                                const uint16_t p1 = f16_from_f32(v);
-                                hp[((((size_t)rt * 3 + tap) * 2 + 0) * 64 + lane) * 8 + e] = p1;
-                                hp[((((size_t)rt * 3 + tap) * 2 + 1) * 64 + lane) * 8 + e] = f16_from_f32((v - f32_from_f16(p1)) * 2048.0f);
-                            }
-                if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.lvc_conv_h16[i]))) != FD_OK) return rc;
-            }
-            {
-                const std::vector<uint16_t> hp = pack_A_h2(f[p + ".convs." + std::to_string(i)].w, fd::C, 3, &lvc_ok);
-                if ((rc = upload(h, hp.data(), hp.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.lvc_conv_h2[n][i]))) != FD_OK)
-                    return rc;
-            }
-        }
-        {   // GEMM B-operand pack: rows in packed-record order, kk = tap*64 + c
-            const std::vector<float> &kc = f[p + ".kernel_predictor.kernel_conv"].w, &kcb = f[p + ".kernel_predictor.kernel_conv"].b;
-            const std::vector<float> &bc = f[p + ".kernel_predictor.bias_conv"].w, &bcb = f[p + ".kernel_predictor.bias_conv"].b;
-            std::vector<float> gp((size_t)(fd::KREC / 32) * 24 * 256), gb(fd::KREC);
-            for (int pt = 0; pt < fd::KREC / 32; ++pt)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int pp = pt * 32 + (lane & 31);
-                    const float *wrow;
-                    if (pp < fd::KW) {
-                        int layer, in, out, tap;
-                        unpack_kernel_index(pp, layer, in, out, tap);
-                        const int row = ((layer * fd::C + in) * 2 * fd::C + out) * 3 + tap;   // [layers,in,out,k] view (modules.py:333-338)
-                        wrow = kc.data() + (size_t)row * fd::HID * 3;
-                        gb[pp] = kcb[row];
-                    } else {
-                        // bias record [layer][mt][row]  ->  bias_conv row layer*64 + out (view [layers,out], modules.py:339-342)
-                        const int q = pp - fd::KW, layer = q >> 6, mt = (q >> 5) & 1, row = q & 31;
-                        const int brow = layer * 64 + 16 * mt + (row & 15) + 32 * (row >> 4);
-                        wrow = bc.data() + (size_t)brow * fd::HID * 3;
-                        gb[pp] = bcb[brow];
-                    }
-                    for (int s4 = 0; s4 < 24; ++s4)
-                        for (int r = 0; r < 4; ++r) {
-                            const int kk = 2 * (4 * s4 + r) + (lane >> 5), tap = kk / fd::HID, c = kk % fd::HID;
-                            gp[(((size_t)pt * 24 + s4) * 64 + lane) * 4 + r] = wrow[c * 3 + tap];
-                        }
-                }
-            UP(gp, w.gemm_pack[n]);
-            UP(gb, w.gemm_bias[n]);
-            // fp16x2 form: w = w1 + 2^-11 * w2, w1 = fp16(w), w2 = fp16((w - w1) * 2^11) (round to nearest even, subnormals kept);
-            // B operand of v_mfma_f32_32x32x16_f16: lane = col + 32*g holds the 8 consecutive k = kg*16 + 8g + e, k = tap*64 + channel
-            std::vector<uint16_t> gx((size_t)(fd::KREC / 32) * 2 * 12 * 64 * 8);
-            for (int pt = 0; pt < fd::KREC / 32; ++pt)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int pp = pt * 32 + (lane & 31), g = lane >> 5;
-                    const float *wrow;
-                    if (pp < fd::KW) {
-                        int layer, in, out, tap;
-                        unpack_kernel_index(pp, layer, in, out, tap);
-                        wrow = kc.data() + (size_t)(((layer * fd::C + in) * 2 * fd::C + out) * 3 + tap) * fd::HID * 3;
-                    } else {
-                        const int q = pp - fd::KW, layer = q >> 6, mt = (q >> 5) & 1, row = q & 31;
-                        wrow = bc.data() + (size_t)(layer * 64 + 16 * mt + (row & 15) + 32 * (row >> 4)) * fd::HID * 3;
-                    }
-                    for (int kg = 0; kg < 12; ++kg)
-                        for (int e = 0; e < 8; ++e) {
-                            const int kk = kg * 16 + g * 8 + e, tap = kk / fd::HID, ch = kk % fd::HID;
-                            const float v = wrow[ch * 3 + tap];
-                            if (!(fabsf(v) < 32768.0f)) f16_ok = false;
-                            const uint16_t p1 = f16_from_f32(v);
-                            const uint16_t p2 = f16_from_f32((v - f32_from_f16(p1)) * 2048.0f);
-                            gx[((((size_t)pt * 2 + 0) * 12 + kg) * 64 + lane) * 8 + e] = p1;
-                            gx[((((size_t)pt * 2 + 1) * 12 + kg) * 64 + lane) * 8 + e] = p2;
-                        }
-                }
-            if ((rc = upload(h, gx.data(), gx.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.gemm_h2_pack[n]))) != FD_OK)
-                return rc;
-            // Winograd F(2,3) over the frame axis (kernel_conv is a k = 3 convolution over frames, modules.py:315-318): per pair of
-            // output frames  y[2p] = m0 + m1 + m2,  y[2p+1] = m1 - m2 + m3  with  m_j = V_j . u_j (K = 64 each),
-            //   V0 = g0, V1 = (g0 + g1 + g2) / 2, V2 = (g0 - g1 + g2) / 2, V3 = -g2        (g_tap = the column's weights of that tap)
-            //   u0 = h[2p-1] - h[2p+1], u1 = h[2p] + h[2p+1], u2 = h[2p+1] - h[2p], u3 = h[2p] - h[2p+2]   (k_h_wino)
-            // B operand: lane = col + 32*g holds the 8 consecutive k = kg*16 + 8g + e, kg = 4 j + k4, channel = 16 k4 + 8 g + e
-            std::vector<uint16_t> gw((size_t)(fd::KREC / 32) * 2 * 16 * 64 * 8);
-            for (int pt = 0; pt < fd::KREC / 32; ++pt)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int pp = pt * 32 + (lane & 31), g = lane >> 5;
-                    const float *wrow;
-                    if (pp < fd::KW) {
-                        int layer, in, out, tap;
-                        unpack_kernel_index(pp, layer, in, out, tap);
-                        wrow = kc.data() + (size_t)(((layer * fd::C + in) * 2 * fd::C + out) * 3 + tap) * fd::HID * 3;
-                    } else {
-                        const int q = pp - fd::KW, layer = q >> 6, mt = (q >> 5) & 1, row = q & 31;
-                        wrow = bc.data() + (size_t)(layer * 64 + 16 * mt + (row & 15) + 32 * (row >> 4)) * fd::HID * 3;
-                    }
-                    for (int kg = 0; kg < 16; ++kg)
-                        for (int e = 0; e < 8; ++e) {
-                            const int j = kg >> 2, ch = (kg & 3) * 16 + g * 8 + e;
-                            const double g0 = wrow[ch * 3 + 0], g1 = wrow[ch * 3 + 1], g2 = wrow[ch * 3 + 2];
-                            const float v = (float)(j == 0 ? g0 : (j == 1 ? 0.5 * (g0 + g1 + g2) : (j == 2 ? 0.5 * (g0 - g1 + g2) : -g2)));
-                            if (!(fabsf(v) < 32768.0f)) w_ok = false;
-                            const uint16_t p1 = f16_from_f32(v);
-                            const uint16_t p2 = f16_from_f32((v - f32_from_f16(p1)) * 2048.0f);
-                            gw[((((size_t)pt * 2 + 0) * 16 + kg) * 64 + lane) * 8 + e] = p1;
-                            gw[((((size_t)pt * 2 + 1) * 16 + kg) * 64 + lane) * 8 + e] = p2;
-                        }
-                }
-            if ((rc = upload(h, gw.data(), gw.size() * sizeof(uint16_t), reinterpret_cast<const void **>(&w.gemm_w_pack[n]))) != FD_OK)
-                return rc;
-        }
-    }
-    w.gemm_f16_ok = f16_ok;
-    w.gemm_w_ok = w_ok;
-    w.lvc_f16_ok = lvc_ok;
-    w.dblock_f16_ok = dblock_ok;
-    w.convt_f16_ok = convt_ok;
-    w.kpf_f16_ok = kpf_ok;
-    {
-        std::vector<int> perm(fd::KW);
-        for (int layer = 0; layer < fd::LAYERS; ++layer)
-            for (int in = 0; in < fd::C; ++in)
-                for (int out = 0; out < 2 * fd::C; ++out)
-                    for (int tap = 0; tap < 3; ++tap)
-                        perm[((layer * fd::C + in) * 2 * fd::C + out) * 3 + tap] = fd::kernel_index(layer, in, out, tap);
-        if ((rc = upload(h, perm.data(), perm.size() * sizeof(int), reinterpret_cast<const void **>(&w.kc_perm))) != FD_OK) return rc;
-        std::vector<int> bperm(fd::KB);
-        for (int layer = 0; layer < fd::LAYERS; ++layer)
-            for (int out = 0; out < 2 * fd::C; ++out) bperm[layer * 64 + out] = fd::bias_index(layer, out) - fd::KW;
-        if ((rc = upload(h, bperm.data(), bperm.size() * sizeof(int), reinterpret_cast<const void **>(&w.bc_perm))) != FD_OK) return rc;
-    }
-#undef UP
-    h->raw.clear();     // host copies are no longer needed
-    h->committed = true;
     return FD_OK;
 }
 

@@ -29,7 +29,6 @@ struct Net {
         std::vector<Conv> convs;
     } blk[8];
     const float *embed_table = nullptr;
-    std::vector<void *> allocs;        // weights
     // workspace, grown to the largest call seen
     float *ws = nullptr;
     size_t ws_floats = 0;
@@ -240,16 +239,9 @@ int create(fd_context *c)
     return FD_OK;
 }
 
-static void free_weights(Net *n)
-{
-    for (void *p : n->allocs) (void)hipFree(p);
-    n->allocs.clear();
-}
-
 void destroy(fd_context *c)
 {
     if (!c->gen) return;
-    free_weights(c->gen);
     if (c->gen->ws) (void)hipFree(c->gen->ws);
     delete c->gen;
     c->gen = nullptr;
@@ -257,27 +249,16 @@ void destroy(fd_context *c)
 
 int hop_total(const fd_context *c) { return c->gen ? c->gen->hop_total : fd::HOPT; }
 
-static int up(fd_context *c, Net *n, const std::vector<float> &v, const float **dst)
-{
-    void *d = nullptr;
-    if (hipMalloc(&d, sizeof(float) * std::max<size_t>(v.size(), 1)) != hipSuccess) { c->err = "fd_commit_weights: out of device memory"; return FD_ERR_HIP; }
-    n->allocs.push_back(d);
-    if (hipMemcpy(d, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { c->err = "fd_commit_weights: upload failed"; return FD_ERR_HIP; }
-    *dst = static_cast<const float *>(d);
-    return FD_OK;
-}
-
-int commit(fd_context *c, const std::map<std::string, FoldedParam> &f)
+int pack_weights(fd_context *c, const std::map<std::string, FoldedParam> &f, WeightImage &img)
 {
     Net *n = c->gen;
-    (void)hipDeviceSynchronize();
-    free_weights(n);
     int rc;
     auto conv = [&](const std::string &name, Conv &cw) -> int {
         const auto it = f.find(name);
         if (it == f.end()) { c->err = "fd_commit_weights: missing parameter " + name; return FD_ERR_MISSING; }
-        if ((rc = up(c, n, it->second.w, &cw.w)) != FD_OK) return rc;
-        return up(c, n, it->second.b, &cw.b);
+        img.add(cw.w, it->second.w);
+        img.add(cw.b, it->second.b);
+        return FD_OK;
     };
     static const int KP_RES_IDX[6] = {1, 3, 6, 8, 11, 13};
     if ((rc = conv("first_audio_conv", n->first)) != FD_OK) return rc;
@@ -308,7 +289,7 @@ int commit(fd_context *c, const std::map<std::string, FoldedParam> &f)
             volatile float arg = (float)j * cst;
             table[j] = expf(arg);
         }
-        if ((rc = up(c, n, table, &n->embed_table)) != FD_OK) return rc;
+        img.add(n->embed_table, table);
     }
     return FD_OK;
 }

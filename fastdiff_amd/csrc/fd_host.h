@@ -1,5 +1,5 @@
-// fd_host.h -- shared by the host translation units of libfastdiff_hip.so (fd_api.cpp, fd_api_ext.cpp, fd_api_train.cpp): the error
-// macros and the few helpers of the core that the other two call.
+// fd_host.h -- shared by the host translation units of libfastdiff_hip.so (fd_api.cpp, fd_weights.cpp, fd_api_ext.cpp, fd_api_train.cpp):
+// the error macros and the few helpers of the core that the others call.
 #pragma once
 #include <stdio.h>
 
@@ -26,6 +26,8 @@ extern std::string g_create_error;      // text of a failed fd_create (no handle
 extern "C" {      // (defined inside fd_api.cpp's extern "C" block; hidden visibility: not part of the ABI)
 // fallback = host: look at the flags of a pending fd_sample before touching device state (no-op when nothing is pending)
 int fd_settle(fd_handle h);
+// drops every captured graph; the caller has synchronised the device
+void drop_graph(fd_context *c);
 // Pinned staging ring (fd_context::stage): the next slot with room for `bytes`, free to be written by the host; ... and the mark behind
 // the copies that read it
 int fd_stage_acquire(fd_handle h, size_t bytes, fd_context::StageSlot **out);

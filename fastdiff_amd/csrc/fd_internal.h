@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <string.h>
 #include <map>
 #include <string>
 #include <vector>
@@ -208,13 +209,26 @@ enum MelVariant { MEL_PWG = 0, MEL_TACOTRON = 1, MEL_VARIANTS = 2 };
 // (fd_generic.hip: any architecture the reference constructor accepts, on runtime-shaped kernels; gen == nullptr for base.yaml's
 // architecture, which runs on the tuned kernel set).
 struct FoldedParam { std::vector<float> w, b; };
+// A weight set as host bytes (fd_weights.cpp builds it, fd_commit_weights uploads it with one allocation and one copy): every piece at
+// a 256-byte-aligned offset, with the pointer field that receives its device address.
+struct WeightImage {
+    std::vector<char> bytes;
+    std::vector<std::pair<const void **, size_t>> fields;      // (destination pointer field, offset into bytes)
+    template <class T> void add(const T *&dst, const std::vector<T> &v)
+    {
+        const size_t off = (bytes.size() + 255) & ~(size_t)255;
+        bytes.resize(off + v.size() * sizeof(T));
+        memcpy(bytes.data() + off, v.data(), v.size() * sizeof(T));
+        fields.push_back({reinterpret_cast<const void **>(&dst), off});
+    }
+};
 namespace fdg {
 struct Net;
 int validate(const fd_config &c, std::string &why);
 int create(fd_context *c);
 void destroy(fd_context *c);
 int hop_total(const fd_context *c);
-int commit(fd_context *c, const std::map<std::string, FoldedParam> &f);
+int pack_weights(fd_context *c, const std::map<std::string, FoldedParam> &f, WeightImage &img);   // its weights, fields = the Net's pointers
 int forward(fd_context *c, const float *x, const float *mel, const float *steps, int B, int T, const int *lens, float *eps_out, hipStream_t stream);
 int sample(fd_context *c, const float *mel, int B, int T, const int *lens, const fd_step *table, int N, int ddim, const float *x_T, const float *z,
            unsigned long long seed, const std::vector<unsigned long long> &ids, float *out, float *seq_out, hipStream_t stream);
@@ -233,7 +247,7 @@ struct fd_context {
     std::vector<unsigned long long> noise_ids; // fd_set_noise_streams: consumed by the next fd_sample
     bool host_fallback = true;                // option "fallback" = "host" (default; settled inside fd_sample unless defer_check) | "graph"
     std::map<std::string, std::pair<std::vector<int64_t>, std::vector<float>>> raw;   // host copies from fd_set_weight
-    std::vector<void *> dev_allocs;          // weight arena pieces
+    void *weight_arena = nullptr;            // the one device allocation behind the committed weights (DevWeights or fdg::Net)
     DevWeights w;
     Workspace ws;
     bool lvc_dx_gather = true;               // option lvc_dx = gather | copy: the frames path's dx kernel reads kernel_conv's frames (fd_kernels_train.hip)

@@ -300,6 +300,69 @@ def test_everything_out_of_fp16_range_falls_back_on_device(gc, oracle64):
     assert gc.maxdiff(y, y_ref) < 3e-6 * float(np.abs(y_ref).max())
 
 
+def _with_folded_weight(sd, name, index, value):
+    """A copy of `sd` whose folded weight of conv `name` holds `value` at `index` = (out, in, tap); the rest of that output row keeps
+    its folded values (weight_v = the folded row, weight_g = its norm).  A plain weight (ConvTranspose) is set directly."""
+    sd = {k: v.copy() for k, v in sd.items()}
+    if name + ".weight" in sd:
+        sd[name + ".weight"][index] = value
+        return sd
+    v, g = sd[name + ".weight_v"].astype(np.float64), sd[name + ".weight_g"].astype(np.float64)
+    o = index[0]
+    row = v[o] * (g[o, 0, 0] / np.sqrt((v[o] ** 2).sum()))
+    row[index[1:]] = value
+    row = row.astype(np.float32)
+    sd[name + ".weight_v"][o] = row
+    sd[name + ".weight_g"][o] = np.float32(np.sqrt((row.astype(np.float64) ** 2).sum()))
+    return sd
+
+
+@pytest.mark.parametrize("family,name,index,value", [pytest.param(*case, id=case[0]) for case in [
+    ("dblock", "downsample.1.conv.2", (5, 7, 1), 7.0e4),
+    ("convt", "lvc_blocks.1.upsample", (3, 9, 11), 7.0e4),
+    ("kp_input", "lvc_blocks.0.kernel_predictor.input_conv.0", (17, 60, 4), 7.0e4),
+    ("kp_residual", "lvc_blocks.2.kernel_predictor.residual_conv.8", (63, 2, 0), -7.0e4),
+    ("lvc_hop8", "lvc_blocks.0.convs.3", (20, 30, 2), 7.0e4),
+    ("lvc_hop64", "lvc_blocks.1.convs.1", (20, 30, 2), -7.0e4),
+    ("kernel_conv", "lvc_blocks.2.kernel_predictor.kernel_conv", (12345, 33, 1), 7.0e4),
+    # each tap fits fp16, the Winograd column (g0 + g1 + g2) / 2 = 45000 does not: the direct fp16x2 GEMM runs
+    ("kernel_conv_winograd", "lvc_blocks.0.kernel_predictor.kernel_conv", (777, 10, slice(0, 3)), 3.0e4),
+]])
+def test_weight_out_of_fp16_range_keeps_its_family_off_the_fp16_pipe(gc, oracle64, family, name, index, value):
+    """A weight the 2-piece fp16 split cannot hold (>= 65520 rounds to infinity in fp16) clears its family's *_ok flag at commit, so
+    that family's kernels run on the fp32 pipe: were the flag wrong, an infinite piece would reach a kernel and nothing would stay
+    finite.  Taps and eps against the float64 oracle on the same weights, relative to their own scale -- or, where a huge
+    pre-activation saturates a gate, within 10x of the float32 oracle's own error on these weights (the fp32 floor)."""
+    import synth
+    sd = _with_folded_weight(synth.synth_state_dict(1234), name, index, value)
+    m = gc.fastdiff_amd.FastDiff()
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()}, strict=True)
+    m = m.cuda().eval()
+    B, T = 1, 7
+    mel, audio = synth.synth_mel(8, B, T), synth.synth_audio(8, B, T)
+    steps = np.array([300.0], np.float32)
+    ref = {}
+    for precision in ("f64", "f32"):
+        o = type(oracle64)(precision)
+        o.set_weights(sd)
+        y_o, ref[precision] = o.forward(audio, mel, steps, taps=True)
+        ref[precision]["y"] = y_o
+    m.set_option("taps", "1")
+    m.set_option("graph", "0")
+    m.set_option("profile", "1")
+    y = gc.run_forward(m, audio, mel, steps)
+    taps = gc.read_taps(m, B, T)
+    if family == "kernel_conv_winograd":
+        launched = m.profile()
+        assert "kp_gemm_f16x2" in launched and "h_wino" not in launched, sorted(launched)
+    assert np.isfinite(y).all()
+    taps["y"] = y
+    for k in ("a1", "a2", "a3", "x0", "x1", "x2", "y"):
+        r64 = ref["f64"][k]
+        bar = max(FWD_TOL, 3e-6 * float(np.abs(r64).max()), 10 * gc.maxdiff(ref["f32"][k], r64))
+        assert gc.maxdiff(taps[k], r64) < bar, (k, gc.maxdiff(taps[k], r64), bar)
+
+
 def test_sampler_hands_over_to_fp32_at_64_frames(gc, sched):
     """The hand-over inside the sampler at a length with tile edges (64 frames, a ragged batch of two): with the first conv scaled by
     3e4 (x grows by about that factor per reverse step: four steps stay finite in float32) every DBlock / ConvTranspose / LVC launch
