@@ -204,9 +204,8 @@ static void release_handle(fd_context *h)
     free_workspace(h);
     if (h->weight_arena) hipFree(h->weight_arena);
     if (h->scratch) hipFree(h->scratch);
-    if (h->lvc_scratch) hipFree(h->lvc_scratch);
-    if (h->kconv_scratch) hipFree(h->kconv_scratch);
-    if (h->cconv_scratch) hipFree(h->cconv_scratch);
+    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch})
+        if (s->p) hipFree(s->p);
     for (auto &sl : h->stage) {
         if (sl.host) hipHostFree(sl.host);
         if (sl.done) hipEventDestroy(sl.done);

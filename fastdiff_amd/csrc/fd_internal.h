@@ -196,6 +196,7 @@ struct Workspace {
 };
 
 struct ProfEntry { std::string name; hipEvent_t e0, e1; };
+struct Scratch { float *p = nullptr; size_t bytes = 0; };      // a device buffer of the handle that grows on demand
 
 // Constant tables of the mel front-end (fd_kernels_mel.hip), built in double precision at fd_create.
 struct MelTables {
@@ -339,12 +340,10 @@ struct fd_context {
     int *flags_host = nullptr;               // pinned, 2 x 32 words: the sticky flags of the pending call(s)
     hipEvent_t flags_done = nullptr, flags_done2 = nullptr;
     void *scratch = nullptr;                 // 64 KB device scratch (abs-max words, ...)
-    float *lvc_scratch = nullptr;            // the LVC operator's frame-major kernel copy (fd_lvc_forward / fd_lvc_backward), grown on demand
-    size_t lvc_scratch_bytes = 0;
-    float *kconv_scratch = nullptr;          // the row-slice partial sums of fd_kconv_backward's dh pass, grown on demand
-    size_t kconv_scratch_bytes = 0;
-    float *cconv_scratch = nullptr;          // per-workgroup partial sums of fd_conv32_backward's dW / db, grown on demand
-    size_t cconv_scratch_bytes = 0;
+    // the training operators' buffers, grown on demand (fd_api_train.cpp): three, so a captured graph's pointers change only with its own
+    Scratch lvc_scratch;                     // the LVC operator's frame-major kernel copy (fd_lvc_forward / fd_lvc_backward)
+    Scratch kconv_scratch;                   // the partial sums of fd_kconv_backward* and fd_input_conv_backward*
+    Scratch cconv_scratch;                   // per-workgroup partial sums of fd_conv32 / conv7 / upsample backward's dW / db
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
     std::map<std::string, std::pair<int64_t, double>> prof_acc;

@@ -61,26 +61,23 @@ hipError_t kconv_backward(const Launch &L, const float *h, const float *W, const
 size_t kconv_w_multi_scratch_floats(int n, int B, int M);
 hipError_t kconv_backward_w_multi(const Launch &L, int n, const float *const *h, const float *const *dout, const float *const *y, float post, int B,
                                   int M, int T, float *const *dW, float *const *dbias, float *scratch);
-// n <= 8 independent convolutions of one shape side by side in one launch each (the three KernelPredictors' front ends): forward of small
-// convolutions, one step of their dx chains (kconv_backward's dh part), the input convolution both ways.  Host arrays of device pointers.
+// n <= 8 independent convolutions of one shape side by side in one launch each (the three KernelPredictors' front ends; a single
+// convolution is n = 1): forward of small convolutions, one step of their dx chains (kconv_backward's dh part), the input convolution
+// both ways.  Host arrays of device pointers.
 hipError_t kconv_forward_multi(const Launch &L, int n, const float *const *h, const float *const *W, const float *const *bias, float *const *out, int B,
                                int M, int T, float post);
+// in_slope != 1 (a chain of such pairs): h is the activated output of the pair below and dh comes out multiplied by that activation's
+// mask (h > 0 ? 1 : in_slope), i.e. as the gradient in front of it
 size_t kconv_x_multi_scratch_floats(int n, int B, int M, int T);
 hipError_t kconv_backward_x_multi(const Launch &L, int n, const float *const *h, const float *const *W, const float *const *y, const float *const *dout,
                                   float *const *dh, int B, int M, int T, float post, float in_slope, float *scratch);
+// the predictor's input convolution with its activation: leaky_relu(Conv1d(80 -> 64, k5, pad 2), post) (modules.py:292-295), T <= 128;
+// the backward takes the activated output y; scratch: input_conv_multi_scratch_floats(n, B) floats
 hipError_t input_conv_forward_multi(const Launch &L, int n, const float *const *x, const float *const *w, const float *const *bias, float *const *out,
                                     int B, int T, float post);
 size_t input_conv_multi_scratch_floats(int n, int B);
 hipError_t input_conv_backward_multi(const Launch &L, int n, const float *const *x, const float *const *w, const float *const *y, const float *const *dy,
                                      float *const *dx, float *const *dw, float *const *db, int B, int T, float post, float *scratch);
-// in_slope != 1 (a chain of such pairs): h is the activated output of the pair below and dh comes out multiplied by that activation's
-// mask (h > 0 ? 1 : in_slope), i.e. as the gradient in front of it
-// the predictor's input convolution with its activation: leaky_relu(Conv1d(80 -> 64, k5, pad 2), post) (modules.py:292-295), T <= 128;
-// the backward takes the activated output y; scratch: input_conv_scratch_floats(B) floats
-size_t input_conv_scratch_floats(int B);
-hipError_t input_conv_forward(const Launch &L, const float *x, const float *w, const float *bias, float *out, int B, int T, float post);
-hipError_t input_conv_backward(const Launch &L, const float *x, const float *w, const float *y, const float *dy, float *dx, float *dw, float *db, int B,
-                               int T, float post, float *scratch);
 // one layer's "x (+ skip) -> leaky_relu -> dilated Conv1d(32 -> 32, k3) -> bias -> (leaky_relu)" forward and backward for the training
 // path (fd_kernels_cconv.hip); scratch: cconv_scratch_floats() floats for the per-workgroup partial sums of dW / db
 bool cconv_supported(int dil, int64_t len);
@@ -99,10 +96,7 @@ size_t convt_scratch_floats(const Launch &L, int r, int B, int64_t len_in);
 hipError_t convt_forward(const Launch &L, const float *x, const float *w, const float *bias, float *y, int B, int64_t len_in, int r);
 hipError_t convt_backward(const Launch &L, const float *x, const float *w, const float *dy, float *dx, float *dw, float *db, int B, int64_t len_in,
                           int r, float *scratch);
-// torch._weight_norm(v, g, 0) on a [rows, cols] view and its backward (fd_kernels_cconv.hip)
-hipError_t weight_norm_forward(const Launch &L, const float *v, const float *g, float *w, float *norm, int64_t rows, int cols);
-hipError_t weight_norm_backward(const Launch &L, const float *v, const float *g, const float *norm, const float *dw, float *dv, float *dg,
-                                int64_t rows, int cols);
-// ... for n tensors in ceil(n / 28) launches: items in HOST memory (include/fastdiff_hip.h: fd_wn_item), passed on as kernel arguments
+// torch._weight_norm(v, g, 0) on [rows, cols] views and its backward for n tensors in ceil(n / 28) launches (fd_kernels_cconv.hip): items
+// in HOST memory (include/fastdiff_hip.h: fd_wn_item), passed on as kernel arguments
 hipError_t weight_norm_multi(const Launch &L, const fd_wn_item *items, int n, bool backward);
 }  // namespace fdk

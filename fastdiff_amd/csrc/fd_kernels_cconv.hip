@@ -438,35 +438,6 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-__global__ void __launch_bounds__(256) k_wn_fwd(const float *__restrict__ v, const float *__restrict__ g, float *__restrict__ w,
-                                                float *__restrict__ norm, int64_t rows, int cols)
-{
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= rows) return;
-    const float *vr = v + r * cols;
-    float ss = 0.0f;
-    for (int c = lane; c < cols; c += 64) ss = fmaf(vr[c], vr[c], ss);
-    const float nrm = sqrtf(wave_sum(ss)), sc = g[r] / nrm;
-    for (int c = lane; c < cols; c += 64) w[r * cols + c] = vr[c] * sc;
-    if (lane == 0) norm[r] = nrm;
-}
-
-__global__ void __launch_bounds__(256) k_wn_bwd(const float *__restrict__ v, const float *__restrict__ g, const float *__restrict__ norm,
-                                                const float *__restrict__ dw, float *__restrict__ dv, float *__restrict__ dg, int64_t rows, int cols)
-{
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= rows) return;
-    const float *vr = v + r * cols, *dr = dw + r * cols;
-    float dot = 0.0f;
-    for (int c = lane; c < cols; c += 64) dot = fmaf(dr[c], vr[c], dot);
-    dot = wave_sum(dot);
-    const float nrm = norm[r], gn = g[r] / nrm, k2 = dot / (nrm * nrm);
-    for (int c = lane; c < cols; c += 64) dv[r * cols + c] = gn * (dr[c] - vr[c] * k2);
-    if (lane == 0) dg[r] = dot / nrm;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The block's up-sampler on the training path: `self.upsample(F.leaky_relu(x, 0.2))` with upsample = ConvTranspose1d(32, 32, 2r, stride r,
 // padding r / 2) (modules.py:163-166,205-206), r = 8, 8, 4:
@@ -628,8 +599,8 @@ namespace fdk {
 
 using namespace fdk_cconv;
 
-// ---- the same for MANY parameter tensors in one launch (the module has 53 weight-normed convolutions: 106 launches of a few
-//      microseconds each per training step otherwise).  The records travel as KERNEL ARGUMENTS (<= WN_CHUNK per launch: 2.1 KB of the
+// ---- weight-norm (above) for MANY parameter tensors in one launch (the module has 53 weight-normed convolutions: 106 launches of a
+//      few microseconds each per training step otherwise; a single tensor is one item).  The records travel as KERNEL ARGUMENTS (<= WN_CHUNK per launch: 2.1 KB of the
 //      4 KB a launch may carry), not through a table in device memory: nothing to upload, nothing whose lifetime a captured graph
 //      would depend on.  first_block: the first workgroup of each tensor (4 rows per workgroup); a workgroup finds its tensor by
 //      bisection.
@@ -703,18 +674,6 @@ hipError_t weight_norm_multi(const Launch &L_, const fd_wn_item *items, int n, b
         if (backward) FD_LAUNCH(L_, "weight_norm_multi_bwd", k_wn_multi_bwd, dim3((unsigned)blocks), dim3(256), 0, c);
         else FD_LAUNCH(L_, "weight_norm_multi_fwd", k_wn_multi_fwd, dim3((unsigned)blocks), dim3(256), 0, c);
     }
-    return hipSuccess;
-}
-
-hipError_t weight_norm_forward(const Launch &L_, const float *v, const float *g, float *w, float *norm, int64_t rows, int cols)
-{
-    FD_LAUNCH(L_, "weight_norm_fwd", k_wn_fwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, v, g, w, norm, rows, cols);
-    return hipSuccess;
-}
-hipError_t weight_norm_backward(const Launch &L_, const float *v, const float *g, const float *norm, const float *dw, float *dv, float *dg,
-                                int64_t rows, int cols)
-{
-    FD_LAUNCH(L_, "weight_norm_bwd", k_wn_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, v, g, norm, dw, dv, dg, rows, cols);
     return hipSuccess;
 }
 

@@ -237,12 +237,11 @@ __global__ void __launch_bounds__(256, 2) k_kc_dw(const float *__restrict__ h, c
 
 // pointer tables that travel as kernel arguments (up to KCS_MULTI convolutions of one shape per launch: blockIdx.z / blockIdx.y)
 constexpr int KCS_MULTI = 8;
-// n > 0: the kernel takes its three input pointers and its output pointer from slot blockIdx.z (k_kc_dh_fold: blockIdx.y) instead of
-// its own arguments: the same launch then serves n independent convolutions of one shape -- the three KernelPredictors of the network
-// have identical front ends (input convolution + residual stack) on different weights, each a chain of latency-bound launches of B
-// workgroups; side by side they are the same chain with 3 B.
+// KcMulti: the kernels below take their three input pointers and their output pointer from slot blockIdx.z (k_kc_dh_fold: blockIdx.y),
+// so that one launch serves n independent convolutions of one shape -- the three KernelPredictors of the network have identical front
+// ends (input convolution + residual stack) on different weights, each a chain of latency-bound launches of B workgroups; side by side
+// they are the same chain with 3 B.  A single convolution is a table of one slot.
 struct KcMulti {
-    int n;
     const float *a[KCS_MULTI], *b[KCS_MULTI], *c[KCS_MULTI];
     float *o[KCS_MULTI];
 };
@@ -279,11 +278,11 @@ __global__ void __launch_bounds__(256) k_kc_dw_sum(const KcsSums sums, int M, in
 //      at M = 64).  Here a workgroup is (utterance, 64 rows): wave = (32-row tile, half of the column tiles), B * M / 64 workgroups.
 //      post: slope of a leaky-relu on the output (1 = none): the predictor follows each of these convolutions with LeakyReLU(0.1)
 //      (modules.py:296-314); the backward kernels then take the activated output y and scale dout by (y > 0 ? 1 : post) as they load it.
-__global__ void __launch_bounds__(256, 2) k_kcs_fwd(const float *__restrict__ h, const float *__restrict__ W, const float *__restrict__ bias,
-                                                    float *__restrict__ out, int B, int M, int T, float post, const KcMulti m)
+__global__ void __launch_bounds__(256, 2) k_kcs_fwd(const KcMulti m, int B, int M, int T, float post)
 {
     __shared__ float hs[CI * LD];
-    if (m.n) { h = m.a[blockIdx.z]; W = m.b[blockIdx.z]; bias = m.c[blockIdx.z]; out = m.o[blockIdx.z]; }
+    const float *__restrict__ h = m.a[blockIdx.z], *__restrict__ W = m.b[blockIdx.z], *__restrict__ bias = m.c[blockIdx.z];
+    float *__restrict__ out = m.o[blockIdx.z];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
     const int b = blockIdx.x, p0 = (blockIdx.y * 2 + (wave & 1)) * 32, ch = wave >> 1;      // ch: column tiles 2 ch, 2 ch + 1
     const bool live = p0 < M;
@@ -396,10 +395,9 @@ __global__ void __launch_bounds__(256, 2) k_kcs_dw(const KcsItems items, int B, 
 // FRAMES: a chunk is one 32-row group of a layer's frame order: its rows of W are gathered (768 B each), its piece of dout is 32
 // consecutive floats of every frame of the utterance.
 template <bool FRAMES, bool ACT = false>
-__global__ void __launch_bounds__(256, 2) k_kc_dh(const float *__restrict__ W, const float *__restrict__ dout, float *__restrict__ part,
-                                                  int B, int M, int T, int prows, const float *__restrict__ y, float post, const KcMulti m)
+__global__ void __launch_bounds__(256, 2) k_kc_dh(const KcMulti m, int B, int M, int T, int prows, float post)
 {
-    if (m.n) { W = m.a[blockIdx.z]; dout = m.b[blockIdx.z]; y = m.c[blockIdx.z]; part = m.o[blockIdx.z]; }
+    const float *__restrict__ W = m.a[blockIdx.z], *__restrict__ dout = m.b[blockIdx.z], *__restrict__ y = m.c[blockIdx.z];
     __shared__ __attribute__((aligned(16))) float ws[32 * KK];
     __shared__ float dsm[32 * LDD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
@@ -472,7 +470,7 @@ __global__ void __launch_bounds__(256, 2) k_kc_dh(const float *__restrict__ W, c
         }
     }
     if (wave_live && tcol < T) {
-        float *g = part + ((int64_t)ks * B + b) * KK * T;
+        float *g = m.o[blockIdx.z] + ((int64_t)ks * B + b) * KK * T;      // (read here, not on entry: the kernel is at its SGPR limit)
 #pragma unroll
         for (int rt = 0; rt < 6; ++rt)
 #pragma unroll
@@ -484,10 +482,10 @@ __global__ void __launch_bounds__(256, 2) k_kc_dh(const float *__restrict__ W, c
 //      hin / in_slope (a chain of "Conv1d, LeakyReLU" pairs: the predictor's residual stack): h is itself the activated output of the
 //      pair below, and dh is wanted in front of THAT activation: dh *= (h > 0 ? 1 : in_slope) on the way out, so the pair below runs
 //      its backward on plain kernels (no mask loads in its two latency-bound launches).  hin = null: dh as it is.
-__global__ void __launch_bounds__(256) k_kc_dh_fold(const float *__restrict__ part, float *__restrict__ dh, int B, int T, int nks,
-                                                    const float *__restrict__ hin, float in_slope, const KcMulti m)
+__global__ void __launch_bounds__(256) k_kc_dh_fold(const KcMulti m, int B, int T, int nks, float in_slope)
 {
-    if (m.n) { part = m.a[blockIdx.y]; hin = m.b[blockIdx.y]; dh = m.o[blockIdx.y]; }
+    const float *__restrict__ part = m.a[blockIdx.y], *__restrict__ hin = m.b[blockIdx.y];
+    float *__restrict__ dh = m.o[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= B * CI * T) return;
     const int t = idx % T, c = (idx / T) % CI, b = idx / (T * CI);
@@ -530,11 +528,11 @@ __device__ __forceinline__ void ic_stage_g(float *__restrict__ gs, const float *
     }
 }
 
-__global__ void __launch_bounds__(256) k_ic_fwd(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
-                                                float *__restrict__ out, int T, float post, const KcMulti m)
+__global__ void __launch_bounds__(256) k_ic_fwd(const KcMulti m, int T, float post)
 {
     __shared__ __attribute__((aligned(16))) float xs[IC_CI * IC_LD];
-    if (m.n) { x = m.a[blockIdx.z]; w = m.b[blockIdx.z]; bias = m.c[blockIdx.z]; out = m.o[blockIdx.z]; }
+    const float *__restrict__ x = m.a[blockIdx.z], *__restrict__ w = m.b[blockIdx.z], *__restrict__ bias = m.c[blockIdx.z];
+    float *__restrict__ out = m.o[blockIdx.z];
     const int b = blockIdx.x, tid = threadIdx.x, o = blockIdx.y * 16 + (tid >> 4), t0 = (tid & 15) * 8;
     ic_stage_x(xs, x, b, T, tid);
     __syncthreads();
@@ -565,11 +563,11 @@ __global__ void __launch_bounds__(256) k_ic_fwd(const float *__restrict__ x, con
 }
 
 // dx[b, c, t] = sum_{o, k} w[o, c, k] g[b, o, t + 2 - k]: workgroup = (utterance, 16 input channels)
-__global__ void __launch_bounds__(256) k_ic_bwd_x(const float *__restrict__ w, const float *__restrict__ dy, const float *__restrict__ y,
-                                                  float *__restrict__ dx, int T, float post, const KcMulti m)
+__global__ void __launch_bounds__(256) k_ic_bwd_x(const KcMulti m, int T, float post)
 {
     __shared__ __attribute__((aligned(16))) float gs[IC_CO * IC_LD];
-    if (m.n) { w = m.a[blockIdx.z]; dy = m.b[blockIdx.z]; y = m.c[blockIdx.z]; dx = m.o[blockIdx.z]; }
+    const float *__restrict__ w = m.a[blockIdx.z], *__restrict__ dy = m.b[blockIdx.z], *__restrict__ y = m.c[blockIdx.z];
+    float *__restrict__ dx = m.o[blockIdx.z];
     const int b = blockIdx.x, tid = threadIdx.x, c = blockIdx.y * 16 + (tid >> 4), t0 = (tid & 15) * 8;
     ic_stage_g(gs, dy, y, b, 0, IC_CO, T, post, tid);
     __syncthreads();
@@ -600,12 +598,12 @@ __global__ void __launch_bounds__(256) k_ic_bwd_x(const float *__restrict__ w, c
 
 // this utterance's share of dW[o, c, k] = sum_t g[o, t] x[c, t + k - 2] and of db[o] = sum_t g[o, t]: part [B][64][400], then [B][64]
 // (k_kc_dw_sum adds the utterances in order).  workgroup = (utterance, 16 output channels), thread = (channel o, 5 input channels)
-__global__ void __launch_bounds__(256) k_ic_bwd_w(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ y,
-                                                  float *__restrict__ part, int B, int T, float post, const KcMulti m)
+__global__ void __launch_bounds__(256) k_ic_bwd_w(const KcMulti m, int B, int T, float post)
 {
     __shared__ __attribute__((aligned(16))) float xs[IC_CI * IC_LD];
-    if (m.n) { x = m.a[blockIdx.z]; dy = m.b[blockIdx.z]; y = m.c[blockIdx.z]; part = m.o[blockIdx.z]; }
     __shared__ __attribute__((aligned(16))) float gs[16 * IC_LD];
+    const float *__restrict__ x = m.a[blockIdx.z], *__restrict__ dy = m.b[blockIdx.z], *__restrict__ y = m.c[blockIdx.z];
+    float *__restrict__ part = m.o[blockIdx.z];
     const int b = blockIdx.x, tid = threadIdx.x, ol = tid >> 4, o = blockIdx.y * 16 + ol, c0 = (tid & 15) * 5;
     ic_stage_x(xs, x, b, T, tid);
     ic_stage_g(gs, dy, y, b, blockIdx.y * 16, 16, T, post, tid);
@@ -690,22 +688,11 @@ hipError_t kconv_forward(const Launch &L, const float *h, const float *W, const 
 {
     if (frames && !kconv_frames_supported(M, T)) return hipErrorInvalidValue;
     if (post != 1.0f && !kconv_act_supported(M, T)) return hipErrorInvalidValue;
-    if (M <= KC_SMALL_M) {
-        FD_LAUNCH(L, "kconv_forward_small", k_kcs_fwd, dim3(B, (M + 63) / 64), dim3(256), 0, h, W, bias, out, B, M, T, post, KcMulti{});
-        return hipSuccess;
-    }
+    if (M <= KC_SMALL_M) return kconv_forward_multi(L, 1, &h, &W, &bias, &out, B, M, T, post);
     const int gx = (M + 127) / 128;
     const int ny0 = pick_ranges(gx, B, 16, 2 * L.ctx->num_cus), bchunk = (B + ny0 - 1) / ny0, ny = (B + bchunk - 1) / bchunk;
     if (frames) FD_LAUNCH(L, "kconv_forward", k_kc_fwd<true>, dim3(gx, ny), dim3(256), 0, h, W, bias, out, B, M, T, bchunk);
     else FD_LAUNCH(L, "kconv_forward", k_kc_fwd<false>, dim3(gx, ny), dim3(256), 0, h, W, bias, out, B, M, T, bchunk);
-    return hipSuccess;
-}
-
-size_t input_conv_scratch_floats(int B) { return (size_t)B * IC_CO * (IC_KK + 1); }
-
-hipError_t input_conv_forward(const Launch &L, const float *x, const float *w, const float *bias, float *out, int B, int T, float post)
-{
-    FD_LAUNCH(L, "input_conv_forward", k_ic_fwd, dim3(B, IC_CO / 16), dim3(256), 0, x, w, bias, out, T, post, KcMulti{});
     return hipSuccess;
 }
 
@@ -716,27 +703,32 @@ static KcsSums one_sum(const float *part, float *dW, float *dbias)
     return s;
 }
 
-hipError_t input_conv_backward(const Launch &L, const float *x, const float *w, const float *y, const float *dy, float *dx, float *dw, float *db, int B,
-                               int T, float post, float *scratch)
+// ---- n <= KCS_MULTI independent convolutions of one shape side by side (KcMulti) -------------------------------------------------
+// slot i of a table = (a[i], b[i], c[i], o[i]); a null list b or c leaves those pointers null
+static KcMulti table(int n, const float *const *a, const float *const *b, const float *const *c, float *const *o)
 {
-    if (dx) FD_LAUNCH(L, "input_conv_backward_x", k_ic_bwd_x, dim3(B, IC_CI / 16), dim3(256), 0, w, dy, y, dx, T, post, KcMulti{});
-    if (dw || db) {
-        FD_LAUNCH(L, "input_conv_backward_w", k_ic_bwd_w, dim3(B, IC_CO / 16), dim3(256), 0, x, dy, y, scratch, B, T, post, KcMulti{});
-        FD_LAUNCH(L, "kconv_backward_w_sum", k_kc_dw_sum, dim3((unsigned)(((int64_t)IC_CO * (IC_KK + 1) + 255) / 256)), dim3(256), 0, one_sum(scratch, dw, db),
-                  IC_CO, B, IC_KK);
-    }
-    return hipSuccess;
+    KcMulti m = {};
+    for (int i = 0; i < n; ++i) { m.a[i] = a[i]; m.b[i] = b ? b[i] : nullptr; m.c[i] = c ? c[i] : nullptr; m.o[i] = o[i]; }
+    return m;
 }
 
-// ---- n <= KCS_MULTI independent convolutions of one shape side by side (KcMulti) -------------------------------------------------
 hipError_t kconv_forward_multi(const Launch &L, int n, const float *const *h, const float *const *W, const float *const *bias, float *const *out, int B,
                                int M, int T, float post)
 {
     if (n < 1 || n > KCS_MULTI || !kconv_act_supported(M, T)) return hipErrorInvalidValue;
-    KcMulti m = {};
-    m.n = n;
-    for (int i = 0; i < n; ++i) { m.a[i] = h[i]; m.b[i] = W[i]; m.c[i] = bias[i]; m.o[i] = out[i]; }
-    FD_LAUNCH(L, "kconv_forward_small", k_kcs_fwd, dim3(B, (M + 63) / 64, n), dim3(256), 0, h[0], W[0], bias[0], out[0], B, M, T, post, m);
+    FD_LAUNCH(L, "kconv_forward_small", k_kcs_fwd, dim3(B, (M + 63) / 64, n), dim3(256), 0, table(n, h, W, bias, out), B, M, T, post);
+    return hipSuccess;
+}
+
+// the two dh passes of n convolutions: m = (W, dout, y or null, partial sums), f = (partial sums, h or null, -, dh) per slot; act: some
+// slot has a y
+static hipError_t dh_passes(const Launch &L, int n, const KcMulti &m, const KcMulti &f, int B, int M, int T, int nks, bool frames, bool act,
+                            float post, float in_slope)
+{
+    if (frames) FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<true, false>), dim3(nks, B, n), dim3(256), 0, m, B, M, T, M / nks, post);
+    else if (act) FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, true>), dim3(nks, B, n), dim3(256), 0, m, B, M, T, M / nks, post);
+    else FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, false>), dim3(nks, B, n), dim3(256), 0, m, B, M, T, M / nks, post);
+    FD_LAUNCH(L, "kconv_backward_h_fold", k_kc_dh_fold, dim3((B * CI * T + 255) / 256, n), dim3(256), 0, f, B, T, nks, in_slope);
     return hipSuccess;
 }
 
@@ -748,7 +740,6 @@ hipError_t kconv_backward_x_multi(const Launch &L, int n, const float *const *h,
     if (n < 1 || n > KCS_MULTI || !kconv_act_supported(M, T)) return hipErrorInvalidValue;
     const int nks = dh_slices(M, B, 2 * L.ctx->num_cus);      // as for ONE convolution (kconv_backward): the same partial sums, the same bits
     KcMulti m = {}, f = {};
-    m.n = f.n = n;
     bool any_y = false;
     for (int i = 0; i < n; ++i) {
         float *part = scratch + (size_t)i * nks * B * KK * T;
@@ -756,44 +747,33 @@ hipError_t kconv_backward_x_multi(const Launch &L, int n, const float *const *h,
         f.a[i] = part; f.b[i] = in_slope != 1.0f ? h[i] : nullptr; f.o[i] = dh[i];
         any_y = any_y || m.c[i];
     }
-    if (any_y) FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, true>), dim3(nks, B, n), dim3(256), 0, W[0], dout[0], m.o[0], B, M, T, M / nks, m.c[0], post, m);
-    else FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, false>), dim3(nks, B, n), dim3(256), 0, W[0], dout[0], m.o[0], B, M, T, M / nks, m.c[0], post, m);
-    FD_LAUNCH(L, "kconv_backward_h_fold", k_kc_dh_fold, dim3((B * CI * T + 255) / 256, n), dim3(256), 0, f.a[0], dh[0], B, T, nks, f.b[0], in_slope, f);
-    return hipSuccess;
+    return dh_passes(L, n, m, f, B, M, T, nks, false, any_y, post, in_slope);
 }
 
 hipError_t input_conv_forward_multi(const Launch &L, int n, const float *const *x, const float *const *w, const float *const *bias, float *const *out,
                                     int B, int T, float post)
 {
     if (n < 1 || n > KCS_MULTI) return hipErrorInvalidValue;
-    KcMulti m = {};
-    m.n = n;
-    for (int i = 0; i < n; ++i) { m.a[i] = x[i]; m.b[i] = w[i]; m.c[i] = bias[i]; m.o[i] = out[i]; }
-    FD_LAUNCH(L, "input_conv_forward", k_ic_fwd, dim3(B, IC_CO / 16, n), dim3(256), 0, x[0], w[0], bias[0], out[0], T, post, m);
+    FD_LAUNCH(L, "input_conv_forward", k_ic_fwd, dim3(B, IC_CO / 16, n), dim3(256), 0, table(n, x, w, bias, out), T, post);
     return hipSuccess;
 }
 
-size_t input_conv_multi_scratch_floats(int n, int B) { return (size_t)n * input_conv_scratch_floats(B); }
+static size_t input_conv_part_floats(int B) { return (size_t)B * IC_CO * (IC_KK + 1); }      // one convolution's part [B][64][400] + [B][64]
+size_t input_conv_multi_scratch_floats(int n, int B) { return (size_t)n * input_conv_part_floats(B); }
 hipError_t input_conv_backward_multi(const Launch &L, int n, const float *const *x, const float *const *w, const float *const *y, const float *const *dy,
                                      float *const *dx, float *const *dw, float *const *db, int B, int T, float post, float *scratch)
 {
     if (n < 1 || n > KCS_MULTI) return hipErrorInvalidValue;
-    if (dx) {
-        KcMulti m = {};
-        m.n = n;
-        for (int i = 0; i < n; ++i) { m.a[i] = w[i]; m.b[i] = dy[i]; m.c[i] = y[i]; m.o[i] = dx[i]; }
-        FD_LAUNCH(L, "input_conv_backward_x", k_ic_bwd_x, dim3(B, IC_CI / 16, n), dim3(256), 0, w[0], dy[0], y[0], dx[0], T, post, m);
-    }
+    if (dx) FD_LAUNCH(L, "input_conv_backward_x", k_ic_bwd_x, dim3(B, IC_CI / 16, n), dim3(256), 0, table(n, w, dy, y, dx), T, post);
     if (dw || db) {
         KcMulti m = {};
         KcsSums su = {};
-        m.n = n;
         for (int i = 0; i < n; ++i) {
-            float *part = scratch + (size_t)i * input_conv_scratch_floats(B);
+            float *part = scratch + (size_t)i * input_conv_part_floats(B);
             m.a[i] = x[i]; m.b[i] = dy[i]; m.c[i] = y[i]; m.o[i] = part;
             su.part[i] = part; su.dW[i] = dw ? dw[i] : nullptr; su.dbias[i] = db ? db[i] : nullptr;
         }
-        FD_LAUNCH(L, "input_conv_backward_w", k_ic_bwd_w, dim3(B, IC_CO / 16, n), dim3(256), 0, x[0], dy[0], y[0], m.o[0], B, T, post, m);
+        FD_LAUNCH(L, "input_conv_backward_w", k_ic_bwd_w, dim3(B, IC_CO / 16, n), dim3(256), 0, m, B, T, post);
         FD_LAUNCH(L, "kconv_backward_w_sum", k_kc_dw_sum, dim3((unsigned)(((int64_t)IC_CO * (IC_KK + 1) + 255) / 256), n), dim3(256), 0, su, IC_CO, B, IC_KK);
     }
     return hipSuccess;
@@ -829,14 +809,8 @@ hipError_t kconv_backward(const Launch &L, const float *h, const float *W, const
     if (y && !kconv_act_supported(M, T)) return hipErrorInvalidValue;
     float *part_h = scratch, *part_w = scratch + (size_t)KC_DH_SLICES * B * KK * T;
     if ((dW || dbias) && M <= KC_SMALL_M) {
-        KcsItems it = {};
-        it.h[0] = h; it.dout[0] = dout; it.y[0] = y; it.part[0] = part_w;
-#define FD_KCS_DW(AL_, ACT_) FD_LAUNCH(L, "kconv_backward_w_small", (k_kcs_dw<AL_, ACT_>), dim3(B, (M + 63) / 64), dim3(256), 0, it, B, M, T, post)
-        if (T % 4 == 0) { if (y) FD_KCS_DW(true, true); else FD_KCS_DW(true, false); }
-        else { if (y) FD_KCS_DW(false, true); else FD_KCS_DW(false, false); }
-#undef FD_KCS_DW
-        FD_LAUNCH(L, "kconv_backward_w_sum", k_kc_dw_sum, dim3((unsigned)(((int64_t)M * (KK + 1) + 255) / 256)), dim3(256), 0, one_sum(part_w, dW, dbias),
-                  M, B, KK);
+        const hipError_t e = kconv_backward_w_multi(L, 1, &h, &dout, &y, post, B, M, T, &dW, &dbias, part_w);
+        if (e != hipSuccess) return e;
     } else if (dW || dbias) {
         const int gx = (M + 127) / 128;
         const int ny0 = pick_ranges(gx, B, KC_DW_RANGES, 2 * L.ctx->num_cus), bchunk = (B + ny0 - 1) / ny0, ny = (B + bchunk - 1) / bchunk;
@@ -846,15 +820,11 @@ hipError_t kconv_backward(const Launch &L, const float *h, const float *W, const
         FD_LAUNCH(L, "kconv_backward_w_sum", k_kc_dw_sum, dim3((unsigned)(((int64_t)M * (KK + 1) + 255) / 256)), dim3(256), 0, one_sum(part_w, dW, dbias),
                   M, ny, KK);
     }
-    if (dh) {
-        const int nks = dh_slices(M, B, 2 * L.ctx->num_cus);
-        if (frames) FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<true, false>), dim3(nks, B), dim3(256), 0, W, dout, part_h, B, M, T, M / nks, (const float *)nullptr, 1.0f, KcMulti{});
-        else if (y) FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, true>), dim3(nks, B), dim3(256), 0, W, dout, part_h, B, M, T, M / nks, y, post, KcMulti{});
-        else FD_LAUNCH(L, "kconv_backward_h", (k_kc_dh<false, false>), dim3(nks, B), dim3(256), 0, W, dout, part_h, B, M, T, M / nks, y, post, KcMulti{});
-        FD_LAUNCH(L, "kconv_backward_h_fold", k_kc_dh_fold, dim3((B * CI * T + 255) / 256), dim3(256), 0, (const float *)part_h, dh, B, T, nks,
-                  in_slope != 1.0f ? h : (const float *)nullptr, in_slope, KcMulti{});
-    }
-    return hipSuccess;
+    if (!dh) return hipSuccess;
+    KcMulti m = {}, f = {};
+    m.a[0] = W; m.b[0] = dout; m.c[0] = y; m.o[0] = part_h;
+    f.a[0] = part_h; f.b[0] = in_slope != 1.0f ? h : nullptr; f.o[0] = dh;
+    return dh_passes(L, 1, m, f, B, M, T, dh_slices(M, B, 2 * L.ctx->num_cus), frames, y != nullptr, post, in_slope);
 }
 
 }  // namespace fdk

@@ -45,6 +45,36 @@ def _stream(device):
     return ct.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _ptrs(ts):
+    """A ctypes array of the tensors' device pointers (None -> NULL): the host-side pointer lists of the *_multi entry points."""
+    return (ct.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _arg(a):
+    if isinstance(a, torch.Tensor):
+        return a.data_ptr()
+    if isinstance(a, (list, tuple)):
+        return _ptrs(a)
+    return a      # None (NULL), or a number
+
+
+def _call(dev, fn, label, *args):
+    """lib.<fn>(handle, *args, stream) on the handle and the current stream of `dev`, its status checked under `label`: a tensor goes in
+    as its device pointer, a list of tensors as a _ptrs() array, None as NULL."""
+    lib, h = _handle(dev)
+    return _capi.check(lib, h, getattr(lib, fn)(h, *[_arg(a) for a in args], _stream(dev)), label)
+
+
+def _f32(*ts):
+    """The inputs as contiguous float32 tensors (what the kernels read; None stays None)."""
+    return [None if t is None else t.contiguous().float() for t in ts]
+
+
+def _cast_back(ctx, *grads):
+    """The gradients in the types of the inputs they belong to (ctx.in_dtypes), as autograd requires; None stays None."""
+    return tuple(None if g is None else g.to(t) for g, t in zip(grads, ctx.in_dtypes))
+
+
 def _batch_strided(k):
     """True if k [B, Cin, Cout, ks, T] is contiguous apart from its batch stride (one layer's slice of a [B, layers, ...] tensor)."""
     _, ci, co, ks, T = k.shape
@@ -64,16 +94,14 @@ class _LVC(torch.autograd.Function):
         B, Cin, L = x.shape
         _, _, Cout, ks, T = kernel.shape
         model_shape = (Cin, Cout, ks) == (32, 64, 3) and int(hop_size) in (8, 64, 256)
-        x, bias = x.contiguous().float(), bias.contiguous().float()
+        x, bias = _f32(x, bias)
         # a layer's slice stays where it lies, and its gradient may go into the shared slot, only for the shape whose kernels take a
         # batch stride (fd_lvc_*_strided: the model's own); every other shape runs on a contiguous copy and owns its gradient
         ctx.strided_ok = kernel.dtype == torch.float32 and model_shape and _batch_strided(kernel)
         if not ctx.strided_ok:
             kernel = kernel.contiguous().float()
         out = torch.empty((B, Cout, L), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_lvc_forward_strided(h, x.data_ptr(), kernel.data_ptr(), kernel.stride(0), bias.data_ptr(), B, Cin, Cout, ks, T,
-                                                       int(hop_size), out.data_ptr(), _stream(x.device)), "fd_lvc_forward")
+        _call(x.device, "fd_lvc_forward_strided", "fd_lvc_forward", x, kernel, kernel.stride(0), bias, B, Cin, Cout, ks, T, int(hop_size), out)
         ctx.save_for_backward(x, kernel)
         ctx.hop = int(hop_size)
         return out.to(ctx.in_dtypes[0])
@@ -97,13 +125,9 @@ class _LVC(torch.autograd.Function):
             else:
                 dk = torch.empty(kernel.shape, device=x.device, dtype=torch.float32)
         db = torch.empty((B, Cout, T), device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_lvc_backward_strided(h, x.data_ptr(), kernel.data_ptr(), kernel.stride(0), dout.data_ptr(), B, Cin, Cout, ks, T,
-                                                        ctx.hop, None if dx is None else dx.data_ptr(), None if dk is None else dk.data_ptr(),
-                                                        0 if dk is None else dk.stride(0), None if db is None else db.data_ptr(), _stream(x.device)),
-                    "fd_lvc_backward")
-        tx, tk, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dk is None else dk.to(tk), None if db is None else db.to(tb), None, None)
+        _call(x.device, "fd_lvc_backward_strided", "fd_lvc_backward", x, kernel, kernel.stride(0), dout, B, Cin, Cout, ks, T, ctx.hop, dx, dk,
+              0 if dk is None else dk.stride(0), db)
+        return _cast_back(ctx, dx, dk, db) + (None, None)
 
 
 class _SplitLayers(torch.autograd.Function):
@@ -144,12 +168,11 @@ class _Gate(torch.autograd.Function):
         if not (x.is_cuda and y.is_cuda):
             raise RuntimeError("fastdiff_amd.gated_residual runs only on a HIP device (no CPU fallback)")
         ctx.in_dtypes = (x.dtype, y.dtype)
-        x, y = x.contiguous().float(), y.contiguous().float()
+        x, y = _f32(x, y)
         B, C, L = x.shape
         assert tuple(y.shape) == (B, 2 * C, L), "gate: y must hold the sigmoid half and the tanh half of every channel of x"
         out = torch.empty_like(x)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_gate_forward(h, x.data_ptr(), y.data_ptr(), B, C, L, out.data_ptr(), _stream(x.device)), "fd_gate_forward")
+        _call(x.device, "fd_gate_forward", "fd_gate_forward", x, y, B, C, L, out)
         ctx.save_for_backward(y)
         return out.to(ctx.in_dtypes[0])
 
@@ -161,8 +184,7 @@ class _Gate(torch.autograd.Function):
             g = dout.contiguous().float()
             B, C2, L = y.shape
             dy = torch.empty_like(y)
-            lib, h = _handle(y.device)
-            _capi.check(lib, h, lib.fd_gate_backward(h, y.data_ptr(), g.data_ptr(), B, C2 // 2, L, dy.data_ptr(), _stream(y.device)), "fd_gate_backward")
+            _call(y.device, "fd_gate_backward", "fd_gate_backward", y, g, B, C2 // 2, L, dy)
             dy = dy.to(ctx.in_dtypes[1])
         return (dout if ctx.needs_input_grad[0] else None), dy
 
@@ -181,13 +203,11 @@ class _KConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, post_slope=1.0):
         ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, weight, bias = _f32(x, weight, bias)
         B, _, T = x.shape
         M = weight.shape[0]
         out = torch.empty((B, M, T), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_kconv_forward_act(h, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, M, T, float(post_slope), out.data_ptr(),
-                                                     _stream(x.device)), "fd_kconv_forward")
+        _call(x.device, "fd_kconv_forward_act", "fd_kconv_forward", x, weight, bias, B, M, T, float(post_slope), out)
         ctx.post = float(post_slope)
         if ctx.post != 1.0:
             ctx.save_for_backward(x, weight, out)
@@ -206,12 +226,8 @@ class _KConv(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty_like(weight) if need_w else None
         db = torch.empty((M,), device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_kconv_backward_act(h, x.data_ptr(), weight.data_ptr(), None if y is None else y.data_ptr(), dout.data_ptr(), B, M, T,
-                                                      ctx.post, 1.0, None if dx is None else dx.data_ptr(), None if dw is None else dw.data_ptr(),
-                                                      None if db is None else db.data_ptr(), _stream(x.device)), "fd_kconv_backward")
-        tx, tw, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dw is None else dw.to(tw), None if db is None else db.to(tb), None)
+        _call(x.device, "fd_kconv_backward_act", "fd_kconv_backward", x, weight, y, dout, B, M, T, ctx.post, 1.0, dx, dw, db)
+        return _cast_back(ctx, dx, dw, db) + (None,)
 
 
 class _SkipFan(torch.autograd.Function):
@@ -226,8 +242,7 @@ class _SkipFan(torch.autograd.Function):
         x = x.contiguous()
         B, C, L = x.shape
         picked = torch.empty((B, C, L // int(factor)), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_fan_forward(h, x.data_ptr(), B * C, L, int(factor), picked.data_ptr(), _stream(x.device)), "fd_fan_forward")
+        _call(x.device, "fd_fan_forward", "fd_fan_forward", x, B * C, L, int(factor), picked)
         ctx.factor, ctx.shape = int(factor), (B, C, L)
         return (picked,) + tuple(x.view_as(x) for _ in range(4))
 
@@ -238,12 +253,7 @@ class _SkipFan(torch.autograd.Function):
         if ref is None:
             return None, None
         dx = torch.empty((B, C, L), device=ref.device, dtype=torch.float32)
-        ptr = lambda g: None if g is None else g.data_ptr()      # noqa: E731
-        gs = [None if g is None else g.contiguous().float() for g in gs]
-        gp = None if gp is None else gp.contiguous().float()
-        lib, h = _handle(ref.device)
-        _capi.check(lib, h, lib.fd_fan_backward(h, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gp), B * C, L, ctx.factor, dx.data_ptr(),
-                                                _stream(ref.device)), "fd_fan_backward")
+        _call(ref.device, "fd_fan_backward", "fd_fan_backward", *_f32(*gs, gp), B * C, L, ctx.factor, dx)
         return dx, None
 
 
@@ -264,12 +274,10 @@ class _InputConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, post_slope):
         ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, weight, bias = _f32(x, weight, bias)
         B, _, T = x.shape
         y = torch.empty((B, 64, T), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_input_conv_forward(h, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, T, float(post_slope), y.data_ptr(),
-                                                      _stream(x.device)), "fd_input_conv_forward")
+        _call(x.device, "fd_input_conv_forward", "fd_input_conv_forward", x, weight, bias, B, T, float(post_slope), y)
         ctx.post = float(post_slope)
         ctx.save_for_backward(x, weight, y)
         return y.to(ctx.in_dtypes[0])
@@ -283,12 +291,8 @@ class _InputConv(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty_like(weight) if need_w else None
         db = torch.empty(64, device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_input_conv_backward(h, x.data_ptr(), weight.data_ptr(), y.data_ptr(), dy.data_ptr(), B, T, ctx.post,
-                                                       None if dx is None else dx.data_ptr(), None if dw is None else dw.data_ptr(),
-                                                       None if db is None else db.data_ptr(), _stream(x.device)), "fd_input_conv_backward")
-        tx, tw, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dw is None else dw.to(tw), None if db is None else db.to(tb), None)
+        _call(x.device, "fd_input_conv_backward", "fd_input_conv_backward", x, weight, y, dy, B, T, ctx.post, dx, dw, db)
+        return _cast_back(ctx, dx, dw, db) + (None,)
 
 
 def input_conv_supported(x, weight):
@@ -312,14 +316,12 @@ class _KConvStack(torch.autograd.Function):
         n = len(params) // 2
         ctx.in_dtype = x.dtype
         ctx.slope, ctx.n = float(slope), n
-        hs = [x.contiguous().float()]
-        ws = [params[2 * j].contiguous().float() for j in range(n)]
+        hs = _f32(x)
+        ws = _f32(*params[0::2])
         B, _, T = hs[0].shape
-        lib, h = _handle(x.device)
         for j in range(n):
             out = torch.empty((B, 64, T), device=x.device, dtype=torch.float32)
-            _capi.check(lib, h, lib.fd_kconv_forward_act(h, hs[-1].data_ptr(), ws[j].data_ptr(), params[2 * j + 1].contiguous().float().data_ptr(), B, 64, T,
-                                                         ctx.slope, out.data_ptr(), _stream(x.device)), "fd_kconv_forward")
+            _call(x.device, "fd_kconv_forward_act", "fd_kconv_forward", hs[-1], ws[j], params[2 * j + 1].contiguous().float(), B, 64, T, ctx.slope, out)
             hs.append(out)
         ctx.save_for_backward(*hs, *ws)
         return hs[-1].to(ctx.in_dtype)
@@ -330,8 +332,6 @@ class _KConvStack(torch.autograd.Function):
         hs, ws = ctx.saved_tensors[:n + 1], ctx.saved_tensors[n + 1:]
         B, _, T = hs[0].shape
         g = dout.contiguous().float()
-        lib, h = _handle(g.device)
-        st = _stream(g.device)
         gs = [None] * n
         # the dx chain first: pair j's gradient in front of its activation (the top pair masks dout with its own output, every other
         # pair receives it masked from the pair above) ...
@@ -342,9 +342,8 @@ class _KConvStack(torch.autograd.Function):
                 g = None
                 break
             dx = torch.empty_like(hs[j])
-            _capi.check(lib, h, lib.fd_kconv_backward_act(h, hs[j].data_ptr(), ws[j].data_ptr(), hs[j + 1].data_ptr() if top else None, g.data_ptr(), B, 64, T,
-                                                          ctx.slope if top else 1.0, 1.0 if bottom else ctx.slope, dx.data_ptr(), None, None, st),
-                        "fd_kconv_backward")
+            _call(dout.device, "fd_kconv_backward_act", "fd_kconv_backward", hs[j], ws[j], hs[j + 1] if top else None, g, B, 64, T,
+                  ctx.slope if top else 1.0, 1.0 if bottom else ctx.slope, dx, None, None)
             g = dx
         # ... then the weight and bias gradients of all pairs in two launches
         want = [j for j in range(n) if ctx.needs_input_grad[2 + 2 * j] or ctx.needs_input_grad[3 + 2 * j]]
@@ -353,18 +352,11 @@ class _KConvStack(torch.autograd.Function):
             js = want[c0:c0 + 8]
             dws = [torch.empty_like(ws[j]) if ctx.needs_input_grad[2 + 2 * j] else None for j in js]
             dbs = [torch.empty(64, device=gs[0].device, dtype=torch.float32) if ctx.needs_input_grad[3 + 2 * j] else None for j in js]
-            arr = lambda ts: (ct.c_void_p * len(js))(*[None if t is None else t.data_ptr() for t in ts])      # noqa: E731
-            _capi.check(lib, h, lib.fd_kconv_backward_w_multi(h, len(js), arr([hs[j] for j in js]), arr([gs[j] for j in js]),
-                                                              arr([hs[j + 1] if j == n - 1 else None for j in js]), B, 64, T, ctx.slope,
-                                                              arr(dws), arr(dbs), st), "fd_kconv_backward_w_multi")
+            _call(dout.device, "fd_kconv_backward_w_multi", "fd_kconv_backward_w_multi", len(js), [hs[j] for j in js], [gs[j] for j in js],
+                  [hs[j + 1] if j == n - 1 else None for j in js], B, 64, T, ctx.slope, dws, dbs)
             for j, dw, db in zip(js, dws, dbs):
                 grads[2 * j], grads[2 * j + 1] = dw, db
         return (None if g is None else g.to(ctx.in_dtype), None) + tuple(grads)
-
-
-def _ptrs(ts):
-    """A ctypes array of the tensors' device pointers (None -> NULL): the host-side pointer lists of the *_multi entry points."""
-    return (ct.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
 class _PredictorFronts(torch.autograd.Function):
@@ -377,22 +369,19 @@ class _PredictorFronts(torch.autograd.Function):
     @staticmethod
     def forward(ctx, slope, n, *args):
         P = len(args) // (2 * n + 3)
-        xs = [t.contiguous().float() for t in args[:P]]
-        par = [t.contiguous().float() for t in args[P:]]
+        xs = _f32(*args[:P])
+        par = _f32(*args[P:])
         per = 2 * n + 2
         win, bin_ = [par[p * per] for p in range(P)], [par[p * per + 1] for p in range(P)]
         ws = [[par[p * per + 2 + 2 * j] for p in range(P)] for j in range(n)]
         bs = [[par[p * per + 3 + 2 * j] for p in range(P)] for j in range(n)]
         B, _, T = xs[0].shape
         dev = xs[0].device
-        lib, h = _handle(dev)
-        st = _stream(dev)
         H = [torch.empty((P, B, 64, T), device=dev, dtype=torch.float32) for _ in range(n + 1)]      # H[0] = c, H[j] = output of pair j
-        _capi.check(lib, h, lib.fd_input_conv_forward_multi(h, P, _ptrs(xs), _ptrs(win), _ptrs(bin_), B, T, float(slope), _ptrs(list(H[0].unbind(0))), st),
-                    "fd_input_conv_forward_multi")
+        _call(dev, "fd_input_conv_forward_multi", "fd_input_conv_forward_multi", P, xs, win, bin_, B, T, float(slope), H[0].unbind(0))
         for j in range(n):
-            _capi.check(lib, h, lib.fd_kconv_forward_act_multi(h, P, _ptrs(list(H[j].unbind(0))), _ptrs(ws[j]), _ptrs(bs[j]), B, 64, T, float(slope),
-                                                               _ptrs(list(H[j + 1].unbind(0))), st), "fd_kconv_forward_act_multi")
+            _call(dev, "fd_kconv_forward_act_multi", "fd_kconv_forward_act_multi", P, H[j].unbind(0), ws[j], bs[j], B, 64, T, float(slope),
+                  H[j + 1].unbind(0))
         out = H[0] + H[n]
         ctx.save_for_backward(*xs, *win, *[w for wj in ws for w in wj], *H)
         ctx.slope, ctx.n, ctx.P = float(slope), n, P
@@ -407,8 +396,6 @@ class _PredictorFronts(torch.autograd.Function):
         H = sv[2 * P + n * P:]
         B, _, T = xs[0].shape
         dev = xs[0].device
-        lib, h = _handle(dev)
-        st = _stream(dev)
         zero = None
         g = []
         for t in gout:      # a predictor whose output took no part in the loss: zeros
@@ -423,9 +410,8 @@ class _PredictorFronts(torch.autograd.Function):
             top, bottom = j == n - 1, j == 0
             gs[j] = cur
             DX = torch.empty((P, B, 64, T), device=dev, dtype=torch.float32)
-            _capi.check(lib, h, lib.fd_kconv_backward_x_multi(h, P, _ptrs(list(H[j].unbind(0))), _ptrs(ws[j]), _ptrs(list(H[n].unbind(0))) if top else None,
-                                                              _ptrs(cur), B, 64, T, slope if top else 1.0, 1.0 if bottom else slope,
-                                                              _ptrs(list(DX.unbind(0))), st), "fd_kconv_backward_x_multi")
+            _call(dev, "fd_kconv_backward_x_multi", "fd_kconv_backward_x_multi", P, H[j].unbind(0), ws[j], H[n].unbind(0) if top else None, cur, B, 64, T,
+                  slope if top else 1.0, 1.0 if bottom else slope, DX.unbind(0))
             cur = list(DX.unbind(0))
         # weight and bias gradients of all P * n pairs, eight per call
         flat = [(p, j) for p in range(P) for j in range(n)]
@@ -433,18 +419,16 @@ class _PredictorFronts(torch.autograd.Function):
         dB = {k: torch.empty(64, device=dev, dtype=torch.float32) for k in flat}
         for c0 in range(0, len(flat), 8):
             ks = flat[c0:c0 + 8]
-            _capi.check(lib, h, lib.fd_kconv_backward_w_multi(h, len(ks), _ptrs([H[j][p] for p, j in ks]), _ptrs([gs[j][p] for p, j in ks]),
-                                                              _ptrs([H[n][p] if j == n - 1 else None for p, j in ks]), B, 64, T, slope,
-                                                              _ptrs([dW[k] for k in ks]), _ptrs([dB[k] for k in ks]), st), "fd_kconv_backward_w_multi")
+            _call(dev, "fd_kconv_backward_w_multi", "fd_kconv_backward_w_multi", len(ks), [H[j][p] for p, j in ks], [gs[j][p] for p, j in ks],
+                  [H[n][p] if j == n - 1 else None for p, j in ks], B, 64, T, slope, [dW[k] for k in ks], [dB[k] for k in ks])
         # c has two readers, the stack and the sum: dc = dx of the bottom pair + the output's gradient
         torch._foreach_add_(cur, gtop)
         need_x = any(ctx.needs_input_grad[2:2 + P])
         DXin = torch.empty((P, B, 80, T), device=dev, dtype=torch.float32) if need_x else None
         dwin = [torch.empty_like(w) for w in win]
         dbin = [torch.empty(64, device=dev, dtype=torch.float32) for _ in range(P)]
-        _capi.check(lib, h, lib.fd_input_conv_backward_multi(h, P, _ptrs(xs), _ptrs(win), _ptrs(list(H[0].unbind(0))), _ptrs(cur), B, T, slope,
-                                                             None if DXin is None else _ptrs(list(DXin.unbind(0))), _ptrs(dwin), _ptrs(dbin), st),
-                    "fd_input_conv_backward_multi")
+        _call(dev, "fd_input_conv_backward_multi", "fd_input_conv_backward_multi", P, xs, win, H[0].unbind(0), cur, B, T, slope,
+              None if DXin is None else DXin.unbind(0), dwin, dbin)
         grads = [None, None] + ([None] * P if DXin is None else list(DXin.unbind(0)))
         for p in range(P):
             grads += [dwin[p], dbin[p]]
@@ -473,16 +457,12 @@ class _KConvSide(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *args):
         P = len(args) // 3
-        xs = [t.contiguous().float() for t in args[:P]]
-        ws = [t.contiguous().float() for t in args[P::2]]
-        bs = [t.contiguous().float() for t in args[P + 1::2]]
+        xs, ws, bs = _f32(*args[:P]), _f32(*args[P::2]), _f32(*args[P + 1::2])
         B, _, T = xs[0].shape
         M = ws[0].shape[0]
         dev = xs[0].device
         out = torch.empty((P, B, M, T), device=dev, dtype=torch.float32)
-        lib, h = _handle(dev)
-        _capi.check(lib, h, lib.fd_kconv_forward_act_multi(h, P, _ptrs(xs), _ptrs(ws), _ptrs(bs), B, M, T, 1.0, _ptrs(list(out.unbind(0))), _stream(dev)),
-                    "fd_kconv_forward_act_multi")
+        _call(dev, "fd_kconv_forward_act_multi", "fd_kconv_forward_act_multi", P, xs, ws, bs, B, M, T, 1.0, out.unbind(0))
         ctx.save_for_backward(*xs, *ws)
         ctx.P = P
         return tuple(out.unbind(0))
@@ -501,15 +481,12 @@ class _KConvSide(torch.autograd.Function):
                 zero = torch.zeros((B, M, T), device=dev, dtype=torch.float32) if zero is None else zero
                 t = zero
             g.append(t.contiguous().float())
-        lib, h = _handle(dev)
-        st = _stream(dev)
         DX = torch.empty((P, B, 64, T), device=dev, dtype=torch.float32) if any(ctx.needs_input_grad[:P]) else None
         if DX is not None:
-            _capi.check(lib, h, lib.fd_kconv_backward_x_multi(h, P, None, _ptrs(ws), None, _ptrs(g), B, M, T, 1.0, 1.0, _ptrs(list(DX.unbind(0))), st),
-                        "fd_kconv_backward_x_multi")
+            _call(dev, "fd_kconv_backward_x_multi", "fd_kconv_backward_x_multi", P, None, ws, None, g, B, M, T, 1.0, 1.0, DX.unbind(0))
         dws = [torch.empty_like(w) for w in ws]
         dbs = [torch.empty(M, device=dev, dtype=torch.float32) for _ in range(P)]
-        _capi.check(lib, h, lib.fd_kconv_backward_w_multi(h, P, _ptrs(xs), _ptrs(g), None, B, M, T, 1.0, _ptrs(dws), _ptrs(dbs), st), "fd_kconv_backward_w_multi")
+        _call(dev, "fd_kconv_backward_w_multi", "fd_kconv_backward_w_multi", P, xs, g, None, B, M, T, 1.0, dws, dbs)
         grads = [None] * P if DX is None else list(DX.unbind(0))
         for dw, db in zip(dws, dbs):
             grads += [dw, db]
@@ -541,12 +518,10 @@ class _Conv7(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, which):
         ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, weight, bias = _f32(x, weight, bias)
         B, _, L = x.shape
         y = torch.empty((B, 32 if which == 0 else 1, L), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_conv7_forward(h, int(which), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, L, y.data_ptr(), _stream(x.device)),
-                    "fd_conv7_forward")
+        _call(x.device, "fd_conv7_forward", "fd_conv7_forward", int(which), x, weight, bias, B, L, y)
         ctx.save_for_backward(x, weight)
         ctx.which = int(which)
         return y.to(ctx.in_dtypes[0])
@@ -560,12 +535,8 @@ class _Conv7(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty_like(weight) if need_w else None
         db = torch.empty(32 if ctx.which == 0 else 1, device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_conv7_backward(h, ctx.which, x.data_ptr(), weight.data_ptr(), dy.data_ptr(), B, L, None if dx is None else dx.data_ptr(),
-                                                  None if dw is None else dw.data_ptr(), None if db is None else db.data_ptr(), _stream(x.device)),
-                    "fd_conv7_backward")
-        tx, tw, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dw is None else dw.to(tw), None if db is None else db.to(tb), None)
+        _call(x.device, "fd_conv7_backward", "fd_conv7_backward", ctx.which, x, weight, dy, B, L, dx, dw, db)
+        return _cast_back(ctx, dx, dw, db) + (None,)
 
 
 def conv7_supported(x, weight):
@@ -586,12 +557,10 @@ class _Upsample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, ratio):
         ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, weight, bias = _f32(x, weight, bias)
         B, _, Lin = x.shape
         y = torch.empty((B, 32, Lin * int(ratio)), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_upsample_forward(h, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, Lin, int(ratio), y.data_ptr(), _stream(x.device)),
-                    "fd_upsample_forward")
+        _call(x.device, "fd_upsample_forward", "fd_upsample_forward", x, weight, bias, B, Lin, int(ratio), y)
         ctx.save_for_backward(x, weight)
         ctx.ratio = int(ratio)
         return y.to(ctx.in_dtypes[0])
@@ -605,12 +574,8 @@ class _Upsample(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty_like(weight) if need_w else None
         db = torch.empty(32, device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_upsample_backward(h, x.data_ptr(), weight.data_ptr(), dy.data_ptr(), B, Lin, ctx.ratio, None if dx is None else dx.data_ptr(),
-                                                     None if dw is None else dw.data_ptr(), None if db is None else db.data_ptr(), _stream(x.device)),
-                    "fd_upsample_backward")
-        tx, tw, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dw is None else dw.to(tw), None if db is None else db.to(tb), None)
+        _call(x.device, "fd_upsample_backward", "fd_upsample_backward", x, weight, dy, B, Lin, ctx.ratio, dx, dw, db)
+        return _cast_back(ctx, dx, dw, db) + (None,)
 
 
 def upsample_supported(x, m):
@@ -636,9 +601,7 @@ class _WeightNorm(torch.autograd.Function):
         rows, cols = v.shape[0], v.numel() // v.shape[0]
         w = torch.empty_like(v)
         norm = torch.empty(rows, device=v.device, dtype=torch.float32)
-        lib, h = _handle(v.device)
-        _capi.check(lib, h, lib.fd_weight_norm_forward(h, v.data_ptr(), g.data_ptr(), rows, cols, w.data_ptr(), norm.data_ptr(), _stream(v.device)),
-                    "fd_weight_norm_forward")
+        _call(v.device, "fd_weight_norm_forward", "fd_weight_norm_forward", v, g, rows, cols, w, norm)
         ctx.save_for_backward(v, g, norm)
         return w
 
@@ -648,9 +611,7 @@ class _WeightNorm(torch.autograd.Function):
         dw = dw.contiguous().float()
         rows, cols = v.shape[0], v.numel() // v.shape[0]
         dv, dg = torch.empty_like(v), torch.empty_like(g)
-        lib, h = _handle(v.device)
-        _capi.check(lib, h, lib.fd_weight_norm_backward(h, v.data_ptr(), g.data_ptr(), norm.data_ptr(), dw.data_ptr(), rows, cols, dv.data_ptr(),
-                                                        dg.data_ptr(), _stream(v.device)), "fd_weight_norm_backward")
+        _call(v.device, "fd_weight_norm_backward", "fd_weight_norm_backward", v, g, norm, dw, rows, cols, dv, dg)
         return dv, dg
 
 
@@ -686,8 +647,7 @@ class _WeightNormAll(torch.autograd.Function):
         tab[:, 3] = N.data_ptr() + 4 * on
         tab[:, 7] = rows
         tab[:, 8] = numel // rows
-        lib, h = _handle(dev)
-        _capi.check(lib, h, lib.fd_weight_norm_multi_forward(h, tab.ctypes.data, n, _stream(dev)), "fd_weight_norm_multi_forward")
+        _call(dev, "fd_weight_norm_multi_forward", "fd_weight_norm_multi_forward", tab.ctypes.data, n)
         ctx.save_for_backward(N, *vs, *gs)
         ctx.tab, ctx.ow, ctx.on, ctx.sizes = tab, ow, on, (numel.tolist(), rows.tolist())
         return tuple(w.view(v.shape) for w, v in zip(W.split(ctx.sizes[0]), vs))
@@ -704,8 +664,7 @@ class _WeightNormAll(torch.autograd.Function):
         tab[:, 4] = [0 if d is None else d.data_ptr() for d in dws]
         tab[:, 5] = DV.data_ptr() + 4 * ctx.ow
         tab[:, 6] = DG.data_ptr() + 4 * ctx.on
-        lib, h = _handle(dev)
-        _capi.check(lib, h, lib.fd_weight_norm_multi_backward(h, tab.ctypes.data, n, _stream(dev)), "fd_weight_norm_multi_backward")
+        _call(dev, "fd_weight_norm_multi_backward", "fd_weight_norm_multi_backward", tab.ctypes.data, n)
         out = []
         for dv, dg, v, g in zip(DV.split(ctx.sizes[0]), DG.split(ctx.sizes[1]), vs, gs):
             out.append(dv.view(v.shape))
@@ -730,17 +689,12 @@ class _Conv32(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, skip, weight, bias, dilation, pre_slope, post_slope):
         ctx.in_dtypes = (x.dtype, None if skip is None else skip.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, skip, weight, bias = _f32(x, skip, weight, bias)
         B, _, L = x.shape
         y = torch.empty_like(x)
-        xs = x
-        if skip is not None:
-            skip = skip.contiguous().float()
-            xs = torch.empty_like(x)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_conv32_forward(h, x.data_ptr(), None if skip is None else skip.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, L,
-                                                  int(dilation), float(pre_slope), float(post_slope), None if skip is None else xs.data_ptr(),
-                                                  y.data_ptr(), _stream(x.device)), "fd_conv32_forward")
+        xs = x if skip is None else torch.empty_like(x)
+        _call(x.device, "fd_conv32_forward", "fd_conv32_forward", x, skip, weight, bias, B, L, int(dilation), float(pre_slope), float(post_slope),
+              None if skip is None else xs, y)
         ctx.save_for_backward(xs, y, weight)
         ctx.cfg = (int(dilation), float(pre_slope), float(post_slope), skip is not None)
         ctx.set_materialize_grads(False)                 # an output nobody differentiates arrives as None, not as a tensor of zeros
@@ -756,25 +710,19 @@ class _Conv32(torch.autograd.Function):
         B, _, L = xs.shape
         need_x = ctx.needs_input_grad[0] or (has_skip and ctx.needs_input_grad[1])
         need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        lib, h = _handle(xs.device)
         if gy is None:                                   # y had no reader: only the pass-through of xs is left
             d = gxs
             dw = torch.zeros_like(weight) if need_w else None
             db = torch.zeros(32, device=xs.device) if need_b else None
         else:
-            gy = gy.contiguous().float()
-            gxs = None if gxs is None else gxs.contiguous().float()
+            gy, gxs = _f32(gy, gxs)
             d = torch.empty_like(xs) if need_x else None
             dw = torch.empty_like(weight) if need_w else None
             db = torch.empty(32, device=xs.device, dtype=torch.float32) if need_b else None
-            _capi.check(lib, h, lib.fd_conv32_backward(h, xs.data_ptr(), y.data_ptr(), weight.data_ptr(), gy.data_ptr(),
-                                                       None if gxs is None else gxs.data_ptr(), B, L, dilation, pre, post,
-                                                       None if d is None else d.data_ptr(), None if dw is None else dw.data_ptr(),
-                                                       None if db is None else db.data_ptr(), _stream(xs.device)), "fd_conv32_backward")
-        tx, ts, tw, tb = ctx.in_dtypes
-        dx = d.to(tx) if (d is not None and ctx.needs_input_grad[0]) else None
-        ds = d.to(ts) if (d is not None and has_skip and ctx.needs_input_grad[1]) else None
-        return dx, ds, (None if dw is None else dw.to(tw)), (None if db is None else db.to(tb)), None, None, None
+            _call(xs.device, "fd_conv32_backward", "fd_conv32_backward", xs, y, weight, gy, gxs, B, L, dilation, pre, post, d, dw, db)
+        dx = d if ctx.needs_input_grad[0] else None
+        ds = d if has_skip and ctx.needs_input_grad[1] else None
+        return _cast_back(ctx, dx, ds, dw, db) + (None, None, None)
 
 
 def conv32_supported(x, weight, dilation):
@@ -890,13 +838,11 @@ class _KConvFrames(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
-        x, weight, bias = x.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        x, weight, bias = _f32(x, weight, bias)
         B, _, T = x.shape
         M = weight.shape[0]
         out = torch.empty((B, M // FRAME, T, FRAME), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_kconv_forward_frames(h, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), B, M, T, out.data_ptr(), _stream(x.device)),
-                    "fd_kconv_forward_frames")
+        _call(x.device, "fd_kconv_forward_frames", "fd_kconv_forward_frames", x, weight, bias, B, M, T, out)
         ctx.save_for_backward(x, weight)
         return out
 
@@ -910,12 +856,8 @@ class _KConvFrames(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty_like(weight) if need_w else None
         db = torch.empty((M,), device=x.device, dtype=torch.float32) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_kconv_backward_frames(h, x.data_ptr(), weight.data_ptr(), dout.data_ptr(), B, M, T,
-                                                         None if dx is None else dx.data_ptr(), None if dw is None else dw.data_ptr(),
-                                                         None if db is None else db.data_ptr(), _stream(x.device)), "fd_kconv_backward_frames")
-        tx, tw, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), None if dw is None else dw.to(tw), None if db is None else db.to(tb))
+        _call(x.device, "fd_kconv_backward_frames", "fd_kconv_backward_frames", x, weight, dout, B, M, T, dx, dw, db)
+        return _cast_back(ctx, dx, dw, db)
 
 
 def kernel_conv_frames_supported(x, weight):
@@ -958,9 +900,7 @@ class _LVCFrames(torch.autograd.Function):
             bias = bias.contiguous().float()
         bbs = bias.stride(0) if B > 1 else 64 * T
         out = torch.empty((B, 64, L), device=x.device, dtype=torch.float32)
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_lvc_forward_frames(h, x.data_ptr(), kernel.data_ptr(), ctx.kbs, bias.data_ptr(), bbs, B, T, int(hop_size),
-                                                      out.data_ptr(), _stream(x.device)), "fd_lvc_forward_frames")
+        _call(x.device, "fd_lvc_forward_frames", "fd_lvc_forward_frames", x, kernel, ctx.kbs, bias, bbs, B, T, int(hop_size), out)
         ctx.save_for_backward(x, kernel)
         ctx.hop = int(hop_size)
         return out.to(ctx.in_dtypes[0])
@@ -984,15 +924,10 @@ class _LVCFrames(torch.autograd.Function):
 
         dk = slot_or_new(ctx.grad_slot, (B, T, FRAME)) if need_k else None
         db = slot_or_new(ctx.bias_slot if ctx.in_dtypes[1] == torch.float32 else None, (B, 64, T)) if need_b else None
-        lib, h = _handle(x.device)
-        _capi.check(lib, h, lib.fd_lvc_backward_frames(h, x.data_ptr(), kernel.data_ptr(), ctx.kbs, dout.data_ptr(), B, T, ctx.hop,
-                                                       None if dx is None else dx.data_ptr(), None if dk is None else dk.data_ptr(),
-                                                       0 if dk is None else (dk.stride(0) if B > 1 else T * FRAME),
-                                                       None if db is None else db.data_ptr(),
-                                                       0 if db is None else (db.stride(0) if B > 1 else 64 * T), _stream(x.device)),
-                    "fd_lvc_backward_frames")
-        tx, tb = ctx.in_dtypes
-        return (None if dx is None else dx.to(tx), dk, None if db is None else db.to(tb), None, None, None)
+        _call(x.device, "fd_lvc_backward_frames", "fd_lvc_backward_frames", x, kernel, ctx.kbs, dout, B, T, ctx.hop, dx, dk,
+              0 if dk is None else (dk.stride(0) if B > 1 else T * FRAME), db, 0 if db is None else (db.stride(0) if B > 1 else 64 * T))
+        dx, db = _cast_back(ctx, dx, db)
+        return dx, dk, db, None, None, None
 
 
 def location_variable_convolution_frames(x, kernel_frames, bias, hop_size, grad_slot=None, bias_slot=None):
