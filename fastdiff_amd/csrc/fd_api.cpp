@@ -160,7 +160,7 @@ int fd_create(const fd_config *cfg, int device, fd_handle *out)
 static void free_workspace(fd_context *c)
 {
     Workspace &w = c->ws;
-    void *ptrs[] = {w.noise, w.embed_h2, w.a[0], w.a[1], w.a[2], w.a[3], w.kp_h0, w.kp_hA, w.kp_hB, w.kpack, w.h_f16, w.range_flag, w.lens_dev, w.uid_dev, w.xsave, w.xA, w.xB,
+    void *ptrs[] = {w.noise, w.embed_h2, w.a[0], w.a[1], w.a[2], w.a[3], w.kp_h0, w.kp_hA, w.kp_hB, w.kpack, w.h_f16, w.range_flag, w.lens_dev, w.uid_dev, w.off_dev, w.xsave, w.xA, w.xB,
                     w.xtap[0], w.xtap[1], w.xtap[2], w.mel, w.mel_rep, w.x, w.eps_acc, w.steps, w.params};
     for (void *p : ptrs)
         if (p) hipFree(p);
@@ -204,7 +204,7 @@ static void release_handle(fd_context *h)
     free_workspace(h);
     if (h->weight_arena) hipFree(h->weight_arena);
     if (h->scratch) hipFree(h->scratch);
-    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch})
+    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch})
         if (s->p) hipFree(s->p);
     for (auto &sl : h->stage) {
         if (sl.host) hipHostFree(sl.host);
@@ -268,6 +268,7 @@ static hipError_t allocate_workspace(fd_context *h, int64_t capB, int64_t frames
 #undef WS
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w.params), sizeof(StepParams));
     if (e == hipSuccess) e = hipMemset(w.params, 0, sizeof(StepParams));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w.off_dev), sizeof(long long) * (size_t)std::max<int64_t>(capB, 64));
     *total_out = total;
     return e;
 }
@@ -453,10 +454,10 @@ int fd_stage_commit(fd_handle h, fd_context::StageSlot *sl, hipStream_t stream)
 
 // One stream at a time per handle: a call on another stream than the previous one first settles what is pending there and then makes
 // the new stream wait for the tail of the handle's last call (workspace, embedding rows and step parameters are reused from call to
-// call).  The tail is an EVENT recorded at the end of every call (mark_tail), not the old stream itself: the caller may have
+// call).  The tail is an EVENT recorded at the end of every call (fd_mark_tail), not the old stream itself: the caller may have
 // destroyed that stream since (its work done), and the runtime does not survive a call on a destroyed stream handle
 // (tools/stream_switch_probe.py: a hipEventRecord there takes the process down); an event outlives its stream.
-static int mark_tail(fd_handle h, hipStream_t s)
+int fd_mark_tail(fd_handle h, hipStream_t s)
 {
     if (!h->ev_switch) FD_HIP(h, hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
     FD_HIP(h, hipEventRecord(h->ev_switch, s));
@@ -464,7 +465,7 @@ static int mark_tail(fd_handle h, hipStream_t s)
     return FD_OK;
 }
 
-static int follow_stream(fd_handle h, hipStream_t s)
+int fd_follow_stream(fd_handle h, hipStream_t s)
 {
     if (h->have_last_stream && h->last_stream != s) {
         const int rc = fd_settle(h);      // (a pending check may redo its call on the old stream: that stream must live until the call is settled)
@@ -502,11 +503,11 @@ static int set_lens(fd_handle h, const int *lens, int B, int T, hipStream_t stre
 int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps, int B, int T, const int *lens,
                float *eps_out, void *stream)
 {
-    if (h) h->noise_ids.clear();                 // stream ids are for the next fd_sample only: a forward in between drops them
+    if (h) { h->noise_ids.clear(); h->noise_offs.clear(); }   // stream ids are for the next fd_sample only: a forward in between drops them
     int rc = check_common(h, B, T, "fd_forward");
     if (rc != FD_OK) return rc;
     if ((rc = fd_settle(h)) != FD_OK) return rc;
-    if ((rc = follow_stream(h, (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = fd_follow_stream(h, (hipStream_t)stream)) != FD_OK) return rc;
     h->embed_valid = false;                      // fd_forward writes its own rows into the same table
     if (!x || !mel || !steps || !eps_out) FD_FAIL(h, FD_ERR_INVALID, "fd_forward: null pointer");
     if (x == eps_out) FD_FAIL(h, FD_ERR_INVALID, "fd_forward: eps_out must not alias x");
@@ -515,7 +516,7 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
             if (lens[b] < 1 || lens[b] > T) FD_FAIL(h, FD_ERR_INVALID, "fd_forward: lens[%d] = %d outside [1, T=%d]", b, lens[b], T);
         if ((rc = fdg::forward(h, x, mel, steps, B, T, lens, eps_out, (hipStream_t)stream)) != FD_OK) return rc;
         h->last_B = B; h->last_T = T;
-        return mark_tail(h, (hipStream_t)stream);
+        return fd_mark_tail(h, (hipStream_t)stream);
     }
     if ((rc = ensure_workspace(h, B, T)) != FD_OK) return rc;
     StepMode mode = h->mode;      // a single forward: its fallbacks inline, its own predictor (the per-call fields' defaults)
@@ -532,7 +533,7 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
     if (e == hipSuccess) e = fdk::run_step(L, io, B, T);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_forward: kernel launch failed: %s", hipGetErrorString(e));
     h->last_B = B; h->last_T = T;
-    return mark_tail(h, (hipStream_t)stream);
+    return fd_mark_tail(h, (hipStream_t)stream);
 }
 
 static int resolve_pending(fd_handle h, unsigned *mask);
@@ -739,17 +740,24 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
     {
         fd_context::StageSlot *sl = nullptr;
         const size_t off_lens = sizeof(StepParams), off_ids = off_lens + ((sizeof(int) * B * np + 7) & ~(size_t)7);
-        if ((rc = fd_stage_acquire(h, off_ids + sizeof(unsigned long long) * B, &sl)) != FD_OK) return rc;
+        const size_t off_offs = off_ids + sizeof(unsigned long long) * B;
+        const bool has_offs = !ids.empty() && !a.offs.empty();
+        if ((rc = fd_stage_acquire(h, off_offs + sizeof(long long) * B, &sl)) != FD_OK) return rc;
         if ((rc = set_lens(h, lens_eff, B, T, stream, "fd_sample", reinterpret_cast<int *>(sl->host + off_lens), &mode.ragged, np)) != FD_OK)
             return rc;
         if (!ids.empty()) {
             memcpy(sl->host + off_ids, ids.data(), sizeof(unsigned long long) * B);
             FD_HIP(h, hipMemcpyAsync(ws.uid_dev, sl->host + off_ids, sizeof(unsigned long long) * B, hipMemcpyHostToDevice, stream));
         }
+        if (has_offs) {
+            memcpy(sl->host + off_offs, a.offs.data(), sizeof(long long) * B);
+            FD_HIP(h, hipMemcpyAsync(ws.off_dev, sl->host + off_offs, sizeof(long long) * B, hipMemcpyHostToDevice, stream));
+        }
         StepParams *p = reinterpret_cast<StepParams *>(sl->host);
         memcpy(p->table, a.table.data(), sizeof(fd_step) * N);
         p->z = a.z; p->seq = a.seq_out; p->seed = a.seed; p->n_steps = N; p->ddim = a.ddim ? 1 : 0; p->step_idx = 0; p->l4 = T * (fd::HOPT / 4);
         p->uids = ids.empty() ? nullptr : ws.uid_dev;
+        p->offs4 = has_offs ? ws.off_dev : nullptr;
         p->l4_io = T_io * (fd::HOPT / 4); p->n4_io = (long long)B * p->l4_io;
         // only the used prefix of the table plus the trailer needs to travel
         const size_t head = sizeof(fd_step) * N;
@@ -763,7 +771,8 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
     hipError_t e = fdk::copy_rows(L, ws.mel, T, a.mel, T_io, T_io, B * fd::COND);
     if (e == hipSuccess && a.x_T) e = fdk::copy_rows(L, ws.x, Lp, a.x_T, L_io, (int)L_io, B);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: input copy failed: %s", hipGetErrorString(e));
-    if (!a.x_T && (e = fdk::init_noise(L, ws.x, B, T * (fd::HOPT / 4), T_io * (fd::HOPT / 4), a.seed, ids.empty() ? nullptr : ws.uid_dev)) != hipSuccess)
+    if (!a.x_T && (e = fdk::init_noise(L, ws.x, B, T * (fd::HOPT / 4), T_io * (fd::HOPT / 4), a.seed, ids.empty() ? nullptr : ws.uid_dev,
+                                       ids.empty() || a.offs.empty() ? nullptr : ws.off_dev)) != hipSuccess)
         FD_FAIL(h, FD_ERR_HIP, "fd_sample: init_noise failed: %s", hipGetErrorString(e));
     if (a.seq_out && (e = fdk::copy_rows(L, a.seq_out, L_io, ws.x, Lp, (int)L_io, B)) != hipSuccess)
         FD_FAIL(h, FD_ERR_HIP, "fd_sample: sequence copy failed: %s", hipGetErrorString(e));
@@ -844,17 +853,18 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
         if ((rc = copy_out()) != FD_OK) return rc;
     }
     h->last_B = B; h->last_T = T;
-    return mark_tail(h, stream);      // (also behind a redo: resolve_call comes through here)
+    return fd_mark_tail(h, stream);      // (also behind a redo: resolve_call comes through here)
 }
 
 int fd_sample(fd_handle h, const float *mel, int B, int T, const int *lens, const fd_step *table, int N, int ddim,
               const float *x_T, const float *z, uint64_t seed, float *out, float *seq_out, void *stream_)
 {
     std::vector<unsigned long long> ids;
-    if (h) ids.swap(h->noise_ids);               // one-shot: fd_set_noise_streams applies to this call only, also when it fails below
+    std::vector<long long> offs;
+    if (h) { ids.swap(h->noise_ids); offs.swap(h->noise_offs); }   // one-shot: fd_set_noise_streams applies to this call only, also when it fails below
     int rc = check_common(h, B, T, "fd_sample");
     if (rc != FD_OK) return rc;
-    if ((rc = follow_stream(h, (hipStream_t)stream_)) != FD_OK) return rc;
+    if ((rc = fd_follow_stream(h, (hipStream_t)stream_)) != FD_OK) return rc;
     if (h->gen) {      // a configuration other than base.yaml's: exact-fp32 kernels, nothing provisional, no graph
         if (!mel || !table || !out) FD_FAIL(h, FD_ERR_INVALID, "fd_sample: null pointer");
         if (N <= 0 || N > 1024) FD_FAIL(h, FD_ERR_INVALID, "fd_sample: N=%d outside 1..1024", N);
@@ -864,7 +874,7 @@ int fd_sample(fd_handle h, const float *mel, int B, int T, const int *lens, cons
         if ((rc = fdg::sample(h, mel, B, T, lens, table, N, ddim, x_T, z, seed, ids, out, seq_out, (hipStream_t)stream_)) != FD_OK) return rc;
         ++h->ticket_counter;
         h->last_B = B; h->last_T = T;
-        return mark_tail(h, (hipStream_t)stream_);
+        return fd_mark_tail(h, (hipStream_t)stream_);
     }
     // A lazily checked previous call (fallback = host, <= 8 steps) is looked at AFTER this call has enqueued its own work -- unless
     // this call cannot be lazy itself, or the workspace must grow first (that waits for the device anyway).
@@ -894,6 +904,7 @@ int fd_sample(fd_handle h, const float *mel, int B, int T, const int *lens, cons
         finish_prev();
         FD_FAIL(h, FD_ERR_INVALID, "fd_sample: fd_set_noise_streams gave %d stream ids but B=%d", (int)ids.size(), B);
     }
+    if (!offs.empty() && offs.size() != ids.size()) { finish_prev(); FD_FAIL(h, FD_ERR_INVALID, "fd_sample: noise offsets without their stream ids"); }
     for (int b = 0; lens && b < B; ++b)
         if (lens[b] < 1 || lens[b] > T) {
             finish_prev();
@@ -907,6 +918,7 @@ int fd_sample(fd_handle h, const float *mel, int B, int T, const int *lens, cons
     a.table.assign(table, table + N);
     a.x_T = x_T; a.z = z; a.seed = seed; a.out = out; a.seq_out = seq_out; a.stream = (hipStream_t)stream_;
     a.ids.swap(ids);
+    a.offs.swap(offs);
     const long long ticket = ++h->ticket_counter;
     h->n_pieces = h->n_pieces_redone = h->n_pieces_fp32 = 0;
     h->call_fp32_mask = 0;
@@ -957,6 +969,7 @@ int fd_set_noise_streams(fd_handle h, const uint64_t *stream_ids, int B)
 {
     if (!h || B < 0 || (B > 0 && !stream_ids)) return FD_ERR_INVALID;
     h->noise_ids.assign(stream_ids, stream_ids + B);
+    h->noise_offs.clear();
     return FD_OK;
 }
 

@@ -260,6 +260,7 @@ int64_t fd_get_counter(fd_handle h, const char *name)
     if (k == "graph_evictions") return h->n_graph_evictions;
     if (k == "graphs_resident") return (int64_t)h->graphs.size();
     if (k == "graphs_retired") return (int64_t)h->retired.size();
+    if (k == "workspace_bytes") return (int64_t)(h->ws.bytes + h->span_scratch.bytes);
     FD_FAIL(h, FD_ERR_INVALID, "fd_get_counter: unknown counter '%s'", name);
 }
 

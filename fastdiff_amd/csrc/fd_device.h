@@ -20,7 +20,8 @@ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint
 
 // Four N(0,1) draws: key = seed, counter = (float4 index, utterance stream id, step stream).  Without per-utterance ids (uid = 0,
 // idx4 = the flat index into the batch) a draw depends on where the utterance sits in the batch; with them (fd_set_noise_streams:
-// idx4 = the index inside the utterance, uid = its id) an utterance gets the same noise however it is batched or sharded.
+// idx4 = the index inside the utterance, uid = its id) an utterance gets the same noise however it is batched or sharded -- and a
+// window of it (fd_sample_span: idx4 += the window's start, StepParams::offs4) the noise of the whole utterance at the same samples.
 __device__ inline float4 philox_normal4(unsigned long long seed, uint32_t stream, uint64_t idx4, unsigned long long uid = 0ull)
 {
     uint32_t r[4];
@@ -59,7 +60,7 @@ __device__ inline float4 sampler_update4(float4 x, float4 e, const StepParams *p
         if (st.add_noise) {
             float4 z;
             if (p->z) z = reinterpret_cast<const float4 *>(p->z)[(int64_t)k * n4_total + i4];
-            else if (p->uids) z = philox_normal4(p->seed, (uint32_t)k, (uint64_t)off4, p->uids[b]);
+            else if (p->uids) z = philox_normal4(p->seed, (uint32_t)k, (uint64_t)(off4 + (p->offs4 ? p->offs4[b] : 0)), p->uids[b]);
             else z = philox_normal4(p->seed, (uint32_t)k, (uint64_t)i4);
             o.x += st.sigma * z.x; o.y += st.sigma * z.y; o.z += st.sigma * z.z; o.w += st.sigma * z.w;
         }

@@ -32,5 +32,8 @@ void drop_graph(fd_context *c);
 // the copies that read it
 int fd_stage_acquire(fd_handle h, size_t bytes, fd_context::StageSlot **out);
 int fd_stage_commit(fd_handle h, fd_context::StageSlot *sl, hipStream_t stream);
+// one stream at a time per handle: a call on another stream first waits for the tail of the handle's last call; ... and the tail's mark
+int fd_follow_stream(fd_handle h, hipStream_t s);
+int fd_mark_tail(fd_handle h, hipStream_t s);
 }
 void fd_prof_drain(fd_context *c);

@@ -116,6 +116,8 @@ struct StepParams {
     int l4_io;             // samples / 4 of one utterance as the CALLER lays it out (x_T, z, seq_out, out): == l4 unless the call's frames were
                            // rounded up to a bucket (fd_context::t_bucket); also what a Philox draw's position is counted in
     long long n4_io;       // B * l4_io: one step's stride in z / seq_out
+    const long long *offs4;   // [B] or null (with uids only): where utterance b's samples start inside a longer utterance, in float4s --
+                              // a draw is keyed on off4 + offs4[b], so a window of fd_sample_span draws what the whole utterance does
 };
 
 enum Stage { ST_EMBED = 0, ST_FIRST, ST_DBLOCK, ST_KP_FRONT, ST_KP_GEMM, ST_CONVT, ST_LVC, ST_FINAL, ST_COUNT };
@@ -176,6 +178,7 @@ struct Workspace {
     float *h_f16 = nullptr;     // fp16 piece image of the predictor hidden state: [3][B][64*ceil(T/64)+2 rows][2 pieces][64] x 2 B
     int *lens_dev = nullptr;    // [B] valid frames per utterance of the current call (ragged batches)
     unsigned long long *uid_dev = nullptr;   // [B] noise stream ids of the current call (fd_set_noise_streams)
+    long long *off_dev = nullptr;            // [B] Philox position offsets (float4s) of the current call (StepParams::offs4)
     float *xsave = nullptr;     // [B][L] x at the start of the call / of the current graph chunk (option fallback = host: what a redo starts from)
     int *range_flag = nullptr;  // (128 words) [0] predictor GEMM, [1 + 4*block + layer] LVC layers, [13 + d] DBlocks,
                                 // [16 + n] ConvTranspose of block n, [19] predictor front: an operand did not fit fp16; 32 words, zeroed every step;
@@ -246,6 +249,8 @@ struct fd_context {
     bool use_graph = true;
     int profile = 0;                          // option "profile": 0 off | 1 the kernels' own begin / end timestamps | 2 ("events") stream events around each launch
     std::vector<unsigned long long> noise_ids; // fd_set_noise_streams: consumed by the next fd_sample
+    std::vector<long long> noise_offs;       // fd_sample_span (fd_api_span.cpp): each window's first sample / 4 in the utterance, consumed
+                                             // with noise_ids (empty: every draw counted from the utterance's start)
     bool host_fallback = true;                // option "fallback" = "host" (default; settled inside fd_sample unless defer_check) | "graph"
     std::map<std::string, std::pair<std::vector<int64_t>, std::vector<float>>> raw;   // host copies from fd_set_weight
     void *weight_arena = nullptr;            // the one device allocation behind the committed weights (DevWeights or fdg::Net)
@@ -313,6 +318,7 @@ struct fd_context {
         float *out = nullptr, *seq_out = nullptr;
         hipStream_t stream = nullptr;
         std::vector<unsigned long long> ids;
+        std::vector<long long> offs;                        // (with ids) StepParams::offs4
     };
     // option fallback = host: the fd_sample call whose range flags have not been looked at yet (fd_sample_check / fd_sample_settle).
     //   lazy (schedules of up to 8 steps = one graph launch): the NEXT fd_sample enqueues its own work first and looks at this call's
@@ -344,6 +350,7 @@ struct fd_context {
     Scratch lvc_scratch;                     // the LVC operator's frame-major kernel copy (fd_lvc_forward / fd_lvc_backward)
     Scratch kconv_scratch;                   // the partial sums of fd_kconv_backward* and fd_input_conv_backward*
     Scratch cconv_scratch;                   // per-workgroup partial sums of fd_conv32 / conv7 / upsample backward's dW / db
+    Scratch span_scratch;                    // fd_sample_span's window batch: mel, injected x_T / z and x_0 of up to 8 windows
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
     std::map<std::string, std::pair<int64_t, double>> prof_acc;
@@ -396,7 +403,23 @@ hipError_t kp_gemm(const Launch &L, int B, int T);
 hipError_t advance_step(const Launch &L);
 hipError_t clear_range_flags(const Launch &L, int set_step = 0);     // before the first step of a call / of a redo: step counter := set_step
 hipError_t mel_frontend(const Launch &L, const float *wav, int B, int64_t n_samples, float *mel, int T);
-hipError_t init_noise(const Launch &L, float *x, int B, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids);
+hipError_t init_noise(const Launch &L, float *x, int B, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids,
+                      const long long *offs4 = nullptr);
+// fd_sample_span's window batch (fd_kernels_span.hip): window b covers utterance frames [start[b], start[b] + len[b])
+constexpr int SPAN_MAX_WINDOWS = 8;
+struct SpanWindows {
+    int n;                               // windows in the batch
+    long long start[SPAN_MAX_WINDOWS];   // first frame of the window in the utterance
+    int len[SPAN_MAX_WINDOWS];           // frames of the window (<= the batch's padded length Wp)
+    long long c0[SPAN_MAX_WINDOWS];      // first frame of the window's centre (what the scatter copies) ...
+    int clen[SPAN_MAX_WINDOWS];          // ... and its frames
+};
+// caller's mel [80][mel_frames] (frames from mel_first), x_T [mel_frames*256], z [nz][mel_frames*256] -> [n][80][Wp], [n][Wp*256],
+// [nz][n][Wp*256]; zero where a window reaches outside the caller's frames or behind its own length.  One launch.
+hipError_t span_gather(const Launch &L, const SpanWindows &w, int Wp, const float *mel, const float *x_T, const float *z, int nz,
+                       long long mel_first, long long mel_frames, float *mel_w, float *x_w, float *z_w);
+// x_0 of the windows [n][Wp*256] -> the caller's out over frames [t0, ...): each window's centre.  One launch.
+hipError_t span_scatter(const Launch &L, const SpanWindows &w, int Wp, const float *x_w, long long t0, float *out);
 hipError_t copy_rows(const Launch &L, float *dst, int64_t dpitch, const float *src, int64_t spitch, int width, int rows, int reps = 1,
                      int64_t rep_stride = 0);
 hipError_t peak_normalize_int16(const Launch &L, const float *wav, int B, int64_t len, int16_t *pcm, const long long *valid_dev);

@@ -341,18 +341,20 @@ hipError_t embed(const Launch &L, const StepIO &io, int B, int n_steps)
 
 // x [B][l4 float4s]; the draw of utterance b at offset off is keyed as in a batch of l4_io float4s per utterance (the caller's own
 // length: the library's buffer may be padded to a frame bucket, fd_api.cpp) -- offsets behind l4_io are padding and stay untouched
-__global__ void k_init_noise(float *x, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids)
+// (offs4, with uids: utterance b is a window that starts offs4[b] float4s into a longer utterance -- fd_sample_span)
+__global__ void k_init_noise(float *x, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids, const long long *offs4)
 {
     const int off = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (off >= l4_io) return;
     const int64_t i = (int64_t)b * l4 + off;
-    if (uids) reinterpret_cast<float4 *>(x)[i] = philox_normal4(seed, 0xFFFFFFFFu, (uint64_t)off, uids[b]);
+    if (uids) reinterpret_cast<float4 *>(x)[i] = philox_normal4(seed, 0xFFFFFFFFu, (uint64_t)(off + (offs4 ? offs4[b] : 0)), uids[b]);
     else reinterpret_cast<float4 *>(x)[i] = philox_normal4(seed, 0xFFFFFFFFu, (uint64_t)((int64_t)b * l4_io + off));
 }
 
-hipError_t init_noise(const Launch &L, float *x, int B, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids)
+hipError_t init_noise(const Launch &L, float *x, int B, int l4, int l4_io, unsigned long long seed, const unsigned long long *uids,
+                      const long long *offs4)
 {
-    FD_LAUNCH(L, "init_noise", k_init_noise, dim3((unsigned)((l4_io + 255) / 256), B), dim3(256), 0, x, l4, l4_io, seed, uids);
+    FD_LAUNCH(L, "init_noise", k_init_noise, dim3((unsigned)((l4_io + 255) / 256), B), dim3(256), 0, x, l4, l4_io, seed, uids, offs4);
     return hipSuccess;
 }
 

@@ -13,7 +13,8 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
     The reference CLI runs B = 1 (config `max_sentences`); batching is this path's extension: the batch goes down with its
     `lens`, so every item is computed exactly as if it ran alone (and the padding costs nothing), then cropped to its length.
 
-Entry points: load_mel_inputs, load_wav_inputs (device mel front-end), collate_test_batch, distributed_sampler_indices, synthesize, test_step
+Entry points: load_mel_inputs, load_wav_inputs (device mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
+synthesize_long (--long_form: one utterance at a time, windowed, any length), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt]`).
 """
@@ -367,6 +368,26 @@ def test_step(model, sample: dict, hparams: dict, diffusion_hyperparams=None, ge
     return out
 
 
+def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
+                    diffusion_hyperparams=None, window_frames=None) -> Dict[str, np.ndarray]:
+    """item_name -> int16 PCM, one utterance at a time through FastDiff.sample_long (windowed: any length, device memory of one window
+    batch).  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same, byte for
+    byte; peak normalisation runs on the whole utterance afterwards (FastDiff.py:110)."""
+    rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
+    hop = model.hop_length
+    out: Dict[str, np.ndarray] = {}
+    for i, it in enumerate(items):
+        c = torch.as_tensor(it["mel"])
+        t = c.shape[0] - 1 if drop_last_frame else c.shape[0]
+        if t < 1:
+            continue
+        mel = c[:t].to(device="cuda", dtype=torch.float32).transpose(0, 1).unsqueeze(0).contiguous()
+        with torch.no_grad():
+            wav = model.sample_long(mel, rows, ddim=False, seed=seed, stream_id=int(it.get("uid", i)), window_frames=window_frames)
+        out[it["item_name"]] = model.peak_normalize_int16(wav)[0, : t * hop].cpu().numpy()
+    return out
+
+
 def save_wavs(pcm: Dict[str, np.ndarray], out_dir: str, sample_rate: int = 22050) -> List[str]:
     from scipy.io import wavfile
     os.makedirs(out_dir, exist_ok=True)
@@ -391,6 +412,8 @@ def main(argv=None):
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (state_dict under ['state_dict']['model'])")
     ap.add_argument("--max_batch", type=int, default=16, help="utterances per padded micro-batch (16: 6 % faster than 8 on a 64-utterance job)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--long_form", action="store_true",
+                    help="vocode each utterance on its own, window by window (FastDiff.sample_long): any length, the same PCM")
     args = ap.parse_args(argv)
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -406,7 +429,11 @@ def main(argv=None):
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
     items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
-    paths = save_wavs(synthesize(model, mine, args.N, args.max_batch, args.seed), args.out_dir)
+    if args.long_form:
+        pcm = synthesize_long(model, mine, args.N, args.seed)
+    else:
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed)
+    paths = save_wavs(pcm, args.out_dir)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 
 

@@ -236,6 +236,31 @@ class FastDiff(nn.Module):
             return [seq[k] for k in range(N + 1)]
         return out
 
+    def sample_long(self, condition, table, ddim=False, x_T=None, noise=None, seed=0, stream_id=0, window_frames=None):
+        """x_0 [1,1,T*256] of ONE utterance of any length T, window by window (fd_sample_span; fastdiff_amd/longform.py): bit-identical
+        to sample(condition, table, ddim, seed=seed, stream_ids=[stream_id]) -- also past the length sample() refuses -- while the
+        device memory stays that of one window batch.  condition [1,80,T] or [80,T]; x_T [1,1,T*256] / noise [N,1,1,T*256] (N <= 8)
+        as in sample(); window_frames: centre frames per window (a multiple of 32), None = the library's default."""
+        from . import longform
+        c = condition if condition.dim() == 3 else condition.unsqueeze(0)
+        assert c.shape[0] == 1, "sample_long vocodes one utterance: condition [1,80,T]"
+        T = c.shape[-1]
+        return longform.sample_span(self, c, 0, T, 0, T, table, ddim=ddim, x_T=x_T, noise=noise, seed=seed, stream_id=stream_id,
+                                    window_frames=window_frames)
+
+    def stream(self, table, ddim=False, seed=0, stream_id=0, chunk_frames=32):
+        """A SampleStream (fastdiff_amd/longform.py) of one utterance whose mel arrives in chunks: push([80,t]) returns the samples
+        that became final, close() the rest; together they equal sample_long on the whole mel.  Lookahead: H = halo_frames(N)
+        frames of mel beyond a frame before it is final (64 frames = 0.74 s at N = 4)."""
+        from . import longform
+        return longform.SampleStream(self, table, ddim=ddim, seed=seed, stream_id=stream_id, chunk_frames=chunk_frames)
+
+    @staticmethod
+    def halo_frames(N):
+        """Frames of halo per side that sample_long / stream add for an N-step schedule (fd_sample_halo_frames)."""
+        from . import longform
+        return longform.halo_frames(N)
+
     def check(self):
         """Settle the last sample() under fallback = "host" (no-op otherwise).  Returns True if it had to be redone."""
         if self._handle is None:

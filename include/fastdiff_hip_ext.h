@@ -45,6 +45,39 @@ FD_API int fd_mel_spectrogram(fd_handle h, const float *wav, int B, int64_t n_sa
 FD_API int fd_set_mel_filterbank(fd_handle h, const float *fb, int n_mels, int n_bins);
 FD_API int fd_get_mel_filterbank(fd_handle h, float *fb_out, int n_mels, int n_bins);
 
+/* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
+ * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
+ * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
+ * with `lens`, its own zero padding at its edges, its Philox noise keyed on the utterance's absolute sample index -- and keeps from each
+ * window the centre that lies at least H frames from its inner edges.  The result is bit-identical to the whole-utterance fd_sample
+ * (with fd_set_noise_streams({stream_id})) on every kept frame unless a window batch handed a stage over to the fp32 kernels (range
+ * check, see fd_sample), and the device memory it needs depends on the window, not on the utterance: an utterance past fd_sample's
+ * B*T*256*32 < 2^31 limit, or one whose mel is still arriving, can be vocoded.  A streaming caller needs H frames of mel beyond the last
+ * frame it asks for: that is the lookahead (64 frames = 0.74 s at N = 4, 22.05 kHz). */
+
+/* Frames of halo per side that fd_sample_span adds for an N-step schedule of the base.yaml architecture (pure host code, no handle, like
+ * fd_kernel_index).  < 0 for N outside 1..1024. */
+FD_API int fd_sample_halo_frames(int N);
+
+/* x_0 on frames [t0, t1) of ONE utterance, computed window by window, with each window as a batch item of fd_sample.
+ *   mel        [1,80,mel_frames] device: utterance frames [mel_first, mel_first + mel_frames)
+ *   utt_frames the utterance's length, or -1 while it is not yet known (streaming); then t1 + H <= mel_first + mel_frames
+ *   mel must cover [max(0, t0 - H), min(utt_frames, t1 + H)), with H = fd_sample_halo_frames(N)
+ *   t0 a multiple of 32; t1 a multiple of 32 unless t1 == utt_frames
+ *   x_T, z     NULL = Philox (seed, stream_id) keyed on the absolute sample index, i.e. the noise that fd_set_noise_streams({stream_id})
+ *              + fd_sample on the whole utterance draws.  Or caller tensors over the same frames as mel ([1,1,mel_frames*256],
+ *              [N,1,1,mel_frames*256]; z only for N <= 8)
+ *   window_frames  centre frames per window (a multiple of 32), 0 = the library's default: windows of max(1024, 4H) frames rounded up
+ *              to 32, centre = that - 2H (N = 4: 1024-frame windows, 896-frame centres)
+ *   out        [1,1,(t1-t0)*256] device
+ * Window starts are multiples of 32 frames (the kernels' frame phase); up to 8 windows and about 16k frames run as one fd_sample batch.
+ * Settles its own range check before it returns, whatever defer_check says.  Settles a pending deferred fd_sample first.
+ * FD_ERR_UNSUPPORTED: a handle of another architecture than base.yaml's, or any stage on the naive kernels (they ignore lens).
+ * FD_ERR_INVALID: t0 / t1 misaligned or t1 > utt_frames, mel not covering the halo, injected z with N > 8. */
+FD_API int fd_sample_span(fd_handle h, const float *mel, int64_t mel_first, int64_t mel_frames, int64_t utt_frames, int64_t t0, int64_t t1,
+                          const fd_step *table, int N, int ddim, const float *x_T, const float *z, uint64_t seed, uint64_t stream_id,
+                          int window_frames, float *out, void *stream);
+
 /* Test / introspection hooks (not on the reference's API surface) -------------------------------------- */
 
 /* Copies an intermediate of the LAST fd_forward to host (synchronises).  Names: "noise" [B,3,80], "a0".."a3",
@@ -80,6 +113,8 @@ FD_API int fd_reset_profile(fd_handle h);
  *   "graph_captures" / "graph_hits" / "graph_evictions"   fd_sample's graph look-ups since fd_create that captured a new graph / found
  *                    one / pushed the least recently used one out; "graphs_resident" / "graphs_retired" = kept now / evicted but not
  *                    yet destroyed (their last replay has not completed).
+ *   "workspace_bytes" device memory of the handle's sampler workspace and of fd_sample_span's window batch (bounded by the window, not
+ *                    by the utterance).
  * Returns the value (>= 0) or a negative status. */
 FD_API int64_t fd_get_counter(fd_handle h, const char *name);
 
