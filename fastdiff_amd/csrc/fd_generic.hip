@@ -9,6 +9,7 @@
 // with T innermost: modules.py:333-338).  Correctness path, not a fast one: nothing here is tiled, staged through LDS or captured in a
 // graph; fd_read_tap / profiling are not offered.  `lens` means what it means on the tuned path: utterance b is computed as if it were alone
 // and lens[b] frames long (every kernel treats positions behind it as the zero padding at the end of a signal and skips the outputs there).
+// The naive set (fd_kernels_naive.hip) runs base.yaml's architecture on the same kernels and stage helpers (declared in fd_kernels.h).
 #include "fd_internal.h"
 #include "fd_device.h"
 #include "fd_kernels.h"
@@ -17,16 +18,14 @@
 
 namespace fdg {
 
-struct Conv { const float *w = nullptr, *b = nullptr; };
-
 struct Net {
     fd_config cfg;
     int nb = 0, hop_total = 1;
     int hop[8] = {0};                  // cond_hop_length of block n (cumulative product of the ratios, FastDiff_model.py:47-49)
-    Conv first, final_, fc_t1, fc_t2;
+    ConvW first, final_, fc_t1, fc_t2;
     struct Blk {
-        Conv fc_t, up, kp_in, kp_res[6], kc, bc, res, dconv[3];
-        std::vector<Conv> convs;
+        ConvW fc_t, up, kp_in, kp_res[6], kc, bc, res, dconv[3];
+        std::vector<ConvW> convs;
     } blk[8];
     const float *embed_table = nullptr;
     // workspace, grown to the largest call seen
@@ -61,33 +60,30 @@ __global__ void g_linear(const float *in, const float *W, const float *bias, flo
     out[i] = swish ? acc / (1.0f + expf(-acc)) : acc;
 }
 
-// y[b][o][t] = post(bias[o] + sum_{i,k} W[o][i][k] * pre(xin(b, i, t + k*dil - pad))) (+ add[b][o][t*add_stride])
-//   xin(b, i, p) = 0 outside [0, Lout), else x[b][i][p * in_stride] (+ in_add[b][i]: the predictor's `c + noise`, modules.py:203 --
-//   added to the signal, not to its zero padding).  in_stride > 1 reads every in_stride-th sample: nearest-neighbour down-sampling by
-//   an integer factor (DiffusionDBlock, modules.py:127-134) without materialising the picked sequence.
-//   lens (nullable) / spf: utterance b is lens[b] * spf output samples long; behind that nothing is computed and nothing is read.
-__global__ void g_conv1d(const float *x, const float *W, const float *bias, float *y, int B, int Cin, int Cout, int K, int dil, int pad,
-                         int64_t Lx, int64_t Lout, int in_stride, const float *in_add, float pre, float post, const float *add,
-                         int64_t Ladd, int add_stride, const int *lens, int spf)
+// what it computes: ConvArgs (fd_kernels.h)
+__global__ void g_conv1d(ConvArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * Cout * Lout) return;
-    const int64_t t = i % Lout;
-    const int o = (int)((i / Lout) % Cout), b = (int)(i / (Lout * Cout));
-    const int64_t Lb = lens ? (int64_t)lens[b] * spf : Lout;
+    if (i >= (int64_t)a.B * a.Cout * a.Lout) return;
+    const int64_t t = i % a.Lout;
+    const int o = (int)((i / a.Lout) % a.Cout), b = (int)(i / (a.Lout * a.Cout));
+    const int64_t Lb = a.lens ? (int64_t)a.lens[b] * a.spf : a.Lout;
     if (t >= Lb) return;
-    float acc = bias[o];
-    for (int c = 0; c < Cin; ++c) {
-        const float *xr = x + ((int64_t)b * Cin + c) * Lx;
-        const float ia = in_add ? in_add[(int64_t)b * Cin + c] : 0.0f;
-        for (int k = 0; k < K; ++k) {
-            const int64_t p = t + (int64_t)k * dil - pad;
-            if (p >= 0 && p < Lb) acc += W[((int64_t)o * Cin + c) * K + k] * act(xr[p * in_stride] + ia, pre);
+    const int pad = a.dil * ((a.K - 1) / 2);
+    const float *ia = a.in_add ? a.in_add + (a.step ? (int64_t)*a.step * a.in_add_step : 0) + (int64_t)b * a.in_add_b : nullptr;
+    float acc = a.bias[o];
+    for (int c = 0; c < a.Cin; ++c) {
+        const float *xr = a.x + ((int64_t)b * a.Cin + c) * a.Lx;
+        const float av = ia ? ia[c] : 0.0f;
+        for (int k = 0; k < a.K; ++k) {
+            const int64_t p = t + (int64_t)k * a.dil - pad;
+            if (p >= 0 && p < Lb) acc += a.w[((int64_t)o * a.Cin + c) * a.K + k] * act(xr[p * a.in_stride] + av, a.pre);
         }
     }
-    acc = act(acc, post);
-    if (add) acc += add[((int64_t)b * Cout + o) * Ladd + t * add_stride];
-    y[i] = acc;
+    acc = act(acc, a.post);
+    if (a.res) acc += a.res[i];
+    if (a.rec) a.y[((int64_t)b * a.Lout + t) * a.rec + a.rec_off + (a.perm ? a.perm[o] : o)] = acc;
+    else a.y[i] = acc;
 }
 
 // ConvTranspose1d(C, C, 2r, stride r, padding r/2 + r%2, output_padding r%2) of leaky_relu(x, 0.2) (modules.py:163-166,205-206):
@@ -121,35 +117,44 @@ __global__ void g_add_inplace(float *x, const float *s, int64_t n, int64_t Lrow,
     x[i] += s[i];
 }
 
-// location_variable_convolution + gate + residual (modules.py:213-217,220-253; its dilation argument is always 1):
+// location_variable_convolution + gate + residual (modules.py:213-217,220-253; its dilation argument is always 1), in place on x:
 //   z[o][l*hop + s] = bias[layer][o][l] + sum_{c,k} ypad[c][l*hop + s + k - (ks-1)/2] * K[layer][c][o][k][l]     (zero pad of the WHOLE signal)
-//   out = x + sigmoid(z[ch]) * tanh(z[ch + C]);   thread = (b, ch, t).  kernels [B][layers*C*2C*ks][T], biases [B][layers*2C][T].
-__global__ void g_lvc_gate(const float *y, const float *kernels, const float *biases, const float *x, float *out, int B, int C, int ks,
-                           int layers, int layer, int hop, int T, const int *lens)
+//   x += sigmoid(z[ch]) * tanh(z[ch + C]);   thread = (b, ch, t).  PACKED: the layout of LvcArgs::packed.
+template <bool PACKED>
+__global__ void g_lvc_gate(LvcArgs a)
 {
-    const int64_t Ln = (int64_t)T * hop;
+    const int C = a.C, ks = a.ks, T = a.T;
+    const int64_t Ln = (int64_t)T * a.hop;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * C * Ln) return;
+    if (i >= (int64_t)a.B * C * Ln) return;
     const int64_t t = i % Ln;
     const int ch = (int)((i / Ln) % C), b = (int)(i / (Ln * C));
-    const int64_t Lnb = lens ? (int64_t)lens[b] * hop : Ln;
+    const int64_t Lnb = a.lens ? (int64_t)a.lens[b] * a.hop : Ln;
     if (t >= Lnb) return;
-    const int l = (int)(t / hop), half = (ks - 1) / 2;
-    const float *kb = kernels + (int64_t)b * layers * C * 2 * C * ks * T;
-    const float *bb = biases + (int64_t)b * layers * 2 * C * T;
-    float zs = bb[((int64_t)layer * 2 * C + ch) * T + l], zt = bb[((int64_t)layer * 2 * C + ch + C) * T + l];
+    const int l = (int)(t / a.hop), half = (ks - 1) / 2;
+    // this utterance's (packed: this frame's) coefficients, and where (c, o, k) / the bias of o lie in them
+    const float *kb = PACKED ? a.kernels + ((int64_t)b * T + l) * fd::KREC : a.kernels + (int64_t)b * a.layers * C * 2 * C * ks * T;
+    const float *bb = PACKED ? kb : a.biases + (int64_t)b * a.layers * 2 * C * T;
+    auto kidx = [&](int c, int o, int k) -> int64_t {
+        if constexpr (PACKED) return fd::kernel_index(a.layer, c, o, k);
+        else return ((((int64_t)a.layer * C + c) * 2 * C + o) * ks + k) * T + l;
+    };
+    auto bidx = [&](int o) -> int64_t {
+        if constexpr (PACKED) return fd::bias_index(a.layer, o);
+        else return ((int64_t)a.layer * 2 * C + o) * T + l;
+    };
+    float zs = bb[bidx(ch)], zt = bb[bidx(ch + C)];
     for (int c = 0; c < C; ++c) {
-        const float *yr = y + ((int64_t)b * C + c) * Ln;
+        const float *yr = a.y + ((int64_t)b * C + c) * Ln;
         for (int k = 0; k < ks; ++k) {
             const int64_t p = t + k - half;
             if (p < 0 || p >= Lnb) continue;
             const float v = yr[p];
-            const int64_t base = (((int64_t)layer * C + c) * 2 * C) * ks;
-            zs += v * kb[(base + (int64_t)ch * ks + k) * T + l];
-            zt += v * kb[(base + (int64_t)(ch + C) * ks + k) * T + l];
+            zs += v * kb[kidx(c, ch, k)];
+            zt += v * kb[kidx(c, ch + C, k)];
         }
     }
-    out[i] = x[i] + (1.0f / (1.0f + expf(-zs))) * tanhf(zt);
+    a.x[i] = a.x[i] + (1.0f / (1.0f + expf(-zs))) * tanhf(zt);
 }
 
 // One reverse step of sampling_given_noise_schedule on x (util.py:219-229), scalar form of fdk::sampler_update4: the same Philox
@@ -198,6 +203,69 @@ static inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); 
 
 #define G_LAUNCH(kern, n, ...) do { hipLaunchKernelGGL(kern, grid1(n), dim3(256), 0, stream, __VA_ARGS__); \
                                     hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
+// the shared kernels: through FD_LAUNCH under `name` for the naive set (L.ctx set), plain for the generic path
+#define REF_LAUNCH(L, name, kern, n, ...) do { if ((L).ctx) FD_LAUNCH(L, name, kern, grid1(n), dim3(256), 0, __VA_ARGS__); \
+                                               else { const hipStream_t stream = (L).stream; G_LAUNCH(kern, n, __VA_ARGS__); } } while (0)
+
+hipError_t conv1d(const fdk::Launch &L, const char *name, const ConvArgs &a)
+{
+    REF_LAUNCH(L, name, g_conv1d, (int64_t)a.B * a.Cout * a.Lout, a);
+    return hipSuccess;
+}
+
+hipError_t convt(const fdk::Launch &L, const char *name, const ConvW &up, const float *x, float *y, int B, int C, int r, int64_t Lin,
+                 const int *lens, int spf_in)
+{
+    REF_LAUNCH(L, name, g_convt, (int64_t)B * C * Lin * r, x, up.w, up.b, y, B, C, r, r / 2 + r % 2, Lin, lens, spf_in);
+    return hipSuccess;
+}
+
+hipError_t dblock(const fdk::Launch &L, const ConvW &res, const ConvW conv[3], const float *x, int64_t Lin, int f, float *const tmp[3],
+                  float *out, int B, int C, const int *lens, int spf)
+{
+    hipError_t e;
+    ConvArgs a(res, x, tmp[0], B, C, C, 1, Lin / f);
+    a.Lx = Lin; a.in_stride = f; a.lens = lens; a.spf = spf;
+    if ((e = conv1d(L, "naive_dblock_res", a)) != hipSuccess) return e;
+    a.K = 3; a.pre = 0.2f;
+    for (int l = 0; l < 3; ++l) {
+        a.w = conv[l].w; a.bias = conv[l].b; a.dil = 1 << l;
+        if (l > 0) { a.x = tmp[l]; a.Lx = a.Lout; a.in_stride = 1; }
+        a.y = l < 2 ? tmp[l + 1] : out;
+        a.res = l < 2 ? nullptr : tmp[0];
+        if ((e = conv1d(L, "naive_dblock_conv", a)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t kp_front(const fdk::Launch &L, const ConvArgs &in, const ConvW res[6], int k, float *ha, float *hb)
+{
+    hipError_t e;
+    if ((e = conv1d(L, "naive_kp_in", in)) != hipSuccess) return e;
+    ConvArgs a(res[0], in.y, nullptr, in.B, in.Cout, in.Cout, k, in.Lout);
+    a.post = 0.1f; a.lens = in.lens; a.spf = in.spf;
+    for (int l = 0; l < 6; ++l) {
+        a.w = res[l].w; a.bias = res[l].b; a.y = (l & 1) ? hb : ha;
+        if (l == 5) a.res = in.y;
+        if ((e = conv1d(L, "naive_kp_res", a)) != hipSuccess) return e;
+        a.x = a.y;
+    }
+    return hipSuccess;
+}
+
+hipError_t lvc_layer(const fdk::Launch &L, const ConvW &conv, const LvcArgs &g)
+{
+    const int64_t ln = (int64_t)g.T * g.hop, n = (int64_t)g.B * g.C * ln;
+    REF_LAUNCH(L, "naive_add_skip", g_add_inplace, n, g.x, g.skip, n, ln, g.C, g.lens, g.hop);
+    ConvArgs a(conv, g.x, g.y, g.B, g.C, g.C, g.ks, ln);
+    for (int i = 0; i < g.layer; ++i) a.dil *= 3;
+    a.pre = 0.2f; a.post = 0.2f; a.lens = g.lens; a.spf = g.hop;
+    const hipError_t e = conv1d(L, "naive_lvc_conv", a);
+    if (e != hipSuccess) return e;
+    if (g.packed) REF_LAUNCH(L, "naive_lvc_gate", g_lvc_gate<true>, n, g);
+    else REF_LAUNCH(L, "naive_lvc_gate", g_lvc_gate<false>, n, g);
+    return hipSuccess;
+}
 
 int validate(const fd_config &c, std::string &why)
 {
@@ -253,7 +321,7 @@ int pack_weights(fd_context *c, const std::map<std::string, FoldedParam> &f, Wei
 {
     Net *n = c->gen;
     int rc;
-    auto conv = [&](const std::string &name, Conv &cw) -> int {
+    auto conv = [&](const std::string &name, ConvW &cw) -> int {
         const auto it = f.find(name);
         if (it == f.end()) { c->err = "fd_commit_weights: missing parameter " + name; return FD_ERR_MISSING; }
         img.add(cw.w, it->second.w);
@@ -354,29 +422,25 @@ static hipError_t forward_dev(Net *n, const Plan &p, const float *x, const float
     const int C = c.inner_channels, CC = c.cond_channels, HID = c.kpnet_hidden_channels, KS = c.lvc_kernel_size, KK = c.kpnet_conv_size;
     const int LY = c.lvc_layers_each_block, T = (int)p.T;
     const int E_IN = c.diffusion_step_embed_dim_in, E_MID = c.diffusion_step_embed_dim_mid, E_OUT = c.diffusion_step_embed_dim_out;
-    const float *none = nullptr;
     // a1, a2: embedding, two swish layers, the per-block fc_t
     G_LAUNCH(g_step_embed, (int64_t)B * (E_IN / 2), steps, t_all, n->embed_table, E_IN / 2, w + p.emb, B);
     G_LAUNCH(g_linear, (int64_t)B * E_MID, (const float *)(w + p.emb), n->fc_t1.w, n->fc_t1.b, w + p.mid, B, E_IN, E_MID, 1);
     G_LAUNCH(g_linear, (int64_t)B * E_OUT, (const float *)(w + p.mid), n->fc_t2.w, n->fc_t2.b, w + p.eout, B, E_MID, E_OUT, 1);
     for (int b = 0; b < n->nb; ++b)
         G_LAUNCH(g_linear, (int64_t)B * CC, (const float *)(w + p.eout), n->blk[b].fc_t.w, n->blk[b].fc_t.b, w + p.noise + (size_t)b * B * CC, B, E_OUT, CC, 0);
+    const fdk::Launch L{nullptr, stream, false};
+    hipError_t e;
     // a3: first_audio_conv
-    G_LAUNCH(g_conv1d, (int64_t)B * C * p.L, x, n->first.w, n->first.b, w + p.a[0], B, 1, C, 7, 1, 3, p.L, p.L, 1, none, 1.0f, 1.0f, none, (int64_t)0, 1, lens, n->hop_total);
+    ConvArgs first(n->first, x, w + p.a[0], B, 1, C, 7, p.L);
+    first.lens = lens; first.spf = n->hop_total;
+    if ((e = conv1d(L, nullptr, first)) != hipSuccess) return e;
     // a4: the DBlocks, factors = the ratios reversed (FastDiff_model.py:63); block d consumes a[d], leaves a[d + 1]
     int64_t len = p.L;
     for (int d = 0; d < n->nb; ++d) {
         const int f = c.upsample_ratios[n->nb - 1 - d];
         const int64_t lo = len / f;
-        const int spf = (int)(lo / T);                // samples per frame at this DBlock's output rate
-        const Net::Blk &k = n->blk[d];
-        const float *src = w + p.a[d];
-        // res = Conv1x1(x) picked at every f-th sample; h = the picked x through three (lrelu 0.2, conv k3 dilation 1, 2, 4); out = h + res
-        G_LAUNCH(g_conv1d, (int64_t)B * C * lo, src, k.res.w, k.res.b, w + p.res, B, C, C, 1, 1, 0, len, lo, f, none, 1.0f, 1.0f, none, (int64_t)0, 1, lens, spf);
-        G_LAUNCH(g_conv1d, (int64_t)B * C * lo, src, k.dconv[0].w, k.dconv[0].b, w + p.h0, B, C, C, 3, 1, 1, len, lo, f, none, 0.2f, 1.0f, none, (int64_t)0, 1, lens, spf);
-        G_LAUNCH(g_conv1d, (int64_t)B * C * lo, (const float *)(w + p.h0), k.dconv[1].w, k.dconv[1].b, w + p.h1, B, C, C, 3, 2, 2, lo, lo, 1, none, 0.2f, 1.0f, none, (int64_t)0, 1, lens, spf);
-        G_LAUNCH(g_conv1d, (int64_t)B * C * lo, (const float *)(w + p.h1), k.dconv[2].w, k.dconv[2].b, w + p.a[d + 1], B, C, C, 3, 4, 4, lo, lo, 1, none, 0.2f, 1.0f,
-                 (const float *)(w + p.res), lo, 1, lens, spf);
+        float *const tmp[3] = {w + p.res, w + p.h0, w + p.h1};
+        if ((e = dblock(L, n->blk[d].res, n->blk[d].dconv, w + p.a[d], len, f, tmp, w + p.a[d + 1], B, C, lens, (int)(lo / T))) != hipSuccess) return e;
         len = lo;
     }
     // the LVC blocks (modules.py:189-218): x starts as the bottom of the down path
@@ -384,45 +448,31 @@ static hipError_t forward_dev(Net *n, const Plan &p, const float *x, const float
     int64_t lin = T;
     for (int b = 0; b < n->nb; ++b) {
         const Net::Blk &k = n->blk[b];
-        const int r = c.upsample_ratios[b], hop = n->hop[b];
-        const int64_t ln = lin * r;
-        const float *skip = w + p.a[n->nb - 1 - b];
-        const float *nz = w + p.noise + (size_t)b * B * CC;
+        const int r = c.upsample_ratios[b];
         // a5: KernelPredictor on c + noise: input conv k5 + lrelu 0.1; h + six (conv, lrelu 0.1); kernel_conv, bias_conv
-        float *h0 = w + p.kph[0], *ha = w + p.kph[1], *hb = w + p.kph[2];
-        G_LAUNCH(g_conv1d, (int64_t)B * HID * T, mel, k.kp_in.w, k.kp_in.b, h0, B, CC, HID, 5, 1, 2, (int64_t)T, (int64_t)T, 1, nz, 1.0f, 0.1f, none, (int64_t)0, 1, lens, 1);
-        const float *cur = h0;
-        for (int j = 0; j < 6; ++j) {
-            float *dst = (j & 1) ? hb : ha;
-            const bool last = j == 5;
-            G_LAUNCH(g_conv1d, (int64_t)B * HID * T, cur, k.kp_res[j].w, k.kp_res[j].b, dst, B, HID, HID, KK, 1, (KK - 1) / 2, (int64_t)T, (int64_t)T, 1, none, 1.0f, 0.1f,
-                     last ? (const float *)h0 : none, (int64_t)T, 1, lens, 1);
-            cur = dst;
-        }
-        G_LAUNCH(g_conv1d, (int64_t)B * LY * C * 2 * C * KS * T, cur, k.kc.w, k.kc.b, w + p.kc, B, HID, LY * C * 2 * C * KS, KK, 1, (KK - 1) / 2, (int64_t)T, (int64_t)T, 1, none,
-                 1.0f, 1.0f, none, (int64_t)0, 1, lens, 1);
-        G_LAUNCH(g_conv1d, (int64_t)B * LY * 2 * C * T, cur, k.bc.w, k.bc.b, w + p.bc, B, HID, LY * 2 * C, KK, 1, (KK - 1) / 2, (int64_t)T, (int64_t)T, 1, none, 1.0f, 1.0f,
-                 none, (int64_t)0, 1, lens, 1);
+        ConvArgs in(k.kp_in, mel, w + p.kph[0], B, CC, HID, 5, T);
+        in.post = 0.1f; in.in_add = w + p.noise + (size_t)b * B * CC; in.in_add_b = CC; in.lens = lens;
+        if ((e = kp_front(L, in, k.kp_res, KK, w + p.kph[1], w + p.kph[2])) != hipSuccess) return e;
+        ConvArgs kc(k.kc, w + p.kph[2], w + p.kc, B, HID, LY * C * 2 * C * KS, KK, T);
+        kc.lens = lens;
+        if ((e = conv1d(L, nullptr, kc)) != hipSuccess) return e;
+        kc.w = k.bc.w; kc.bias = k.bc.b; kc.y = w + p.bc; kc.Cout = LY * 2 * C;
+        if ((e = conv1d(L, nullptr, kc)) != hipSuccess) return e;
         // a6: x = upsample(lrelu(x, 0.2)) into the ping-pong buffer the input does not occupy
         float *dst = (xcur == w + p.xa) ? w + p.xb : w + p.xa;
-        float *oth = (dst == w + p.xa) ? w + p.xb : w + p.xa;
-        G_LAUNCH(g_convt, (int64_t)B * C * ln, xcur, k.up.w, k.up.b, dst, B, C, r, r / 2 + r % 2, lin, lens, (int)(lin / T));
+        if ((e = convt(L, nullptr, k.up, xcur, dst, B, C, r, lin, lens, (int)(lin / T))) != hipSuccess) return e;
         // a7-a9: per layer x += skip; y = lrelu(conv_{ks, dilation 3^i}(lrelu(x))); x = x + gate(LVC(y))
-        int dil = 1;
         for (int i = 0; i < LY; ++i) {
-            G_LAUNCH(g_add_inplace, (int64_t)B * C * ln, dst, skip, (int64_t)B * C * ln, ln, C, lens, hop);
-            G_LAUNCH(g_conv1d, (int64_t)B * C * ln, (const float *)dst, k.convs[i].w, k.convs[i].b, w + p.y, B, C, C, KS, dil, dil * ((KS - 1) / 2), ln, ln, 1, none, 0.2f, 0.2f,
-                     none, (int64_t)0, 1, lens, hop);
-            G_LAUNCH(g_lvc_gate, (int64_t)B * C * ln, (const float *)(w + p.y), (const float *)(w + p.kc), (const float *)(w + p.bc), (const float *)dst, oth, B, C, KS, LY, i, hop, T, lens);
-            std::swap(dst, oth);
-            dil *= 3;
+            const LvcArgs g = {dst, w + p.a[n->nb - 1 - b], w + p.y, false, w + p.kc, w + p.bc, B, C, KS, LY, i, n->hop[b], T, lens};
+            if ((e = lvc_layer(L, k.convs[i], g)) != hipSuccess) return e;
         }
         xcur = dst;
-        lin = ln;
+        lin *= r;
     }
     // a10: final_conv
-    G_LAUNCH(g_conv1d, (int64_t)B * p.L, xcur, n->final_.w, n->final_.b, eps_out, B, C, 1, 7, 1, 3, p.L, p.L, 1, none, 1.0f, 1.0f, none, (int64_t)0, 1, lens, n->hop_total);
-    return hipSuccess;
+    ConvArgs fin(n->final_, xcur, eps_out, B, C, 1, 7, p.L);
+    fin.lens = lens; fin.spf = n->hop_total;
+    return conv1d(L, nullptr, fin);
 }
 
 // the caller's `lens` (host, nullable) -> the workspace's device copy, or NULL when every utterance fills the batch

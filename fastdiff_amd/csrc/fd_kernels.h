@@ -1,4 +1,5 @@
-// fd_kernels.h -- internal: per-stage entry points of the naive and the fast (MFMA) kernel sets.
+// fd_kernels.h -- internal: per-stage entry points of the naive and the fast (MFMA) kernel sets, and the reference kernels behind the
+// naive set and the generic path.
 #pragma once
 #include "fd_internal.h"
 
@@ -100,3 +101,58 @@ hipError_t convt_backward(const Launch &L, const float *x, const float *w, const
 // in HOST memory (include/fastdiff_hip.h: fd_wn_item), passed on as kernel arguments
 hipError_t weight_norm_multi(const Launch &L, const fd_wn_item *items, int n, bool backward);
 }  // namespace fdk
+
+// The exact-fp32 reference kernels (fd_generic.hip): one thread per output, runtime shapes, fp32 multiply-adds in a fixed order.  The
+// generic path runs any configuration on them; the naive set (option kernels[.<stage>] = naive) runs base.yaml's on the tuned workspace.
+// A Launch with ctx set (the naive set) goes through FD_LAUNCH under the given name; ctx == null (the generic path) launches plain on
+// L.stream, unprofiled.
+namespace fdg {
+// y[b][o][t] = post(bias[o] + sum_{c,k} w[o][c][k] * pre(xin(b, c, t + k*dil - dil*(K-1)/2))) (+ res[b][o][t]),  K odd
+//   xin(b, c, p) = 0 outside [0, Lout), else x[b][c][p * in_stride] (+ in_add[b][c]: the predictor's `c + noise`, modules.py:203 --
+//   added to the signal, not to its zero padding).  in_stride > 1 reads every in_stride-th sample: nearest-neighbour down-sampling by
+//   an integer factor (DiffusionDBlock, modules.py:127-134) without materialising the picked sequence.
+//   lens (nullable) / spf: utterance b is lens[b] * spf output samples long; behind that nothing is computed and nothing is read.
+struct ConvArgs {
+    const float *x, *w, *bias;
+    float *y;
+    int B, Cin, Cout, K;
+    int64_t Lx, Lout;                  // row lengths of x and y
+    int dil = 1, in_stride = 1;
+    float pre = 1.0f, post = 1.0f;     // leaky ReLU slopes, 1 = identity
+    const float *in_add = nullptr;     // in_add[s * in_add_step + b * in_add_b + c], s = *step (device: the sampler's graphs) or 0
+    int64_t in_add_b = 0, in_add_step = 0;
+    const int *step = nullptr;
+    const float *res = nullptr;
+    const int *lens = nullptr;
+    int spf = 1;
+    int rec = 0, rec_off = 0;          // rec > 0: y[(b*Lout + t)*rec + rec_off + (perm ? perm[o] : o)] (the naive kernel_conv's records)
+    const int *perm = nullptr;
+    ConvArgs(const ConvW &cw, const float *x_, float *y_, int B_, int Cin_, int Cout_, int K_, int64_t L)
+        : x(x_), w(cw.w), bias(cw.b), y(y_), B(B_), Cin(Cin_), Cout(Cout_), K(K_), Lx(L), Lout(L) {}
+};
+hipError_t conv1d(const fdk::Launch &L, const char *name, const ConvArgs &a);
+// ConvTranspose1d(C, C, 2r, stride r, padding r/2 + r%2, output_padding r%2) of leaky_relu(x, 0.2): [B][C][Lin] -> [B][C][Lin*r]
+hipError_t convt(const fdk::Launch &L, const char *name, const ConvW &up, const float *x, float *y, int B, int C, int r, int64_t Lin,
+                 const int *lens, int spf_in);
+// DiffusionDBlock (modules.py:116-134) on x [B][C][Lin], f = the down-sampling factor: res = Conv1x1(x) at every f-th sample; h = the
+// picked x through three (lrelu 0.2, conv k3 dilation 1, 2, 4); out = h + res.  tmp: res, h after the first and the second conv.
+hipError_t dblock(const fdk::Launch &L, const ConvW &res, const ConvW conv[3], const float *x, int64_t Lin, int f, float *const tmp[3],
+                  float *out, int B, int C, const int *lens, int spf);
+// the KernelPredictor's front (modules.py:292-318): `in` = its input conv k5 + lrelu 0.1 on c + noise into h0 = in.y, then six (conv
+// k, lrelu 0.1) with h0 added behind the last: h0 -> ha -> hb -> ha -> hb -> ha -> hb, the result in hb
+hipError_t kp_front(const fdk::Launch &L, const ConvArgs &in, const ConvW res[6], int k, float *ha, float *hb);
+// one LVC layer (modules.py:208-217), in place on x [B][C][T*hop]: x += skip; y = lrelu(conv_{ks, dilation 3^layer}(lrelu(x, 0.2)), 0.2);
+// x += sigmoid(z[ch]) * tanh(z[ch + C]) with z the location-variable convolution of y by the layer's predicted kernels
+struct LvcArgs {
+    float *x;
+    const float *skip;
+    float *y;                          // scratch [B][C][T*hop]
+    // packed: kernels = the block's records [B][T][fd::KREC] (fd::kernel_index / bias_index: C = 32, ks = 3), biases unused;
+    // else the reference layout as kernel_conv / bias_conv leave it, [B][layers*C*2C*ks][T] / [B][layers*2C][T] (modules.py:333-338)
+    bool packed;
+    const float *kernels, *biases;
+    int B, C, ks, layers, layer, hop, T;
+    const int *lens;
+};
+hipError_t lvc_layer(const fdk::Launch &L, const ConvW &conv, const LvcArgs &a);
+}  // namespace fdg

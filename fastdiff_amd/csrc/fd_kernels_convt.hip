@@ -1,5 +1,5 @@
 // fd_kernels_convt.hip -- a6 the LVC block's ConvTranspose1d up-sampler (modules.py:163-166,205-206)
-// (one stage of the gfx950 kernel set; shared device helpers: fd_kernels_common.h; the one-thread-per-output twins: fd_kernels_naive.hip)
+// (one stage of the gfx950 kernel set; shared device helpers: fd_kernels_common.h; the one-thread-per-output twins: the naive set, fd_kernels_naive.hip on the reference kernels of fd_generic.hip)
 #include "fd_kernels_common.h"
 
 namespace fdk_fast {

@@ -1,5 +1,5 @@
 // fd_kernels_first_final.hip -- a3 first_audio_conv, a10 final_conv + the reverse-step update (FastDiff_model.py:34-36,67-68,89,100; util.py:219-229)
-// (one stage of the gfx950 kernel set; shared device helpers: fd_kernels_common.h; the one-thread-per-output twins: fd_kernels_naive.hip)
+// (one stage of the gfx950 kernel set; shared device helpers: fd_kernels_common.h; the one-thread-per-output twins: the naive set, fd_kernels_naive.hip on the reference kernels of fd_generic.hip)
 #include "fd_kernels_common.h"
 
 namespace fdk_fast {
