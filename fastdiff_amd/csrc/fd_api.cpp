@@ -14,9 +14,9 @@
 
 std::string g_create_error;
 
-// rows of the predictor GEMM's fp16 image per utterance (gx_rows in fd_kernels_kp.hip: 128-frame windows + 2 halo rows)
-// (... or, for the Winograd form k_kp_gemm_w, 32 frame PAIRS of four 256-byte sub-rows per 64-frame window: whichever is larger)
-static inline int gx_rows_host(int T) { return std::max(((T + 127) / 128) * 128 + 2, ((T + 63) / 64) * 128); }
+// 256-byte rows of the predictor GEMM's fp16 image per utterance: the direct form's (gx_rows: whole item windows + 2 halo rows) or the
+// Winograd form's (gw_pairs pair rows of four such rows each), whichever is larger -- both from the kernels' own definitions (fd_kernels.h)
+static inline int gx_rows_host(int T) { return std::max(fdk_fast::gx_rows(T), fdk_fast::gw_pairs(T) * (fdk_fast::GW_ROWB / fdk_fast::GX_ROWB)); }
 
 // ------------------------------------------------------------------------------------------------
 // profiling helpers (declared in fd_internal.h)
@@ -256,7 +256,7 @@ static hipError_t allocate_workspace(fd_context *h, int64_t capB, int64_t frames
     WS(w.kp_h0, (size_t)fd::NBLK * fd::HID * pframes); WS(w.kp_hA, (size_t)fd::NBLK * fd::HID * pframes);
     WS(w.kp_hB, (size_t)fd::NBLK * fd::HID * pframes);
     WS(w.kpack, (size_t)fd::NBLK * pframes * fd::KREC);
-    WS(w.h_f16, (size_t)fd::NBLK * prows * 64 + 1024);      // + slack for the rounded-up last DMA
+    WS(w.h_f16, (size_t)fd::NBLK * prows * (fdk_fast::GX_ROWB / f) + 1024);      // + slack for the rounded-up last DMA
     WS(w.mel_rep, (size_t)fd::COND * pframes);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w.lens_dev), sizeof(int) * (size_t)std::max<int64_t>(plens, 64));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w.uid_dev), sizeof(unsigned long long) * (size_t)std::max<int64_t>(capB, 64));

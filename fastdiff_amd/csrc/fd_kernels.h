@@ -3,6 +3,17 @@
 #pragma once
 #include "fd_internal.h"
 
+// Geometry of the predictor GEMM's fp16 piece images (fd_kernels_kp.hip), shared by the kernels that write and read them and the host
+// code that sizes the workspace behind them (fd_api.cpp): one definition, so that a DMA never reads behind the allocation.
+namespace fdk_fast {
+constexpr int GX_CT = 4;                          // direct form: frame tiles (of 32) per item
+constexpr int GX_ROWB = 2 * 128;                  // bytes per row (frame) of its image: [piece][64 ch] fp16
+constexpr int GW_PAIRS = 32;                      // Winograd form: pairs per item (64 frames)
+constexpr int GW_ROWB = 1024;                     // bytes per pair row: [4 j][2 pieces][64 ch] fp16
+__host__ __device__ inline int gx_rows(int T) { return ((T + GX_CT * 32 - 1) / (GX_CT * 32)) * (GX_CT * 32) + 2; }   // image rows per (block, utterance)
+__host__ __device__ inline int gw_pairs(int T) { return ((T + 2 * GW_PAIRS - 1) / (2 * GW_PAIRS)) * GW_PAIRS; }      // image rows (pairs) per (block, entry)
+}  // namespace fdk_fast
+
 namespace fdk {
 // naive set (fd_kernels_naive.hip)
 hipError_t naive_first_conv(const Launch &L, const StepIO &io, int B, int T);

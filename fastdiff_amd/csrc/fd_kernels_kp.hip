@@ -425,9 +425,8 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm(const float *__restrict__ h 
 // the result is closer than an fp32 sgemm.  fp16 subnormals are honoured by v_cvt and by the MFMA
 // (tools/ubench/f16_probe.hip), so small values lose nothing; operands of magnitude >= 32768 do not fit: k_h_split raises
 // a flag for them, this kernel then leaves the step to the fp32 kernel that follows it in the stream.
-constexpr int GX_CT = 4;                        // frame tiles per item
+// (GX_CT frame tiles per item, GX_ROWB bytes per row of the piece image, gx_rows: fd_kernels.h, where the host sizes the image by them)
 constexpr int GX_ROWS = GX_CT * 32 + 2;         // 130 rows: frames t_begin-1 .. t_begin+128
-constexpr int GX_ROWB = 2 * 128;                // bytes per row of the piece image: [piece][64 ch] fp16
 constexpr int GX_WINB = GX_ROWS * GX_ROWB;      // 33280 B per item window
 constexpr int GX_NDMA = (GX_WINB + 4095) / 4096;   // 4 KB (256 lanes x 16 B) DMA rounds per window: 8 full + 1 partial
 constexpr int GX_BUFB = GX_NDMA * 4096;         // LDS bytes per buffer (the partial round is padded to a whole wave)
@@ -438,8 +437,6 @@ constexpr int GX_BUFB = GX_NDMA * 4096;         // LDS bytes per buffer (the par
 #ifndef FD_GX_STORE_AUX
 #define FD_GX_STORE_AUX 2
 #endif
-
-__host__ __device__ inline int gx_rows(int T) { return ((T + GX_CT * 32 - 1) / (GX_CT * 32)) * (GX_CT * 32) + 2; }   // image rows per (block, utterance)
 
 
 // h (fp32 [3][B][64][T]) -> fp16 piece image [3][B][row = t+1][piece][64 channels]; rows 0 and > T are zero.
@@ -476,25 +473,92 @@ typedef __attribute__((address_space(3))) void *lds_ptr_t;
 
 struct GxItem { int blk, xg, b, chunk; };
 
-// Async copy of one item window (16896 B, contiguous in the piece image) into an LDS buffer: 16 B per lane, LDS side linear
+// The persistent schedule of the two fp16x2 GEMM kernels (2 x #CU workgroups, all three LVC blocks in one launch).
+// Work items: id = ((block*XG + column group)*B + utterance)*chunks + chunk; a column group (128 columns, the weights a
+// workgroup keeps in registers) spans ny = B*chunks consecutive ids, one per item window of the block's h image.
+// Schedule: workgroup w first does whole groups w, w + #wg, ...: all workgroups then walk the windows in step, and a window
+// is fetched from HBM once per XCD instead of once per workgroup (the 2 GB output stream turns L2 over every few
+// microseconds).  The groups that do not divide evenly are cut into equal contiguous id ranges at the end.
+struct GxWalk {
+    static constexpr int XG = fd::KREC / 128;
+    int B, chunks, ny, n_wg, w, q, base, r0, r1;
+    int n_mine, left0;         // items of this workgroup; of its first run
+    __device__ __forceinline__ GxWalk(int B_, int chunks_per_utt, int n_items, int n_wg_, int w_)
+        : B(B_), chunks(chunks_per_utt), ny(B_ * chunks_per_utt), n_wg(n_wg_), w(w_)
+    {
+        q = (fd::NBLK * XG) / n_wg; base = q * n_wg * ny;
+        const int rest = n_items - base;
+        r0 = (int)((int64_t)w * rest / n_wg); r1 = (int)((int64_t)(w + 1) * rest / n_wg);
+        n_mine = q * ny + (r1 - r0);
+        left0 = (q > 0) ? ny : (r1 - r0);
+    }
+    __device__ __forceinline__ GxItem decode(int id) const
+    {
+        GxItem it;
+        it.blk = id / (XG * ny);
+        const int rem = id - it.blk * (XG * ny);
+        it.xg = rem / ny;
+        const int yy = rem - it.xg * ny;
+        it.b = yy / chunks;
+        it.chunk = yy - it.b * chunks;
+        return it;
+    }
+    __device__ __forceinline__ GxItem first() const { return decode((q > 0) ? w * ny : base + r0); }
+    // the item of the next id, without decode's divisions
+    __device__ __forceinline__ GxItem advance(GxItem it) const
+    {
+        if (++it.chunk == chunks) {
+            it.chunk = 0;
+            if (++it.b == B) {
+                it.b = 0;
+                if (++it.xg == XG) { it.xg = 0; ++it.blk; }
+            }
+        }
+        return it;
+    }
+};
+// Where a workgroup is on its walk: `run` and `left`, plain locals of the kernel (ids of a run are consecutive; `left` counts the current
+// item too; start: 0, walk.left0).  GX_WALK_NEXT declares `nxt`, the item behind `cur` (cur itself when there is none: !more), and moves
+// the two on.  A macro, not a member: counters that the compiler meets as members of GxWalk, through references or in a returned
+// aggregate come out in another order among the loop's copies, and the instruction stream moves (tools/isa_diff.py).
+#define GX_WALK_NEXT(walk, cur, more, nxt, run, left)                                                                  \
+    GxItem nxt = cur;                                                                                                  \
+    if (more) {                                                                                                        \
+        if (left > 1) nxt = (walk).advance(cur);                                                                       \
+        else {                                           /* next run: the next whole group, or the tail range */       \
+            ++run;                                                                                                     \
+            nxt = (walk).decode(run < (walk).q ? (run * (walk).n_wg + (walk).w) * (walk).ny : (walk).base + (walk).r0); \
+            left = (run < (walk).q ? (walk).ny : (walk).r1 - (walk).r0) + 1;                                           \
+        }                                                                                                              \
+    }                                                                                                                  \
+    --left
+
+// Async copy of one item window (contiguous in the piece image, ROUNDS x 4 KB) into an LDS buffer: 16 B per lane, LDS side linear
 // (M0 = wave-uniform LDS base, lane i lands at base + 16*i).  Issued as inline asm on purpose: for the builtin the compiler
 // puts a full vmcnt(0) in front of the next ds_read of ANY LDS address, which would serialise the copy with the MFMAs of the
-// current item; the waits are counted by hand in gx_item instead.
-__device__ __forceinline__ void gx_dma(const char *hx, char *lds_buf, const GxItem &it, int B, int R, int wave_u, int lane)
+// current item; the waits are counted by hand in gx_item / gw_item instead.
+// PARTIAL_LAST: the last round is one wave's share only (rounded to a whole wave; the image has slack behind it)
+template <int ROUNDS, bool PARTIAL_LAST>
+__device__ __forceinline__ void gx_window_dma(const char *src /*the window + wave_u * 1024: uniform*/, char *lds_buf, int wave_u, int lane)
 {
-#ifndef FD_GX_NO_FETCH
-    const char *src = hx + (((int64_t)it.blk * B + it.b) * R + it.chunk * (GX_CT * 32)) * GX_ROWB + wave_u * 1024;    // uniform
     const unsigned dst = (unsigned)(uintptr_t)(lds_ptr_t)(lds_buf + wave_u * 1024);
     const unsigned voff = lane * 16;
     unsigned keep;
 #pragma unroll
-    for (int j = 0; j < GX_NDMA; ++j) {
-        if (j == GX_NDMA - 1 && wave_u != 0) break;      // the last 512 B (rounded to one wave; the image has slack behind it)
+    for (int j = 0; j < ROUNDS; ++j) {
+        if (PARTIAL_LAST && j == ROUNDS - 1 && wave_u != 0) break;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep)
                      : "v"(voff), "s"(src + j * 4096), "s"(dst + j * 4096)
                      : "memory");
     }
+}
+
+// the direct form's window: 130 rows from the chunk's first frame - 1 (8 full rounds + 512 B)
+__device__ __forceinline__ void gx_dma(const char *hx, char *lds_buf, const GxItem &it, int B, int R, int wave_u, int lane)
+{
+#ifndef FD_GX_NO_FETCH
+    gx_window_dma<GX_NDMA, true>(hx + (((int64_t)it.blk * B + it.b) * R + it.chunk * (GX_CT * 32)) * GX_ROWB + wave_u * 1024, lds_buf, wave_u, lane);
 #endif
 }
 
@@ -595,50 +659,18 @@ __device__ __forceinline__ void gx_item(char *lds, const GxItem &cur, bool more,
 __global__ void __launch_bounds__(256, 2) k_kp_gemm_h2(const char *__restrict__ hx /*[3][B][R][2][64] fp16*/, float *__restrict__ kpack,
                                                        const float4 *g0, const float4 *g1, const float4 *g2, const float *gb0,
                                                        const float *gb1, const float *gb2, const int *__restrict__ range_flag, int B,
-                                                       int T, int R, int chunks_per_utt, int n_items, const int *__restrict__ lens,
-                                                       int blk0, int nblk)
+                                                       int T, int R, int chunks_per_utt, int n_items, const int *__restrict__ lens)
 {
-    // blk0, nblk: the LVC blocks this launch computes (0, 3: all of them; option overlap = gemm launches block 0 alone and the other
-    // two next to the LVC layers of the block before them); n_items counts the items of those blocks only
     __shared__ __attribute__((aligned(16))) char lds[2 * GX_BUFB];     // 2 x 36 KB
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int XG = fd::KREC / 128;
     if (*range_flag != 0) return;      // out-of-range operands (raised by the producer of h): the fp32 kernel behind us does this step
 
-    // Work items: id = ((block*XG + column group)*B + utterance)*chunks + chunk; a column group (128 columns, the weights a
-    // workgroup keeps in registers) spans ny = B*chunks consecutive ids, one per 64-frame window of the block's h image.
-    // Schedule: workgroup w first does whole groups w, w + #wg, ...: all workgroups then walk the windows in step, and a window
-    // is fetched from HBM once per XCD instead of once per workgroup (the 2 GB output stream turns L2 over every few
-    // microseconds).  The groups that do not divide evenly are cut into equal contiguous id ranges at the end.
-    const int ny = B * chunks_per_utt, n_wg = gridDim.x, w = blockIdx.x;
-    const int q = (nblk * XG) / n_wg, base = q * n_wg * ny, rest = n_items - base;
-    const int r0 = (int)((int64_t)w * rest / n_wg), r1 = (int)((int64_t)(w + 1) * rest / n_wg);
-    const int n_mine = q * ny + (r1 - r0);
+    GxWalk walk(B, chunks_per_utt, n_items, gridDim.x, blockIdx.x);
+    const int n_mine = walk.n_mine;
     if (n_mine <= 0) return;
-    auto decode = [&](int id) {
-        GxItem it;
-        it.blk = id / (XG * ny);
-        const int rem = id - it.blk * (XG * ny);
-        it.blk += blk0;
-        it.xg = rem / ny;
-        const int yy = rem - it.xg * ny;
-        it.b = yy / chunks_per_utt;
-        it.chunk = yy - it.b * chunks_per_utt;
-        return it;
-    };
-    auto advance = [&](GxItem it) {
-        if (++it.chunk == chunks_per_utt) {
-            it.chunk = 0;
-            if (++it.b == B) {
-                it.b = 0;
-                if (++it.xg == XG) { it.xg = 0; ++it.blk; }
-            }
-        }
-        return it;
-    };
-    int run = 0, left = (q > 0) ? ny : (r1 - r0);          // ids of a run are consecutive; `left` counts the current item too
-    GxItem cur = decode((q > 0) ? w * ny : base + r0);
+    int run = 0, left = walk.left0;
+    GxItem cur = walk.first();
 
     // byte offsets of the A-operand reads of a tile: row = frame + tap, slot = (8*piece + 2*k4 + hi) ^ (row & 15)
     int aoff[2][12];
@@ -685,16 +717,7 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_h2(const char *__restrict__ 
                 __builtin_amdgcn_s_waitcnt(0x0F70);
             }
             const bool more = (i + half + 1 < n_mine);
-            GxItem nxt = cur;
-            if (more) {
-                if (left > 1) nxt = advance(cur);
-                else {                                           // next run: the next whole group, or the tail range
-                    ++run;
-                    nxt = decode(run < q ? (run * n_wg + w) * ny : base + r0);
-                    left = (run < q ? ny : r1 - r0) + 1;
-                }
-            }
-            --left;
+            GX_WALK_NEXT(walk, cur, more, nxt, run, left);
             const int Tb = frames_of(lens, cur.b, T);
             const bool full = (Tb % 32 == 0) || (cur.chunk * (GX_CT * 32) + GX_CT * 32 <= Tb);
             if (half == 0) {
@@ -728,10 +751,8 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_h2(const char *__restrict__ 
 // A work item = (block, 128-column group, entry, 32 pairs = 64 frames): its 32 KB window is one linear DMA; 48 matrix instructions and
 // 32 stores per wave.  Registers: 128 of stationary weight pieces, acc + lo, and the two output tiles as finished fp32 values.
 // =================================================================================================
-constexpr int GW_PAIRS = 32;                      // pairs per item (64 frames)
-constexpr int GW_ROWB = 1024;                     // bytes per pair row: [4 j][2 pieces][64 ch] fp16
+// (GW_PAIRS pairs per item, GW_ROWB bytes per pair row, gw_pairs: fd_kernels.h)
 constexpr int GW_WINB = GW_PAIRS * GW_ROWB;       // 32 KB per window = 8 DMA rounds of 4 KB
-__host__ __device__ inline int gw_pairs(int T) { return ((T + 2 * GW_PAIRS - 1) / (2 * GW_PAIRS)) * GW_PAIRS; }      // image rows (pairs) per (block, entry)
 
 // h (fp32 [3][B][64][T]) -> the transformed piece image.  Thread = (pair p, 8-channel group g): eight neighbouring lanes write the eight
 // 16-byte slots of one 128-byte half of a sub-row (whole lines), and read their channels' four frames 2p-1 .. 2p+2 (the inner two as one
@@ -779,19 +800,9 @@ __global__ void __launch_bounds__(256) k_h_wino(const float *__restrict__ h, cha
 
 __device__ __forceinline__ void gw_dma(const char *wx, char *lds_buf, const GxItem &it, int B, int P, int wave_u, int lane)
 {
-#ifdef FD_GW_NO_FETCH      // probe: what do the window copies cost the short items?
-    return;
+#ifndef FD_GW_NO_FETCH      // (probe: what do the window copies cost the short items?)
+    gx_window_dma<GW_WINB / 4096, false>(wx + (((int64_t)it.blk * B + it.b) * P + it.chunk * GW_PAIRS) * GW_ROWB + wave_u * 1024, lds_buf, wave_u, lane);
 #endif
-    const char *src = wx + (((int64_t)it.blk * B + it.b) * P + it.chunk * GW_PAIRS) * GW_ROWB + wave_u * 1024;    // uniform
-    const unsigned dst = (unsigned)(uintptr_t)(lds_ptr_t)(lds_buf + wave_u * 1024);
-    const unsigned voff = lane * 16;
-    unsigned keep;
-#pragma unroll
-    for (int j = 0; j < GW_WINB / 4096; ++j)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(src + j * 4096), "s"(dst + j * 4096)
-                     : "memory");
 }
 
 // One item: 32 pairs.  Vector-memory order per item: [DMA of the next window] [16 stores of the even frames] [16 of the odd ones].
@@ -890,36 +901,12 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ w
     __shared__ __attribute__((aligned(16))) char lds[2 * GW_WINB];     // 2 x 32 KB
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int XG = fd::KREC / 128;
     if (*range_flag != 0) return;      // out-of-range operands: the fp32 kernel behind us does this step
-    // the schedule of k_kp_gemm_h2: whole column groups in step first (a window is fetched from HBM once per XCD), equal id ranges last
-    const int ny = B * chunks_per_utt, n_wg = gridDim.x, w = blockIdx.x;
-    const int q = (fd::NBLK * XG) / n_wg, base = q * n_wg * ny, rest = n_items - base;
-    const int r0 = (int)((int64_t)w * rest / n_wg), r1 = (int)((int64_t)(w + 1) * rest / n_wg);
-    const int n_mine = q * ny + (r1 - r0);
+    GxWalk walk(B, chunks_per_utt, n_items, gridDim.x, blockIdx.x);
+    const int n_mine = walk.n_mine;
     if (n_mine <= 0) return;
-    auto decode = [&](int id) {
-        GxItem it;
-        it.blk = id / (XG * ny);
-        const int rem = id - it.blk * (XG * ny);
-        it.xg = rem / ny;
-        const int yy = rem - it.xg * ny;
-        it.b = yy / chunks_per_utt;
-        it.chunk = yy - it.b * chunks_per_utt;
-        return it;
-    };
-    auto advance = [&](GxItem it) {
-        if (++it.chunk == chunks_per_utt) {
-            it.chunk = 0;
-            if (++it.b == B) {
-                it.b = 0;
-                if (++it.xg == XG) { it.xg = 0; ++it.blk; }
-            }
-        }
-        return it;
-    };
-    int run = 0, left = (q > 0) ? ny : (r1 - r0);
-    GxItem cur = decode((q > 0) ? w * ny : base + r0);
+    int run = 0, left = walk.left0;
+    GxItem cur = walk.first();
     // byte offsets of the A-operand reads: pair row l31, slot = (8*piece + 2*k4 + hi) ^ (row & 15); the sub-row j adds the constant 256 j
     int aoff[2][4];
 #pragma unroll
@@ -937,7 +924,7 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ w
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (half == 1 && i + 1 >= n_mine) break;
-            if (cur.blk != have_blk || cur.xg != have_xg) {
+            if (cur.blk != have_blk || cur.xg != have_xg) {      // new column group, as in k_kp_gemm_h2 (there: why the wait is spelled out)
                 const float4 *gp = cur.blk == 0 ? g0 : (cur.blk == 1 ? g1 : g2);
                 const float *gb = cur.blk == 0 ? gb0 : (cur.blk == 1 ? gb1 : gb2);
                 const int ptile = cur.xg * 4 + wave_u;
@@ -950,16 +937,7 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ w
                 __builtin_amdgcn_s_waitcnt(0x0F70);
             }
             const bool more = (i + half + 1 < n_mine);
-            GxItem nxt = cur;
-            if (more) {
-                if (left > 1) nxt = advance(cur);
-                else {
-                    ++run;
-                    nxt = decode(run < q ? (run * n_wg + w) * ny : base + r0);
-                    left = (run < q ? ny : r1 - r0) + 1;
-                }
-            }
-            --left;
+            GX_WALK_NEXT(walk, cur, more, nxt, run, left);
             const int Tb = frames_of(lens, cur.b, T);
             const bool full = cur.chunk * (2 * GW_PAIRS) + 2 * GW_PAIRS <= Tb;
             if (half == 0) {
@@ -1017,50 +995,56 @@ hipError_t fast_kp_front(const Launch &L, const StepIO &io, int B, int T)
     return hipSuccess;
 }
 
+// A form's launch: utterances cut into `chunks` windows, items = (block, 128-column group, utterance, window), a persistent grid of 2
+// workgroups per CU
+struct GemmGrid { int chunks, items, grid; };
+static GemmGrid gemm_grid(const fd_context *c, int B, int chunks)
+{
+    const int items = fd::NBLK * (fd::KREC / 128) * B * chunks;
+    return {chunks, items, items < 2 * c->num_cus ? items : 2 * c->num_cus};
+}
+
 hipError_t fast_kp_gemm(const Launch &L, int B, int T)
 {
     // all three blocks in one persistent launch, 2 workgroups per CU (a launch per block, next to or between the LVC layers, was
     // measured and did not pay: LABBOOK.md)
     fd_context *c = L.ctx;
     const DevWeights &w = c->w;
-    const int tiles_per_utt = (T + 31) / 32;
-    const int chunks_per_utt = (tiles_per_utt + GEMM_CT - 1) / GEMM_CT;
-    const int chunk_tiles = (tiles_per_utt + chunks_per_utt - 1) / chunks_per_utt;     // balanced, <= GEMM_CT
-    const int n_items = fd::NBLK * (fd::KREC / 128) * B * chunks_per_utt;
-    const int grid = n_items < 2 * c->num_cus ? n_items : 2 * c->num_cus;              // persistent: 2 workgroups per CU
     const StepMode &m = *L.mode;
     const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
     const Pipe pipe = fd_pipe(m, m.gemm_f16 && w.gemm_f16_ok, 0);
     const bool f16 = pipe != PIPE_F32_ONLY;
     if (f16 && m.gemm_wino && w.gemm_w_ok) {
         // Winograd F(2,3) over the frame axis: the transformed piece image from the front's fp32 h, then 2/3 of the direct form's matrix work
-        const int P = gw_pairs(T), chunks = P / GW_PAIRS, items = fd::NBLK * (fd::KREC / 128) * B * chunks;
-        const int grid2 = items < 2 * c->num_cus ? items : 2 * c->num_cus;
+        const int P = gw_pairs(T);
+        const GemmGrid g = gemm_grid(c, B, P / GW_PAIRS);
         FD_LAUNCH(L, "h_wino", k_h_wino, dim3((8 * P + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
                   reinterpret_cast<char *>(c->ws.h_f16), c->ws.range_flag, B, T, P, lens);
-        FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_w, dim3(grid2), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
+        FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_w, dim3(g.grid), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[0]), reinterpret_cast<const float4 *>(w.gemm_w_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, P, chunks, items, lens);
+                  (const int *)c->ws.range_flag, B, T, P, g.chunks, g.items, lens);
         if (pipe == PIPE_F16_ONLY) return hipSuccess;
     } else if (f16) {
         const int R = gx_rows(T);
-        const int chunks = (T + GX_CT * 32 - 1) / (GX_CT * 32), items = fd::NBLK * (fd::KREC / 128) * B * chunks;
-        const int grid2 = items < 2 * c->num_cus ? items : 2 * c->num_cus;
+        const GemmGrid g = gemm_grid(c, B, (T + GX_CT * 32 - 1) / (GX_CT * 32));
         if (!front_writes_h_image(m, w))      // (else the fp16-pipe predictor front wrote the image)
             FD_LAUNCH(L, "h_split", k_h_split, dim3((32 * R + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
                       reinterpret_cast<unsigned *>(c->ws.h_f16), c->ws.range_flag, B, T, R, lens);
-        FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_h2, dim3(grid2), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
+        FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_h2, dim3(g.grid), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[0]), reinterpret_cast<const float4 *>(w.gemm_h2_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, R, chunks, items, lens, 0, fd::NBLK);
+                  (const int *)c->ws.range_flag, B, T, R, g.chunks, g.items, lens);
         if (pipe == PIPE_F16_ONLY) return hipSuccess;
     }
     // fp32 matrix pipe: the whole job when the fp16 form is off, otherwise an early-exit launch that only works when
     // k_h_split found operands outside the fp16 range
-    FD_LAUNCH(L, f16 ? "kp_gemm_fp32_fallback" : "kp_gemm", k_kp_gemm, dim3(grid), dim3(256), 0, (const float *)c->ws.kp_hB, c->ws.kpack,
-              w.gemm_pack[0], w.gemm_pack[1], w.gemm_pack[2], w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2], B, T, chunks_per_utt,
-              chunk_tiles, n_items, f16 ? (const int *)c->ws.range_flag : (const int *)nullptr, lens);
+    const int tiles_per_utt = (T + 31) / 32;
+    const GemmGrid g = gemm_grid(c, B, (tiles_per_utt + GEMM_CT - 1) / GEMM_CT);
+    const int chunk_tiles = (tiles_per_utt + g.chunks - 1) / g.chunks;     // balanced, <= GEMM_CT
+    FD_LAUNCH(L, f16 ? "kp_gemm_fp32_fallback" : "kp_gemm", k_kp_gemm, dim3(g.grid), dim3(256), 0, (const float *)c->ws.kp_hB, c->ws.kpack,
+              w.gemm_pack[0], w.gemm_pack[1], w.gemm_pack[2], w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2], B, T, g.chunks,
+              chunk_tiles, g.items, f16 ? (const int *)c->ws.range_flag : (const int *)nullptr, lens);
     return hipSuccess;
 }
 
