@@ -204,7 +204,7 @@ static void release_handle(fd_context *h)
     free_workspace(h);
     if (h->weight_arena) hipFree(h->weight_arena);
     if (h->scratch) hipFree(h->scratch);
-    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch})
+    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->step_scratch})
         if (s->p) hipFree(s->p);
     for (auto &sl : h->stage) {
         if (sl.host) hipHostFree(sl.host);

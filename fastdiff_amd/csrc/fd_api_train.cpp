@@ -578,4 +578,69 @@ int fd_gate_backward(fd_handle h, const float *y, const float *dout, int B, int 
     return run(h, stream, "fd_gate_backward", [&](const fdk::Launch &La) { return fdk::gate_backward(La, y, dout, dy, B, C, L); });
 }
 
+// The rest of a training step (fd_kernels_step.hip): the draws, the loss, clip + guard + AdamW.  Partial sums and the optimizer's
+// per-step scalars live in the step scratch buffer.
+static bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int fd_train_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int B, int64_t L, uint64_t seed, const fd_train_state *state,
+                  uint64_t iter_host, float *x_t, float *z, float *steps, void *stream)
+{
+    const char *who = "fd_train_draw";
+    if (!h) return FD_ERR_INVALID;
+    if (!x0 || !alpha || !x_t || !z || !steps) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (T_train < 1 || L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d, L=%lld (a multiple of 4)", who, T_train, (long long)L);
+    if (!aligned(x0, 16) || !aligned(x_t, 16) || !aligned(z, 16) || !aligned(state, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: x0, x_t and z must be 16-byte aligned, state 8-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::train_draw(La, x0, alpha, T_train, B, L, seed, state, iter_host, x_t, z, steps); });
+}
+
+static int check_mse(fd_handle h, int64_t n, const char *who)
+{
+    if (n < 1 || n >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: n=%lld", who, (long long)n);      // (2^24 workgroups)
+    return FD_OK;
+}
+
+int fd_mse_forward(fd_handle h, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, void *stream)
+{
+    const char *who = "fd_mse_forward";
+    if (!h) return FD_ERR_INVALID;
+    if (!eps || !z || !loss || !aligned(state, 8)) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer (or a state that is not 8-byte aligned)", who);
+    FD_TRY(check_mse(h, n, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats(fdk::mse_blocks(n)));
+        return e != hipSuccess ? e : fdk::mse_forward(La, eps, z, n, loss, state, h->step_scratch.p);
+    });
+}
+
+int fd_mse_backward(fd_handle h, const float *eps, const float *z, const float *dloss, int64_t n, float *deps, void *stream)
+{
+    const char *who = "fd_mse_backward";
+    if (!h) return FD_ERR_INVALID;
+    if (!eps || !z || !dloss || !deps) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_mse(h, n, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::mse_backward(La, eps, z, dloss, n, deps); });
+}
+
+int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, void *stream)
+{
+    const char *who = "fd_adamw_multi";
+    if (!h) return FD_ERR_INVALID;
+    if (!items || !hyper || !state || !aligned(hyper, 8) || !aligned(state, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer (hyper and state: device memory, 8-byte aligned)", who);
+    if (n <= 0 || n > 65536) FD_FAIL(h, FD_ERR_INVALID, "%s: n=%d", who, n);
+    for (int i = 0; i < n; ++i) {
+        const fd_adamw_item &I = items[i];
+        if (I.numel <= 0 || I.numel >= ((int64_t)1 << 32) || !I.p || !I.m || !I.v)
+            FD_FAIL(h, FD_ERR_INVALID, "%s: item %d: numel=%lld or a null pointer", who, i, (long long)I.numel);
+    }
+    if (fdk::adamw_blocks(items, n) > ((int64_t)1 << 24))      // (workgroup indices are int; 2^36 elements is far beyond any model here)
+        FD_FAIL(h, FD_ERR_UNSUPPORTED, "%s: more than 2^24 workgroups of %d elements in one call", who, FD_STEP_RUN * 256);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats(fdk::adamw_blocks(items, n)));
+        return e != hipSuccess ? e : fdk::adamw_multi(La, items, n, hyper, state, h->step_scratch.p);
+    });
+}
+
 }  // extern "C"

@@ -351,6 +351,7 @@ struct fd_context {
     Scratch kconv_scratch;                   // the partial sums of fd_kconv_backward* and fd_input_conv_backward*
     Scratch cconv_scratch;                   // per-workgroup partial sums of fd_conv32 / conv7 / upsample backward's dW / db
     Scratch span_scratch;                    // fd_sample_span's window batch: mel, injected x_T / z and x_0 of up to 8 windows
+    Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
     std::map<std::string, std::pair<int64_t, double>> prof_acc;

@@ -111,6 +111,16 @@ hipError_t convt_backward(const Launch &L, const float *x, const float *w, const
 // torch._weight_norm(v, g, 0) on [rows, cols] views and its backward for n tensors in ceil(n / 28) launches (fd_kernels_cconv.hip): items
 // in HOST memory (include/fastdiff_hip.h: fd_wn_item), passed on as kernel arguments
 hipError_t weight_norm_multi(const Launch &L, const fd_wn_item *items, int n, bool backward);
+// the rest of a training step (fd_kernels_step.hip; include/fastdiff_hip_train.h): the draws, the loss, clip + guard + AdamW.
+// scratch: step_scratch_floats(mse_blocks(n) or adamw_blocks(items, n)) floats of the handle's step scratch
+size_t step_scratch_floats(int64_t blocks);
+int64_t mse_blocks(int64_t n);
+int64_t adamw_blocks(const fd_adamw_item *items, int n);
+hipError_t train_draw(const Launch &L, const float *x0, const float *alpha, int T_train, int B, int64_t len, uint64_t seed,
+                      const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps);
+hipError_t mse_forward(const Launch &L, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, float *scratch);
+hipError_t mse_backward(const Launch &L, const float *eps, const float *z, const float *dloss, int64_t n, float *deps);
+hipError_t adamw_multi(const Launch &L, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch);
 }  // namespace fdk
 
 // The exact-fp32 reference kernels (fd_generic.hip): one thread per output, runtime shapes, fp32 multiply-adds in a fixed order.  The

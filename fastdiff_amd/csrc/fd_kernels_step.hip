@@ -1,0 +1,332 @@
+// fd_kernels_step.hip -- the rest of a training step around the denoiser's forward and backward (include/fastdiff_hip_train.h, last
+// section): the draws of theta_timestep_loss, the MSE loss both ways, and clip_grad_norm_ + non-finite guard + AdamW over all
+// parameter tensors.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
+// update is skipped -- is read from and written to device memory, so a captured step replays with fresh draws and no host round trip.
+//
+// Sums (loss, squared gradient norm): a thread adds RUN = FD_STEP_RUN elements serially, the 256 threads of a workgroup are added by a
+// butterfly inside each wave and a fixed tree over the four waves, the per-workgroup results go to the handle's step scratch, and one
+// final workgroup adds those by the same tree, 256 at a time and then the up to 256 results of that (65536 partial sums, 2^28
+// elements).  An element therefore passes through RUN + ceil(log2(n / RUN)) additions at most up to that size: the bound of
+// tests/test_train_step.py.  No atomics: the order, and with it the result, is the same every run.
+//
+// All memory-bound and small next to the step (15.3 M parameters: 7 streams of 61 MB; the loss: 3 of 2 MB).  Tensors of the optimizer
+// are addressed element-wise, 256 consecutive floats per wave-group instruction: parameter and gradient tensors are views of arbitrary
+// offset and length (a weight-norm g of 1 element next to a 24576 x 64 x 3 weight), so no 16-byte alignment can be assumed there.
+#include <algorithm>
+
+#include "fd_kernels.h"
+#include "fd_device.h"
+
+// x_t and the optimizer's update are defined operation by operation (torch evaluates them as separate element-wise passes): no
+// multiply-add contraction in this file.  (fmaf() calls stay what they say.)
+#pragma clang fp contract(off)
+
+namespace fdk {
+namespace {
+
+constexpr int RUN = FD_STEP_RUN;
+constexpr int WG = 256;
+constexpr int TILE = RUN * WG;             // elements per workgroup
+
+// inf or NaN, on the bits.  The build (-fno-honor-nans) lets the compiler assume that no float it computes with is a NaN -- it turns a
+// plain exponent test on a value that also feeds an fma into "is infinite" -- so the bits pass through an empty asm first.
+__device__ __forceinline__ bool not_finite(float v)
+{
+    unsigned u = __float_as_uint(v);
+    asm volatile("" : "+v"(u));
+    return (u & 0x7F800000u) == 0x7F800000u;
+}
+
+// the sum of v over the workgroup's 256 threads, in every thread: butterfly inside a wave, then (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ float block_sum(float v)
+{
+    __shared__ float ws[WG / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float r = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    __syncthreads();      // (ws is free again: the final workgroup calls this in a loop)
+    return r;
+}
+
+// ---- the draws ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WG) k_train_draw(const float4 *x0, const float *alpha, uint32_t T_train, int64_t l4, int64_t n4,
+                                                   unsigned long long seed, const fd_train_state *state, unsigned long long iter_host,
+                                                   float4 *x_t, float4 *z, float *steps)
+{
+    const int64_t i4 = (int64_t)blockIdx.x * WG + threadIdx.x;
+    if (i4 >= n4) return;
+    const unsigned long long it = state ? state->iter : iter_host;
+    const int64_t b = i4 / l4;
+    uint32_t r[4];
+    philox4x32_10((uint32_t)(b >> 2), (uint32_t)((uint64_t)(b >> 2) >> 32) ^ (uint32_t)it, 0xFFFFFFFDu, 0x5EEDu ^ (uint32_t)(it >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r);
+    const int c = (int)(b & 3);
+    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
+    const uint32_t ts = (uint32_t)(((uint64_t)w * (uint64_t)T_train) >> 32);      // < T_train
+    if (i4 == b * l4) steps[b] = (float)ts;
+    const float a = alpha[ts];
+    const float d = sqrtf(1.0f - a * a);
+    const float4 q = philox_normal4(seed, 0xFFFFFFFEu, (uint64_t)i4, it);
+    const float4 x = x0[i4];
+    z[i4] = q;
+    x_t[i4] = make_float4(a * x.x + d * q.x, a * x.y + d * q.y, a * x.z + d * q.z, a * x.w + d * q.w);
+}
+
+// ---- the loss ----------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WG) k_mse_partial(const float *eps, const float *z, int64_t n, float *partial)
+{
+    const int64_t base = (int64_t)blockIdx.x * TILE + threadIdx.x;
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        const int64_t i = base + (int64_t)j * WG;
+        if (i < n) {
+            const float d = eps[i] - z[i];
+            acc = fmaf(d, d, acc);
+        }
+    }
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+// the final workgroup's sum of P per-workgroup results, a tree as well: groups of 256 through block_sum into LDS, then those (P <= 65536,
+// i.e. 2^28 elements; beyond that a thread first adds every 65536th serially).  Adding the zeros of an incomplete group is exact.
+__device__ __forceinline__ float final_sum(const float *partial, int64_t P)
+{
+    __shared__ float level[WG];
+    constexpr int64_t SPAN = (int64_t)WG * WG;
+    if (P <= WG) return block_sum(threadIdx.x < P ? partial[threadIdx.x] : 0.0f);
+    for (int c = 0; c < WG; ++c) {
+        float acc = 0.0f;
+        for (int64_t i = (int64_t)c * WG + threadIdx.x; i < P; i += SPAN) acc += partial[i];
+        acc = (int64_t)c * WG < P ? block_sum(acc) : 0.0f;      // (uniform over the workgroup)
+        if (threadIdx.x == 0) level[c] = acc;
+    }
+    __syncthreads();
+    return block_sum(level[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(WG) k_mse_final(const float *partial, int64_t P, int64_t n, float *loss, fd_train_state *state)
+{
+    const float total = final_sum(partial, P);
+    if (threadIdx.x == 0) {
+        const float l = (float)((double)total / (double)n);
+        *loss = l;
+        if (state) state->loss = l;
+    }
+}
+
+__global__ void __launch_bounds__(WG) k_mse_backward(const float *eps, const float *z, const float *dloss, int64_t n, float *deps)
+{
+    const float s = (float)(2.0 * (double)*dloss / (double)n);
+    const int64_t base = (int64_t)blockIdx.x * TILE + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        const int64_t i = base + (int64_t)j * WG;
+        if (i < n) deps[i] = (eps[i] - z[i]) * s;
+    }
+}
+
+// ---- clip + guard + AdamW -------------------------------------------------------------------------------------------------------------
+// The records travel as kernel arguments (<= AD_CHUNK per launch: 2.8 KB of the 4 KB a launch may carry), as weight_norm_multi's do.
+// first_block: the first workgroup of each tensor (TILE elements per workgroup, no workgroup straddles two tensors).
+constexpr int AD_CHUNK = 64;
+struct AdamChunk {
+    fd_adamw_item it[AD_CHUNK];
+    int first_block[AD_CHUNK + 1];
+    int n;
+    int part0;      // this launch's first slot in the partial sums
+    int last;       // the step's last launch: it advances the state
+};
+
+// what the final workgroup of the norm decides for the update launches (the head of the step scratch)
+struct AdamDecision {
+    float clip, decay, w1, beta2, w2, step_size, bc2_sqrt, eps;
+    int skip;
+};
+constexpr int DEC_FLOATS = 16;
+static_assert(sizeof(AdamDecision) <= DEC_FLOATS * sizeof(float), "the decision record's slot");
+
+__device__ __forceinline__ int ad_find_item(const AdamChunk &c, int blk)
+{
+    int lo = 0, hi = c.n;      // first_block[lo] <= blk < first_block[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (c.first_block[mid] <= blk) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(WG) k_adamw_norm(const AdamChunk c, float *partial, unsigned *flags)
+{
+    const int it = ad_find_item(c, blockIdx.x);
+    const float *g = c.it[it].g;
+    const int64_t numel = c.it[it].numel;
+    const int64_t base = (int64_t)(blockIdx.x - c.first_block[it]) * TILE + threadIdx.x;
+    float acc = 0.0f;
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        const int64_t i = base + (int64_t)j * WG;
+        if (i < numel) {
+            const float v = g[i];
+            acc = fmaf(v, v, acc);
+            bad |= not_finite(v) ? 1 : 0;
+        }
+    }
+    acc = block_sum(acc);
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        partial[c.part0 + blockIdx.x] = acc;
+        flags[c.part0 + blockIdx.x] = bad ? 1u : 0u;
+    }
+}
+
+__device__ __forceinline__ double ipow(double x, unsigned long long t)      // x^t by squaring: a few double roundings
+{
+    double r = 1.0;
+    while (t) {
+        if (t & 1ull) r *= x;
+        x *= x;
+        t >>= 1;
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(WG) k_adamw_final(const float *partial, const unsigned *flags, int64_t P, const fd_adamw_hyper *hyper,
+                                                    fd_train_state *state, AdamDecision *dec)
+{
+    int bad = 0;
+    for (int64_t i = threadIdx.x; i < P; i += WG) bad |= (int)flags[i];
+    const float total = final_sum(partial, P);
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0) return;
+    const float norm = sqrtf(total);
+    const fd_adamw_hyper hy = *hyper;
+    const unsigned long long t = state->applied + 1ull;
+    AdamDecision d;
+    d.skip = (bad || not_finite(norm)) ? 1 : 0;
+    const float coef = (float)hy.max_norm / (norm + 1e-6f);
+    d.clip = (hy.max_norm != 0.0 && !d.skip && coef < 1.0f) ? coef : 1.0f;
+    d.decay = (float)(1.0 - hy.lr * hy.weight_decay);
+    d.w1 = (float)(1.0 - hy.beta1);
+    d.beta2 = (float)hy.beta2;
+    d.w2 = (float)(1.0 - hy.beta2);
+    d.step_size = (float)(hy.lr / (1.0 - ipow(hy.beta1, t)));
+    d.bc2_sqrt = (float)sqrt(1.0 - ipow(hy.beta2, t));
+    d.eps = (float)hy.eps;
+    *dec = d;
+    state->grad_norm = norm;
+}
+
+__global__ void __launch_bounds__(WG) k_adamw_update(const AdamChunk c, const AdamDecision *dec, fd_train_state *state)
+{
+    const AdamDecision d = *dec;
+    if (c.last && blockIdx.x == 0 && threadIdx.x == 0) {      // nothing else in this launch reads the state
+        state->iter += 1ull;
+        if (d.skip) state->skipped += 1ull; else state->applied += 1ull;
+    }
+    if (d.skip || (int)blockIdx.x >= c.first_block[c.n]) return;
+    const int it = ad_find_item(c, blockIdx.x);
+    const float *g = c.it[it].g;
+    float *p = c.it[it].p, *m = c.it[it].m, *v = c.it[it].v;
+    const int64_t numel = c.it[it].numel;
+    const int64_t base = (int64_t)(blockIdx.x - c.first_block[it]) * TILE + threadIdx.x;
+#pragma unroll 4
+    for (int j = 0; j < RUN; ++j) {
+        const int64_t i = base + (int64_t)j * WG;
+        if (i < numel) {
+            const float gi = g[i] * d.clip;
+            float pi = p[i] * d.decay, mi = m[i], vi = v[i];
+            mi = mi + d.w1 * (gi - mi);
+            vi = vi * d.beta2 + (d.w2 * gi) * gi;
+            const float denom = sqrtf(vi) / d.bc2_sqrt + d.eps;
+            pi = pi - (d.step_size * mi) / denom;
+            p[i] = pi;
+            m[i] = mi;
+            v[i] = vi;
+        }
+    }
+}
+
+inline int64_t tiles(int64_t n) { return (n + TILE - 1) / TILE; }
+
+}  // namespace
+
+size_t step_scratch_floats(int64_t blocks) { return (size_t)DEC_FLOATS + 2 * (size_t)blocks; }
+int64_t mse_blocks(int64_t n) { return tiles(n); }
+int64_t adamw_blocks(const fd_adamw_item *items, int n)
+{
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i)
+        if (items[i].g) blocks += tiles(items[i].numel);
+    return blocks;
+}
+
+hipError_t train_draw(const Launch &L_, const float *x0, const float *alpha, int T_train, int B, int64_t len, uint64_t seed,
+                      const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps)
+{
+    const int64_t l4 = len / 4, n4 = l4 * B;
+    FD_LAUNCH(L_, "train_draw", k_train_draw, dim3((unsigned)((n4 + WG - 1) / WG)), dim3(WG), 0, reinterpret_cast<const float4 *>(x0), alpha,
+              (uint32_t)T_train, l4, n4, (unsigned long long)seed, state, (unsigned long long)iter_host, reinterpret_cast<float4 *>(x_t),
+              reinterpret_cast<float4 *>(z), steps);
+    return hipSuccess;
+}
+
+hipError_t mse_forward(const Launch &L_, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, float *scratch)
+{
+    float *partial = scratch + DEC_FLOATS;
+    const int64_t P = tiles(n);
+    FD_LAUNCH(L_, "mse_partial", k_mse_partial, dim3((unsigned)P), dim3(WG), 0, eps, z, n, partial);
+    FD_LAUNCH(L_, "mse_final", k_mse_final, dim3(1), dim3(WG), 0, (const float *)partial, P, n, loss, state);
+    return hipSuccess;
+}
+
+hipError_t mse_backward(const Launch &L_, const float *eps, const float *z, const float *dloss, int64_t n, float *deps)
+{
+    FD_LAUNCH(L_, "mse_backward", k_mse_backward, dim3((unsigned)tiles(n)), dim3(WG), 0, eps, z, dloss, n, deps);
+    return hipSuccess;
+}
+
+// items: HOST memory
+hipError_t adamw_multi(const Launch &L_, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch)
+{
+    const int64_t P = adamw_blocks(items, n);
+    AdamDecision *dec = reinterpret_cast<AdamDecision *>(scratch);
+    float *partial = scratch + DEC_FLOATS;
+    unsigned *flags = reinterpret_cast<unsigned *>(partial + P);
+    // the tensors that took part, AD_CHUNK per launch
+    std::vector<AdamChunk> chunks;
+    int part0 = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!items[i].g) continue;
+        if (chunks.empty() || chunks.back().n == AD_CHUNK) {
+            if (!chunks.empty()) part0 += chunks.back().first_block[AD_CHUNK];
+            AdamChunk c;
+            memset(&c, 0, sizeof(c));
+            c.part0 = part0;
+            chunks.push_back(c);
+        }
+        AdamChunk &c = chunks.back();
+        c.it[c.n] = items[i];
+        const int blocks = c.first_block[c.n] + (int)tiles(items[i].numel);
+        for (int k = ++c.n; k <= AD_CHUNK; ++k) c.first_block[k] = blocks;
+    }
+    if (chunks.empty()) {      // no gradient at all: the norm is 0, the state still advances
+        AdamChunk c;
+        memset(&c, 0, sizeof(c));
+        chunks.push_back(c);
+    }
+    chunks.back().last = 1;
+    for (const AdamChunk &c : chunks)
+        if (c.first_block[c.n] > 0) FD_LAUNCH(L_, "adamw_norm", k_adamw_norm, dim3((unsigned)c.first_block[c.n]), dim3(WG), 0, c, partial, flags);
+    FD_LAUNCH(L_, "adamw_final", k_adamw_final, dim3(1), dim3(WG), 0, (const float *)partial, (const unsigned *)flags, P, hyper, state, dec);
+    for (const AdamChunk &c : chunks)
+        if (c.first_block[c.n] > 0 || c.last)
+            FD_LAUNCH(L_, "adamw_update", k_adamw_update, dim3((unsigned)std::max(c.first_block[c.n], 1)), dim3(WG), 0, c, (const AdamDecision *)dec, state);
+    return hipSuccess;
+}
+
+}  // namespace fdk

@@ -935,3 +935,84 @@ def location_variable_convolution_frames(x, kernel_frames, bias, hop_size, grad_
     with respect to the frames comes back in the "grad" order (what kernel_conv1d_frames' backward reads).  grad_slot / bias_slot: the
     slots split_layers hands out with the slices of the frames / of bias_conv's [B, layers, 64, T] output."""
     return _LVCFrames.apply(x, kernel_frames, bias, hop_size, grad_slot, bias_slot)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The rest of a training step (include/fastdiff_hip_train.h, last section): the draws, the loss, clip + guard + AdamW
+# ---------------------------------------------------------------------------------------------------------------------------------
+TS_STREAM, Z_STREAM = 0xFFFFFFFD, 0xFFFFFFFE      # the Philox streams of a training step's ts and z (DESIGN.md 3.4)
+
+
+class AdamWHyper(ct.Structure):
+    """fd_adamw_hyper."""
+    _fields_ = [(k, ct.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
+
+
+def new_train_state(device):
+    """A zeroed fd_train_state: 32 bytes of device memory, as four int64 words (iter, applied, skipped, {grad_norm, loss})."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def read_train_state(state):
+    """fd_train_state -> dict (synchronises)."""
+    import numpy as np
+    raw = state.cpu().numpy()
+    f = raw[3:4].view(np.float32)
+    return {"iter": int(raw[0]) & 0xFFFFFFFFFFFFFFFF, "applied": int(raw[1]) & 0xFFFFFFFFFFFFFFFF, "skipped": int(raw[2]) & 0xFFFFFFFFFFFFFFFF,
+            "grad_norm": float(f[0]), "loss": float(f[1])}
+
+
+def train_draw(x0, alpha, T_train, seed=0, iteration=0, state=None, out=None):
+    """The draws of theta_timestep_loss (util.py:312-318) on the device (fd_train_draw): x0 [B, 1, L] (L a multiple of 4), alpha [T_train]
+    on the same device -> (x_t, z, steps [B, 1] float32).  The step index that keys the draws is state's `iter` (read on the device when
+    the kernel runs: a captured call draws anew on every replay) or, without a state, `iteration`.  out: (x_t, z, steps) to write into."""
+    if not x0.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.train_draw runs only on a HIP device (no CPU fallback)")
+    x0, alpha = _f32(x0, alpha)
+    B, L = x0.shape[0], x0.numel() // x0.shape[0]
+    assert alpha.numel() == int(T_train) and alpha.device == x0.device, "alpha: [T_train] on the device of the audio"
+    x_t, z, steps = out if out is not None else (torch.empty_like(x0), torch.empty_like(x0), torch.empty((B, 1), device=x0.device, dtype=torch.float32))
+    _call(x0.device, "fd_train_draw", "fd_train_draw", x0, alpha, int(T_train), B, L, int(seed) & 0xFFFFFFFFFFFFFFFF, state,
+          int(iteration) & 0xFFFFFFFFFFFFFFFF, x_t, z, steps)
+    return x_t, z, steps
+
+
+class _MSE(torch.autograd.Function):
+    """nn.MSELoss() (util.py:307,325) as one fixed-order sum forward (fd_mse_forward) and one pass backward (fd_mse_backward); z is the
+    target: it receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, eps, z, state):
+        ctx.in_dtypes = (eps.dtype,)
+        eps, z = _f32(eps, z)
+        assert eps.shape == z.shape
+        loss = torch.empty((), device=eps.device, dtype=torch.float32)
+        _call(eps.device, "fd_mse_forward", "fd_mse_forward", eps, z, eps.numel(), loss, state)
+        ctx.save_for_backward(eps, z)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eps, z = ctx.saved_tensors
+        deps = torch.empty_like(eps)
+        _call(eps.device, "fd_mse_backward", "fd_mse_backward", eps, z, dloss.contiguous().float(), eps.numel(), deps)
+        return _cast_back(ctx, deps) + (None, None)
+
+
+def mse_loss(eps, z, state=None):
+    """mean((eps - z)^2) on the HIP kernels, differentiable in eps; state (a new_train_state tensor) also receives the loss."""
+    if not (eps.is_cuda and z.is_cuda):
+        raise RuntimeError("fastdiff_amd.lvc_op.mse_loss runs only on a HIP device (no CPU fallback)")
+    return _MSE.apply(eps, z, state)
+
+
+def adamw_multi(items, hyper, state):
+    """clip_grad_norm_ + non-finite guard + AdamW.step() over all tensors (fd_adamw_multi).  items: [(p, g or None, m, v)] float32
+    contiguous HIP tensors; hyper: a device tensor holding an AdamWHyper; state: a new_train_state tensor."""
+    import numpy as np
+    tab = np.zeros((len(items), 5), dtype=np.int64)      # fd_adamw_item: p, g, m, v, numel
+    for i, (p, g, m, v) in enumerate(items):
+        assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and p.dtype == m.dtype == v.dtype == torch.float32
+        assert g is None or (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == p.numel())
+        tab[i] = (p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+    _call(state.device, "fd_adamw_multi", "fd_adamw_multi", tab.ctypes.data, len(items), hyper, state)

@@ -206,18 +206,33 @@ def sampling_given_noise_schedule(net, size, diffusion_hyperparams, inference_no
     return trajectory if return_sequence else x
 
 
-def theta_timestep_loss(net, X, diffusion_hyperparams, reverse=False):
-    """MSE(eps_theta(x_t, mel, t), z) at a random training step per item; same signature as util.py:291-325.
+def theta_timestep_loss(net, X, diffusion_hyperparams, reverse=False, *, noise_source="reference", seed=0, iteration=0):
+    """MSE(eps_theta(x_t, mel, t), z) at a random training step per item; same positional signature as util.py:291-325.
 
     FastDiffTask.validation_step reports this quantity under no_grad (FastDiff.py:52-57): one denoiser evaluation on the inference
     kernels.  _training_step (FastDiff.py:44-49) calls the same function with the module in train() mode and autograd recording:
     FastDiff.forward then builds the graph of fastdiff_amd/train.py (location-variable convolutions forward and backward on the HIP
     operator), and loss.backward() fills the gradients of the module's weight_g / weight_v / bias parameters.
-    Random draws follow the reference order: torch.randint for the steps, then std_normal for z (both on the CPU generator)."""
+    Random draws follow the reference order: torch.randint for the steps, then std_normal for z (both on the CPU generator).
+    Keyword-only: noise_source="device" draws the steps and z with the on-device Philox generator instead, keyed by (seed, iteration)
+    -- pass the training step's number as `iteration` -- forms x_t in the same kernel and evaluates the loss on the fixed-order HIP sum
+    (lvc_op.train_draw / mse_loss); nothing is drawn on the host and nothing is copied to the device.  Usable under no_grad as well."""
     assert type(X) == tuple and len(X) == 2
     mel_spectrogram, audio = X
     T_train, alpha = diffusion_hyperparams["T"], diffusion_hyperparams["alpha"]
     n_items = audio.shape[0]
+    if noise_source == "device":
+        from .lvc_op import train_draw, mse_loss
+        alpha = alpha.to(audio.device)
+        x_t, z, steps = train_draw(audio, alpha, T_train, seed=seed, iteration=iteration)
+        x_t, z = x_t.view(audio.shape), z.view(audio.shape)
+        eps = net((x_t, mel_spectrogram, steps))
+        loss = mse_loss(eps, z)
+        if reverse:
+            alpha_t = alpha[steps.long().view(n_items, 1, 1)]
+            return loss, (x_t - (1 - alpha_t ** 2.).sqrt() * eps) / alpha_t
+        return loss
+    assert noise_source == "reference", noise_source
     ts = torch.randint(T_train, size=(n_items, 1, 1)).cuda()
     z = std_normal(audio.shape)
     alpha_t = alpha.to(ts.device)[ts]

@@ -183,6 +183,60 @@ FD_API int fd_conv32_backward(fd_handle h, const float *xs, const float *y, cons
                               int64_t L, int dilation, float pre_slope, float post_slope, float *dxs, float *dweight, float *dbias,
                               void *stream);
 
+/* The rest of a training step (FastDiffTask._training_step, FastDiff.py:44-49; theta_timestep_loss, util.py:291-325; base_task.py:231-233;
+ * FastDiff.py:121-125) around the forward and backward above: the draws of a step, the loss, the global gradient norm with its clip, the
+ * non-finite guard and AdamW -- with every per-step quantity in DEVICE memory, so that a whole step is one graph replay that draws anew,
+ * and the host never waits for it.  Sums run in a fixed order (per-thread runs of FD_STEP_RUN elements, a tree inside the workgroup,
+ * per-workgroup partial sums in a scratch buffer of the handle, one final workgroup): no floating-point atomics, two runs agree bit for
+ * bit.  Calls on one handle must be ordered on one stream, and the first call at a new size must not sit inside a graph capture (the
+ * scratch buffer grows then).  Growing frees the old buffer: a graph captured earlier on this handle has its address baked in and must
+ * not be replayed after a LARGER fd_mse_forward / fd_adamw_multi call on the same handle (capture again) -- as with the scratch buffers
+ * of the backward operators above.  At most 2^36 elements per call.
+ *
+ * fd_train_state: 32 bytes of device memory owned by the caller (zero it before the first step).  Only kernels write it. */
+typedef struct fd_train_state {
+    uint64_t iter;        /* steps drawn so far: the id slot of the step's Philox draws */
+    uint64_t applied;     /* optimizer steps applied (AdamW's `step`) */
+    uint64_t skipped;     /* optimizer steps skipped because a gradient was not finite */
+    float grad_norm;      /* global L2 norm of the gradients of the last step, before clipping */
+    float loss;           /* loss of the last step */
+} fd_train_state;
+#define FD_STEP_RUN 16     /* elements a thread adds up serially in the sums of this section (the rest of a sum is a tree) */
+
+/* The draws of theta_timestep_loss (util.py:312-318) on the device: x0 [B,1,L] -> steps [B,1] (float, as the network takes them),
+ * z [B,1,L] ~ N(0, I) and x_t = alpha[ts] * x0 + sqrt(1 - alpha[ts]^2) * z, every operation rounded on its own (what torch evaluates on
+ * the same z, bit for bit).  With `it` = state ? state->iter (read on the device: a replay draws anew) : iter_host,
+ *   ts[b] = (w * T_train) >> 32 (64-bit product), w = word b & 3 of Philox4x32-10 keyed (seed, stream 0xFFFFFFFD, position b >> 2, id it),
+ *   z[b,t] = component (b L + t) & 3 of the generator's normal4 keyed (seed, stream 0xFFFFFFFE, position (b L + t) >> 2, id it)
+ * (oracle/philox.py is the host twin).  alpha: device [T_train]; L a multiple of 4; x0, x_t, z 16-byte aligned. */
+FD_API int fd_train_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int B, int64_t L, uint64_t seed,
+                         const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps, void *stream);
+
+/* nn.MSELoss() (util.py:307,325) and its backward: *loss = mean((eps - z)^2) (also into state->loss when state is not NULL);
+ * deps = *dloss * 2 (eps - z) / n.  loss, dloss: device scalars. */
+FD_API int fd_mse_forward(fd_handle h, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, void *stream);
+FD_API int fd_mse_backward(fd_handle h, const float *eps, const float *z, const float *dloss, int64_t n, float *deps, void *stream);
+
+/* torch.nn.utils.clip_grad_norm_(params, max_norm) (norm type 2), the reference's NaN-gradient guard (trainer.py:320-327) and
+ * torch.optim.AdamW.step() (amsgrad = False) for n parameter tensors in 2 ceil(n / 64) + 1 launches.  items: n records in HOST memory,
+ * passed on as kernel arguments (as fd_wn_item); g == NULL: the parameter took no part in the step and is left alone.  hyper: DEVICE
+ * memory (a learning-rate schedule is a copy of 8 bytes between replays); max_norm == 0: no clipping.
+ *   norm = ||all g||_2 -> state->grad_norm;   c = max_norm ? min(1, max_norm / (norm + 1e-6)) : 1;   t = state->applied + 1
+ *   norm finite:  g' = c g;  p *= 1 - lr wd;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *                 p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);   state->applied += 1
+ *   else:         no p, m or v is written;   state->skipped += 1
+ * and state->iter += 1 either way, in the last launch (behind every read of it in stream order). */
+typedef struct fd_adamw_item {
+    float *p;             /* [numel] parameter */
+    const float *g;       /* [numel] gradient, or NULL */
+    float *m, *v;         /* [numel] exp_avg, exp_avg_sq */
+    int64_t numel;
+} fd_adamw_item;
+typedef struct fd_adamw_hyper {
+    double lr, beta1, beta2, eps, weight_decay, max_norm;      /* doubles, as torch keeps them: 1 - beta2 is then the optimizer's own */
+} fd_adamw_hyper;
+FD_API int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

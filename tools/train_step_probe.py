@@ -35,6 +35,94 @@ def timed(fn, warm=2, reps=5):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
+def full_step_row(B, T, rounds=7, reps=10):
+    """A real training step both ways, alternating within one call, device-synchronised wall time per step (median and range over
+    `rounds` rounds of `reps` steps):
+      (a) fastdiff_amd.TrainStep.step: batch copy + one graph replay (draws, forward, loss, backward, clip, guard, AdamW on the device);
+      (b) the recipe without it: CPU randint + std_normal + copy, x_t on the device, replay of the forward + backward graph,
+          clip_grad_norm_, the reference's NaN scan (trainer.py:320-327), torch.optim.AdamW.step();
+      (c) the forward + backward graph of (b) alone (the figure the rows above report)."""
+    import statistics
+    from fastdiff_amd import schedules, sampler
+    dh = schedules.training_hyperparams()
+    alpha = dh["alpha"].cuda()
+    mel = (torch.rand(B, 80, T) * 7.5 - 6.0).cuda()
+    wav = (0.3 * torch.randn(B, 1, T * 256)).cuda()
+    try:
+        ma, mb = fastdiff_amd.FastDiff().cuda().train(), fastdiff_amd.FastDiff().cuda().train()
+        mb.load_state_dict(ma.state_dict())
+        # (a)
+        ts = fastdiff_amd.TrainStep(ma, dh, seed=1)
+        ts.step(mel, wav)
+        torch.cuda.synchronize()
+        # (b): static inputs of the captured forward + backward
+        x_s, z_s, st_s = torch.empty_like(wav), torch.empty_like(wav), torch.empty(B, 1, device="cuda")
+        opt = torch.optim.AdamW(mb.parameters(), lr=2e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0)
+
+        def draw():
+            t = torch.randint(dh["T"], size=(B, 1, 1)).cuda()
+            z = sampler.std_normal(wav.shape)
+            a = alpha[t]
+            x_s.copy_(a * wav + (1 - a ** 2.).sqrt() * z)
+            z_s.copy_(z)
+            st_s.copy_(t.view(B, 1))
+
+        def fb():
+            eps = train.differentiable_forward(mb, (x_s, mel, st_s), lvc=None)
+            F.mse_loss(eps, z_s).backward()
+
+        draw()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                mb.zero_grad(set_to_none=True)
+                fb()
+        torch.cuda.current_stream().wait_stream(side)
+        mb.zero_grad(set_to_none=True)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            fb()
+
+        def recipe():
+            draw()
+            graph.replay()
+            torch.nn.utils.clip_grad_norm_(mb.parameters(), 1.0)
+            for _, p in mb.named_parameters():
+                if (p.grad is not None) and torch.isnan(p.grad.float()).any():
+                    raise RuntimeError("NaN gradient")
+            opt.step()
+
+        runs = {"(a) TrainStep.step, replayed": lambda: ts.step(mel, wav), "(b) draws on the CPU + forward/backward replay + clip + NaN scan + torch AdamW": recipe,
+                "(c) forward + backward replay alone": graph.replay}
+        times = {k: [] for k in runs}
+        for _ in range(rounds):
+            for k, fn in runs.items():
+                times[k].append(timed(fn, warm=2, reps=reps))
+        print(f"  a real training step at B={B} T={T}, {rounds} alternating rounds of {reps} steps (ms per step: median [min .. max]):")
+        for k, v in times.items():
+            print(f"    {k}: {statistics.median(v):8.3f} [{min(v):.3f} .. {max(v):.3f}]")
+        st = ts.state()
+        print(f"    TrainStep state after the run: {st}")
+        # launches of one step: the kernels of the same calls run eagerly, counted by the profiler (the graph holds the same launches)
+        from torch.profiler import profile, ProfilerActivity
+        eager = fastdiff_amd.TrainStep(ma, dh, seed=1, graph=False)
+        eager.step(mel, wav)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+            eager.step(mel, wav)
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()]
+        ours = [n for n in names if any(k in n for k in ("k_train_draw", "k_mse_", "k_adamw_"))]
+        print(f"    kernel launches of one full step (eager, profiler): {len(names)}, of them draw / loss / optimizer: {len(ours)}")
+    except Exception:      # noqa: BLE001 -- the rows behind this one still run; the probe then ends non-zero
+        import traceback
+        traceback.print_exc()
+        print("  the full-step row FAILED (traceback above)")
+        return False
+    return True
+
+
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
@@ -109,6 +197,7 @@ def main():
         graph_run(" [predictor activations as torch nodes]", _train_fuse_act=False)
         graph_run(" [reference kernel tensor + transposes]", _train_frames=False)
         graph_run("")
+    full_ok = full_step_row(B, T)
     for hop in (8, 64, 256):
         L = T * hop
         y = torch.randn(B, 32, L, device="cuda", requires_grad=True)
@@ -126,7 +215,8 @@ def main():
             tf, tfb = timed(f), timed(fb)
             flops = 2.0 * B * L * 64 * 96
             print(f"  hop {hop:3d} {name:14s}: forward {tf:7.3f} ms ({flops / tf / 1e9:6.1f} TFLOP/s)   forward+backward {tfb:7.3f} ms ({3 * flops / tfb / 1e9:6.1f} TFLOP/s)")
+    return full_ok
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(0 if main() else 1)
