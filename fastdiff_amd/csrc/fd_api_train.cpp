@@ -596,6 +596,25 @@ int fd_train_draw(fd_handle h, const float *x0, const float *alpha, int T_train,
     return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::train_draw(La, x0, alpha, T_train, B, L, seed, state, iter_host, x_t, z, steps); });
 }
 
+int fd_train_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
+                     uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs, float *mels,
+                     int64_t *picked, void *stream)
+{
+    const char *who = "fd_train_collate";
+    if (!h) return FD_ERR_INVALID;
+    if (!wav_arena || !mel_arena || !frame_off || !wavs || !mels || !picked) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (n_items < 1 || n_items > ((int64_t)1 << 28)) FD_FAIL(h, FD_ERR_INVALID, "%s: n_items=%lld (1..2^28)", who, (long long)n_items);
+    if (hop < 4 || hop % 4 != 0 || F < 1 || (int64_t)F * hop >= ((int64_t)1 << 31))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: hop=%d (a multiple of 4), F=%d", who, hop, F);
+    if (world < 1 || rank < 0 || rank >= world) FD_FAIL(h, FD_ERR_INVALID, "%s: rank=%d of world=%d", who, rank, world);
+    if (!aligned(wav_arena, 16) || !aligned(wavs, 16) || !aligned(frame_off, 8) || !aligned(picked, 8) || !aligned(state, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: wav_arena and wavs must be 16-byte aligned, frame_off, picked and state 8-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::train_collate(La, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, rank, world, wavs, mels, picked);
+    });
+}
+
 static int check_mse(fd_handle h, int64_t n, const char *who)
 {
     if (n < 1 || n >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: n=%lld", who, (long long)n);      // (2^24 workgroups)

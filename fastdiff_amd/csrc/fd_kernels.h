@@ -118,6 +118,10 @@ int64_t mse_blocks(int64_t n);
 int64_t adamw_blocks(const fd_adamw_item *items, int n);
 hipError_t train_draw(const Launch &L, const float *x0, const float *alpha, int T_train, int B, int64_t len, uint64_t seed,
                       const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps);
+// one launch, no scratch: slot b's utterance and window chosen on the device, waveform copied, mel block transposed to [80, F]
+hipError_t train_collate(const Launch &L, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                         int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
+                         float *mels, int64_t *picked);
 hipError_t mse_forward(const Launch &L, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, float *scratch);
 hipError_t mse_backward(const Launch &L, const float *eps, const float *z, const float *dloss, int64_t n, float *deps);
 hipError_t adamw_multi(const Launch &L, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch);

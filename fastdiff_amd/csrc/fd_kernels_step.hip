@@ -1,6 +1,6 @@
 // fd_kernels_step.hip -- the rest of a training step around the denoiser's forward and backward (include/fastdiff_hip_train.h, last
-// section): the draws of theta_timestep_loss, the MSE loss both ways, and clip_grad_norm_ + non-finite guard + AdamW over all
-// parameter tensors.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
+// section): the batch cut from a device-resident corpus, the draws of theta_timestep_loss, the MSE loss both ways, and
+// clip_grad_norm_ + non-finite guard + AdamW over all parameter tensors.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
 // update is skipped -- is read from and written to device memory, so a captured step replays with fresh draws and no host round trip.
 //
 // Sums (loss, squared gradient norm): a thread adds RUN = FD_STEP_RUN elements serially, the 256 threads of a workgroup are added by a
@@ -72,6 +72,97 @@ __global__ void __launch_bounds__(WG) k_train_draw(const float4 *x0, const float
     const float4 x = x0[i4];
     z[i4] = q;
     x_t[i4] = make_float4(a * x.x + d * q.x, a * x.y + d * q.y, a * x.z + d * q.z, a * x.w + d * q.w);
+}
+
+// ---- the batch ---------------------------------------------------------------------------------------------------------------------
+// A training batch cut from a device-resident corpus (include/fastdiff_hip_train.h: fd_train_collate; fastdiff_amd/corpus.py holds the
+// arenas and the host twin of the choice).  Which utterance and which window slot b of step `it` takes is a pure function of
+// (seed, it, b, rank, world, n, T_item - F), recomputed by every thread (a few dozen Philox calls, uniform over the workgroup).
+__device__ __forceinline__ void philox_keyed(unsigned long long seed, uint32_t stream, uint64_t pos, unsigned long long uid, uint32_t r[4])
+{
+    philox4x32_10((uint32_t)pos, (uint32_t)(pos >> 32) ^ (uint32_t)uid, stream, 0x5EEDu ^ (uint32_t)(uid >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r);
+}
+
+// pi_e(j): a 4-round balanced Feistel network on 2k bits (4^k >= n > 4^(k-1)), walked along its cycle until it lands below n -- a
+// bijection of [0, n) for every epoch e, evaluated per element.  Round function: word 0 of the generator keyed (seed, stream
+// 0xFFFFFFFB, position = half ^ (round << 28), id = e); n <= 2^28 keeps the round number clear of the half.
+__device__ __forceinline__ uint64_t collate_perm(uint64_t j, uint64_t n, unsigned long long seed, unsigned long long e)
+{
+    int k = 0;
+    while (((uint64_t)1 << (2 * k)) < n) ++k;
+    const uint32_t mask = ((uint32_t)1 << k) - 1u;
+    uint64_t x = j;
+    do {
+        uint32_t l = (uint32_t)(x >> k), r = (uint32_t)x & mask;
+#pragma unroll 1
+        for (uint32_t round = 0; round < 4; ++round) {
+            uint32_t w[4];
+            philox_keyed(seed, 0xFFFFFFFBu, (uint64_t)(r ^ (round << 28)), e, w);
+            const uint32_t t = l ^ (w[0] & mask);
+            l = r;
+            r = t;
+        }
+        x = ((uint64_t)l << k) | r;
+    } while (x >= n);
+    return x;
+}
+
+constexpr int CL_MELS = 80;                      // mel bins of a frame
+constexpr int CL_TF = 64;                        // frames per transposed tile: one wave writes 64 consecutive floats of a mel row
+constexpr int CL_LD = CL_MELS + 1;               // tile row stride: 81 = 17 mod 32, so the 64 frames of a column read fall on distinct banks
+constexpr int CL_WAV4 = 4 * WG;                  // float4s of waveform a workgroup copies
+
+// grid (mel tiles + waveform chunks, B).  Source of the mel: the contiguous [F, 80] block of the arena, read element-wise in order
+// (coalesced), written into LDS row by row; destination [80, F]: a wave reads one column of the tile and writes 64 consecutive floats.
+__global__ void __launch_bounds__(WG) k_train_collate(const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
+                                                      int hop, int F, int B, unsigned long long seed, const fd_train_state *state,
+                                                      unsigned long long iter_host, int rank, int world, int mel_tiles, float *wavs,
+                                                      float *mels, int64_t *picked)
+{
+    __shared__ float tile[CL_TF * CL_LD];
+    const int b = blockIdx.y;
+    const unsigned long long it = state ? state->iter : iter_host;
+    const uint64_t g = (it * (uint64_t)B + (uint64_t)b) * (uint64_t)world + (uint64_t)rank;
+    const uint64_t epoch = g / (uint64_t)n_items;
+    const int64_t item = (int64_t)collate_perm(g % (uint64_t)n_items, (uint64_t)n_items, seed, epoch);
+    const int64_t first = frame_off[item];
+    const int64_t range = frame_off[item + 1] - first - F;      // the window starts in [0, range)
+    uint32_t r[4];
+    philox_keyed(seed, 0xFFFFFFFCu, (uint64_t)(b >> 2), it, r);
+    const int c = b & 3;
+    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
+    const bool ok = range >= 1 && range < ((int64_t)1 << 32);   // (a table that breaks the corpus' filter: nothing is read)
+    const int64_t start = ok ? (int64_t)(((uint64_t)w * (uint64_t)range) >> 32) : -1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        picked[2 * b] = item;
+        picked[2 * b + 1] = start;
+    }
+    if (!ok) return;
+    if ((int)blockIdx.x < mel_tiles) {
+        const int f0 = (int)blockIdx.x * CL_TF;
+        const int nf = min(CL_TF, F - f0);
+        const float *src = mel_arena + (first + start + f0) * CL_MELS;
+        for (int e = threadIdx.x; e < nf * CL_MELS; e += WG) {
+            const int f = e / CL_MELS;
+            tile[f * CL_LD + (e - f * CL_MELS)] = src[e];
+        }
+        __syncthreads();
+        float *dst = mels + (int64_t)b * CL_MELS * F + f0;
+        const int f = threadIdx.x & 63;
+        if (f < nf)
+            for (int m = threadIdx.x >> 6; m < CL_MELS; m += WG / 64) dst[(int64_t)m * F + f] = tile[f * CL_LD + m];
+    } else {
+        const int64_t l4 = (int64_t)F * (hop / 4);
+        const float4 *src = reinterpret_cast<const float4 *>(wav_arena + (first + start) * hop);
+        float4 *dst = reinterpret_cast<float4 *>(wavs) + (int64_t)b * l4;
+        const int64_t base = (int64_t)((int)blockIdx.x - mel_tiles) * CL_WAV4 + threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < CL_WAV4 / WG; ++j) {
+            const int64_t i = base + (int64_t)j * WG;
+            if (i < l4) dst[i] = src[i];
+        }
+    }
 }
 
 // ---- the loss ----------------------------------------------------------------------------------------------------------------------
@@ -272,6 +363,19 @@ hipError_t train_draw(const Launch &L_, const float *x0, const float *alpha, int
     FD_LAUNCH(L_, "train_draw", k_train_draw, dim3((unsigned)((n4 + WG - 1) / WG)), dim3(WG), 0, reinterpret_cast<const float4 *>(x0), alpha,
               (uint32_t)T_train, l4, n4, (unsigned long long)seed, state, (unsigned long long)iter_host, reinterpret_cast<float4 *>(x_t),
               reinterpret_cast<float4 *>(z), steps);
+    return hipSuccess;
+}
+
+hipError_t train_collate(const Launch &L_, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                         int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
+                         float *mels, int64_t *picked)
+{
+    const int mel_tiles = (F + CL_TF - 1) / CL_TF;
+    const int64_t l4 = (int64_t)F * (hop / 4);
+    const int wav_chunks = (int)((l4 + CL_WAV4 - 1) / CL_WAV4);
+    FD_LAUNCH(L_, "train_collate", k_train_collate, dim3((unsigned)(mel_tiles + wav_chunks), (unsigned)B), dim3(WG), 0, wav_arena, mel_arena,
+              frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host, rank, world, mel_tiles, wavs, mels,
+              picked);
     return hipSuccess;
 }
 

@@ -977,6 +977,26 @@ def train_draw(x0, alpha, T_train, seed=0, iteration=0, state=None, out=None):
     return x_t, z, steps
 
 
+def train_collate(corpus, batch_size, seed=0, iteration=0, state=None, rank=0, world_size=1, out=None):
+    """The batch of a step cut on the device from a corpus.TrainCorpus that lies there (fd_train_collate) -> (mels [B, 80, F], wavs
+    [B, 1, F * hop], picked [B, 2] int64 = (item, start frame) per slot; corpus.plan(...) gives the same picks on the host).  The step
+    index is state's `iter` (read on the device: a captured call cuts a new batch on every replay) or, without a state, `iteration`;
+    rank / world_size: slot b stands at position (it B + b) world_size + rank of the endless item order.  out: (mels, wavs, picked)."""
+    if not corpus.wav.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.train_collate runs only on a HIP device (no CPU fallback): corpus.to(device) uploads the corpus")
+    dev, B, F, hop = corpus.wav.device, int(batch_size), corpus.frames, corpus.hop_size
+    if out is None:
+        out = (torch.empty((B, 80, F), device=dev, dtype=torch.float32), torch.empty((B, 1, F * hop), device=dev, dtype=torch.float32),
+               torch.empty((B, 2), device=dev, dtype=torch.int64))
+    mels, wavs, picked = out
+    for t, shape, dtype in ((mels, (B, 80, F), torch.float32), (wavs, (B, 1, F * hop), torch.float32), (picked, (B, 2), torch.int64)):
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev, "out: (mels [B, 80, F], wavs [B, 1, F hop], picked [B, 2] int64)"
+    assert state is None or state.device == dev
+    _call(dev, "fd_train_collate", "fd_train_collate", corpus.wav, corpus.mel, corpus.frame_off, corpus.n_items, hop, F, B,
+          int(seed) & 0xFFFFFFFFFFFFFFFF, state, int(iteration) & 0xFFFFFFFFFFFFFFFF, int(rank), int(world_size), wavs, mels, picked)
+    return mels, wavs, picked
+
+
 class _MSE(torch.autograd.Function):
     """nn.MSELoss() (util.py:307,325) as one fixed-order sum forward (fd_mse_forward) and one pass backward (fd_mse_backward); z is the
     target: it receives no gradient."""

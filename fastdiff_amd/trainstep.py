@@ -12,6 +12,13 @@ bias corrections, and whether the update is skipped because a gradient is not fi
         loss = ts.step(mels, wavs)                                       # a device tensor; nothing synchronises
         if it % 100 == 0: print(ts.state())                              # this does
 
+With a corpus in device memory (fastdiff_amd/corpus.py) the batch is cut inside the step as well (lvc_op.train_collate, keyed by the same
+device-side step index as the draws), step() takes no argument and no byte of the batch crosses the bus:
+
+    ts = fastdiff_amd.TrainStep(model, diffusion_hyperparams, corpus=corpus, batch_size=20)
+    for it in range(steps):
+        loss = ts.step()                                                 # ts.picked: the (item, start frame) of every slot
+
 The library's scratch buffers are per device and grow by free + allocate: a captured step has their addresses baked in, so a LARGER
 training call on the same device after the capture (a second TrainStep on a bigger model, a bigger batch through the eager training
 path) invalidates it -- one model per process and device, as for the training operators in general (lvc_op._handle).
@@ -24,7 +31,7 @@ from . import lvc_op
 
 class TrainStep:
     def __init__(self, model, diffusion_hyperparams, lr=2e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, clip_grad_norm=1.0, seed=0,
-                 graph=True):
+                 graph=True, *, corpus=None, batch_size=None, rank=0, world_size=1):
         self.model = model
         self.params = list(model.parameters())
         if not self.params or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params):
@@ -44,6 +51,17 @@ class TrainStep:
         self.exp_avg = [t.view(p.shape) for t, p in zip(self._m.split(sizes), self.params)]
         self.exp_avg_sq = [t.view(p.shape) for t, p in zip(self._v.split(sizes), self.params)]
         self._key = self._graph = self.loss = None
+        # the batch source of step(): rank / world_size only shape the plan (corpus.plan), the step itself stays single-process
+        self.corpus, self.batch_size, self.rank, self.world_size, self.picked = corpus, None, int(rank), int(world_size), None
+        if corpus is not None:
+            if batch_size is None or int(batch_size) < 1:
+                raise ValueError("TrainStep: a corpus needs batch_size")
+            if corpus.device != self.device:
+                raise RuntimeError(f"TrainStep: the corpus lies on {corpus.device}, the module on {self.device} (corpus.to(device) uploads it)")
+            if not 0 <= self.rank < self.world_size:
+                raise ValueError(f"TrainStep: rank={rank} of world_size={world_size}")
+            self.batch_size = int(batch_size)
+            self.picked = torch.zeros((self.batch_size, 2), dtype=torch.int64, device=self.device)      # (item, start frame) of the last batch
         self.mel = self.wav = self.x_t = self.z = self.steps = None      # the static buffers of the current batch shape
 
     # ---- hyper-parameters and state ------------------------------------------------------------------------------------------------
@@ -111,8 +129,15 @@ class TrainStep:
         self._state.copy_(torch.tensor([int(extra.get("iter", step)), step, int(extra.get("skipped", 0)), 0], dtype=torch.int64))
 
     # ---- the step ----------------------------------------------------------------------------------------------------------------------
-    def _run(self, state):
-        """The calls of one step on the current stream; state: the fd_train_state the optimizer advances."""
+    def _collate(self):
+        lvc_op.train_collate(self.corpus, self.batch_size, seed=self.seed, state=self._state, rank=self.rank, world_size=self.world_size,
+                             out=(self.mel, self.wav, self.picked))
+
+    def _run(self, state, collate=False):
+        """The calls of one step on the current stream; state: the fd_train_state the optimizer advances; collate: the batch comes
+        from the corpus (it only reads the state, like the draw)."""
+        if collate:
+            self._collate()
         lvc_op.train_draw(self.wav, self.alpha, self.T_train, seed=self.seed, state=self._state, out=(self.x_t, self.z, self.steps))
         eps = self.model((self.x_t, self.mel, self.steps))
         loss = lvc_op.mse_loss(eps, self.z, state)
@@ -121,7 +146,7 @@ class TrainStep:
         lvc_op.adamw_multi(list(zip(self.params, grads, self.exp_avg, self.exp_avg_sq)), self._hyper_dev, state)
         return loss.detach()
 
-    def _warm_up(self):
+    def _warm_up(self, collate=False):
         """Three steps outside the capture (the library's scratch buffers grow on first use, which a capture cannot contain) that leave
         no trace: the draws only read the state, and the optimizer runs on a spare state with one more item whose only gradient element
         is NaN -- every launch of the step happens, the guard keeps it from writing a parameter or a moment."""
@@ -132,6 +157,8 @@ class TrainStep:
         with torch.cuda.stream(side):
             for _ in range(3):
                 self.model.zero_grad(set_to_none=True)
+                if collate:
+                    self._collate()
                 lvc_op.train_draw(self.wav, self.alpha, self.T_train, seed=self.seed, state=self._state, out=(self.x_t, self.z, self.steps))
                 loss = lvc_op.mse_loss(self.model((self.x_t, self.mel, self.steps)), self.z, spare)
                 loss.backward()
@@ -140,36 +167,49 @@ class TrainStep:
         torch.cuda.current_stream(self.device).wait_stream(side)
         self.model.zero_grad(set_to_none=True)
 
-    def _prepare(self, mels, wavs):
-        B, L = wavs.shape[0], wavs.shape[-1]
-        if wavs.dim() != 3 or wavs.shape[1] != 1 or L % 4 != 0:
+    def _prepare(self, mel_shape, wav_shape):
+        B, L = wav_shape[0], wav_shape[-1]
+        if len(wav_shape) != 3 or wav_shape[1] != 1 or L % 4 != 0:
             raise ValueError("TrainStep.step: wavs [B, 1, L] with L a multiple of 4")
         self._graph = self.loss = None
-        self.mel = torch.empty(tuple(mels.shape), device=self.device, dtype=torch.float32)
+        self.mel = torch.empty(tuple(mel_shape), device=self.device, dtype=torch.float32)
         self.wav, self.x_t, self.z = (torch.empty((B, 1, L), device=self.device, dtype=torch.float32) for _ in range(3))
         self.steps = torch.empty((B, 1), device=self.device, dtype=torch.float32)
 
-    def step(self, mels, wavs):
+    def step(self, mels=None, wavs=None):
         """One training step on the batch (mels [B, 80, T], wavs [B, 1, T * hop]): draws, forward, loss, backward, clip, AdamW.  Returns
         the loss as a device tensor (overwritten by the next step) and does not synchronise.  With graph=True the first step at a
-        batch shape warms up and captures; every later one is a copy of the batch into static buffers and one replay."""
+        batch shape warms up and captures; every later one is a copy of the batch into static buffers and one replay.
+        Without arguments the batch is cut from the constructor's corpus inside the step (`picked` then holds its items and start
+        frames, corpus.plan(state()["iter"], batch_size, seed, rank, world_size) says the same beforehand): a replay and nothing else."""
         if not (self.model.training and torch.is_grad_enabled()):
             raise RuntimeError("TrainStep.step needs the module in train() mode and gradients enabled")
-        key = (tuple(mels.shape), tuple(wavs.shape))
+        collate = mels is None and wavs is None
+        if collate:
+            if self.corpus is None:
+                raise RuntimeError("TrainStep.step() without a batch needs a TrainStep built with corpus= and batch_size=")
+            B, F = self.batch_size, self.corpus.frames
+            shapes = ((B, 80, F), (B, 1, F * self.corpus.hop_size))
+        elif mels is None or wavs is None:
+            raise TypeError("TrainStep.step: mels and wavs, or neither")
+        else:
+            shapes = (tuple(mels.shape), tuple(wavs.shape))
+        key = shapes + (collate,)
         if key != self._key:
-            self._prepare(mels, wavs)
+            self._prepare(*shapes)
             self._key = key
-        self.mel.copy_(mels, non_blocking=True)
-        self.wav.copy_(wavs, non_blocking=True)
+        if not collate:
+            self.mel.copy_(mels, non_blocking=True)
+            self.wav.copy_(wavs, non_blocking=True)
         if not self.use_graph:
             self.model.zero_grad(set_to_none=True)
-            self.loss = self._run(self._state)
+            self.loss = self._run(self._state, collate)
             return self.loss
         if self._graph is None:
-            self._warm_up()
+            self._warm_up(collate)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self.loss = self._run(self._state)
+                self.loss = self._run(self._state, collate)
             self._graph = graph
         self._graph.replay()
         return self.loss

@@ -212,6 +212,23 @@ typedef struct fd_train_state {
 FD_API int fd_train_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int B, int64_t L, uint64_t seed,
                          const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps, void *stream);
 
+/* The batch of a step, cut on the device from a corpus that lives there (what VocoderDataset.__getitem__ + collater,
+ * tasks/vocoder/dataset_utils.py:80-160, build on the host; fastdiff_amd/corpus.py: TrainCorpus holds the arenas, TrainCorpus.plan is the
+ * host twin of the choice).  One launch, no scratch buffer of the handle, no atomics.
+ *   wav_arena [sum T_i * hop]   mel_arena [sum T_i, 80] (frame-major)   frame_off [n_items + 1] = the frame prefix sums   (device)
+ *   wavs [B,1,F*hop]   mels [B,80,F]   picked [B,2] = (item, start frame) per slot                                          (device)
+ * Every item must be longer than the window, T_i > F (a slot whose item is not gets start = -1 and is left unwritten).
+ * With `it` = state ? state->iter (read on the device: a replay cuts a new batch) : iter_host, slot b takes
+ *   g = (it B + b) world + rank (mod 2^64),   e = g / n_items,   item = pi_e(g % n_items),
+ *   start = (w * (T_item - F)) >> 32 (64-bit product), w = word b & 3 of Philox4x32-10 keyed (seed, stream 0xFFFFFFFC, position b >> 2, id it),
+ * pi_e = a 4-round balanced Feistel network on 2k bits (k the smallest with 4^k >= n_items; halves hi = x >> k, lo = x & (2^k - 1);
+ * a round: (hi, lo) <- (lo, hi ^ (F & (2^k - 1))), F = word 0 of Philox keyed (seed, stream 0xFFFFFFFB, position lo ^ (round << 28),
+ * id e)), applied again while the value is >= n_items: a bijection of [0, n_items) per epoch e.
+ * hop a multiple of 4; n_items <= 2^28; wav_arena, wavs 16-byte aligned. */
+FD_API int fd_train_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                            int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
+                            float *mels, int64_t *picked, void *stream);
+
 /* nn.MSELoss() (util.py:307,325) and its backward: *loss = mean((eps - z)^2) (also into state->loss when state is not NULL);
  * deps = *dloss * 2 (eps - z) / n.  loss, dloss: device scalars. */
 FD_API int fd_mse_forward(fd_handle h, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, void *stream);

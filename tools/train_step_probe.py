@@ -2,7 +2,9 @@
 i.e. B = 20 utterance crops of T = 100 frames -- through FastDiff.forward in train() mode + loss.backward(), with the location-variable
 convolution (a) on the HIP operator (fd_lvc_forward / fd_lvc_backward) and (b) as the reference states it, pad + unfold + einsum on
 PyTorch-ROCm (modules.py:220-253 with dilation 1), on the same GPU; then the operator alone, forward and backward, per hop size.
-Usage: python tools/train_step_probe.py [B] [T]"""
+The corpus rows: the replayed step fed from a device-resident TrainCorpus against the same step fed by a host loop that cuts the same
+windows with numpy and copies them up.
+Usage: python tools/train_step_probe.py [B] [T] [corpus]      (corpus: only the corpus rows)"""
 import os
 import sys
 import time
@@ -123,7 +125,63 @@ def full_step_row(B, T, rounds=7, reps=10):
     return True
 
 
+def corpus_rows(B, T, rounds=7, reps=10, n_items=200):
+    """Where the batch comes from, alternating within one call (device-synchronised wall time per step, median and range over `rounds`
+    rounds of `reps` steps), on a synthetic corpus of `n_items` utterances of T + 1 .. 8 T frames:
+      (a) TrainStep.step(): the batch cut inside the replayed step from the corpus in device memory;
+      (b) TrainStep.step(mels, wavs): a single-process host loop computes the same picks (corpus.plan), cuts them out of the host arenas
+          with numpy (slice, transpose, stack) and hands pageable tensors to the step, which copies them up and replays;
+      (host) the host part of (b) alone, no device work."""
+    import statistics
+    import numpy as np
+    from fastdiff_amd import schedules
+    try:
+        dh = schedules.training_hyperparams()
+        rng = np.random.RandomState(0)
+        lengths = rng.randint(T + 1, 8 * T + 1, size=n_items)
+        items = [{"mel": (rng.rand(n, 80) * 7.5 - 6.0).astype(np.float32), "wav": (0.3 * rng.randn(n * 256)).astype(np.float32)} for n in lengths]
+        cpu = fastdiff_amd.TrainCorpus(items, hop_size=256, max_samples=T * 256, device="cpu")
+        dev = cpu.to("cuda")
+        mel_h, wav_h, off = cpu.mel.numpy(), cpu.wav.numpy(), cpu.frame_off_host
+        ma, mb = fastdiff_amd.FastDiff().cuda().train(), fastdiff_amd.FastDiff().cuda().train()
+        mb.load_state_dict(ma.state_dict())
+        ta = fastdiff_amd.TrainStep(ma, dh, seed=1, corpus=dev, batch_size=B)
+        tb = fastdiff_amd.TrainStep(mb, dh, seed=1)
+        count = [0]
+
+        def host_cut():
+            picks, starts = cpu.plan(count[0], B, seed=1)
+            count[0] += 1
+            first = off[picks] + starts
+            mels = np.stack([mel_h[p: p + T].T for p in first])
+            wavs = np.stack([wav_h[p * 256: (p + T) * 256] for p in first])[:, None, :]
+            return torch.from_numpy(np.ascontiguousarray(mels)), torch.from_numpy(np.ascontiguousarray(wavs))
+
+        ta.step()
+        tb.step(*host_cut())
+        torch.cuda.synchronize()
+        same = torch.equal(ta.mel, tb.mel) and torch.equal(ta.wav, tb.wav)
+        runs = {"(a) step() from the device-resident corpus, replayed": ta.step, "(b) step(mels, wavs) fed by a host loop (plan + numpy cut + copy), replayed": lambda: tb.step(*host_cut()),
+                "(host) plan + numpy cut alone": host_cut}
+        times = {k: [] for k in runs}
+        for _ in range(rounds):
+            for k, fn in runs.items():
+                times[k].append(timed(fn, warm=2, reps=reps))
+        print(f"  the batch source at B={B} T={T}, corpus of {cpu.n_items} items ({cpu.wav.numel() * 4 / 1e6:.0f} MB of waveform), {rounds} alternating rounds of {reps} steps (ms per step: median [min .. max]):")
+        for k, v in times.items():
+            print(f"    {k}: {statistics.median(v):8.3f} [{min(v):.3f} .. {max(v):.3f}]")
+        print(f"    first batch of (a) and (b) identical: {same};  state of (a): {ta.state()}")
+    except Exception:      # noqa: BLE001
+        import traceback
+        traceback.print_exc()
+        print("  the corpus rows FAILED (traceback above)")
+        return False
+    return True
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[3] == "corpus":
+        return corpus_rows(int(sys.argv[1]), int(sys.argv[2]))
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     torch.manual_seed(0)
@@ -198,6 +256,7 @@ def main():
         graph_run(" [reference kernel tensor + transposes]", _train_frames=False)
         graph_run("")
     full_ok = full_step_row(B, T)
+    full_ok = corpus_rows(B, T) and full_ok
     for hop in (8, 64, 256):
         L = T * hop
         y = torch.randn(B, 32, L, device="cuda", requires_grad=True)
