@@ -21,6 +21,10 @@ class FdStep(ct.Structure):
                 ("c1", ct.c_float), ("c2", ct.c_float), ("c3", ct.c_float), ("add_noise", ct.c_int32)]
 
 
+class FdWeightRef(ct.Structure):
+    _fields_ = [("name", ct.c_char_p), ("data", ct.c_void_p), ("dims", ct.POINTER(ct.c_int64)), ("ndim", ct.c_int32), ("reserved", ct.c_int32)]
+
+
 class FdKernelStat(ct.Structure):
     _fields_ = [("name", ct.c_char * 48), ("launches", ct.c_int64), ("total_ms", ct.c_double)]
 
@@ -35,7 +39,7 @@ def step_table(rows):
 
 
 EXPORTS = ["fd_default_config", "fd_create", "fd_destroy", "fd_last_error", "fd_set_weight", "fd_commit_weights",
-           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
+           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
            "fd_get_profile", "fd_reset_profile", "fd_get_counter", "fd_version", "fd_abi_revision"]
 
 _lib = None
@@ -64,6 +68,10 @@ def load():
     lib.fd_destroy.argtypes = [vp]
     lib.fd_set_weight.argtypes = [vp, ct.c_char_p, vp, ct.POINTER(ct.c_int64), ci]
     lib.fd_commit_weights.argtypes = [vp]
+    lib.fd_refresh_weights_device.argtypes = [vp, ct.POINTER(FdWeightRef), ci, vp]
+    lib.fd_get_weight_image.argtypes = [vp, vp, ct.POINTER(ct.c_size_t)]
+    lib.fd_get_weight_flags.argtypes = [vp, ct.POINTER(ct.c_uint)]
+    lib.fd_pack_source.argtypes = [ct.c_char_p, ci, ci, ci]
     lib.fd_forward.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp]
     lib.fd_sample.argtypes = [vp, vp, ci, ci, vp, ct.POINTER(FdStep), ci, ci, vp, vp, ct.c_uint64, vp, vp, vp]
     lib.fd_set_noise_streams.argtypes = [vp, vp, ci]

@@ -203,6 +203,9 @@ static void release_handle(fd_context *h)
     drop_graph(h);
     free_workspace(h);
     if (h->weight_arena) hipFree(h->weight_arena);
+    if (h->refresh_dev) hipFree(h->refresh_dev);
+    if (h->refresh_bad) hipHostFree(h->refresh_bad);
+    if (h->refresh_done) hipEventDestroy(h->refresh_done);
     if (h->scratch) hipFree(h->scratch);
     for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->step_scratch})
         if (s->p) hipFree(s->p);
@@ -426,7 +429,7 @@ static int check_common(fd_handle h, int B, int T, const char *who)
     if ((int64_t)B * T * fdg::hop_total(h) * (h->gen ? h->cfg.inner_channels : fd::C) >= (int64_t)1 << 31)
         FD_FAIL(h, FD_ERR_INVALID, "%s: B*T too large for one call (B=%d, T=%d); split the batch", who, B, T);
     FD_HIP(h, hipSetDevice(h->device));
-    return FD_OK;
+    return fd_settle_refresh(h);
 }
 
 // Pinned staging (fd_context::stage): the next slot of the ring with room for `bytes`, free to be written by the host.

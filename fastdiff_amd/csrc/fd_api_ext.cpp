@@ -258,6 +258,8 @@ int64_t fd_get_counter(fd_handle h, const char *name)
     if (k == "graph_captures") return h->n_graph_captures;
     if (k == "graph_hits") return h->n_graph_hits;
     if (k == "graph_evictions") return h->n_graph_evictions;
+    if (k == "weight_refreshes") return h->n_refreshes;
+    if (k == "refresh_graph_drops") return h->n_refresh_graph_drops;
     if (k == "graphs_resident") return (int64_t)h->graphs.size();
     if (k == "graphs_retired") return (int64_t)h->retired.size();
     if (k == "workspace_bytes") return (int64_t)(h->ws.bytes + h->span_scratch.bytes);

@@ -40,6 +40,8 @@ int fd_sample_span(fd_handle h, const float *mel, int64_t mel_first, int64_t mel
     int rc = fd_settle(h);
     if (rc != FD_OK) return rc;
     if (!h->committed) FD_FAIL(h, FD_ERR_STATE, "fd_sample_span: weights not committed (call fd_commit_weights after fd_set_weight)");
+    FD_HIP(h, hipSetDevice(h->device));
+    if ((rc = fd_settle_refresh(h)) != FD_OK) return rc;
     for (int i = 0; i < ST_COUNT; ++i)
         if (!h->mode.fast[i])
             FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_sample_span: needs the fast kernel set; the naive kernels (option kernels.<stage> = naive) "

@@ -26,6 +26,9 @@ extern std::string g_create_error;      // text of a failed fd_create (no handle
 extern "C" {      // (defined inside fd_api.cpp's extern "C" block; hidden visibility: not part of the ABI)
 // fallback = host: look at the flags of a pending fd_sample before touching device state (no-op when nothing is pending)
 int fd_settle(fd_handle h);
+// the range flags of a pending fd_refresh_weights_device (fd_weights.cpp): waits for that refresh alone; a flag that changed drops the
+// graphs.  Every inference entry point calls it before it chooses a kernel family (no-op when nothing is pending)
+int fd_settle_refresh(fd_handle h);
 // drops every captured graph; the caller has synchronised the device
 void drop_graph(fd_context *c);
 // Pinned staging ring (fd_context::stage): the next slot with room for `bytes`, free to be written by the host; ... and the mark behind

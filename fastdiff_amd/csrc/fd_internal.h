@@ -254,7 +254,18 @@ struct fd_context {
     bool host_fallback = true;                // option "fallback" = "host" (default; settled inside fd_sample unless defer_check) | "graph"
     std::map<std::string, std::pair<std::vector<int64_t>, std::vector<float>>> raw;   // host copies from fd_set_weight
     void *weight_arena = nullptr;            // the one device allocation behind the committed weights (DevWeights or fdg::Net)
+    size_t weight_bytes = 0;                 // ... and its size (fd_get_weight_image)
     DevWeights w;
+    // fd_refresh_weights_device (fd_weights.cpp) rebuilds the arena in place on a stream.  Its work lists and the word its kernels OR
+    // the out-of-range families into live in refresh_dev (allocated by the first refresh); the word is copied to refresh_bad (pinned)
+    // behind the kernels, and the first inference call after a refresh waits for refresh_done alone and looks at it
+    // (fd_settle_refresh) before it chooses a kernel family: w.*_ok are stale while refresh_pending.
+    void *refresh_dev = nullptr;
+    size_t refresh_dev_bytes = 0;
+    unsigned *refresh_bad = nullptr;
+    hipEvent_t refresh_done = nullptr;
+    bool refresh_pending = false;
+    long long n_refreshes = 0, n_refresh_graph_drops = 0;
     Workspace ws;
     bool lvc_dx_gather = true;               // option lvc_dx = gather | copy: the frames path's dx kernel reads kernel_conv's frames (fd_kernels_train.hip)
     // the step embedding and the three fc_t rows of every reverse step depend on the schedule's t values and the weights only: kept from

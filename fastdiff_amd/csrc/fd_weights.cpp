@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "fd_host.h"
+#include "fd_wpack.h"
 
 // ------------------------------------------------------------------------------------------------
 // expected state_dict (FastDiff_model.py:13-72; modules.py:116-125,141-187,257-318)
@@ -47,30 +48,41 @@ static int64_t numel(const std::vector<int64_t> &d)
     return n;
 }
 
-extern "C" int fd_set_weight(fd_handle h, const char *name, const float *host_data, const int64_t *dims, int ndim)
+// The shape a state_dict key must have (<parameter>.weight | weight_v | weight_g | bias), empty for a key the module does not have
+static std::vector<int64_t> expected_dims(const std::vector<ParamSpec> &specs, const std::string &key)
 {
-    if (!h || !name || !host_data || !dims || ndim <= 0 || ndim > 4) return FD_ERR_INVALID;
-    const std::string key(name);
-    // find the owning parameter and the expected shape of this tensor
-    const std::vector<ParamSpec> specs = param_specs(h->cfg);
-    std::vector<int64_t> expect;
     for (const auto &s : specs) {
         if (key.compare(0, s.name.size(), s.name) != 0 || key.size() <= s.name.size() || key[s.name.size()] != '.') continue;
         const std::string suffix = key.substr(s.name.size() + 1);
-        if (suffix == "weight" || suffix == "weight_v") expect = s.dims;
-        else if (suffix == "weight_g") { expect = {s.dims[0], 1, 1}; }
-        else if (suffix == "bias") expect = {s.transposed_conv ? s.dims[1] : s.dims[0]};
-        else continue;
-        break;
+        if (suffix == "weight" || suffix == "weight_v") return s.dims;
+        if (suffix == "weight_g") return {s.dims[0], 1, 1};
+        if (suffix == "bias") return {s.transposed_conv ? s.dims[1] : s.dims[0]};
     }
-    if (expect.empty()) FD_FAIL(h, FD_ERR_INVALID, "fd_set_weight: unexpected key '%s' (not in the FastDiff state_dict)", name);
-    std::vector<int64_t> got(dims, dims + ndim);
+    return {};
+}
+
+// ... and the check of one tensor against it, for fd_set_weight and fd_refresh_weights_device alike
+static int check_dims(fd_handle h, const char *who, const std::vector<ParamSpec> &specs, const char *name, const int64_t *dims, int ndim)
+{
+    const std::vector<int64_t> expect = expected_dims(specs, name);
+    if (expect.empty()) FD_FAIL(h, FD_ERR_INVALID, "%s: unexpected key '%s' (not in the FastDiff state_dict)", who, name);
+    const std::vector<int64_t> got(dims, dims + ndim);
     if (got != expect) {
         std::string a, b;
         for (auto v : got) a += std::to_string(v) + ",";
         for (auto v : expect) b += std::to_string(v) + ",";
-        FD_FAIL(h, FD_ERR_INVALID, "fd_set_weight: size mismatch for %s: got [%s] expected [%s]", name, a.c_str(), b.c_str());
+        FD_FAIL(h, FD_ERR_INVALID, "%s: size mismatch for %s: got [%s] expected [%s]", who, name, a.c_str(), b.c_str());
     }
+    return FD_OK;
+}
+
+extern "C" int fd_set_weight(fd_handle h, const char *name, const float *host_data, const int64_t *dims, int ndim)
+{
+    if (!h || !name || !host_data || !dims || ndim <= 0 || ndim > 4) return FD_ERR_INVALID;
+    const std::string key(name);
+    const int rcd = check_dims(h, "fd_set_weight", param_specs(h->cfg), name, dims, ndim);
+    if (rcd != FD_OK) return rcd;
+    const std::vector<int64_t> got(dims, dims + ndim);
     auto &slot = h->raw[key];
     slot.first = got;
     slot.second.assign(host_data, host_data + numel(got));
@@ -110,62 +122,14 @@ int fold_param(fd_context *h, const ParamSpec &s, Folded &out)
     return FD_OK;
 }
 
+using namespace fdp;      // the layouts: fd_wpack.h, shared with the device packer
+
 // Conv weight [cout][cin][ks] -> MFMA A-operand pack [mt][s4][lane][4], kk = tap*cin + ci = 2*(4*s4+r) + (lane>>5)
 std::vector<float> pack_A(const std::vector<float> &w, int cout, int cin, int ks)
 {
-    const int ns4 = cin * ks / 8, nmt = cout / 32;
-    std::vector<float> p((size_t)nmt * ns4 * 256);
-    for (int mt = 0; mt < nmt; ++mt)
-        for (int s4 = 0; s4 < ns4; ++s4)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int o = mt * 32 + (lane & 31), kk = 2 * (4 * s4 + r) + (lane >> 5);
-                    const int tap = kk / cin, ci = kk % cin;
-                    p[(((size_t)mt * ns4 + s4) * 64 + lane) * 4 + r] = w[((size_t)o * cin + ci) * ks + tap];
-                }
+    std::vector<float> p((size_t)(cout / 32) * (cin * ks / 8) * 256);
+    for (size_t d = 0; d < p.size(); ++d) p[d] = w[pack_A_src((int)d, cin, ks)];
     return p;
-}
-
-// IEEE binary16 <-> binary32 on the host (round to nearest even, subnormals kept): the weight pieces of the fp16x2 GEMM.
-uint16_t f16_from_f32(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-    u &= 0x7FFFFFFFu;
-    if (u > 0x7F800000u) return sign | 0x7E00u;                  // NaN
-    if (u >= 0x477FF000u) return sign | 0x7C00u;                 // >= 65520 rounds to infinity
-    if (u < 0x38800000u) {                                       // below 2^-14: subnormal, a multiple of 2^-24
-        float ax;
-        memcpy(&ax, &u, 4);
-        return sign | (uint16_t)lrintf(ax * 16777216.0f);        // current rounding mode = nearest even; 1024 = smallest normal
-    }
-    uint32_t hbits = (((u >> 23) - 112u) << 10) | ((u & 0x7FFFFFu) >> 13);
-    const uint32_t rem = u & 0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (hbits & 1u))) ++hbits;   // a carry into the exponent is the correct result
-    return sign | (uint16_t)hbits;
-}
-float f32_from_f16(uint16_t hb)
-{
-    const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, exp = (hb >> 10) & 0x1Fu, man = hb & 0x3FFu;
-    float v;
-    if (exp == 0) v = (float)man * (1.0f / 16777216.0f);
-    else if (exp == 31) { const uint32_t u = 0x7F800000u | (man << 13); memcpy(&v, &u, 4); }
-    else { const uint32_t u = ((exp + 112u) << 23) | (man << 13); memcpy(&v, &u, 4); }
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u |= sign;
-    memcpy(&v, &u, 4);
-    return v;
-}
-
-// The fp16x2 form of a weight: v = hi + 2^-11 lo, hi = fp16(v), lo = fp16((v - hi) * 2^11).  False when v does not fit the range the
-// fp16-pipe kernels accept (|v| < 32768).
-bool split_f16(float v, uint16_t &hi, uint16_t &lo)
-{
-    hi = f16_from_f32(v);
-    lo = f16_from_f32((v - f32_from_f16(hi)) * 2048.0f);
-    return fabsf(v) < 32768.0f;
 }
 
 // fp16 pieces of value(o, i) as [outer][piece][inner], and whether every value fits (the *_ok flag of the pack's kernel family)
@@ -180,43 +144,21 @@ template <class F> Pieces pieces(int outer, int inner, F value)
     return p;
 }
 
-// Position i of a [kg][64 lane][8 e] run of 32x32x16 fp16 operands: lane = row + 32*g holds the 8 consecutive k = 16*kg + 8*g + e.
-struct Op16 { int row, k; };
-inline Op16 op16(int i) { return {(i >> 3) & 31, 16 * (i >> 9) + 8 * ((i >> 8) & 1) + (i & 7)}; }
-
 // fp16 pieces of a conv weight [cout][cin][ks] (cout a multiple of 32) in 32x32x16 A-operand order:
 // [mt = out/32][piece][kg][lane = out%32 + 32*g][8], k = tap*cin + in
 Pieces pack_A_h2(const std::vector<float> &w, int cin, int ks, int cout = 32)
 {
-    return pieces(cout / 32, cin * ks / 16 * 512, [&](int mt, int i) {
-        const Op16 q = op16(i);
-        return w[((size_t)(mt * 32 + q.row) * cin + q.k % cin) * ks + q.k / cin];
-    });
-}
-
-void unpack_kernel_index(int p, int &layer, int &in, int &out, int &tap)
-{
-    layer = p / fd::KLAYER;
-    const int q = p % fd::KLAYER, e = q & 7, lane = (q >> 3) & 63, mk = q >> 9;
-    const int mt = mk / 6, kg = mk % 6, kk = kg * 16 + 8 * (lane >> 5) + e, row = lane & 31;
-    tap = kk / fd::C; in = kk % fd::C;
-    out = 16 * mt + (row & 15) + 32 * (row >> 4);      // inverse of kernel_tile / kernel_row
+    return pieces(cout / 32, cin * ks / 16 * 512, [&](int mt, int i) { return w[pack_A_h2_src(mt, i, cin, ks)]; });
 }
 
 // The kernel_conv or bias_conv row behind packed column pp of the predictor GEMM: its weights [HID][3] and its bias.
 struct GemmColumn { const float *w; float b; };
 GemmColumn gemm_column(const Folded &kc, const Folded &bc, int pp)
 {
-    if (pp < fd::KW) {
-        int layer, in, out, tap;
-        unpack_kernel_index(pp, layer, in, out, tap);
-        const int row = ((layer * fd::C + in) * 2 * fd::C + out) * 3 + tap;   // [layers,in,out,k] view (modules.py:333-338)
-        return {kc.w.data() + (size_t)row * fd::HID * 3, kc.b[row]};
-    }
-    // bias record [layer][mt][row]  ->  bias_conv row layer*64 + out (view [layers,out], modules.py:339-342)
-    const int q = pp - fd::KW, layer = q >> 6, mt = (q >> 5) & 1, row = q & 31;
-    const int brow = layer * 64 + 16 * mt + (row & 15) + 32 * (row >> 4);
-    return {bc.w.data() + (size_t)brow * fd::HID * 3, bc.b[brow]};
+    bool bias_conv;
+    const int row = gemm_column_row(pp, &bias_conv);
+    const Folded &f = bias_conv ? bc : kc;
+    return {f.w.data() + (size_t)row * fd::HID * 3, f.b[row]};
 }
 
 // Every weight of the tuned kernel set (DevWeights) as a host image; sets the *_ok flags.  The pointer fields are written by upload().
@@ -237,9 +179,8 @@ void pack_tuned(const FoldedSet &f, DevWeights &w, WeightImage &img)
     {   // the same weights in the order the last LVC layer holds its outputs: channel = 16 mt + 4 hi + (r & 3) + 8 (r >> 2)
         const std::vector<float> &fw = F("final_conv.0").w;
         std::vector<float> ff(4 * 8 * 8, 0.0f);
-        for (int part = 0; part < 4; ++part)
-            for (int r = 0; r < 8; ++r)
-                for (int k = 0; k < 7; ++k) ff[(part * 8 + r) * 8 + k] = fw[(16 * (part >> 1) + 4 * (part & 1) + (r & 3) + 8 * (r >> 2)) * 7 + k];
+        for (int d = 0; d < 4 * 8 * 8; ++d)
+            if (final_fuse_src(d) >= 0) ff[d] = fw[final_fuse_src(d)];
         img.add(w.final_fuse, ff);
     }
     // embed MLP, transposed
@@ -276,24 +217,13 @@ void pack_tuned(const FoldedSet &f, DevWeights &w, WeightImage &img)
         img.add(w.fc_t_T[n], transpose(F(p + ".fc_t").w, fd::COND, fd::E_OUT));
         add_conv(p + ".upsample", w.blk[n].up);
         {   // ConvTranspose1d weight [in][out][2r] -> per-phase MFMA A operands [ph][s4][lane][4], kk = sel*32 + i
-            const int r = fd::ratio(n), ks = 2 * r, pd = r / 2;
+            const int r = fd::ratio(n);
             const std::vector<float> &uw = F(p + ".upsample").w;
-            // sel 0: the nearer input position (jA), sel 1: the one before it (jB = jA - 1, tap + r)
-            auto tap = [&](int ph, int sel) { const int kA = (ph < pd) ? ph + pd : ph - pd; return sel ? kA + r : kA; };
             std::vector<float> up((size_t)r * 8 * 256);
-            for (int ph = 0; ph < r; ++ph)
-                for (int s4 = 0; s4 < 8; ++s4)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int q = 0; q < 4; ++q) {
-                            const int kk = 2 * (4 * s4 + q) + (lane >> 5), i = kk & 31, o = lane & 31;
-                            up[(((size_t)ph * 8 + s4) * 64 + lane) * 4 + q] = uw[((size_t)i * fd::C + o) * ks + tap(ph, kk >> 5)];
-                        }
+            for (size_t d = 0; d < up.size(); ++d) up[d] = uw[up_pack_src((int)d, r)];
             img.add(w.up_pack[n], up);
             // the same per-phase slices as fp16 pieces: [ph][piece][4 kg][64 lane = out + 32*g][8], k = 16*kg + 8*g + e = sel*32 + i
-            add_h2(w.up_h2[n], w.convt_f16_ok, pieces(r, 4 * 512, [&](int ph, int i) {
-                       const Op16 q = op16(i);
-                       return uw[((size_t)(q.k & 31) * fd::C + q.row) * ks + tap(ph, q.k >> 5)];
-                   }));
+            add_h2(w.up_h2[n], w.convt_f16_ok, pieces(r, 4 * 512, [&](int ph, int i) { return uw[up_h2_src(ph, i, r)]; }));
         }
         add_conv(p + ".kernel_predictor.input_conv.0", w.blk[n].kp_in);
         img.add(w.kp_in_pack[n], pack_A(F(p + ".kernel_predictor.input_conv.0").w, fd::HID, fd::COND, 5));
@@ -311,10 +241,7 @@ void pack_tuned(const FoldedSet &f, DevWeights &w, WeightImage &img)
             add_conv(p + ".convs." + std::to_string(i), w.blk[n].convs[i]);
             img.add(w.lvc_conv_pack[n][i], pack_A(cw, fd::C, fd::C, 3));
             if (n == 0)      // hop 8: 16x16x32 tiles [rt][tap][piece][64 lane][8]: lane = out%16 + 16*g holds input channels 8g .. 8g+7 of one tap
-                add_h2(w.lvc_conv_h16[i], w.lvc_f16_ok, pieces(2 * 3, 512, [&](int rt_tap, int idx) {
-                           const int rt = rt_tap / 3, tap = rt_tap % 3, lane = idx >> 3, out = 16 * rt + (lane & 15), in = 8 * (lane >> 4) + (idx & 7);
-                           return cw[((size_t)out * fd::C + in) * 3 + tap];
-                       }));
+                add_h2(w.lvc_conv_h16[i], w.lvc_f16_ok, pieces(2 * 3, 512, [&](int rt_tap, int idx) { return cw[lvc_h16_src(rt_tap, idx)]; }));
             add_h2(w.lvc_conv_h2[n][i], w.lvc_f16_ok, pack_A_h2(cw, fd::C, 3));
         }
         // the predictor GEMM's B operands: one column per packed-record position pp, kk = tap*64 + channel
@@ -324,32 +251,22 @@ void pack_tuned(const FoldedSet &f, DevWeights &w, WeightImage &img)
         {   // fp32: [ptile][24 s4][lane][4], kk = 2*(4*s4+r) + (lane>>5)
             std::vector<float> gp((size_t)(fd::KREC / 32) * 24 * 256), gb(fd::KREC);
             for (int pt = 0; pt < fd::KREC / 32; ++pt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s4 = 0; s4 < 24; ++s4)
-                        for (int r = 0; r < 4; ++r) {
-                            const int kk = 2 * (4 * s4 + r) + (lane >> 5), tap = kk / fd::HID, c = kk % fd::HID;
-                            gp[(((size_t)pt * 24 + s4) * 64 + lane) * 4 + r] = col[pt * 32 + (lane & 31)].w[c * 3 + tap];
-                        }
+                for (int d = 0; d < 24 * 256; ++d) {
+                    const TilePos q = gemm_pack_pos(d);
+                    gp[(size_t)pt * 24 * 256 + d] = col[pt * 32 + q.col].w[q.widx];
+                }
             for (int pp = 0; pp < fd::KREC; ++pp) gb[pp] = col[pp].b;
             img.add(w.gemm_pack[n], gp);
             img.add(w.gemm_bias[n], gb);
         }
         // fp16x2 form, B operand of v_mfma_f32_32x32x16_f16: [ptile][piece][12 kg][lane = col + 32*g][8], k = tap*64 + channel
         add_h2(w.gemm_h2_pack[n], w.gemm_f16_ok, pieces(fd::KREC / 32, 12 * 512, [&](int pt, int i) {
-                   const Op16 q = op16(i);
-                   return col[pt * 32 + q.row].w[(q.k % fd::HID) * 3 + q.k / fd::HID];
+                   const TilePos q = gemm_h2_pos(i);
+                   return col[pt * 32 + q.col].w[q.widx];
                }));
-        // Winograd F(2,3) over the frame axis (kernel_conv is a k = 3 convolution over frames, modules.py:315-318): per pair of
-        // output frames  y[2p] = m0 + m1 + m2,  y[2p+1] = m1 - m2 + m3  with  m_j = V_j . u_j (K = 64 each),
-        //   V0 = g0, V1 = (g0 + g1 + g2) / 2, V2 = (g0 - g1 + g2) / 2, V3 = -g2        (g_tap = the column's weights of that tap)
-        //   u0 = h[2p-1] - h[2p+1], u1 = h[2p] + h[2p+1], u2 = h[2p+1] - h[2p], u3 = h[2p] - h[2p+2]   (k_h_wino)
-        // B operand [ptile][piece][16 kg][lane = col + 32*g][8]: k = 64 j + channel
+        // Winograd F(2,3) over the frame axis (fd_wpack.h: gemm_w_value): B operand [ptile][piece][16 kg][lane = col + 32*g][8], k = 64 j + channel
         add_h2(w.gemm_w_pack[n], w.gemm_w_ok, pieces(fd::KREC / 32, 16 * 512, [&](int pt, int i) {
-                   const Op16 q = op16(i);
-                   const int j = q.k >> 6, ch = q.k & 63;
-                   const float *wrow = col[pt * 32 + q.row].w;
-                   const double g0 = wrow[ch * 3 + 0], g1 = wrow[ch * 3 + 1], g2 = wrow[ch * 3 + 2];
-                   return (float)(j == 0 ? g0 : (j == 1 ? 0.5 * (g0 + g1 + g2) : (j == 2 ? 0.5 * (g0 - g1 + g2) : -g2)));
+                   return gemm_w_value(i, [&](int c) { return col[pt * 32 + c].w; });
                }));
     }
     std::vector<int> perm(fd::KW);
@@ -377,6 +294,7 @@ int upload(fd_context *h, const WeightImage &img)
         FD_FAIL(h, FD_ERR_HIP, "fd_commit_weights: weight upload failed: %s", hipGetErrorString(e));
     }
     h->weight_arena = d;
+    h->weight_bytes = img.bytes.size();
     for (const auto &fl : img.fields) *fl.first = static_cast<const char *>(d) + fl.second;
     return FD_OK;
 }
@@ -396,6 +314,8 @@ extern "C" int fd_commit_weights(fd_handle h)
     h->committed = false;            // until the new set is complete: a failed re-commit must not leave the old flag over freed weights
     if (h->weight_arena) (void)hipFree(h->weight_arena);
     h->weight_arena = nullptr;
+    h->weight_bytes = 0;
+    h->refresh_pending = false;      // (the device is idle: a refresh's flags are moot, the new set brings its own)
     h->w = DevWeights();
     drop_graph(h);
 
@@ -420,4 +340,254 @@ extern "C" int fd_commit_weights(fd_handle h)
     h->raw.clear();     // host copies are no longer needed
     h->committed = true;
     return FD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same packs rebuilt on the device, in place, from live parameter tensors (fd_kernels_wpack.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct LiveParam { const float *w = nullptr, *v = nullptr, *g = nullptr, *b = nullptr; };
+
+// The work lists of one refresh: what pack_tuned does, restated as jobs over the arena's own slots.  Weight norm folds into the
+// reference-layout slot of its parameter (ConvW::w -- the arena already holds every folded weight once, so those slots are the folded
+// staging and nothing is held twice); `live` jobs read the caller's tensors, `packs` jobs the slots, so they run behind them.
+struct RefreshJobs {
+    std::vector<fdk::FoldJob> fold;
+    std::vector<fdk::PackJob> live, packs;
+    fdk::GemmJobs gemm;
+    int fold_blocks = 0, live_blocks = 0, pack_blocks = 0;
+
+    void add_fold(const float *v, const float *g, const float *dst, int rows, int per)
+    {
+        const int rpb = fdk::wpack_fold_rows(per);
+        fold.push_back({v, g, const_cast<float *>(dst), rows, per, rpb, fold_blocks});
+        fold_blocks += (rows + rpb - 1) / rpb;
+    }
+    void add(std::vector<fdk::PackJob> &list, int &blocks, int kind, const float *src, const void *dst, int n, int p0 = 0, int p1 = 0,
+             int inner = 1, int flag = 0)
+    {
+        list.push_back({src, const_cast<void *>(dst), kind, n, p0, p1, inner, flag, blocks, 0});
+        const int units = kind >= fdk::WP_A_H2 ? n / 8 : (n + 3) / 4;
+        blocks += (units + 255) / 256;
+    }
+    void copy(const float *src, const float *dst, int64_t n) { add(live, live_blocks, fdk::WP_COPY, src, dst, (int)n); }
+    void pack(int kind, const float *src, const void *dst, int n, int p0 = 0, int p1 = 0, int inner = 1, int flag = 0)
+    {
+        add(packs, pack_blocks, kind, src, dst, n, p0, p1, inner, flag);
+    }
+    void pack_A(const float *src, const float *dst, int cout, int cin, int ks) { pack(fdk::WP_PACK_A, src, dst, cout / 32 * (cin * ks / 8) * 256, cin, ks); }
+    void pack_A_h2(const float *src, const uint16_t *dst, int cout, int cin, int ks, int flag)
+    {
+        const int inner = cin * ks / 16 * 512;
+        pack(fdk::WP_A_H2, src, dst, cout / 32 * inner, cin, ks, inner, flag);
+    }
+};
+
+int build_refresh_jobs(fd_context *h, const std::vector<ParamSpec> &specs, const std::map<std::string, LiveParam> &live, RefreshJobs &J)
+{
+    const DevWeights &w = h->w;
+    std::map<std::string, const ParamSpec *> spec;
+    for (const auto &s : specs) spec[s.name] = &s;
+    // a parameter into its reference-layout slot: the bias copied, the weight folded or copied
+    auto conv = [&](const std::string &name, const ConvW &cw) {
+        const ParamSpec &s = *spec.at(name);
+        const LiveParam &p = live.at(name);
+        const int64_t nw = numel(s.dims);
+        J.copy(p.b, cw.b, s.transposed_conv ? s.dims[1] : s.dims[0]);
+        if (p.v) J.add_fold(p.v, p.g, cw.w, (int)s.dims[0], (int)(nw / s.dims[0]));
+        else J.copy(p.w, cw.w, nw);
+    };
+    conv("first_audio_conv", w.first);
+    conv("final_conv.0", w.final_);
+    J.pack(fdk::WP_FINAL_FUSE, w.final_.w, w.final_fuse, 4 * 8 * 8);
+    // the embed MLP has no reference-layout slot: transposed straight from the caller's tensors
+    const struct { const char *name; const float *T, *b; int rows, cols; } mlp[2] = {{"fc_t1", w.fc_t1_T, w.fc_t1_b, fd::E_MID, fd::E_IN},
+                                                                                   {"fc_t2", w.fc_t2_T, w.fc_t2_b, fd::E_OUT, fd::E_MID}};
+    for (const auto &m : mlp) {
+        const LiveParam &p = live.at(m.name);
+        if (p.v) FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_refresh_weights_device: %s is weight-normed (a Linear of the reference is not): use fd_set_weight + fd_commit_weights", m.name);
+        J.add(J.live, J.live_blocks, fdk::WP_TRANSPOSE, p.w, m.T, m.rows * m.cols, m.rows, m.cols);
+        J.copy(p.b, m.b, m.rows);
+    }
+    for (int n = 0; n < fd::NBLK; ++n) {
+        const std::string p = "lvc_blocks." + std::to_string(n), d = "downsample." + std::to_string(n);
+        conv(d + ".residual_dense", w.down[n].res);
+        for (int i = 0; i < 3; ++i) conv(d + ".conv." + std::to_string(i), w.down[n].conv[i]);
+        for (int i = 0; i < 4; ++i) {      // conv 0..2: K = 96, residual 1x1: K = 32
+            const float *src = i < 3 ? w.down[n].conv[i].w : w.down[n].res.w;
+            J.pack_A(src, w.down_pack[n][i], fd::C, fd::C, i < 3 ? 3 : 1);
+            J.pack_A_h2(src, w.down_h2[n][i], fd::C, fd::C, i < 3 ? 3 : 1, OK_DBLOCK);
+        }
+        conv(p + ".fc_t", w.blk[n].fc_t);
+        J.pack(fdk::WP_TRANSPOSE, w.blk[n].fc_t.w, w.fc_t_T[n], fd::COND * fd::E_OUT, fd::COND, fd::E_OUT);
+        conv(p + ".upsample", w.blk[n].up);
+        const int r = fd::ratio(n);
+        J.pack(fdk::WP_UP_PACK, w.blk[n].up.w, w.up_pack[n], r * 8 * 256, r);
+        J.pack(fdk::WP_UP_H2, w.blk[n].up.w, w.up_h2[n], r * 4 * 512, r, 0, 4 * 512, OK_CONVT);
+        conv(p + ".kernel_predictor.input_conv.0", w.blk[n].kp_in);
+        J.pack_A(w.blk[n].kp_in.w, w.kp_in_pack[n], fd::HID, fd::COND, 5);
+        J.pack_A_h2(w.blk[n].kp_in.w, w.kp_in_h2[n], fd::HID, fd::COND, 5, OK_KPF);
+        for (int j = 0; j < 6; ++j) {
+            conv(p + ".kernel_predictor.residual_conv." + std::to_string(KP_RES_IDX[j]), w.blk[n].kp_res[j]);
+            J.pack_A(w.blk[n].kp_res[j].w, w.kp_res_pack[n][j], fd::HID, fd::HID, 3);
+            J.pack_A_h2(w.blk[n].kp_res[j].w, w.kp_res_h2[n][j], fd::HID, fd::HID, 3, OK_KPF);
+        }
+        conv(p + ".kernel_predictor.kernel_conv", w.blk[n].kc);
+        conv(p + ".kernel_predictor.bias_conv", w.blk[n].bc);
+        for (int i = 0; i < fd::LAYERS; ++i) {
+            const float *cw = w.blk[n].convs[i].w;
+            conv(p + ".convs." + std::to_string(i), w.blk[n].convs[i]);
+            J.pack_A(cw, w.lvc_conv_pack[n][i], fd::C, fd::C, 3);
+            if (n == 0) J.pack(fdk::WP_H16, cw, w.lvc_conv_h16[i], 2 * 3 * 512, 0, 0, 512, OK_LVC);
+            J.pack_A_h2(cw, w.lvc_conv_h2[n][i], fd::C, fd::C, 3, OK_LVC);
+        }
+        J.gemm.blk[n] = {w.blk[n].kc.w, w.blk[n].kc.b, w.blk[n].bc.w, w.blk[n].bc.b, const_cast<float *>(w.gemm_pack[n]),
+                         const_cast<float *>(w.gemm_bias[n]), const_cast<uint16_t *>(w.gemm_h2_pack[n]), const_cast<uint16_t *>(w.gemm_w_pack[n])};
+    }
+    return FD_OK;
+}
+
+unsigned ok_mask(const DevWeights &w)
+{
+    return (w.gemm_f16_ok ? OK_GEMM : 0) | (w.gemm_w_ok ? OK_GEMM_W : 0) | (w.lvc_f16_ok ? OK_LVC : 0) | (w.dblock_f16_ok ? OK_DBLOCK : 0) |
+           (w.convt_f16_ok ? OK_CONVT : 0) | (w.kpf_f16_ok ? OK_KPF : 0);
+}
+
+}  // namespace
+
+extern "C" int fd_refresh_weights_device(fd_handle h, const fd_weight_ref *items, int n, void *stream_)
+{
+    if (!h || !items || n <= 0) return FD_ERR_INVALID;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (h->gen)
+        FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_refresh_weights_device: the packs of base.yaml's architecture only; this handle runs another "
+                                       "configuration (fd_set_weight + fd_commit_weights)");
+    if (!h->committed || !h->weight_arena)
+        FD_FAIL(h, FD_ERR_INVALID, "fd_refresh_weights_device: no committed weights to refresh (fd_commit_weights lays the arena out; call it once first)");
+    // every tensor against the state_dict, before anything is written
+    const std::vector<ParamSpec> specs = param_specs(h->cfg);
+    std::map<std::string, LiveParam> live;
+    for (int i = 0; i < n; ++i) {
+        const fd_weight_ref &it = items[i];
+        if (!it.name || !it.data || !it.dims || it.ndim <= 0 || it.ndim > 4) FD_FAIL(h, FD_ERR_INVALID, "fd_refresh_weights_device: item %d is incomplete", i);
+        const int rc = check_dims(h, "fd_refresh_weights_device", specs, it.name, it.dims, it.ndim);
+        if (rc != FD_OK) return rc;
+        const std::string key(it.name);
+        const size_t dot = key.rfind('.');
+        LiveParam &p = live[key.substr(0, dot)];
+        const std::string suffix = key.substr(dot + 1);
+        (suffix == "weight" ? p.w : suffix == "weight_v" ? p.v : suffix == "weight_g" ? p.g : p.b) = it.data;
+    }
+    for (const auto &s : specs) {
+        const LiveParam &p = live[s.name];
+        if (!p.b) FD_FAIL(h, FD_ERR_INVALID, "fd_refresh_weights_device: missing tensor %s.bias", s.name.c_str());
+        if (!(p.v && p.g) && !p.w) FD_FAIL(h, FD_ERR_INVALID, "fd_refresh_weights_device: missing tensor %s.weight (or weight_g/weight_v)", s.name.c_str());
+        if (!(p.v && p.g)) live[s.name].v = live[s.name].g = nullptr;      // like the host fold: weight_v and weight_g together, else weight
+    }
+    RefreshJobs J;
+    int rc = build_refresh_jobs(h, specs, live, J);
+    if (rc != FD_OK) return rc;
+
+    FD_HIP(h, hipSetDevice(h->device));
+    if ((rc = fd_settle(h)) != FD_OK) return rc;      // a pending host check would otherwise run its call again on the NEW weights
+    if ((rc = fd_follow_stream(h, stream)) != FD_OK) return rc;
+    // device memory of the lists: [256 bytes: the word of out-of-range families][fold][live][packs].  The same size at every call.
+    const size_t fold_b = J.fold.size() * sizeof(fdk::FoldJob), live_b = J.live.size() * sizeof(fdk::PackJob), pack_b = J.packs.size() * sizeof(fdk::PackJob);
+    const size_t lists_b = fold_b + live_b + pack_b, need = 256 + lists_b;
+    if (h->refresh_dev_bytes < need) {      // the first refresh (outside any capture); never again
+        if (h->refresh_dev) {
+            FD_HIP(h, hipDeviceSynchronize());
+            (void)hipFree(h->refresh_dev);
+            h->refresh_dev = nullptr;
+            h->refresh_dev_bytes = 0;
+        }
+        FD_HIP(h, hipMalloc(&h->refresh_dev, need));
+        h->refresh_dev_bytes = need;
+    }
+    if (!h->refresh_bad) FD_HIP(h, hipHostMalloc(reinterpret_cast<void **>(&h->refresh_bad), sizeof(unsigned), hipHostMallocDefault));
+    if (!h->refresh_done) FD_HIP(h, hipEventCreateWithFlags(&h->refresh_done, hipEventDisableTiming));
+    char *dev = static_cast<char *>(h->refresh_dev);
+    unsigned *bad = reinterpret_cast<unsigned *>(dev);
+    fd_context::StageSlot *sl = nullptr;
+    if ((rc = fd_stage_acquire(h, lists_b, &sl)) != FD_OK) return rc;
+    memcpy(sl->host, J.fold.data(), fold_b);
+    memcpy(sl->host + fold_b, J.live.data(), live_b);
+    memcpy(sl->host + fold_b + live_b, J.packs.data(), pack_b);
+    FD_HIP(h, hipMemsetAsync(bad, 0, sizeof(unsigned), stream));
+    FD_HIP(h, hipMemcpyAsync(dev + 256, sl->host, lists_b, hipMemcpyHostToDevice, stream));
+    if ((rc = fd_stage_commit(h, sl, stream)) != FD_OK) return rc;
+
+    h->embed_valid = false;      // the cached embedding rows are the old weights'
+    fdk::Launch L = {h, stream, false};
+    hipError_t e = fdk::wpack_fold(L, reinterpret_cast<const fdk::FoldJob *>(dev + 256), (int)J.fold.size(), J.fold_blocks);
+    if (e == hipSuccess) e = fdk::wpack_gather(L, reinterpret_cast<const fdk::PackJob *>(dev + 256 + fold_b), (int)J.live.size(), J.live_blocks, bad);
+    if (e == hipSuccess)
+        e = fdk::wpack_gather(L, reinterpret_cast<const fdk::PackJob *>(dev + 256 + fold_b + live_b), (int)J.packs.size(), J.pack_blocks, bad);
+    if (e == hipSuccess) e = fdk::wpack_gemm(L, J.gemm, bad);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_refresh_weights_device: kernel launch failed: %s", hipGetErrorString(e));
+    FD_HIP(h, hipMemcpyAsync(h->refresh_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    FD_HIP(h, hipEventRecord(h->refresh_done, stream));
+    h->refresh_pending = true;
+    ++h->n_refreshes;
+    return fd_mark_tail(h, stream);
+}
+
+// The flags of the last refresh, once: a changed flag changes which kernels a step launches, which the captured graphs have baked in.
+extern "C" int fd_settle_refresh(fd_handle h)
+{
+    if (!h->refresh_pending) return FD_OK;
+    FD_HIP(h, hipEventSynchronize(h->refresh_done));
+    h->refresh_pending = false;
+    const unsigned ok = OK_ALL & ~*h->refresh_bad;
+    if (ok == ok_mask(h->w)) return FD_OK;
+    const int rc = fd_settle(h);
+    if (rc != FD_OK) return rc;
+    FD_HIP(h, hipDeviceSynchronize());
+    h->w.gemm_f16_ok = ok & OK_GEMM; h->w.gemm_w_ok = ok & OK_GEMM_W; h->w.lvc_f16_ok = ok & OK_LVC;
+    h->w.dblock_f16_ok = ok & OK_DBLOCK; h->w.convt_f16_ok = ok & OK_CONVT; h->w.kpf_f16_ok = ok & OK_KPF;
+    drop_graph(h);
+    ++h->n_refresh_graph_drops;
+    return FD_OK;
+}
+
+extern "C" int fd_get_weight_image(fd_handle h, void *host_buf, size_t *nbytes)
+{
+    if (!h || !nbytes) return FD_ERR_INVALID;
+    if (!h->committed || !h->weight_arena) FD_FAIL(h, FD_ERR_STATE, "fd_get_weight_image: weights not committed");
+    if (!host_buf) { *nbytes = h->weight_bytes; return FD_OK; }
+    if (*nbytes < h->weight_bytes) FD_FAIL(h, FD_ERR_INVALID, "fd_get_weight_image: buffer of %zu bytes, the image has %zu", *nbytes, h->weight_bytes);
+    FD_HIP(h, hipSetDevice(h->device));
+    FD_HIP(h, hipDeviceSynchronize());
+    FD_HIP(h, hipMemcpy(host_buf, h->weight_arena, h->weight_bytes, hipMemcpyDeviceToHost));
+    *nbytes = h->weight_bytes;
+    return FD_OK;
+}
+
+extern "C" int fd_get_weight_flags(fd_handle h, unsigned *ok)
+{
+    if (!h || !ok) return FD_ERR_INVALID;
+    if (!h->committed) FD_FAIL(h, FD_ERR_STATE, "fd_get_weight_flags: weights not committed");
+    if (h->gen) FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_get_weight_flags: the flags of the tuned kernel set; this handle runs another configuration");
+    FD_HIP(h, hipSetDevice(h->device));
+    const int rc = fd_settle_refresh(h);
+    if (rc != FD_OK) return rc;
+    *ok = ok_mask(h->w);
+    return FD_OK;
+}
+
+extern "C" int fd_pack_source(const char *pack, int p0, int p1, int pos)
+{
+    if (!pack || pos < 0) return FD_ERR_INVALID;
+    const std::string k(pack);
+    if (k == "pack_a") return pack_A_src(pos, p0, p1);
+    if (k == "a_h2") { const int inner = p0 * p1 / 16 * 512; return pack_A_h2_src(pos / inner, pos % inner, p0, p1); }
+    if (k == "up") return up_pack_src(pos, p0);
+    if (k == "up_h2") return up_h2_src(pos / 2048, pos % 2048, p0);
+    if (k == "h16") return lvc_h16_src(pos / 512, pos % 512);
+    if (k == "final_fuse") return final_fuse_src(pos) < 0 ? fd::C * 7 : final_fuse_src(pos);
+    if (k == "gemm_row") { bool b; const int row = gemm_column_row(pos, &b); return b ? fd::KW + row : row; }
+    if (k == "gemm") { const TilePos q = gemm_pack_pos(pos); return q.col * fd::HID * 3 + q.widx; }
+    if (k == "gemm_h2") { const TilePos q = gemm_h2_pos(pos); return q.col * fd::HID * 3 + q.widx; }
+    return FD_ERR_INVALID;
 }

@@ -127,6 +127,10 @@ class FastDiff(nn.Module):
         self._options = {"fallback": "host", "defer_check": "1"}
         self._param_list = None                # the parameter tensors _state_signature last walked (see there)
         self._sig_calls = 0
+        # Set by whoever writes the parameters behind torch's back (TrainStep.step: its optimizer kernel takes raw pointers, so neither
+        # data_ptr nor _version moves): the next inference call then refreshes the handle's weights first (refresh_weights).
+        self._weights_dirty = False
+        self.last_refresh = None               # how the weights last reached the handle: "device", or "host: <why>"
 
     # ---- reference API --------------------------------------------------------------------------------
     def apply_weight_norm(self):
@@ -445,8 +449,8 @@ class FastDiff(nn.Module):
         self._invalidate_params()
         return super().load_state_dict(*args, **kwargs)
 
-    def _ready(self, device):
-        """Create the context on `device` if needed and (re)upload weights when any parameter changed."""
+    def _ensure_handle(self, device):
+        """The library and this module's context on `device`, created if needed (weights not looked at)."""
         lib = _capi.load()
         idx = device.index if device.index is not None else torch.cuda.current_device()
         if self._handle is None or self._handle_device != idx:
@@ -475,11 +479,72 @@ class FastDiff(nn.Module):
             for variant, a in self.__dict__.get("_mel_banks", {}).items():      # caller-supplied filter banks follow the module to a new device
                 _capi.check(lib, h, lib.fd_set_option(h, b"mel", variant.encode()), "fd_set_option")
                 _capi.check(lib, h, lib.fd_set_mel_filterbank(h, a.ctypes.data, 80, 513), "fd_set_mel_filterbank")
+        return lib
+
+    def _ready(self, device):
+        """Create the context on `device` if needed and (re)upload weights when any parameter changed."""
+        lib = self._ensure_handle(device)
         sig = self._state_signature()
         if sig != self._synced_state:
             self._upload_weights(lib)
             self._synced_state = sig
+            self._weights_dirty = False
+            self.last_refresh = "host: a parameter tensor was moved, loaded or written in place"
+        elif self._weights_dirty:
+            self.refresh_weights()
         return lib, self._handle
+
+    def refresh_weights(self, stream=None):
+        """Bring the inference handle's weights up to date with the parameters as they are NOW, on the device: the operand packs are
+        rebuilt in place from the live tensors (fd_refresh_weights_device), asynchronously on `stream` (a torch.cuda.Stream; None = the
+        current one), and the captured graphs stay valid.  For whoever writes parameters without torch noticing -- TrainStep.step sets
+        the module's dirty flag, and the next forward() / sample() calls this by itself; call it directly after writing parameters through
+        raw pointers of your own.  `last_refresh` says what happened: "device", or "host: <why>" when the weights went through
+        fd_set_weight / fd_commit_weights instead (the module's parameters are not on a HIP device; an architecture other than
+        base.yaml's; the handle's first weights, which lay the arena out; a parameter that is not contiguous float32)."""
+        p = next(self.parameters())
+        if not p.is_cuda:
+            if self._handle is None:       # nothing holds weights yet: the first inference call uploads them
+                self.last_refresh = "host: the parameters are not on a HIP device (no handle yet: uploaded by the first inference call)"
+                return
+            lib, why = _capi.load(), "the parameters are not on a HIP device"
+        else:
+            lib, why = self._ensure_handle(p.device), None
+            sd = self.state_dict()
+            if self._synced_state is None:
+                why = "the handle's first weights (fd_commit_weights lays the arena out)"
+            elif not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in sd.values()):
+                why = "a parameter is not a contiguous float32 tensor on the device"
+            else:
+                names = [k.encode() for k in sd]
+                dims = [(ct.c_int64 * t.dim())(*t.shape) for t in sd.values()]
+                items = (_capi.FdWeightRef * len(sd))(*[_capi.FdWeightRef(k, t.data_ptr(), d, t.dim(), 0)
+                                                        for k, t, d in zip(names, sd.values(), dims)])
+                s = self._stream(p.device) if stream is None else ct.c_void_p(getattr(stream, "cuda_stream", stream))
+                rc = lib.fd_refresh_weights_device(self._handle, items, len(sd), s)
+                if rc == _capi.FD_ERR_UNSUPPORTED:
+                    why = lib.fd_last_error(self._handle).decode()
+                else:
+                    _capi.check(lib, self._handle, rc, "fd_refresh_weights_device")
+        if why is not None:
+            self._upload_weights(lib)
+        self.last_refresh = "device" if why is None else "host: " + why
+        self._synced_state = self._state_signature()
+        self._weights_dirty = False
+
+    def weight_image(self):
+        """The handle's committed weight image as bytes (numpy uint8; fd_get_weight_image).  Synchronises.  For tests."""
+        lib, n = _capi.load(), ct.c_size_t(0)
+        _capi.check(lib, self._handle, lib.fd_get_weight_image(self._handle, None, ct.byref(n)), "fd_get_weight_image")
+        buf = np.empty(n.value, np.uint8)
+        _capi.check(lib, self._handle, lib.fd_get_weight_image(self._handle, buf.ctypes.data, ct.byref(n)), "fd_get_weight_image")
+        return buf
+
+    def weight_flags(self):
+        """The six fp16-range flags of the handle's weights as bits (fd_get_weight_flags); waits for a pending refresh.  For tests."""
+        lib, m = _capi.load(), ct.c_uint(0)
+        _capi.check(lib, self._handle, lib.fd_get_weight_flags(self._handle, ct.byref(m)), "fd_get_weight_flags")
+        return int(m.value)
 
     def _upload_weights(self, lib):
         h = self._handle

@@ -201,6 +201,9 @@ class TrainStep:
         if not collate:
             self.mel.copy_(mels, non_blocking=True)
             self.wav.copy_(wavs, non_blocking=True)
+        # the optimizer writes the parameters through raw pointers, which no tensor version counts: tell the module that its inference
+        # handle holds older weights (FastDiff._ready then refreshes them on the device before its next inference call)
+        self.model._weights_dirty = True
         if not self.use_graph:
             self.model.zero_grad(set_to_none=True)
             self.loss = self._run(self._state, collate)

@@ -78,7 +78,49 @@ FD_API int fd_sample_span(fd_handle h, const float *mel, int64_t mel_first, int6
                           const fd_step *table, int N, int ddim, const float *x_T, const float *z, uint64_t seed, uint64_t stream_id,
                           int window_frames, float *out, void *stream);
 
+/* Weights from live device tensors (no counterpart in the reference, whose modules read their own parameters).  fd_set_weight +
+ * fd_commit_weights go through the host and rebuild everything a handle holds: a new weight arena, every captured graph dropped, the
+ * device synchronised.  A training loop that evaluates its model every few hundred steps (FastDiff.py:52-119) changes only the VALUES:
+ * fd_refresh_weights_device rebuilds every operand pack of the tuned kernel set IN PLACE, on the device, from the parameter tensors where
+ * they lie -- weight norm folded as fd_commit_weights folds it (per row the double sum of squares in index order, one correctly rounded
+ * float division), the packs gathered through the same index functions as the host packer's (csrc/fd_wpack.h) -- so the arena ends up
+ * byte-equal to a host commit of the same tensors, no pointer of the handle changes, and the captured graphs stay valid.
+ *   items      HOST array of n tensors; name / dims as fd_set_weight takes them (<parameter>.weight, or .weight_v + .weight_g, and
+ *              .bias); data: DEVICE pointer on the handle's device, float32, contiguous.  They are read by kernels enqueued on `stream`:
+ *              keep them alive and unwritten until those have run (stream order suffices).  fc_t1 / fc_t2 must come as .weight.
+ *   Asynchronous on `stream`; allocates only at the first call (a work list of a few KB; never inside a capture); never synchronises
+ *   the device.  Ordered like every other call of the handle (one stream at a time, fastdiff_hip.h); settles a pending deferred
+ *   fd_sample first, which would otherwise be redone on the new weights.  The cached step-embedding rows are invalidated.
+ *   Range flags: whether every weight of a kernel family fits the fp16 range decides which kernels that family launches, and a captured
+ *   graph has the choice baked in.  The kernels OR the families that do not fit into one device word; the first inference call after a
+ *   refresh waits for the refresh alone, reads that word, and only if a family changed sides -- a weight left or re-entered
+ *   |w| < 32768 -- synchronises and drops the graphs.
+ * FD_ERR_UNSUPPORTED: a handle of another architecture than base.yaml's (use fd_set_weight + fd_commit_weights), fc_t1 / fc_t2 given
+ * weight-normed.  FD_ERR_INVALID: no committed weights yet (fd_commit_weights lays the arena out once), an unknown key, a wrong shape, a
+ * missing tensor.  Nothing has been written when an error is returned.  A later fd_set_weight + fd_commit_weights works as before. */
+typedef struct fd_weight_ref {
+    const char *name;
+    const float *data;
+    const int64_t *dims;
+    int32_t ndim, reserved;
+} fd_weight_ref;
+FD_API int fd_refresh_weights_device(fd_handle h, const fd_weight_ref *items, int n, void *stream);
+
 /* Test / introspection hooks (not on the reference's API surface) -------------------------------------- */
+
+/* The committed weight image (the arena of the tuned kernel set, or the generic path's weights) as bytes; host_buf NULL: *nbytes := its
+ * size.  Synchronises the device.  Two handles hold equal images exactly when they hold the same weights in the same packs. */
+FD_API int fd_get_weight_image(fd_handle h, void *host_buf, size_t *nbytes);
+/* The six range flags of the tuned kernel set's weights as bits (1 = every weight of the family fits fp16): 1 predictor GEMM, 2 its
+ * Winograd form, 4 LVC convs, 8 DBlocks, 16 ConvTranspose, 32 predictor front.  Settles a pending refresh's flags (waits for it). */
+FD_API int fd_get_weight_flags(fd_handle h, unsigned *ok_mask);
+/* The layout functions both weight packers share (csrc/fd_wpack.h), for tests (pure host code, no handle): the index into the folded
+ * source tensor that destination position `pos` of a pack holds.  pack: "pack_a" / "a_h2" (p0 = cin, p1 = ks: fp32 / fp16-piece
+ * A operands of a conv weight [cout][cin][ks]; a_h2: pos = mt * inner + i over one piece), "up" / "up_h2" (p0 = ratio r: ConvTranspose
+ * weight [32][32][2r]; up_h2: pos = ph * 2048 + i), "h16" (pos = (rt*3 + tap) * 512 + idx into [32][32][3]), "final_fuse" (into [32][7];
+ * 224 = the pad), "gemm_row" (pos = packed record position: kernel_conv row, or 24576 + bias_conv row), "gemm" / "gemm_h2" (pos inside a
+ * 32-column tile: column * 192 + weight).  < 0: unknown pack. */
+FD_API int fd_pack_source(const char *pack, int p0, int p1, int pos);
 
 /* Copies an intermediate of the LAST fd_forward to host (synchronises).  Names: "noise" [B,3,80], "a0".."a3",
  * "kp_h<n>" [B,64,T], "kpack<n>" [B,T,24832] (packed predicted kernels+bias of block n), "x<n>" [B,32,L_n],
@@ -113,6 +155,8 @@ FD_API int fd_reset_profile(fd_handle h);
  *   "graph_captures" / "graph_hits" / "graph_evictions"   fd_sample's graph look-ups since fd_create that captured a new graph / found
  *                    one / pushed the least recently used one out; "graphs_resident" / "graphs_retired" = kept now / evicted but not
  *                    yet destroyed (their last replay has not completed).
+ *   "weight_refreshes" fd_refresh_weights_device calls since fd_create; "refresh_graph_drops" = of those, the ones after which a range
+ *                    flag had changed and the graphs were dropped.
  *   "workspace_bytes" device memory of the handle's sampler workspace and of fd_sample_span's window batch (bounded by the window, not
  *                    by the utterance).
  * Returns the value (>= 0) or a negative status. */
