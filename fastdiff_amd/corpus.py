@@ -176,6 +176,24 @@ class TrainCorpus:
         starts = (w * (self.lengths[items] - self.frames).astype(np.uint64)) >> _S32
         return items, starts.astype(np.int64)
 
+    def eval_plan(self, batch, batch_size, seed=0, fill=False):
+        """picks [B, 2] int64: what fd_eval_collate reports for batch `batch` of an evaluation pass -- equal, not close.  Slot b is item
+        batch B + b at start (w (T - F)) >> 32, w the start word of plan() under id = batch; a slot behind the last item is (-1, -1).
+        fill=True: what the kernel CUTS instead, i.e. such a slot reads (n - 1, its start in item n - 1).  Pure integer numpy."""
+        B, n, j = int(batch_size), self.n_items, int(batch) & _M64
+        if B < 1:
+            raise ValueError(f"TrainCorpus.eval_plan: batch_size={batch_size}")
+        g = np.array([(j * B + b) & _M64 for b in range(B)], dtype=object)
+        active = np.array([x < n for x in g], bool)
+        items = np.array([int(x) if x < n else n - 1 for x in g], np.int64)
+        b = np.arange(B, dtype=np.uint64)
+        w = np.stack(_words(seed, START_STREAM, b >> np.uint64(2), np.uint64(j)), axis=-1)[np.arange(B), (b & np.uint64(3)).astype(np.int64)]
+        starts = ((w * (self.lengths[items] - self.frames).astype(np.uint64)) >> _S32).astype(np.int64)
+        picks = np.stack([items, starts], axis=1)
+        if not fill:
+            picks[~active] = -1
+        return picks
+
     def cut(self, items, starts):
         """(mels [B, 80, F], wavs [B, 1, F hop]) by torch slicing of the arenas, on their device: the reference's collater on given
         picks.  For inspection and tests; the training path is lvc_op.train_collate."""

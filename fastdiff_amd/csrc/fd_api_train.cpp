@@ -662,4 +662,53 @@ int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adam
     });
 }
 
+// An evaluation pass (fd_kernels_step.hip): the batch in item order, per-item distances, accumulators in device memory.
+int fd_eval_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
+                    uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked, void *stream)
+{
+    const char *who = "fd_eval_collate";
+    if (!h) return FD_ERR_INVALID;
+    if (!wav_arena || !mel_arena || !frame_off || !wavs || !mels || !picked) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (n_items < 1 || n_items > ((int64_t)1 << 28)) FD_FAIL(h, FD_ERR_INVALID, "%s: n_items=%lld (1..2^28)", who, (long long)n_items);
+    if (hop < 4 || hop % 4 != 0 || F < 1 || (int64_t)F * hop >= ((int64_t)1 << 31))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: hop=%d (a multiple of 4), F=%d", who, hop, F);
+    if (!aligned(wav_arena, 16) || !aligned(wavs, 16) || !aligned(frame_off, 8) || !aligned(picked, 8) || !aligned(state, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: wav_arena and wavs must be 16-byte aligned, frame_off, picked and state 8-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::eval_collate(La, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, wavs, mels, picked);
+    });
+}
+
+int fd_item_distance(fd_handle h, const float *a, const float *b, int B, int64_t n, int kind, float *out, void *stream)
+{
+    const char *who = "fd_item_distance";
+    if (!h) return FD_ERR_INVALID;
+    if (!a || !b || !out) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (n < 1 || (int64_t)B * n >= ((int64_t)1 << 36) || (kind != 0 && kind != 1))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: n=%lld, kind=%d (0 squared, 1 absolute)", who, (long long)n, kind);
+    if (!aligned(a, 16) || !aligned(b, 16)) FD_FAIL(h, FD_ERR_INVALID, "%s: a and b must be 16-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats((int64_t)B * fdk::item_distance_blocks(n)));
+        return e != hipSuccess ? e : fdk::item_distance(La, a, b, B, n, kind, out, h->step_scratch.p);
+    });
+}
+
+int fd_eval_accumulate(fd_handle h, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,
+                       fd_eval_state *acc, float *item_out, fd_train_state *advance, void *stream)
+{
+    const char *who = "fd_eval_accumulate";
+    if (!h) return FD_ERR_INVALID;
+    if (!values || !picked || !acc) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (bins < 1 || bins > FD_EVAL_MAX_BINS || T_train < 1)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: bins=%d (1..%d), T_train=%d", who, bins, FD_EVAL_MAX_BINS, T_train);
+    if (!aligned(picked, 8) || !aligned(acc, 8) || !aligned(advance, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: picked, acc and advance must be 8-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::eval_accumulate(La, values, steps, picked, B, T_train, bins, acc, item_out, advance);
+    });
+}
+
 }  // extern "C"

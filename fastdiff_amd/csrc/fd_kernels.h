@@ -122,6 +122,14 @@ hipError_t train_draw(const Launch &L, const float *x0, const float *alpha, int 
 hipError_t train_collate(const Launch &L, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
                          int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
                          float *mels, int64_t *picked);
+// an evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate, fd_item_distance, fd_eval_accumulate).  item_distance's scratch:
+// step_scratch_floats(B * item_distance_blocks(n)) floats of the handle's step scratch
+hipError_t eval_collate(const Launch &L, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                        int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked);
+int64_t item_distance_blocks(int64_t n);
+hipError_t item_distance(const Launch &L, const float *a, const float *b, int B, int64_t n, int kind, float *out, float *scratch);
+hipError_t eval_accumulate(const Launch &L, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,
+                           fd_eval_state *acc, float *item_out, fd_train_state *advance);
 hipError_t mse_forward(const Launch &L, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, float *scratch);
 hipError_t mse_backward(const Launch &L, const float *eps, const float *z, const float *dloss, int64_t n, float *deps);
 hipError_t adamw_multi(const Launch &L, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch);

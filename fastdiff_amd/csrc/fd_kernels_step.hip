@@ -113,6 +113,37 @@ constexpr int CL_TF = 64;                        // frames per transposed tile: 
 constexpr int CL_LD = CL_MELS + 1;               // tile row stride: 81 = 17 mod 32, so the 64 frames of a column read fall on distinct banks
 constexpr int CL_WAV4 = 4 * WG;                  // float4s of waveform a workgroup copies
 
+// What a workgroup of either collater copies once its slot's first frame is known: workgroups [0, mel_tiles) one transposed mel tile
+// each, the others CL_WAV4 float4s of waveform.  tile: CL_TF * CL_LD floats of LDS.
+__device__ __forceinline__ void collate_copy(float *tile, const float *wav_arena, const float *mel_arena, int64_t frame0, int hop, int F, int b,
+                                             int mel_tiles, float *wavs, float *mels)
+{
+    if ((int)blockIdx.x < mel_tiles) {
+        const int f0 = (int)blockIdx.x * CL_TF;
+        const int nf = min(CL_TF, F - f0);
+        const float *src = mel_arena + (frame0 + f0) * CL_MELS;
+        for (int e = threadIdx.x; e < nf * CL_MELS; e += WG) {
+            const int f = e / CL_MELS;
+            tile[f * CL_LD + (e - f * CL_MELS)] = src[e];
+        }
+        __syncthreads();
+        float *dst = mels + (int64_t)b * CL_MELS * F + f0;
+        const int f = threadIdx.x & 63;
+        if (f < nf)
+            for (int m = threadIdx.x >> 6; m < CL_MELS; m += WG / 64) dst[(int64_t)m * F + f] = tile[f * CL_LD + m];
+    } else {
+        const int64_t l4 = (int64_t)F * (hop / 4);
+        const float4 *src = reinterpret_cast<const float4 *>(wav_arena + frame0 * hop);
+        float4 *dst = reinterpret_cast<float4 *>(wavs) + (int64_t)b * l4;
+        const int64_t base = (int64_t)((int)blockIdx.x - mel_tiles) * CL_WAV4 + threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < CL_WAV4 / WG; ++j) {
+            const int64_t i = base + (int64_t)j * WG;
+            if (i < l4) dst[i] = src[i];
+        }
+    }
+}
+
 // grid (mel tiles + waveform chunks, B).  Source of the mel: the contiguous [F, 80] block of the arena, read element-wise in order
 // (coalesced), written into LDS row by row; destination [80, F]: a wave reads one column of the tile and writes 64 consecutive floats.
 __global__ void __launch_bounds__(WG) k_train_collate(const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
@@ -139,30 +170,37 @@ __global__ void __launch_bounds__(WG) k_train_collate(const float *wav_arena, co
         picked[2 * b + 1] = start;
     }
     if (!ok) return;
-    if ((int)blockIdx.x < mel_tiles) {
-        const int f0 = (int)blockIdx.x * CL_TF;
-        const int nf = min(CL_TF, F - f0);
-        const float *src = mel_arena + (first + start + f0) * CL_MELS;
-        for (int e = threadIdx.x; e < nf * CL_MELS; e += WG) {
-            const int f = e / CL_MELS;
-            tile[f * CL_LD + (e - f * CL_MELS)] = src[e];
-        }
-        __syncthreads();
-        float *dst = mels + (int64_t)b * CL_MELS * F + f0;
-        const int f = threadIdx.x & 63;
-        if (f < nf)
-            for (int m = threadIdx.x >> 6; m < CL_MELS; m += WG / 64) dst[(int64_t)m * F + f] = tile[f * CL_LD + m];
-    } else {
-        const int64_t l4 = (int64_t)F * (hop / 4);
-        const float4 *src = reinterpret_cast<const float4 *>(wav_arena + (first + start) * hop);
-        float4 *dst = reinterpret_cast<float4 *>(wavs) + (int64_t)b * l4;
-        const int64_t base = (int64_t)((int)blockIdx.x - mel_tiles) * CL_WAV4 + threadIdx.x;
-#pragma unroll
-        for (int j = 0; j < CL_WAV4 / WG; ++j) {
-            const int64_t i = base + (int64_t)j * WG;
-            if (i < l4) dst[i] = src[i];
-        }
+    collate_copy(tile, wav_arena, mel_arena, first + start, hop, F, b, mel_tiles, wavs, mels);
+}
+
+// The batch of an evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate; TrainCorpus.eval_plan is the host twin): slot b of
+// batch `it` is item g = it B + b itself, in order and without wrapping; the window start is the training collater's draw (same
+// stream, position and word, the id = the batch index).  A slot behind the last item is cut from item n - 1 -- the forward then reads
+// finite data -- and reported as (-1, -1): fd_eval_accumulate leaves it out.
+__global__ void __launch_bounds__(WG) k_eval_collate(const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
+                                                     int hop, int F, int B, unsigned long long seed, const fd_train_state *state,
+                                                     unsigned long long iter_host, int mel_tiles, float *wavs, float *mels, int64_t *picked)
+{
+    __shared__ float tile[CL_TF * CL_LD];
+    const int b = blockIdx.y;
+    const unsigned long long it = state ? state->iter : iter_host;
+    const uint64_t g = it * (uint64_t)B + (uint64_t)b;
+    const bool active = g < (uint64_t)n_items;
+    const int64_t item = active ? (int64_t)g : n_items - 1;
+    const int64_t first = frame_off[item];
+    const int64_t range = frame_off[item + 1] - first - F;
+    uint32_t r[4];
+    philox_keyed(seed, 0xFFFFFFFCu, (uint64_t)(b >> 2), it, r);
+    const int c = b & 3;
+    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
+    const bool ok = range >= 1 && range < ((int64_t)1 << 32);
+    const int64_t start = ok ? (int64_t)(((uint64_t)w * (uint64_t)range) >> 32) : -1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        picked[2 * b] = active ? item : -1;
+        picked[2 * b + 1] = active ? start : -1;
     }
+    if (!ok) return;
+    collate_copy(tile, wav_arena, mel_arena, first + start, hop, F, b, mel_tiles, wavs, mels);
 }
 
 // ---- the loss ----------------------------------------------------------------------------------------------------------------------
@@ -217,6 +255,102 @@ __global__ void __launch_bounds__(WG) k_mse_backward(const float *eps, const flo
     for (int j = 0; j < RUN; ++j) {
         const int64_t i = base + (int64_t)j * WG;
         if (i < n) deps[i] = (eps[i] - z[i]) * s;
+    }
+}
+
+// ---- an evaluation pass: per-item distances and the accumulators ---------------------------------------------------------------------
+// fd_item_distance: out[i] = mean over item i's n elements of (a - b)^2 (kind 0) or |a - b| (kind 1).  grid (P, B): workgroup (p, i) sums
+// 16-byte slots [p * ED_SLOTS, (p + 1) * ED_SLOTS) of item i, a thread RUN / 4 of them = a serial run of RUN elements, then block_sum; the P
+// partial sums of an item lie together in the scratch and one final workgroup per item adds them (final_sum).  No workgroup touches two
+// items.  The slots of an item are the ALIGNED float4s of the whole [B, n] array that it overlaps (n need not be a multiple of 4): a slot
+// that lies wholly inside the item is one 16-byte load per operand, its first and last slot may be shared with a neighbour (or end
+// behind the array) and are read element by element, the item's own elements only -- a neighbour's inf never enters the sum.
+constexpr int ED_SLOTS = (RUN / 4) * WG;          // float4 slots per workgroup
+static_assert(RUN % 4 == 0, "a thread's run is whole float4s");
+
+__device__ __forceinline__ float dist_add(float acc, float x, float y, int kind)
+{
+    const float d = x - y;
+    return kind == 0 ? fmaf(d, d, acc) : acc + fabsf(d);
+}
+
+__global__ void __launch_bounds__(WG) k_item_distance_partial(const float *a, const float *b, int64_t n, int kind, int P, float *partial)
+{
+    const int64_t lo = (int64_t)blockIdx.y * n, hi = lo + n;      // the item's elements in the whole array
+    const int64_t s_lo = lo >> 2, s_hi = (hi + 3) >> 2;           // its slots
+    const float4 *a4 = reinterpret_cast<const float4 *>(a), *b4 = reinterpret_cast<const float4 *>(b);
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < RUN / 4; ++j) {
+        const int64_t s = s_lo + (int64_t)blockIdx.x * ED_SLOTS + (int64_t)j * WG + threadIdx.x;
+        if (s >= s_hi) continue;
+        const int64_t e = s << 2;
+        if (e >= lo && e + 4 <= hi) {
+            const float4 x = a4[s], y = b4[s];
+            acc = dist_add(acc, x.x, y.x, kind);
+            acc = dist_add(acc, x.y, y.y, kind);
+            acc = dist_add(acc, x.z, y.z, kind);
+            acc = dist_add(acc, x.w, y.w, kind);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (e + k >= lo && e + k < hi) acc = dist_add(acc, a[e + k], b[e + k], kind);
+        }
+    }
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * P + blockIdx.x] = acc;
+}
+
+__global__ void __launch_bounds__(WG) k_item_distance_final(const float *partial, int P, int64_t n, float *out)
+{
+    const float total = final_sum(partial + (int64_t)blockIdx.x * P, P);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)((double)total / (double)n);
+}
+
+// fd_eval_accumulate: one workgroup.  Thread k < bins walks the slots in order and adds those of bin k; thread ACC_TOTAL walks them for
+// the totals, the per-item output and the batch counter.  Every sum is therefore formed in slot order.  Whether a value takes part is
+// decided on its bits (not_finite): the build lets the compiler drop ordinary NaN compares.
+constexpr int ACC_TOTAL = FD_EVAL_MAX_BINS;
+constexpr int ACC_WG = 2 * FD_EVAL_MAX_BINS;
+
+__global__ void __launch_bounds__(ACC_WG) k_eval_accumulate(const float *values, const float *steps, const int64_t *picked, int B, int T_train,
+                                                            int bins, fd_eval_state *acc, float *item_out, fd_train_state *advance)
+{
+    const int t = threadIdx.x;
+    if (t == ACC_TOTAL) {
+        double sum = acc->sum;
+        uint64_t count = acc->count, bad = acc->nonfinite;
+        for (int b = 0; b < B; ++b) {
+            const int64_t item = picked[2 * b];
+            if (item < 0) continue;
+            const float v = values[b];
+            if (item_out) item_out[item] = v;
+            if (not_finite(v)) {
+                ++bad;
+            } else {
+                sum += (double)v;
+                ++count;
+            }
+        }
+        acc->sum = sum;
+        acc->count = count;
+        acc->nonfinite = bad;
+        if (advance) advance->iter += 1ull;
+    } else if (steps && t < bins) {
+        double sum = acc->bin_sum[t];
+        uint64_t count = acc->bin_count[t];
+        for (int b = 0; b < B; ++b) {
+            if (picked[2 * b] < 0) continue;
+            const float v = values[b], ts = steps[b];
+            if (not_finite(v) || not_finite(ts)) continue;
+            int64_t bin = ((int64_t)ts * bins) / T_train;
+            bin = bin < 0 ? 0 : (bin >= bins ? bins - 1 : bin);      // (a step outside [0, T_train) lands in an end bin)
+            if (bin != t) continue;
+            sum += (double)v;
+            ++count;
+        }
+        acc->bin_sum[t] = sum;
+        acc->bin_count[t] = count;
     }
 }
 
@@ -376,6 +510,40 @@ hipError_t train_collate(const Launch &L_, const float *wav_arena, const float *
     FD_LAUNCH(L_, "train_collate", k_train_collate, dim3((unsigned)(mel_tiles + wav_chunks), (unsigned)B), dim3(WG), 0, wav_arena, mel_arena,
               frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host, rank, world, mel_tiles, wavs, mels,
               picked);
+    return hipSuccess;
+}
+
+hipError_t eval_collate(const Launch &L_, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                        int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked)
+{
+    const int mel_tiles = (F + CL_TF - 1) / CL_TF;
+    const int64_t l4 = (int64_t)F * (hop / 4);
+    const int wav_chunks = (int)((l4 + CL_WAV4 - 1) / CL_WAV4);
+    FD_LAUNCH(L_, "eval_collate", k_eval_collate, dim3((unsigned)(mel_tiles + wav_chunks), (unsigned)B), dim3(WG), 0, wav_arena, mel_arena,
+              frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host, mel_tiles, wavs, mels, picked);
+    return hipSuccess;
+}
+
+// workgroups per item: the most slots an item of n elements overlaps (one more than n / 4 when its ends can lie inside slots)
+int64_t item_distance_blocks(int64_t n)
+{
+    const int64_t slots = n % 4 == 0 ? n / 4 : (n + 3) / 4 + 1;
+    return (slots + ED_SLOTS - 1) / ED_SLOTS;
+}
+
+hipError_t item_distance(const Launch &L_, const float *a, const float *b, int B, int64_t n, int kind, float *out, float *scratch)
+{
+    float *partial = scratch + DEC_FLOATS;
+    const int P = (int)item_distance_blocks(n);
+    FD_LAUNCH(L_, "item_distance_partial", k_item_distance_partial, dim3((unsigned)P, (unsigned)B), dim3(WG), 0, a, b, n, kind, P, partial);
+    FD_LAUNCH(L_, "item_distance_final", k_item_distance_final, dim3((unsigned)B), dim3(WG), 0, (const float *)partial, P, n, out);
+    return hipSuccess;
+}
+
+hipError_t eval_accumulate(const Launch &L_, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,
+                           fd_eval_state *acc, float *item_out, fd_train_state *advance)
+{
+    FD_LAUNCH(L_, "eval_accumulate", k_eval_accumulate, dim3(1), dim3(ACC_WG), 0, values, steps, picked, B, T_train, bins, acc, item_out, advance);
     return hipSuccess;
 }
 

@@ -1036,3 +1036,71 @@ def adamw_multi(items, hyper, state):
         assert g is None or (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == p.numel())
         tab[i] = (p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
     _call(state.device, "fd_adamw_multi", "fd_adamw_multi", tab.ctypes.data, len(items), hyper, state)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# An evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate, fd_item_distance, fd_eval_accumulate; fastdiff_amd/validate.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+EVAL_MAX_BINS = 64
+_EVAL_WORDS = 4 + 2 * EVAL_MAX_BINS      # fd_eval_state as 8-byte words: sum, count, nonfinite, reserved, bin_sum[64], bin_count[64]
+
+
+def new_eval_state(device):
+    """A zeroed fd_eval_state: 1056 bytes of device memory as int64 words (the double sums are read through a float64 view)."""
+    return torch.zeros(_EVAL_WORDS, dtype=torch.int64, device=device)
+
+
+def read_eval_state(acc, bins=EVAL_MAX_BINS):
+    """fd_eval_state -> {"sum", "count", "nonfinite", "bin_sum" [bins] float64, "bin_count" [bins] int64} (synchronises)."""
+    import numpy as np
+    raw = acc.cpu().numpy()
+    f = raw.view(np.float64)
+    return {"sum": float(f[0]), "count": int(raw[1]), "nonfinite": int(raw[2]), "bin_sum": f[4: 4 + bins].copy(),
+            "bin_count": raw[4 + EVAL_MAX_BINS: 4 + EVAL_MAX_BINS + bins].copy()}
+
+
+def eval_collate(corpus, batch_size, seed=0, iteration=0, state=None, out=None):
+    """The batch of an evaluation pass cut on the device (fd_eval_collate) -> (mels [B, 80, F], wavs [B, 1, F * hop], picked [B, 2] int64):
+    slot b of batch `it` is item it B + b itself; a slot behind the last item is filled from the last item and reported as (-1, -1).
+    corpus.eval_plan(it, B, seed) gives the same picks on the host.  The batch index is state's `iter` (read on the device) or, without
+    a state, `iteration`.  out: (mels, wavs, picked) to write into."""
+    if not corpus.wav.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.eval_collate runs only on a HIP device (no CPU fallback): corpus.to(device) uploads the corpus")
+    dev, B, F, hop = corpus.wav.device, int(batch_size), corpus.frames, corpus.hop_size
+    if out is None:
+        out = (torch.empty((B, 80, F), device=dev, dtype=torch.float32), torch.empty((B, 1, F * hop), device=dev, dtype=torch.float32),
+               torch.empty((B, 2), device=dev, dtype=torch.int64))
+    mels, wavs, picked = out
+    for t, shape, dtype in ((mels, (B, 80, F), torch.float32), (wavs, (B, 1, F * hop), torch.float32), (picked, (B, 2), torch.int64)):
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev, "out: (mels [B, 80, F], wavs [B, 1, F hop], picked [B, 2] int64)"
+    assert state is None or state.device == dev
+    _call(dev, "fd_eval_collate", "fd_eval_collate", corpus.wav, corpus.mel, corpus.frame_off, corpus.n_items, hop, F, B,
+          int(seed) & 0xFFFFFFFFFFFFFFFF, state, int(iteration) & 0xFFFFFFFFFFFFFFFF, wavs, mels, picked)
+    return mels, wavs, picked
+
+
+def item_distance(a, b, kind=0, out=None):
+    """out[i] = mean over item i of (a - b)^2 (kind 0) or |a - b| (kind 1) for a, b [B, ...] (fd_item_distance): fixed-order sums, two
+    calls agree bit for bit, an item's value depends on that item's elements alone."""
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("fastdiff_amd.lvc_op.item_distance runs only on a HIP device (no CPU fallback)")
+    a, b = _f32(a, b)
+    assert a.shape == b.shape and a.dim() >= 1 and a.numel() > 0 and kind in (0, 1)
+    B = a.shape[0]
+    if out is None:
+        out = torch.empty(B, device=a.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B,) and out.dtype == torch.float32 and out.is_contiguous() and out.device == a.device
+    _call(a.device, "fd_item_distance", "fd_item_distance", a, b, B, a.numel() // B, int(kind), out)
+    return out
+
+
+def eval_accumulate(values, picked, acc, steps=None, T_train=1, bins=1, item_out=None, advance=None):
+    """Add the values [B] of a batch's active slots (picked [B, 2] from eval_collate) to the fd_eval_state `acc` in slot order
+    (fd_eval_accumulate); with steps [B] also to bin (ts bins) // T_train; item_out[item] = value; advance: the pass's train state,
+    whose batch index goes up by one behind this call."""
+    dev, B = values.device, values.numel()
+    for t, n, dtype in ((values, B, torch.float32), (steps, B, torch.float32), (picked, 2 * B, torch.int64), (acc, _EVAL_WORDS, torch.int64),
+                        (advance, 4, torch.int64), (item_out, None, torch.float32)):
+        assert t is None or (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and n in (None, t.numel())), \
+            "eval_accumulate: contiguous HIP tensors of one device: values / steps [B] float32, picked [B, 2] int64"
+    _call(dev, "fd_eval_accumulate", "fd_eval_accumulate", values, steps, picked, B, int(T_train), int(bins), acc, item_out, advance)

@@ -254,6 +254,48 @@ typedef struct fd_adamw_hyper {
 } fd_adamw_hyper;
 FD_API int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, void *stream);
 
+/* An evaluation pass over a held-out corpus on the device (fastdiff_amd/validate.py: Validator): every item exactly once,
+ * windows and draws a pure function of (seed, batch index), everything accumulated in device memory.  A pass keeps an fd_train_state
+ * of its own whose `iter` is the batch index (zeroed at the start of a pass); fd_train_draw is used as it is on that state and seed.
+ *
+ * fd_eval_collate: the batch of an evaluation pass; arguments and limits as fd_train_collate (no rank / world: the held-out loader is
+ * neither shuffled nor sharded, vocoder_base.py:29).  With `it` = state ? state->iter : iter_host, slot b stands at g = it B + b
+ * (< 2^64) and takes
+ *   g <  n_items: item g,           picked[b] = (g, start)
+ *   g >= n_items: item n_items - 1, picked[b] = (-1, -1)      (inactive: filled so that the forward reads finite data)
+ *   start = (w * (T_item - F)) >> 32, w = word b & 3 of Philox4x32-10 keyed (seed, stream 0xFFFFFFFC, position b >> 2, id it)
+ * -- the training collater's start draw; no new stream.  TrainCorpus.eval_plan is the host twin. */
+FD_API int fd_eval_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
+                           int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels,
+                           int64_t *picked, void *stream);
+
+/* out[i] = mean over item i's n elements of (a - b)^2 (kind 0) or |a - b| (kind 1); a, b [B, n] (device, float32, contiguous, the
+ * arrays 16-byte aligned; n need not be a multiple of 4), out [B].  Sums as above in this section: a thread adds a run of FD_STEP_RUN
+ * elements (four 16-byte loads per operand; only an item's first and last 16 bytes are read element-wise where n or the item's
+ * offset is no multiple of 4), a tree inside the workgroup, per-workgroup partial sums in the handle's step scratch, one final
+ * workgroup per item.  A workgroup never touches two items: a non-finite element spoils its own item's value only.  No atomics; two runs agree bit
+ * for bit.  B n < 2^36. */
+FD_API int fd_item_distance(fd_handle h, const float *a, const float *b, int B, int64_t n, int kind, float *out, void *stream);
+
+/* The accumulators of a pass: caller-owned device memory, zeroed before the pass; only fd_eval_accumulate writes it. */
+#define FD_EVAL_MAX_BINS 64
+typedef struct fd_eval_state {
+    double sum;                              /* of the finite values of active slots, added in slot order */
+    uint64_t count;                          /* how many */
+    uint64_t nonfinite;                      /* active slots whose value was inf or NaN (not added anywhere) */
+    uint64_t reserved;
+    double bin_sum[FD_EVAL_MAX_BINS];        /* the same per bin of the diffusion step */
+    uint64_t bin_count[FD_EVAL_MAX_BINS];
+} fd_eval_state;
+
+/* One launch of one workgroup.  For every slot b with picked[b][0] >= 0, in slot order: item_out[picked[b][0]] = values[b] (item_out
+ * nullable); a finite values[b] is added (as double) to acc->sum with count += 1 and, when steps is not NULL, to bin
+ * (ts * bins) / T_train, ts = (integer) steps[b] as fd_train_draw writes it; a non-finite one only counts in acc->nonfinite.  Inactive
+ * slots contribute nothing.  advance (nullable): the pass's fd_train_state; its `iter` += 1, behind every read of it in stream order
+ * (as fd_adamw_multi does for a training step).  1 <= bins <= FD_EVAL_MAX_BINS; T_train >= 1. */
+FD_API int fd_eval_accumulate(fd_handle h, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,
+                              fd_eval_state *acc, float *item_out, fd_train_state *advance, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
