@@ -662,6 +662,22 @@ int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adam
     });
 }
 
+int fd_ema_multi(fd_handle h, const fd_ema_item *items, int n, const fd_ema_hyper *hyper, const fd_train_state *state, fd_ema_state *ema,
+                 void *stream)
+{
+    const char *who = "fd_ema_multi";
+    if (!h) return FD_ERR_INVALID;
+    if (!items || !hyper || !state || !ema || !aligned(hyper, 8) || !aligned(state, 8) || !aligned(ema, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer (hyper, state and ema: device memory, 8-byte aligned)", who);
+    if (n <= 0 || n > 65536) FD_FAIL(h, FD_ERR_INVALID, "%s: n=%d", who, n);
+    for (int i = 0; i < n; ++i) {
+        const fd_ema_item &I = items[i];
+        if (I.numel <= 0 || I.numel >= ((int64_t)1 << 32) || !I.p || !I.e || !aligned(I.p, 4) || !aligned(I.e, 4))
+            FD_FAIL(h, FD_ERR_INVALID, "%s: item %d: numel=%lld, a null pointer or one that is not 4-byte aligned", who, i, (long long)I.numel);
+    }
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::ema_multi(La, items, n, hyper, state, ema); });
+}
+
 // An evaluation pass (fd_kernels_step.hip): the batch in item order, per-item distances, accumulators in device memory.
 int fd_eval_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
                     uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked, void *stream)

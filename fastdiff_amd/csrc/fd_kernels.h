@@ -133,6 +133,8 @@ hipError_t eval_accumulate(const Launch &L, const float *values, const float *st
 hipError_t mse_forward(const Launch &L, const float *eps, const float *z, int64_t n, float *loss, fd_train_state *state, float *scratch);
 hipError_t mse_backward(const Launch &L, const float *eps, const float *z, const float *dloss, int64_t n, float *deps);
 hipError_t adamw_multi(const Launch &L, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch);
+// e += w (p - e) over n tensors behind the optimizer (fd_ema_multi): one deciding thread, then ceil(n / 64) update launches; no scratch
+hipError_t ema_multi(const Launch &L, const fd_ema_item *items, int n, const fd_ema_hyper *hyper, const fd_train_state *state, fd_ema_state *ema);
 }  // namespace fdk
 
 // The exact-fp32 reference kernels (fd_generic.hip): one thread per output, runtime shapes, fp32 multiply-adds in a fixed order.  The

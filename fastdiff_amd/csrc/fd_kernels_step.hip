@@ -1,6 +1,6 @@
 // fd_kernels_step.hip -- the rest of a training step around the denoiser's forward and backward (include/fastdiff_hip_train.h, last
 // section): the batch cut from a device-resident corpus, the draws of theta_timestep_loss, the MSE loss both ways, and
-// clip_grad_norm_ + non-finite guard + AdamW over all parameter tensors.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
+// clip_grad_norm_ + non-finite guard + AdamW over all parameter tensors, and an optional moving average of them behind it.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
 // update is skipped -- is read from and written to device memory, so a captured step replays with fresh draws and no host round trip.
 //
 // Sums (loss, squared gradient norm): a thread adds RUN = FD_STEP_RUN elements serially, the 256 threads of a workgroup are added by a
@@ -476,6 +476,84 @@ __global__ void __launch_bounds__(WG) k_adamw_update(const AdamChunk c, const Ad
     }
 }
 
+// ---- an exponential moving average of the parameters ---------------------------------------------------------------------------------
+// fd_ema_multi (include/fastdiff_hip_train.h): e += w (p - e) over all tensors, behind the optimizer in stream order.  One thread decides
+// -- whether the optimizer applied a step since the average last moved, and the weight of this update -- and stores that in the caller's
+// fd_ema_state; the update launches only read it, as k_adamw_update reads k_adamw_final's record.  No scratch of the handle, no atomics.
+// The records travel as kernel arguments (<= EMA_CHUNK per launch: 1.8 KB); TILE elements per workgroup, no workgroup straddles two
+// tensors.
+constexpr int EMA_CHUNK = 64;
+struct EmaChunk {
+    fd_ema_item it[EMA_CHUNK];
+    int first_block[EMA_CHUNK + 1];
+    int n;
+};
+
+__global__ void __launch_bounds__(64) k_ema_decide(const fd_ema_hyper *hyper, const fd_train_state *state, fd_ema_state *ema)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const fd_ema_hyper hy = *hyper;
+    const unsigned long long updates = ema->updates, applied = state->applied;
+    const int apply = applied > ema->seen_applied ? 1 : 0;
+    double decay = hy.decay;
+    if (hy.warmup != 0.0) {
+        const double ramp = (1.0 + (double)updates) / (10.0 + (double)updates);
+        decay = ramp < decay ? ramp : decay;
+    }
+    ema->w = (float)(1.0 - decay);
+    ema->apply = apply;
+    if (apply) {
+        ema->seen_applied = applied;
+        ema->updates = updates + 1ull;
+    }
+}
+
+__device__ __forceinline__ float ema_step(float e, float p, float w) { return e + w * (p - e); }
+
+__global__ void __launch_bounds__(WG) k_ema_update(const EmaChunk c, const fd_ema_state *ema)
+{
+    if (!ema->apply) return;
+    const float w = ema->w;
+    int lo = 0, hi = c.n;      // first_block[lo] <= blockIdx.x < first_block[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (c.first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    const float *p = c.it[lo].p;
+    float *e = c.it[lo].e;
+    const int64_t numel = c.it[lo].numel;
+    const int64_t tile0 = (int64_t)((int)blockIdx.x - c.first_block[lo]) * TILE;      // the tile's first element
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(e)) & 15) == 0) {
+        // 16 bytes per lane over the whole float4s of the tensor; its last numel % 4 elements one by one (they lie in the last tile)
+        const float4 *p4 = reinterpret_cast<const float4 *>(p);
+        float4 *e4 = reinterpret_cast<float4 *>(e);
+        const int64_t n4 = numel >> 2;
+        const int64_t base = (tile0 >> 2) + threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < RUN / 4; ++j) {
+            const int64_t i = base + (int64_t)j * WG;
+            if (i < n4) {
+                const float4 pv = p4[i];
+                float4 ev = e4[i];
+                ev.x = ema_step(ev.x, pv.x, w);
+                ev.y = ema_step(ev.y, pv.y, w);
+                ev.z = ema_step(ev.z, pv.z, w);
+                ev.w = ema_step(ev.w, pv.w, w);
+                e4[i] = ev;
+            }
+        }
+        const int64_t t = (n4 << 2) + threadIdx.x;
+        if (t < numel && t >= tile0 && t < tile0 + TILE) e[t] = ema_step(e[t], p[t], w);
+    } else {
+        const int64_t base = tile0 + threadIdx.x;
+#pragma unroll 4
+        for (int j = 0; j < RUN; ++j) {
+            const int64_t i = base + (int64_t)j * WG;
+            if (i < numel) e[i] = ema_step(e[i], p[i], w);
+        }
+    }
+}
+
 inline int64_t tiles(int64_t n) { return (n + TILE - 1) / TILE; }
 
 }  // namespace
@@ -598,6 +676,23 @@ hipError_t adamw_multi(const Launch &L_, const fd_adamw_item *items, int n, cons
     for (const AdamChunk &c : chunks)
         if (c.first_block[c.n] > 0 || c.last)
             FD_LAUNCH(L_, "adamw_update", k_adamw_update, dim3((unsigned)std::max(c.first_block[c.n], 1)), dim3(WG), 0, c, (const AdamDecision *)dec, state);
+    return hipSuccess;
+}
+
+// items: HOST memory.  1 + ceil(n / EMA_CHUNK) launches.
+hipError_t ema_multi(const Launch &L_, const fd_ema_item *items, int n, const fd_ema_hyper *hyper, const fd_train_state *state, fd_ema_state *ema)
+{
+    FD_LAUNCH(L_, "ema_decide", k_ema_decide, dim3(1), dim3(1), 0, hyper, state, ema);
+    for (int i0 = 0; i0 < n; i0 += EMA_CHUNK) {
+        EmaChunk c;
+        memset(&c, 0, sizeof(c));
+        c.n = std::min(EMA_CHUNK, n - i0);
+        for (int k = 0; k < c.n; ++k) {
+            c.it[k] = items[i0 + k];
+            c.first_block[k + 1] = c.first_block[k] + (int)tiles(items[i0 + k].numel);
+        }
+        FD_LAUNCH(L_, "ema_update", k_ema_update, dim3((unsigned)c.first_block[c.n]), dim3(WG), 0, c, (const fd_ema_state *)ema);
+    }
     return hipSuccess;
 }
 

@@ -1038,6 +1038,38 @@ def adamw_multi(items, hyper, state):
     _call(state.device, "fd_adamw_multi", "fd_adamw_multi", tab.ctypes.data, len(items), hyper, state)
 
 
+def new_ema_state(device):
+    """A zeroed fd_ema_state: 24 bytes of device memory, as three int64 words (updates, seen_applied, {w, apply})."""
+    return torch.zeros(3, dtype=torch.int64, device=device)
+
+
+def read_ema_state(ema_state):
+    """fd_ema_state -> dict (synchronises)."""
+    import numpy as np
+    raw = ema_state.cpu().numpy()
+    tail = raw[2:3]
+    return {"updates": int(raw[0]) & 0xFFFFFFFFFFFFFFFF, "seen_applied": int(raw[1]) & 0xFFFFFFFFFFFFFFFF,
+            "w": float(tail.view(np.float32)[0]), "apply": int(tail.view(np.int32)[1])}
+
+
+def ema_multi(items, hyper, state, ema_state):
+    """e += w (p - e) over all tensors, behind adamw_multi on the same stream (fd_ema_multi).  items: [(p, e)] float32 contiguous HIP
+    tensors of equal size that do not overlap; hyper: a device tensor of two float64 (fd_ema_hyper: decay, warmup); state: the
+    new_train_state tensor the optimizer advances (only read); ema_state: a new_ema_state tensor.  Nothing moves unless the
+    optimizer applied a step since the last update.  Does not synchronise."""
+    import numpy as np
+    dev = ema_state.device
+    assert hyper.dtype == torch.float64 and hyper.numel() == 2 and hyper.is_contiguous() and hyper.device == dev, "hyper: two float64 on the device"
+    assert state.dtype == torch.int64 and state.numel() == 4 and state.device == dev, "state: a new_train_state tensor on the device"
+    assert ema_state.dtype == torch.int64 and ema_state.numel() == 3 and ema_state.is_cuda, "ema_state: a new_ema_state tensor"
+    tab = np.zeros((len(items), 3), dtype=np.int64)      # fd_ema_item: p, e, numel
+    for i, (p, e) in enumerate(items):
+        assert p.is_contiguous() and e.is_contiguous() and p.dtype == e.dtype == torch.float32 and p.numel() == e.numel()
+        assert p.device == dev and e.device == dev
+        tab[i] = (p.data_ptr(), e.data_ptr(), p.numel())
+    _call(dev, "fd_ema_multi", "fd_ema_multi", tab.ctypes.data, len(items), hyper, state, ema_state)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # An evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate, fd_item_distance, fd_eval_accumulate; fastdiff_amd/validate.py)
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -131,6 +131,9 @@ class FastDiff(nn.Module):
         # data_ptr nor _version moves): the next inference call then refreshes the handle's weights first (refresh_weights).
         self._weights_dirty = False
         self.last_refresh = None               # how the weights last reached the handle: "device", or "host: <why>"
+        # Where the inference handle's weights come from (use_weights): None = the live parameters, else a mapping name -> tensor
+        self._weights_source = None
+        self._weights_label = None
 
     # ---- reference API --------------------------------------------------------------------------------
     def apply_weight_norm(self):
@@ -489,10 +492,58 @@ class FastDiff(nn.Module):
             self._upload_weights(lib)
             self._synced_state = sig
             self._weights_dirty = False
-            self.last_refresh = "host: a parameter tensor was moved, loaded or written in place"
+            self.last_refresh = "host: a parameter tensor was moved, loaded or written in place" + self._source_suffix()
         elif self._weights_dirty:
             self.refresh_weights()
         return lib, self._handle
+
+    def use_weights(self, source=None):
+        """Choose what the inference entry points (forward under no_grad, sample, ...) compute with: None = the live parameters, or a
+        fastdiff_amd.ParamEMA, or a mapping from every name of state_dict() to a tensor of that shape (device tensors are packed on the
+        device like the parameters, anything else goes through the host).  Wrong names or shapes raise here.  The call only records the
+        source and marks the handle's weights as stale: the next inference call repacks them (refresh_weights), and so does the first
+        one after every TrainStep.step -- a ParamEMA's shadow has moved by then.  The differentiable forward (train() mode with
+        gradients enabled) reads the live parameters whatever the source is.  Returns the previous source."""
+        previous = self._weights_source
+        self._weights_label = self.check_weights_source(source)
+        self._weights_source = source
+        self._weights_dirty = True
+        return previous
+
+    def check_weights_source(self, source):
+        """Raise ValueError unless `source` is something use_weights takes for this module; returns its label for `last_refresh`."""
+        if source is None:
+            return None
+        tensors = getattr(source, "tensors", source)
+        if not hasattr(tensors, "keys"):
+            raise ValueError(f"FastDiff.use_weights: a ParamEMA or a mapping from name to tensor is expected, got {type(source).__name__}")
+        want = self.state_dict()
+        missing = [k for k in want if k not in tensors]
+        extra = [k for k in tensors.keys() if k not in want]
+        if missing or extra:
+            raise ValueError(f"FastDiff.use_weights: the source's names are not the module's (missing {missing[:3]}, unexpected {extra[:3]})")
+        for k, t in want.items():
+            if not torch.is_tensor(tensors[k]) or tuple(tensors[k].shape) != tuple(t.shape):
+                raise ValueError(f"FastDiff.use_weights: {k}: expected a tensor of shape {list(t.shape)}, got "
+                                 f"{list(tensors[k].shape) if torch.is_tensor(tensors[k]) else type(tensors[k]).__name__}")
+        return type(source).__name__
+
+    @property
+    def weights_source(self):
+        """What use_weights recorded last (None: the live parameters)."""
+        return self._weights_source
+
+    def _source_suffix(self):
+        return "" if self._weights_source is None else f" (source: {self._weights_label})"
+
+    def _weight_tensors(self):
+        """name -> tensor of the recorded source, in state_dict() order."""
+        sd = self.state_dict()
+        src = self._weights_source
+        if src is None:
+            return sd
+        tensors = getattr(src, "tensors", src)
+        return {k: tensors[k].detach() for k in sd}
 
     def refresh_weights(self, stream=None):
         """Bring the inference handle's weights up to date with the parameters as they are NOW, on the device: the operand packs are
@@ -501,7 +552,8 @@ class FastDiff(nn.Module):
         the module's dirty flag, and the next forward() / sample() calls this by itself; call it directly after writing parameters through
         raw pointers of your own.  `last_refresh` says what happened: "device", or "host: <why>" when the weights went through
         fd_set_weight / fd_commit_weights instead (the module's parameters are not on a HIP device; an architecture other than
-        base.yaml's; the handle's first weights, which lay the arena out; a parameter that is not contiguous float32)."""
+        base.yaml's; the handle's first weights, which lay the arena out; a parameter that is not contiguous float32).  With a source
+        chosen by use_weights the tensors are that source's, and both strings end in " (source: <its type>)"."""
         p = next(self.parameters())
         if not p.is_cuda:
             if self._handle is None:       # nothing holds weights yet: the first inference call uploads them
@@ -510,7 +562,7 @@ class FastDiff(nn.Module):
             lib, why = _capi.load(), "the parameters are not on a HIP device"
         else:
             lib, why = self._ensure_handle(p.device), None
-            sd = self.state_dict()
+            sd = self._weight_tensors()
             if self._synced_state is None:
                 why = "the handle's first weights (fd_commit_weights lays the arena out)"
             elif not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in sd.values()):
@@ -528,7 +580,7 @@ class FastDiff(nn.Module):
                     _capi.check(lib, self._handle, rc, "fd_refresh_weights_device")
         if why is not None:
             self._upload_weights(lib)
-        self.last_refresh = "device" if why is None else "host: " + why
+        self.last_refresh = ("device" if why is None else "host: " + why) + self._source_suffix()
         self._synced_state = self._state_signature()
         self._weights_dirty = False
 
@@ -548,7 +600,7 @@ class FastDiff(nn.Module):
 
     def _upload_weights(self, lib):
         h = self._handle
-        for name, t in self.state_dict().items():
+        for name, t in self._weight_tensors().items():
             a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
             dims = (ct.c_int64 * a.ndim)(*a.shape)
             rc = lib.fd_set_weight(h, name.encode(), a.ctypes.data, dims, a.ndim)

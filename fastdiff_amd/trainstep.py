@@ -19,6 +19,11 @@ device-side step index as the draws), step() takes no argument and no byte of th
     for it in range(steps):
         loss = ts.step()                                                 # ts.picked: the (item, start frame) of every slot
 
+With ema_decay the step also keeps an exponential moving average of the parameters (fastdiff_amd/ema.py: ParamEMA; the reference has
+none), updated behind the optimizer inside the same replay and only when the optimizer applied the step:
+
+    ts = fastdiff_amd.TrainStep(model, diffusion_hyperparams, ema_decay=0.999)      # ts.ema; model.use_weights(ts.ema) vocodes from it
+
 The library's scratch buffers are per device and grow by free + allocate: a captured step has their addresses baked in, so a LARGER
 training call on the same device after the capture (a second TrainStep on a bigger model, a bigger batch through the eager training
 path) invalidates it -- one model per process and device, as for the training operators in general (lvc_op._handle).
@@ -31,7 +36,7 @@ from . import lvc_op
 
 class TrainStep:
     def __init__(self, model, diffusion_hyperparams, lr=2e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, clip_grad_norm=1.0, seed=0,
-                 graph=True, *, corpus=None, batch_size=None, rank=0, world_size=1):
+                 graph=True, *, ema_decay=None, ema_warmup=True, corpus=None, batch_size=None, rank=0, world_size=1):
         self.model = model
         self.params = list(model.parameters())
         if not self.params or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params):
@@ -63,6 +68,11 @@ class TrainStep:
             self.batch_size = int(batch_size)
             self.picked = torch.zeros((self.batch_size, 2), dtype=torch.int64, device=self.device)      # (item, start frame) of the last batch
         self.mel = self.wav = self.x_t = self.z = self.steps = None      # the static buffers of the current batch shape
+        # the average of the parameters (None: off, and no launch of the step is about it)
+        self.ema = None
+        if ema_decay is not None:
+            from .ema import ParamEMA
+            self.ema = ParamEMA(model, decay=ema_decay, warmup=ema_warmup)
 
     # ---- hyper-parameters and state ------------------------------------------------------------------------------------------------
     def _write_hyper(self):
@@ -90,11 +100,14 @@ class TrainStep:
         step = float(st["applied"])
         group = self._group_template()
         group["params"] = list(range(len(self.params)))
-        return {"state": {i: {"step": torch.tensor(step), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
-                          for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq))},
-                "param_groups": [group],
-                # what torch's layout has no place for (torch.optim.AdamW.load_state_dict ignores the key)
-                "train_step": {"iter": st["iter"], "skipped": st["skipped"], "clip_grad_norm": self.hyper["max_norm"], "seed": self.seed}}
+        sd = {"state": {i: {"step": torch.tensor(step), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
+                        for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq))},
+              "param_groups": [group],
+              # what torch's layout has no place for (torch.optim.AdamW.load_state_dict ignores the keys)
+              "train_step": {"iter": st["iter"], "skipped": st["skipped"], "clip_grad_norm": self.hyper["max_norm"], "seed": self.seed}}
+        if self.ema is not None:
+            sd["ema"] = self.ema.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         """From state_dict()'s layout, i.e. also from a torch.optim.AdamW over the same parameters (one parameter group).  A parameter
@@ -102,7 +115,8 @@ class TrainStep:
         optimizer one for all).  With state_dict()'s own "train_step" entry the draw counter, the skipped count and clip_grad_norm
         come back as saved; a dictionary that went through a torch optimizer has lost it, and the draw counter then continues at the
         step count -- after a run with skipped steps that repeats the draws of that many iterations -- while clip_grad_norm and the
-        seed stay the constructor's."""
+        seed stay the constructor's.  With ema_decay: an "ema" entry (ParamEMA.state_dict()) is restored; without one the average starts
+        again from the parameters as they are now -- load the module's state_dict first."""
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
             raise ValueError("TrainStep.load_state_dict: one parameter group over the module's parameters is expected")
@@ -127,6 +141,11 @@ class TrainStep:
             self.hyper["max_norm"] = float(extra["clip_grad_norm"])
             self._write_hyper()
         self._state.copy_(torch.tensor([int(extra.get("iter", step)), step, int(extra.get("skipped", 0)), 0], dtype=torch.int64))
+        if self.ema is not None:
+            if sd.get("ema") is not None:
+                self.ema.load_state_dict(sd["ema"])
+            else:
+                self.ema.reset(seen_applied=step)
 
     # ---- the step ----------------------------------------------------------------------------------------------------------------------
     def _collate(self):
@@ -144,13 +163,17 @@ class TrainStep:
         loss.backward()
         grads = [None if p.grad is None else p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in self.params]
         lvc_op.adamw_multi(list(zip(self.params, grads, self.exp_avg, self.exp_avg_sq)), self._hyper_dev, state)
+        if self.ema is not None:
+            self.ema.update(state)
         return loss.detach()
 
     def _warm_up(self, collate=False):
         """Three steps outside the capture (the library's scratch buffers grow on first use, which a capture cannot contain) that leave
         no trace: the draws only read the state, and the optimizer runs on a spare state with one more item whose only gradient element
-        is NaN -- every launch of the step happens, the guard keeps it from writing a parameter or a moment."""
+        is NaN -- every launch of the step happens, the guard keeps it from writing a parameter or a moment.  The average's launches
+        run on the spare state and a spare fd_ema_state: no step was applied there, so the shadow and its record stay as they are."""
         spare = lvc_op.new_train_state(self.device)
+        spare_ema = lvc_op.new_ema_state(self.device) if self.ema is not None else None
         poison = tuple(torch.full((1,), v, device=self.device) for v in (0.0, float("nan"), 0.0, 0.0))
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
@@ -164,6 +187,8 @@ class TrainStep:
                 loss.backward()
                 grads = [None if p.grad is None else p.grad.contiguous() for p in self.params]
                 lvc_op.adamw_multi(list(zip(self.params, grads, self.exp_avg, self.exp_avg_sq)) + [poison], self._hyper_dev, spare)
+                if self.ema is not None:
+                    self.ema.update(spare, spare_ema)
         torch.cuda.current_stream(self.device).wait_stream(side)
         self.model.zero_grad(set_to_none=True)
 

@@ -36,7 +36,7 @@ DEFAULT_SEED = 0x56414C      # "VAL"
 
 
 class Validator:
-    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None):
+    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None):
         if int(batch_size) < 1:
             raise ValueError(f"Validator: batch_size={batch_size} (at least 1)")
         if not 1 <= int(bins) <= lvc_op.EVAL_MAX_BINS:
@@ -45,6 +45,11 @@ class Validator:
         if not params or not all(p.is_cuda for p in params):
             raise RuntimeError("fastdiff_amd.Validator needs the module's parameters on a HIP device (no CPU fallback)")
         self.model, self.device = model, params[0].device
+        # what run() computes with: None = whatever the module uses (the live parameters unless its use_weights said otherwise), else a
+        # source as FastDiff.use_weights takes it (a ParamEMA, a mapping name -> tensor), chosen for the pass and handed back after it
+        self.weights = weights
+        if weights is not None:
+            model.check_weights_source(weights)      # names and shapes: refused now, not inside a pass
         if corpus.device != self.device:
             raise RuntimeError(f"Validator: the corpus lies on {corpus.device}, the module on {self.device} (corpus.to(device) uploads it)")
         if corpus.hop_size != model.hop_length:
@@ -103,14 +108,19 @@ class Validator:
 
     def run(self):
         """One pass: ceil(n / B) batches enqueued on the current stream, nothing read back (with sample_schedule: one wait per batch).
-        The module's `training` flag is as before afterwards."""
+        The module's `training` flag is as before afterwards.  With weights= the module computes from that source during the pass and
+        from its previous one after it; its packs are marked stale, so the next inference call builds them again from that one."""
         was_training = self.model.training
         self.model.eval()
+        switched = self.weights is not None
+        previous = self.model.use_weights(self.weights) if switched else None
         try:
             self.begin()
             for j in range(self.n_batches):
                 self.batch(j)
         finally:
+            if switched:
+                self.model.use_weights(previous)
             self.model.train(was_training)
         return self
 

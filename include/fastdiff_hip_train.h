@@ -254,6 +254,33 @@ typedef struct fd_adamw_hyper {
 } fd_adamw_hyper;
 FD_API int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, void *stream);
 
+/* An exponential moving average of n parameter tensors (fastdiff_amd/ema.py: ParamEMA; the reference has none), in 1 + ceil(n / 64)
+ * launches behind fd_adamw_multi in stream order.  It reads fd_train_state and never writes it; no scratch buffer of the handle, no
+ * atomics.  items: n records in HOST memory, passed on as kernel arguments (as fd_adamw_item); p and e must not overlap.  Tensors whose
+ * p and e are both 16-byte aligned are read and written 16 bytes per lane, the others element by element.  With u = ema->updates as it
+ * stands before the call, in double precision:
+ *   apply   = state->applied > ema->seen_applied      (a step the non-finite guard skipped did not advance `applied`: nothing moves)
+ *   decay_t = warmup != 0 ? min(decay, (1 + u) / (10 + u)) : decay;      w = (float)(1 - decay_t)
+ *   apply:    e = e + w * (p - e) for every element, each operation rounded on its own;
+ *             ema->seen_applied = state->applied;  ema->updates = u + 1
+ * ema->w and ema->apply are stored either way (what the update launches read). */
+typedef struct fd_ema_item {
+    const float *p;       /* [numel] parameter */
+    float *e;             /* [numel] its average */
+    int64_t numel;
+} fd_ema_item;
+typedef struct fd_ema_hyper {
+    double decay, warmup; /* DEVICE memory, as fd_adamw_hyper: a decay schedule is a copy of 8 bytes between replays */
+} fd_ema_hyper;
+typedef struct fd_ema_state { /* 24 bytes of DEVICE memory owned by the caller (zero it first).  Only kernels write it. */
+    uint64_t updates;      /* updates applied so far */
+    uint64_t seen_applied; /* state->applied at the last one */
+    float w;               /* 1 - decay_t of the last call */
+    int32_t apply;         /* whether the last call moved the average */
+} fd_ema_state;
+FD_API int fd_ema_multi(fd_handle h, const fd_ema_item *items, int n, const fd_ema_hyper *hyper, const fd_train_state *state,
+                        fd_ema_state *ema, void *stream);
+
 /* An evaluation pass over a held-out corpus on the device (fastdiff_amd/validate.py: Validator): every item exactly once,
  * windows and draws a pure function of (seed, batch index), everything accumulated in device memory.  A pass keeps an fd_train_state
  * of its own whose `iter` is the batch index (zeroed at the start of a pass); fd_train_draw is used as it is on that state and seed.
