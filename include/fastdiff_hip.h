@@ -164,7 +164,8 @@ FD_API int fd_sample_settle(fd_handle h, int64_t ticket);
 FD_API int fd_set_noise_streams(fd_handle h, const uint64_t *stream_ids, int B);
 
 /* Options (key = value; the first value is the default).  Each one selects between code paths that ship tested; measured-and-rejected
- * variants are not options (LABBOOK.md keeps their numbers).
+ * variants are not options (LABBOOK.md keeps their numbers).  tests/test_tile_borders.py holds every intermediate of the variants behind
+ * "gemm", "lvc", "conv", "gemm_form", "lvc_h8" and "kernels" to the float64 oracle at each tile border.
  *   "gemm" | "lvc" | "conv" = "f16x2" | "fp32"   the predictor GEMM / the LVC layers / DBlocks + ConvTranspose + predictor front on the
  *                          fp16 matrix pipe with 2-piece operands (22 significant bits, fp32 accumulation) or on the exact-fp32 one
  *   "gemm_form" = "winograd" | "direct"   the fp16x2 predictor GEMM evaluates kernel_conv's three taps as Winograd F(2,3) over the frame
