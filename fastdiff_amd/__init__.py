@@ -10,7 +10,9 @@ fastdiff_amd.TrainStep runs a whole training step -- draws, loss, clip, AdamW in
 fed from a device-resident fastdiff_amd.TrainCorpus whose batches are cut inside that replay (fastdiff_amd/corpus.py);
 fastdiff_amd.Validator runs a held-out pass on the device over fixed draws, with the loss per noise level (fastdiff_amd/validate.py);
 fastdiff_amd.ParamEMA keeps an exponential moving average of the parameters on the device, updated inside TrainStep's replay, and
-FastDiff.use_weights lets the inference kernels compute from it (fastdiff_amd/ema.py).
+FastDiff.use_weights lets the inference kernels compute from it (fastdiff_amd/ema.py);
+FastDiff.sample_long / stream vocode one utterance of any length window by window, FastDiff.sample_long_batch / stream_pool
+(fastdiff_amd.StreamPool) many utterances or live streams in shared window batches (fastdiff_amd/longform.py).
 """
 from .model import FastDiff  # noqa: F401
 from . import sampler, schedules  # noqa: F401
@@ -20,8 +22,9 @@ from .trainstep import TrainStep  # noqa: F401
 from .corpus import TrainCorpus  # noqa: F401
 from .validate import Validator  # noqa: F401
 from .ema import ParamEMA  # noqa: F401
+from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss"]

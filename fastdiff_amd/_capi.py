@@ -41,6 +41,22 @@ class FdEmaState(ct.Structure):
     _fields_ = [("updates", ct.c_uint64), ("seen_applied", ct.c_uint64), ("w", ct.c_float), ("apply", ct.c_int32)]
 
 
+class FdSpan(ct.Structure):
+    _fields_ = [("mel", ct.c_void_p), ("mel_pitch", ct.c_int64), ("mel_cap", ct.c_int64), ("mel_first", ct.c_int64),
+                ("mel_frames", ct.c_int64), ("utt_frames", ct.c_int64), ("t0", ct.c_int64), ("t1", ct.c_int64),
+                ("stream_id", ct.c_uint64), ("out", ct.c_void_p)]
+
+
+class FdSpanWindow(ct.Structure):
+    _fields_ = [("span", ct.c_int32), ("batch", ct.c_int32), ("len", ct.c_int32), ("clen", ct.c_int32), ("start", ct.c_int64),
+                ("c0", ct.c_int64)]
+
+
+class FdRingChunk(ct.Structure):
+    _fields_ = [("ring", ct.c_void_p), ("pitch", ct.c_int64), ("cap", ct.c_int64), ("first_frame", ct.c_int64), ("src", ct.c_void_p),
+                ("src_pitch", ct.c_int64), ("frames", ct.c_int64)]
+
+
 def step_table(rows):
     """[{t, c_eps, c_div, sigma, c1, c2, c3, add_noise}] (executed first -> last) -> the fd_step array fd_sample takes."""
     steps = (FdStep * len(rows))()
@@ -51,7 +67,7 @@ def step_table(rows):
 
 
 EXPORTS = ["fd_default_config", "fd_create", "fd_destroy", "fd_last_error", "fd_set_weight", "fd_commit_weights",
-           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
+           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
            "fd_get_profile", "fd_reset_profile", "fd_get_counter", "fd_version", "fd_abi_revision"]
 
 _lib = None
@@ -90,6 +106,9 @@ def load():
     lib.fd_sample_halo_frames.argtypes = [ci]
     i64, u64 = ct.c_int64, ct.c_uint64
     lib.fd_sample_span.argtypes = [vp, vp, i64, i64, i64, i64, i64, ct.POINTER(FdStep), ci, ci, vp, vp, u64, u64, ci, vp, vp]
+    lib.fd_sample_spans_plan.argtypes = [ct.POINTER(FdSpan), ci, ci, ci, ct.POINTER(FdSpanWindow), ci, ct.POINTER(ci)]
+    lib.fd_sample_spans.argtypes = [vp, ct.POINTER(FdSpan), ci, ct.POINTER(FdStep), ci, ci, u64, ci, vp]
+    lib.fd_mel_ring_append.argtypes = [vp, ct.POINTER(FdRingChunk), ci, vp]
     lib.fd_sample_check.argtypes = [vp]
     lib.fd_sample_ticket.argtypes = [vp]
     lib.fd_sample_ticket.restype = ct.c_int64

@@ -262,6 +262,8 @@ int64_t fd_get_counter(fd_handle h, const char *name)
     if (k == "refresh_graph_drops") return h->n_refresh_graph_drops;
     if (k == "graphs_resident") return (int64_t)h->graphs.size();
     if (k == "graphs_retired") return (int64_t)h->retired.size();
+    if (k == "span_batches") return h->n_span_batches;
+    if (k == "span_windows") return h->n_span_windows;
     if (k == "workspace_bytes") return (int64_t)(h->ws.bytes + h->span_scratch.bytes);
     FD_FAIL(h, FD_ERR_INVALID, "fd_get_counter: unknown counter '%s'", name);
 }

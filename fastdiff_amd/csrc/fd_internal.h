@@ -361,7 +361,9 @@ struct fd_context {
     Scratch lvc_scratch;                     // the LVC operator's frame-major kernel copy (fd_lvc_forward / fd_lvc_backward)
     Scratch kconv_scratch;                   // the partial sums of fd_kconv_backward* and fd_input_conv_backward*
     Scratch cconv_scratch;                   // per-workgroup partial sums of fd_conv32 / conv7 / upsample backward's dW / db
-    Scratch span_scratch;                    // fd_sample_span's window batch: mel, injected x_T / z and x_0 of up to 8 windows
+    Scratch span_scratch;                    // a window batch of fd_sample_span / fd_sample_spans: window records, mel, injected x_T / z, x_0
+    Scratch ring_scratch;                    // fd_mel_ring_append's chunk records
+    long long n_span_batches = 0, n_span_windows = 0;   // fd_get_counter: fd_sample calls / windows made by the span entry points
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -432,6 +434,23 @@ hipError_t span_gather(const Launch &L, const SpanWindows &w, int Wp, const floa
                        long long mel_first, long long mel_frames, float *mel_w, float *x_w, float *z_w);
 // x_0 of the windows [n][Wp*256] -> the caller's out over frames [t0, ...): each window's centre.  One launch.
 hipError_t span_scatter(const Launch &L, const SpanWindows &w, int Wp, const float *x_w, long long t0, float *out);
+// fd_sample_spans' window batch: windows of MANY utterances, each with its own source (a plain buffer or a ring) and destination.  The
+// records lie in device memory (uploaded through the handle's pinned staging ring), one per batch item.
+struct SpanRec {
+    const float *src;                    // channel c, utterance frame f at src[c * pitch + col(f)]
+    float *dst;                          // where the window's centre goes: its span's out + (c0 - t0) * 256
+    long long pitch, cap;                // cap 0: col(f) = f - mel_first; > 0: col(f) = f % cap
+    long long mel_first, mel_frames;     // the utterance frames the source holds
+    long long start, c0;                 // first frame of the window / of its centre
+    int len, clen;                       // frames of the window (<= Wp) / of its centre
+    long long pad_;                      // (80 bytes: a multiple of 16)
+};
+constexpr int SPANS_MAX_WINDOWS = 32;
+// recs [n] device.  gather: -> mel_w [n][80][Wp]; scatter: x_w [n][Wp*256] -> each record's dst.  One launch each.
+hipError_t spans_gather(const Launch &L, const SpanRec *recs, int n, int Wp, float *mel_w);
+hipError_t spans_scatter(const Launch &L, const SpanRec *recs, int n, int Wp, int max_clen, const float *x_w);
+// chunks [n] device (max_frames = the longest): frame first_frame + i of src -> column (first_frame + i) % cap of each ring row
+hipError_t ring_append(const Launch &L, const fd_ring_chunk *chunks, int n, long long max_frames);
 hipError_t copy_rows(const Launch &L, float *dst, int64_t dpitch, const float *src, int64_t spitch, int width, int rows, int reps = 1,
                      int64_t rep_stride = 0);
 hipError_t peak_normalize_int16(const Launch &L, const float *wav, int B, int64_t len, int16_t *pcm, const long long *valid_dev);

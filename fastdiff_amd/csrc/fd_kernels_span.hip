@@ -1,6 +1,7 @@
-// fd_kernels_span.hip -- the two copies around a window batch of fd_sample_span (fd_api_span.cpp): the caller's long tensors into the
-// padded [n][..][Wp] batch that fd_sample takes, and each window's exact centre of x_0 back into the caller's output.  The denoiser
-// itself runs on the tuned kernels, unchanged.
+// fd_kernels_span.hip -- the two copies around a window batch of fd_sample_span / fd_sample_spans (fd_api_span.cpp): the caller's long
+// tensors into the padded [n][..][Wp] batch that fd_sample takes, and each window's exact centre of x_0 back into the caller's output.
+// The denoiser itself runs on the tuned kernels, unchanged.  k_span_* serve one utterance with injected noise (windows by value);
+// k_spans_* serve windows of many utterances, plain buffers and rings, from records in device memory; k_ring_append feeds the rings.
 #include <algorithm>
 
 #include "fd_kernels.h"
@@ -70,6 +71,74 @@ hipError_t span_gather(const Launch &L, const SpanWindows &w, int Wp, const floa
 hipError_t span_scatter(const Launch &L, const SpanWindows &w, int Wp, const float *x_w, long long t0, float *out)
 {
     FD_LAUNCH(L, "span_scatter", k_span_scatter, dim3(span_blocks((int64_t)Wp * fd::HOPT), w.n), dim3(256), 0, w, Wp, x_w, t0, out);
+    return hipSuccess;
+}
+
+// blockIdx.y = destination row r of mel_w [n][80][Wp]: window r / 80, channel r % 80.  Element i is utterance frame start + i, read at
+// its plain or ring column when it lies inside the window's own length and inside the frames the source holds, else 0.  Validity is
+// decided on UTTERANCE frames, never on ring columns: a ring slot still holds the frames of whoever used it before, and a 32-aligned
+// window start may reach in front of mel_first (further than the halo from every sample the window keeps).  Consecutive lanes read
+// consecutive columns; a ring window is at most two such runs per row.
+__global__ void k_spans_gather(const SpanRec *__restrict__ recs, int Wp, float *__restrict__ mel_w)
+{
+    const int r = blockIdx.y;
+    const SpanRec w = recs[r / fd::COND];
+    const float *src = w.src + (int64_t)(r % fd::COND) * w.pitch;
+    float *dst = mel_w + (int64_t)r * Wp;
+    const int64_t held_end = w.mel_first + w.mel_frames;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < Wp; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = w.start + i;
+        float v = 0.0f;
+        if (i < w.len && f >= w.mel_first && f < held_end) v = src[w.cap > 0 ? f % w.cap : f - w.mel_first];
+        dst[i] = v;
+    }
+}
+
+// blockIdx.y = window b: samples [(c0 - start) * 256, + clen * 256) of its x_0 row -> its record's dst.  The source is 16-byte aligned
+// (rows of Wp * 256 floats in a 256-byte aligned buffer); a destination that is too moves 16 bytes per lane, any other goes float by
+// float -- chosen per window.
+__global__ void k_spans_scatter(const SpanRec *__restrict__ recs, int Wp, const float *__restrict__ x_w)
+{
+    const int b = blockIdx.y;
+    const SpanRec w = recs[b];
+    const int64_t n_el = (int64_t)w.clen * fd::HOPT;
+    const float *src = x_w + (int64_t)b * Wp * fd::HOPT + (w.c0 - w.start) * fd::HOPT;
+    float *dst = w.dst;
+    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(src);
+        float4 *d4 = reinterpret_cast<float4 *>(dst);
+        for (int64_t i = first; i < n_el / 4; i += stride) d4[i] = s4[i];
+    } else {
+        for (int64_t i = first; i < n_el; i += stride) dst[i] = src[i];
+    }
+}
+
+// blockIdx.z = chunk, blockIdx.y = channel: src[c][i] -> ring[c][(first_frame + i) % cap], i < frames (<= cap: the host checked)
+__global__ void k_ring_append(const fd_ring_chunk *__restrict__ chunks)
+{
+    const fd_ring_chunk c = chunks[blockIdx.z];
+    const float *src = c.src + (int64_t)blockIdx.y * c.src_pitch;
+    float *dst = c.ring + (int64_t)blockIdx.y * c.pitch;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.frames; i += (int64_t)gridDim.x * blockDim.x)
+        dst[(c.first_frame + i) % c.cap] = src[i];
+}
+
+hipError_t spans_gather(const Launch &L, const SpanRec *recs, int n, int Wp, float *mel_w)
+{
+    FD_LAUNCH(L, "spans_gather", k_spans_gather, dim3(span_blocks(Wp), n * fd::COND), dim3(256), 0, recs, Wp, mel_w);
+    return hipSuccess;
+}
+
+hipError_t spans_scatter(const Launch &L, const SpanRec *recs, int n, int Wp, int max_clen, const float *x_w)
+{
+    FD_LAUNCH(L, "spans_scatter", k_spans_scatter, dim3(span_blocks((int64_t)max_clen * (fd::HOPT / 4)), n), dim3(256), 0, recs, Wp, x_w);
+    return hipSuccess;
+}
+
+hipError_t ring_append(const Launch &L, const fd_ring_chunk *chunks, int n, long long max_frames)
+{
+    FD_LAUNCH(L, "ring_append", k_ring_append, dim3(span_blocks(max_frames), fd::COND, n), dim3(256), 0, chunks);
     return hipSuccess;
 }
 

@@ -262,6 +262,22 @@ class FastDiff(nn.Module):
         from . import longform
         return longform.SampleStream(self, table, ddim=ddim, seed=seed, stream_id=stream_id, chunk_frames=chunk_frames)
 
+    def sample_long_batch(self, mels, table, ddim=False, seed=0, stream_ids=None, window_frames=None):
+        """A list of x_0 [1,1,T_i*256], one per utterance of `mels` (a list of [80,T_i] or [1,80,T_i] tensors of any lengths), from ONE
+        fd_sample_spans call: the windows of all utterances share the sampler's batches.  Element i equals
+        sample_long(mels[i], table, ddim, seed=seed, stream_id=stream_ids[i], window_frames=window_frames) bit for bit; stream_ids
+        default to range(len(mels)).  Distinct utterances need distinct stream ids."""
+        from . import longform
+        return longform.sample_long_batch(self, mels, table, ddim=ddim, seed=seed, stream_ids=stream_ids, window_frames=window_frames)
+
+    def stream_pool(self, table, ddim=False, seed=0, chunk_frames=32, max_streams=64, max_feed_frames=256):
+        """A StreamPool (fastdiff_amd/longform.py): up to max_streams live streams whose mel lies in device rings; open / feed / close
+        per stream, and one step() vocodes whatever became ready on all of them in one fd_sample_spans call.  A stream's pieces
+        equal stream(table, ddim, seed, stream_id, chunk_frames) on the same chunks, hence sample_long, bit for bit."""
+        from . import longform
+        return longform.StreamPool(self, table, ddim=ddim, seed=seed, chunk_frames=chunk_frames, max_streams=max_streams,
+                                   max_feed_frames=max_feed_frames)
+
     @staticmethod
     def halo_frames(N):
         """Frames of halo per side that sample_long / stream add for an N-step schedule (fd_sample_halo_frames)."""
@@ -377,7 +393,7 @@ class FastDiff(nn.Module):
         return buf
 
     def counter(self, name):
-        """fd_get_counter: "pieces" / "pieces_redone" / "pieces_fp32" / "fp32_mask" of the last long sample() call, "calls_redone"."""
+        """fd_get_counter: "pieces" / "pieces_redone" / "pieces_fp32" / "fp32_mask" of the last long sample() call, "calls_redone", "span_batches", "span_windows", ...."""
         lib = _capi.load()
         return int(_capi.check(lib, self._handle, lib.fd_get_counter(self._handle, name.encode()), "fd_get_counter"))
 

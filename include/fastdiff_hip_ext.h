@@ -70,13 +70,67 @@ FD_API int fd_sample_halo_frames(int N);
  *   window_frames  centre frames per window (a multiple of 32), 0 = the library's default: windows of max(1024, 4H) frames rounded up
  *              to 32, centre = that - 2H (N = 4: 1024-frame windows, 896-frame centres)
  *   out        [1,1,(t1-t0)*256] device
- * Window starts are multiples of 32 frames (the kernels' frame phase); up to 8 windows and about 16k frames run as one fd_sample batch.
+ * Window starts are multiples of 32 frames (the kernels' frame phase); about 16k frames run as one fd_sample batch: up to 32 windows
+ * with Philox noise (the call is then one span of fd_sample_spans, below), up to 8 with injected x_T / z.
  * Settles its own range check before it returns, whatever defer_check says.  Settles a pending deferred fd_sample first.
  * FD_ERR_UNSUPPORTED: a handle of another architecture than base.yaml's, or any stage on the naive kernels (they ignore lens).
  * FD_ERR_INVALID: t0 / t1 misaligned or t1 > utt_frames, mel not covering the halo, injected z with N > 8. */
 FD_API int fd_sample_span(fd_handle h, const float *mel, int64_t mel_first, int64_t mel_frames, int64_t utt_frames, int64_t t0, int64_t t1,
                           const fd_step *table, int N, int ddim, const float *x_T, const float *z, uint64_t seed, uint64_t stream_id,
                           int window_frames, float *out, void *stream);
+
+/* Frame ranges of MANY utterances in shared window batches: a directory of long recordings, or the chunks that became ready on a set
+ * of live streams, vocoded with the sampler's batch filled instead of one call per utterance ("Many utterances per
+ * window batch").  One fd_span is what one fd_sample_span call takes, Philox noise only, with the mel either in a plain buffer or in a
+ * ring that fd_mel_ring_append feeds. */
+typedef struct fd_span {          /* one frame range of one utterance */
+    const float *mel;             /* device; channel c, utterance frame f at mel[c*mel_pitch + col(f)] */
+    int64_t mel_pitch;            /* floats between channel rows */
+    int64_t mel_cap;              /* 0: col(f) = f - mel_first (a plain buffer); > 0: col(f) = f % mel_cap (a ring) */
+    int64_t mel_first, mel_frames;/* the utterance frames the buffer holds; mel_frames <= mel_cap for a ring */
+    int64_t utt_frames;           /* or -1: not known yet */
+    int64_t t0, t1;               /* same rules as fd_sample_span */
+    uint64_t stream_id;
+    float *out;                   /* device, [(t1 - t0) * 256] */
+} fd_span;
+/* One window of the plan: batch item of fd_sample call number `batch`, utterance frames [start, start + len) of span `span`, of which
+ * the centre [c0, c0 + clen) is kept. */
+typedef struct fd_span_window { int32_t span, batch, len, clen; int64_t start, c0; } fd_span_window;
+/* `frames` frames of src ([80][frames] device, rows src_pitch floats apart) = utterance frames first_frame .. of a ring of `cap` columns
+ * (rows `pitch` floats apart) */
+typedef struct fd_ring_chunk { float *ring; int64_t pitch, cap, first_frame; const float *src; int64_t src_pitch, frames; } fd_ring_chunk;
+
+/* The plan fd_sample_spans runs (pure host code, no handle; the pointers of the spans are not looked at).  Every span is cut into
+ * windows by fd_sample_span's rules -- centres of C = window_frames (0 = the default above) frames, window start max(0, floor32(c0 - H)),
+ * window end min(utt_frames, c0 + clen + H) -- and the windows of ALL spans fill the batches in span order: a batch holds at most 32
+ * windows and at most 16384 padded frames, and a span may continue in the next batch.  *Wp = the padded frames of every batch item,
+ * which follow the centre actually needed: min(C, the longest span rounded up to 32) plus the halos, so 32 one-chunk stream windows do
+ * not reserve 32 default-size windows (the workspace costs about 298 KB per padded frame).
+ * Returns the number of windows and writes the first max_windows of them (windows NULL: counts only); 0 for n_spans = 0.
+ * FD_ERR_INVALID: a refusal of fd_sample_span in any span, a ring with mel_frames > mel_cap, mel_pitch shorter than a row. */
+FD_API int fd_sample_spans_plan(const fd_span *spans, int n_spans, int N, int window_frames, fd_span_window *windows, int max_windows,
+                                int *Wp);
+
+/* x_0 of every span, written to its own `out`.  Per batch of the plan: one gather launch (k_spans_gather: plain or ring columns ->
+ * [Bw,80,Wp]), one fd_sample with lens, each window's stream id and absolute sample offset, Philox noise (`seed` per call, stream_id per
+ * span), its range check settled, one scatter launch (k_spans_scatter).  Preconditions and status codes of fd_sample_span; n_spans = 0
+ * succeeds and does nothing.
+ *   - The caller gives distinct utterances distinct stream_ids: two utterances with one id draw the same noise at the same samples.
+ *   - The outputs of one call must not overlap (each span's [(t1-t0)*256] floats; any alignment -- a 16-byte aligned one is copied 16
+ *     bytes per lane).  The mel buffers are only read and may be shared.
+ *   - Every span's result is bit-identical to its own fd_sample_span call, whatever else shares the call, while no batch hands a stage
+ *     over to the fp32 kernels: a batch that raised a range flag is redone as a whole, so a window that shares it with the offending
+ *     one is then computed on the fp32 twins too.  That is already the rule among the windows of one utterance.
+ *   - Counter "calls_redone" (fd_get_counter) tells when this happened. */
+FD_API int fd_sample_spans(fd_handle h, const fd_span *spans, int n_spans, const fd_step *table, int N, int ddim, uint64_t seed,
+                           int window_frames, void *stream);
+
+/* Appends mel to rings on the device, n <= 4096 chunks in one launch (k_ring_append): frame first_frame + i of a chunk goes to column
+ * (first_frame + i) % cap of each of the ring's 80 rows.  A ring keeps the last `cap` frames of its utterance; a span on it names the
+ * frames it still holds (mel_first, mel_frames) and the gather decides validity on those utterance frames, never on columns, so a
+ * reused ring need not be cleared.  The chunks of one call must not write the same column of the same ring.  Asynchronous on `stream`.
+ * FD_ERR_INVALID: frames > cap, pitch < cap, src_pitch < frames, a null pointer. */
+FD_API int fd_mel_ring_append(fd_handle h, const fd_ring_chunk *chunks, int n, void *stream);
 
 /* Weights from live device tensors (no counterpart in the reference, whose modules read their own parameters).  fd_set_weight +
  * fd_commit_weights go through the host and rebuild everything a handle holds: a new weight arena, every captured graph dropped, the
@@ -157,6 +211,7 @@ FD_API int fd_reset_profile(fd_handle h);
  *                    yet destroyed (their last replay has not completed).
  *   "weight_refreshes" fd_refresh_weights_device calls since fd_create; "refresh_graph_drops" = of those, the ones after which a range
  *                    flag had changed and the graphs were dropped.
+ *   "span_batches" / "span_windows"   fd_sample calls made by fd_sample_span and fd_sample_spans since fd_create / the windows in them.
  *   "workspace_bytes" device memory of the handle's sampler workspace and of fd_sample_span's window batch (bounded by the window, not
  *                    by the utterance).
  * Returns the value (>= 0) or a negative status. */
