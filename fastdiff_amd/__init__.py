@@ -11,6 +11,9 @@ fed from a device-resident fastdiff_amd.TrainCorpus whose batches are cut inside
 fastdiff_amd.Validator runs a held-out pass on the device over fixed draws, with the loss per noise level (fastdiff_amd/validate.py);
 fastdiff_amd.ParamEMA keeps an exponential moving average of the parameters on the device, updated inside TrainStep's replay, and
 FastDiff.use_weights lets the inference kernels compute from it (fastdiff_amd/ema.py);
+fastdiff_amd.NoisePredictor is a scheduling network of this project's own design (the reference ships none), fastdiff_amd.PhiStep trains it
+on the device against the frozen denoiser, and noise_scheduling(..., search="device") derives a short schedule from it without a host
+round trip per iteration (fastdiff_amd/noisepred.py, phistep.py);
 FastDiff.sample_long / stream vocode one utterance of any length window by window, FastDiff.sample_long_batch / stream_pool
 (fastdiff_amd.StreamPool) many utterances or live streams in shared window batches (fastdiff_amd/longform.py).
 """
@@ -22,9 +25,11 @@ from .trainstep import TrainStep  # noqa: F401
 from .corpus import TrainCorpus  # noqa: F401
 from .validate import Validator  # noqa: F401
 from .ema import ParamEMA  # noqa: F401
+from .noisepred import NoisePredictor  # noqa: F401
+from .phistep import PhiStep  # noqa: F401
 from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
-                   map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss)
+                   map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
-           "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss"]
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+           "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

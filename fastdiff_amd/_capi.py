@@ -67,7 +67,7 @@ def step_table(rows):
 
 
 EXPORTS = ["fd_default_config", "fd_create", "fd_destroy", "fd_last_error", "fd_set_weight", "fd_commit_weights",
-           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
+           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_bandpool_forward", "fd_bandpool_backward", "fd_npred_head_forward", "fd_npred_head_backward", "fd_phi_draw", "fd_phi_residual_forward", "fd_sched_init", "fd_sched_begin", "fd_sched_update", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
            "fd_get_profile", "fd_reset_profile", "fd_get_counter", "fd_version", "fd_abi_revision"]
 
 _lib = None
@@ -160,6 +160,15 @@ def load():
     lib.fd_mse_backward.argtypes = [vp, vp, vp, vp, ct.c_int64, vp, vp]
     lib.fd_adamw_multi.argtypes = [vp, vp, ci, vp, vp, vp]
     lib.fd_ema_multi.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    lib.fd_bandpool_forward.argtypes = [vp, vp, vp, vp, ci, ct.c_int64, vp, vp]
+    lib.fd_bandpool_backward.argtypes = [vp, vp, vp, vp, vp, ci, ct.c_int64, vp, vp, vp]
+    lib.fd_npred_head_forward.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]
+    lib.fd_npred_head_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.fd_phi_draw.argtypes = [vp, vp, vp, ci, ci, ci, ct.c_int64, ct.c_uint64, vp, ct.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    lib.fd_phi_residual_forward.argtypes = [vp, vp, vp, vp, vp, ci, ct.c_int64, vp, vp, vp]
+    lib.fd_sched_init.argtypes = [vp, vp, cf, cf, vp]
+    lib.fd_sched_begin.argtypes = [vp, vp, vp, ci, ct.c_double, vp, ci, ci, vp, ci, vp]
+    lib.fd_sched_update.argtypes = [vp, vp, vp, vp, ct.c_int64, vp, vp]
     lib.fd_set_option.argtypes = [vp, ct.c_char_p, ct.c_char_p]
     lib.fd_read_tap.argtypes = [vp, ct.c_char_p, vp, ct.c_int64]
     lib.fd_read_tap.restype = ct.c_int64

@@ -727,4 +727,129 @@ int fd_eval_accumulate(fd_handle h, const float *values, const float *steps, con
     });
 }
 
+// The scheduling network, the pieces of its training step and the schedule search (fd_kernels_phi.hip).
+static int check_npred(fd_handle h, int B, int R, const char *who)
+{
+    FD_TRY(check_batch(h, B, who));
+    if (R != B && R != 1) FD_FAIL(h, FD_ERR_INVALID, "%s: R=%d (B=%d or 1)", who, R, B);
+    return FD_OK;
+}
+
+static int check_bandpool(fd_handle h, const float *x, int B, int64_t L, const char *who)
+{
+    FD_TRY(check_batch(h, B, who));
+    if (L < 64 || L % 32 != 0 || L >= ((int64_t)1 << 31)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 32, at least 64)", who, (long long)L);
+    if (!aligned(x, 16)) FD_FAIL(h, FD_ERR_INVALID, "%s: x must be 16-byte aligned", who);
+    return FD_OK;
+}
+
+int fd_bandpool_forward(fd_handle h, const float *x, const float *W, const float *b, int B, int64_t L, float *feat, void *stream)
+{
+    const char *who = "fd_bandpool_forward";
+    if (!h) return FD_ERR_INVALID;
+    if (!x || !W || !b || !feat) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_bandpool(h, x, B, L, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, fdk::bandpool_scratch_floats(B, L, false));
+        return e != hipSuccess ? e : fdk::bandpool_forward(La, x, W, b, B, L, feat, h->step_scratch.p);
+    });
+}
+
+int fd_bandpool_backward(fd_handle h, const float *x, const float *W, const float *b, const float *dfeat, int B, int64_t L, float *dW, float *db,
+                         void *stream)
+{
+    const char *who = "fd_bandpool_backward";
+    if (!h) return FD_ERR_INVALID;
+    if (!x || !W || !b || !dfeat || !dW || !db) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_bandpool(h, x, B, L, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, fdk::bandpool_scratch_floats(B, L, true));
+        return e != hipSuccess ? e : fdk::bandpool_backward(La, x, W, b, dfeat, B, L, dW, db, h->step_scratch.p);
+    });
+}
+
+int fd_npred_head_forward(fd_handle h, const float *feat, const float *beta_next, const float *delta2, int R, const float *W1, const float *b1,
+                          const float *W2, const float *b2, int B, float *beta_hat, float *ratio, void *stream)
+{
+    const char *who = "fd_npred_head_forward";
+    if (!h) return FD_ERR_INVALID;
+    if (!feat || !beta_next || !delta2 || !W1 || !b1 || !W2 || !b2 || !beta_hat || !ratio) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_npred(h, B, R, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::npred_head_forward(La, feat, beta_next, delta2, R, W1, b1, W2, b2, B, beta_hat, ratio); });
+}
+
+int fd_npred_head_backward(fd_handle h, const float *feat, const float *beta_next, const float *delta2, const float *W1, const float *b1,
+                           const float *W2, const float *b2, const float *dbeta_hat, int B, float *dW1, float *db1, float *dW2, float *db2,
+                           float *dfeat, void *stream)
+{
+    const char *who = "fd_npred_head_backward";
+    if (!h) return FD_ERR_INVALID;
+    if (!feat || !beta_next || !delta2 || !W1 || !b1 || !W2 || !b2 || !dbeta_hat || !dW1 || !db1 || !dW2 || !db2 || !dfeat)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::npred_head_backward(La, feat, beta_next, delta2, W1, b1, W2, b2, dbeta_hat, B, dW1, db1, dW2, db2, dfeat);
+    });
+}
+
+int fd_phi_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int tau, int B, int64_t L, uint64_t seed, const fd_train_state *state,
+                uint64_t iter_host, float *x_t, float *z, float *steps, float *beta_nxt, float *delta, float *delta2, void *stream)
+{
+    const char *who = "fd_phi_draw";
+    if (!h) return FD_ERR_INVALID;
+    if (!x0 || !alpha || !x_t || !z || !steps || !beta_nxt || !delta || !delta2) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (tau < 0 || T_train < 1 || (int64_t)T_train <= 2 * (int64_t)tau) FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d must exceed 2 tau=%d", who, T_train, 2 * tau);
+    if (L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 4)", who, (long long)L);
+    if (!aligned(x0, 16) || !aligned(x_t, 16) || !aligned(z, 16) || !aligned(state, 8))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: x0, x_t and z must be 16-byte aligned, state 8-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::phi_draw(La, x0, alpha, T_train, tau, B, L, seed, state, iter_host, x_t, z, steps, beta_nxt, delta, delta2);
+    });
+}
+
+int fd_phi_residual_forward(fd_handle h, const float *eps, const float *z, const float *delta, const float *beta_hat, int B, int64_t L, float *m,
+                            float *s, void *stream)
+{
+    const char *who = "fd_phi_residual_forward";
+    if (!h) return FD_ERR_INVALID;
+    if (!eps || !z || !delta || !beta_hat || !m || !s) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 4)", who, (long long)L);
+    if (!aligned(eps, 16) || !aligned(z, 16)) FD_FAIL(h, FD_ERR_INVALID, "%s: eps and z must be 16-byte aligned", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const hipError_t e = grow(h->step_scratch, 2 * (size_t)B * (size_t)fdk::phi_residual_blocks(L));
+        return e != hipSuccess ? e : fdk::phi_residual_forward(La, eps, z, delta, beta_hat, B, L, m, s, h->step_scratch.p);
+    });
+}
+
+int fd_sched_init(fd_handle h, fd_sched_state *state, float betaN, float alphaN, void *stream)
+{
+    const char *who = "fd_sched_init";
+    if (!h) return FD_ERR_INVALID;
+    if (!state || !aligned(state, 4)) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::sched_init(La, state, betaN, alphaN); });
+}
+
+int fd_sched_begin(fd_handle h, fd_sched_state *state, const float *beta_hat, int n_hat, double rho, const float *alpha, int T_train, int ddim,
+                   float *steps_out, int B, void *stream)
+{
+    const char *who = "fd_sched_begin";
+    if (!h) return FD_ERR_INVALID;
+    if (!state || !alpha || !steps_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    FD_TRY(check_batch(h, B, who));
+    if (T_train < 1 || (beta_hat && n_hat < 1)) FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d, n_hat=%d", who, T_train, n_hat);
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::sched_begin(La, state, beta_hat, n_hat, rho, alpha, T_train, ddim ? 1 : 0, steps_out, B); });
+}
+
+int fd_sched_update(fd_handle h, fd_sched_state *state, float *x, const float *eps, int64_t n, float *cond_out, void *stream)
+{
+    const char *who = "fd_sched_update";
+    if (!h) return FD_ERR_INVALID;
+    if (!state || !x || !eps || !cond_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
+    if (n < 4 || n % 4 != 0 || n >= ((int64_t)1 << 36) || !aligned(x, 16) || !aligned(eps, 16))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: n=%lld (a multiple of 4), x and eps 16-byte aligned", who, (long long)n);
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::sched_update(La, state, x, eps, n, cond_out); });
+}
+
 }  // extern "C"

@@ -135,6 +135,27 @@ hipError_t mse_backward(const Launch &L, const float *eps, const float *z, const
 hipError_t adamw_multi(const Launch &L, const fd_adamw_item *items, int n, const fd_adamw_hyper *hyper, fd_train_state *state, float *scratch);
 // e += w (p - e) over n tensors behind the optimizer (fd_ema_multi): one deciding thread, then ceil(n / 64) update launches; no scratch
 hipError_t ema_multi(const Launch &L, const fd_ema_item *items, int n, const fd_ema_hyper *hyper, const fd_train_state *state, fd_ema_state *ema);
+// the scheduling network, the pieces of its training step and the schedule search (fd_kernels_phi.hip; include/fastdiff_hip_train.h, last
+// section).  scratch: bandpool_scratch_floats(B, L, backward) / 2 B phi_residual_blocks(L) floats of the handle's step scratch
+size_t bandpool_scratch_floats(int B, int64_t L, bool backward);
+hipError_t bandpool_forward(const Launch &L_, const float *x, const float *W, const float *bias, int B, int64_t L, float *feat, float *scratch);
+hipError_t bandpool_backward(const Launch &L_, const float *x, const float *W, const float *bias, const float *dfeat, int B, int64_t L, float *dW,
+                             float *db, float *scratch);
+hipError_t npred_head_forward(const Launch &L_, const float *feat, const float *beta_next, const float *delta2, int R, const float *W1,
+                              const float *b1, const float *W2, const float *b2, int B, float *beta_hat, float *ratio);
+hipError_t npred_head_backward(const Launch &L_, const float *feat, const float *beta_next, const float *delta2, const float *W1, const float *b1,
+                               const float *W2, const float *b2, const float *dbeta_hat, int B, float *dW1, float *db1, float *dW2, float *db2,
+                               float *dfeat);
+hipError_t phi_draw(const Launch &L_, const float *x0, const float *alpha, int T_train, int tau, int B, int64_t len, uint64_t seed,
+                    const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps, float *beta_nxt, float *delta,
+                    float *delta2);
+int64_t phi_residual_blocks(int64_t len);
+hipError_t phi_residual_forward(const Launch &L_, const float *eps, const float *z, const float *delta, const float *beta_hat, int B, int64_t len,
+                                float *m, float *s, float *scratch);
+hipError_t sched_init(const Launch &L_, fd_sched_state *state, float betaN, float alphaN);
+hipError_t sched_begin(const Launch &L_, fd_sched_state *state, const float *beta_hat, int n_hat, double rho, const float *alpha, int T_train,
+                       int ddim, float *steps_out, int B);
+hipError_t sched_update(const Launch &L_, fd_sched_state *state, float *x, const float *eps, int64_t n, float *cond_out);
 }  // namespace fdk
 
 // The exact-fp32 reference kernels (fd_generic.hip): one thread per output, runtime shapes, fp32 multiply-adds in a fixed order.  The

@@ -1136,3 +1136,169 @@ def eval_accumulate(values, picked, acc, steps=None, T_train=1, bins=1, item_out
         assert t is None or (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and n in (None, t.numel())), \
             "eval_accumulate: contiguous HIP tensors of one device: values / steps [B] float32, picked [B, 2] int64"
     _call(dev, "fd_eval_accumulate", "fd_eval_accumulate", values, steps, picked, B, int(T_train), int(bins), acc, item_out, advance)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The scheduling network, the pieces of its training step and the schedule search (include/fastdiff_hip_train.h, last section;
+# fastdiff_amd/noisepred.py, phistep.py, sampler.noise_scheduling(search="device"))
+# ---------------------------------------------------------------------------------------------------------------------------------
+PHI_TS_STREAM, PHI_Z_STREAM = 0xFFFFFFFA, 0xFFFFFFF9      # the Philox streams of phi_loss's ts and z
+
+
+class _BandPool(torch.autograd.Function):
+    """feat[b, c] = log(1e-6 + mean_f (bias[c] + sum_k W[c, k] x[b, 32 f + k])^2) (fd_bandpool_forward / _backward); x is data: it
+    receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x, weight, bias = _f32(x, weight, bias)
+        B, L = x.shape
+        assert tuple(weight.shape) == (32, 64) and tuple(bias.shape) == (32,)
+        feat = torch.empty((B, 32), device=x.device, dtype=torch.float32)
+        _call(x.device, "fd_bandpool_forward", "fd_bandpool_forward", x, weight, bias, B, L, feat)
+        ctx.save_for_backward(x, weight, bias)
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        x, weight, bias = ctx.saved_tensors
+        dW, db = torch.empty_like(weight), torch.empty_like(bias)
+        _call(x.device, "fd_bandpool_backward", "fd_bandpool_backward", x, weight, bias, dfeat.contiguous().float(), x.shape[0], x.shape[1], dW, db)
+        return None, dW, db
+
+
+def band_pool(x, weight, bias):
+    """The band energies of NoisePredictor: x [B, L] (L a multiple of 32, >= 64), weight [32, 64], bias [32] -> feat [B, 32]."""
+    if not x.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.band_pool runs only on a HIP device (no CPU fallback)")
+    assert x.dim() == 2 and x.shape[1] >= 64 and x.shape[1] % 32 == 0, "x [B, L] with L a multiple of 32, at least 64"
+    return _BandPool.apply(x, weight, bias)
+
+
+class _NPredHead(torch.autograd.Function):
+    """The 34 -> 64 -> 1 head of NoisePredictor (fd_npred_head_forward / _backward) -> (beta_hat [R], ratio [B]); only beta_hat carries a
+    gradient, to feat and the four parameter tensors.  The condition is data."""
+
+    @staticmethod
+    def forward(ctx, feat, beta_next, delta2, w1, b1, w2, b2):
+        feat, beta_next, delta2, w1, b1, w2, b2 = _f32(feat, beta_next, delta2, w1, b1, w2, b2)
+        B, R = feat.shape[0], beta_next.numel()
+        assert delta2.numel() == R and R in (1, B) and tuple(w1.shape) == (64, 34) and w2.numel() == 64
+        beta_hat = torch.empty(R, device=feat.device, dtype=torch.float32)
+        ratio = torch.empty(B, device=feat.device, dtype=torch.float32)
+        _call(feat.device, "fd_npred_head_forward", "fd_npred_head_forward", feat, beta_next, delta2, R, w1, b1, w2, b2, B, beta_hat, ratio)
+        ctx.save_for_backward(feat, beta_next, delta2, w1, b1, w2, b2)
+        ctx.mark_non_differentiable(ratio)
+        return beta_hat, ratio
+
+    @staticmethod
+    def backward(ctx, dbeta, _dratio):
+        feat, beta_next, delta2, w1, b1, w2, b2 = ctx.saved_tensors
+        B = feat.shape[0]
+        if beta_next.numel() != B:
+            raise RuntimeError("NoisePredictor: one condition for a batch of several items (R = 1) is a no_grad form")
+        dfeat = torch.empty_like(feat)
+        dw1, db1, dw2, db2 = (torch.empty_like(t) for t in (w1, b1, w2, b2))
+        _call(feat.device, "fd_npred_head_backward", "fd_npred_head_backward", feat, beta_next, delta2, w1, b1, w2, b2, dbeta.contiguous().float(), B,
+              dw1, db1, dw2, db2, dfeat)
+        return dfeat, None, None, dw1, db1, dw2, db2
+
+
+def npred_head(feat, beta_next, delta2, w1, b1, w2, b2):
+    if not feat.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.npred_head runs only on a HIP device (no CPU fallback)")
+    return _NPredHead.apply(feat, beta_next, delta2, w1, b1, w2, b2)
+
+
+def phi_draw(x0, alpha, T_train, tau, seed=0, iteration=0, state=None, out=None):
+    """The draws of phi_loss (util.py:340-350) on the device (fd_phi_draw): x0 [B, 1, L] -> (x_t, z, steps [B, 1], beta_nxt [B, 1],
+    delta [B, 1], delta2 [B, 1]); the step index as in train_draw.  out: the six tensors to write into."""
+    if not x0.is_cuda:
+        raise RuntimeError("fastdiff_amd.lvc_op.phi_draw runs only on a HIP device (no CPU fallback)")
+    x0, alpha = _f32(x0, alpha)
+    B, L = x0.shape[0], x0.numel() // x0.shape[0]
+    assert alpha.numel() == int(T_train) and alpha.device == x0.device, "alpha: [T_train] on the device of the audio"
+    if out is None:
+        out = (torch.empty_like(x0), torch.empty_like(x0)) + tuple(torch.empty((B, 1), device=x0.device, dtype=torch.float32) for _ in range(4))
+    x_t, z, steps, beta_nxt, delta, delta2 = out
+    _call(x0.device, "fd_phi_draw", "fd_phi_draw", x0, alpha, int(T_train), int(tau), B, L, int(seed) & 0xFFFFFFFFFFFFFFFF, state,
+          int(iteration) & 0xFFFFFFFFFFFFFFFF, x_t, z, steps, beta_nxt, delta, delta2)
+    return x_t, z, steps, beta_nxt, delta, delta2
+
+
+def phi_draw_plan(seed, it, B, T_train, tau):
+    """The host twin of fd_phi_draw's step choice: ts [B] int64, each in [tau, T_train - tau)."""
+    import numpy as np
+    T_train, tau = int(T_train), int(tau)
+    if T_train <= 2 * tau:
+        raise ValueError(f"phi_draw_plan: T_train={T_train} must exceed 2 tau={2 * tau}")
+    from .corpus import _words
+    b = np.arange(int(B), dtype=np.uint64)
+    w = np.stack(_words(seed, PHI_TS_STREAM, b >> np.uint64(2), np.uint64(int(it) & 0xFFFFFFFFFFFFFFFF)), axis=-1)[np.arange(int(B)), (b & np.uint64(3)).astype(np.int64)]
+    return (tau + ((w * np.uint64(T_train - 2 * tau)) >> np.uint64(32))).astype(np.int64)
+
+
+class _PhiResidual(torch.autograd.Function):
+    """m[b] = mean_t (delta z - (beta_hat / delta) eps)^2 on fixed-order sums (fd_phi_residual_forward); the backward is
+    dbeta_hat[b] = dm[b] (-2 / delta[b]) s[b] with s[b] = mean_t r eps from the same pass.  Only beta_hat receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, eps, z, delta, beta_hat):
+        ctx.hat_shape = beta_hat.shape
+        eps, z, delta, beta_hat = _f32(eps, z, delta, beta_hat)
+        B = eps.shape[0]
+        assert eps.shape == z.shape and delta.numel() == B and beta_hat.numel() == B
+        m, s = (torch.empty(B, device=eps.device, dtype=torch.float32) for _ in range(2))
+        _call(eps.device, "fd_phi_residual_forward", "fd_phi_residual_forward", eps, z, delta, beta_hat, B, eps.numel() // B, m, s)
+        ctx.save_for_backward(delta, s)
+        return m
+
+    @staticmethod
+    def backward(ctx, dm):
+        delta, s = ctx.saved_tensors
+        return None, None, None, (dm * (-2.0 / delta.view(-1)) * s).view(ctx.hat_shape)
+
+
+def phi_residual(eps, z, delta, beta_hat):
+    """eps, z [B, 1, L] (L a multiple of 4), delta, beta_hat [B]-like -> m [B]; differentiable in beta_hat."""
+    if not (eps.is_cuda and z.is_cuda):
+        raise RuntimeError("fastdiff_amd.lvc_op.phi_residual runs only on a HIP device (no CPU fallback)")
+    return _PhiResidual.apply(eps, z, delta, beta_hat)
+
+
+SCHED_MAX_STEPS = 64
+_SCHED_WORDS = 4 + SCHED_MAX_STEPS + 2 + 4 + 2      # fd_sched_state as 4-byte words
+
+
+def new_sched_state(device, betaN, alphaN):
+    """An fd_sched_state in device memory, initialised on the device (fd_sched_init)."""
+    state = torch.zeros(_SCHED_WORDS, dtype=torch.int32, device=device)
+    lib, h = _handle(device)
+    _capi.check(lib, h, lib.fd_sched_init(h, state.data_ptr(), float(betaN), float(alphaN), _stream(device)), "fd_sched_init")
+    return state
+
+
+def read_sched_state(state):
+    """fd_sched_state -> dict (synchronises: the one read of a search)."""
+    import numpy as np
+    raw = state.cpu().numpy()
+    f = raw.view(np.float32)
+    n = int(raw[3])
+    return {"alpha_cur": float(f[0]), "beta_cur": float(f[1]), "stopped": int(raw[2]), "n_found": n, "found": f[4: 4 + n].copy(),
+            "step": float(f[4 + SCHED_MAX_STEPS])}
+
+
+def sched_begin(state, beta_hat, rho, alpha, ddim, steps_out):
+    dev = state.device
+    if beta_hat is not None:
+        assert beta_hat.is_cuda and beta_hat.dtype == torch.float32 and beta_hat.is_contiguous() and beta_hat.numel() >= 1
+    lib, h = _handle(dev)
+    _capi.check(lib, h, lib.fd_sched_begin(h, state.data_ptr(), None if beta_hat is None else beta_hat.data_ptr(),
+                                           0 if beta_hat is None else beta_hat.numel(), float(rho), alpha.data_ptr(), alpha.numel(), int(bool(ddim)),
+                                           steps_out.data_ptr(), steps_out.numel(), _stream(dev)), "fd_sched_begin")
+
+
+def sched_update(state, x, eps, cond_out):
+    assert x.is_contiguous() and eps.is_contiguous() and x.dtype == eps.dtype == torch.float32 and x.shape == eps.shape
+    assert cond_out.numel() == 2 and cond_out.dtype == torch.float32 and cond_out.is_contiguous()
+    _call(state.device, "fd_sched_update", "fd_sched_update", state, x, eps, x.numel(), cond_out)

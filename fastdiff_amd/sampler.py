@@ -34,6 +34,14 @@ def compute_hyperparams_given_schedule(beta):
     return {"T": len(beta), "beta": beta, "alpha": alpha, "sigma": sigma}
 
 
+def calc_diffusion_hyperparams(T, beta_0, beta_T, tau, N, beta_N, alpha_N, rho):
+    """The training table of a linear beta schedule plus what phi_loss and noise_scheduling read (util.py:127-155):
+    compute_hyperparams_given_schedule(linspace(beta_0, beta_T, T))'s four entries and "tau", "N", "betaN", "alphaN", "rho"."""
+    dh = compute_hyperparams_given_schedule(torch.linspace(beta_0, beta_T, T))
+    dh["tau"], dh["N"], dh["betaN"], dh["alphaN"], dh["rho"] = tau, N, beta_N, alpha_N, rho
+    return dh
+
+
 def map_noise_scale_to_time_step(alpha_infer, alpha):
     """Fractional training step whose noise level equals alpha_infer (util.py:394-404).
 
@@ -245,17 +253,43 @@ def theta_timestep_loss(net, X, diffusion_hyperparams, reverse=False, *, noise_s
     return loss
 
 
-def phi_loss(net, X, diffusion_hyperparams):
-    """The BDDM loss of the scheduling network (util.py:328-362); same signature.  Needs `net.noise_pred(x_t [B, L], (beta_next
-    [B, 1], delta^2 [B, 1]))` -- the network the reference calls but never defines, so with the stock module it
-    ends, there as here, in AttributeError after the denoiser evaluation.  The denoiser evaluation itself is FastDiff.forward:
-    the inference kernels under no_grad, the autograd graph of fastdiff_amd/train.py otherwise.
-    Random draws in the reference's order: torch.randint for the steps, then std_normal for z."""
+def phi_loss_from_draw(net, noise_pred, mel, draw):
+    """phi_loss on a device draw (lvc_op.phi_draw's six tensors): the frozen denoiser under no_grad on the inference kernels, the
+    predictor with autograd, the residual's two means on the fixed-order HIP sums (lvc_op.phi_residual: m, with its own backward),
+    and the reference's algebra on the [B] tensors that remain.  Nothing here waits for the device."""
+    from .lvc_op import phi_residual
+    x_t, z, steps, beta_nxt, delta, delta2 = draw
+    B = x_t.shape[0]
+    with torch.no_grad():
+        eps = net((x_t, mel, steps))
+    beta_hat = noise_pred(x_t.view(B, -1), (beta_nxt, delta2)).reshape(B)
+    m = phi_residual(eps, z, delta, beta_hat)
+    delta2 = delta2.view(B)
+    loss = (m / (2. * (delta2 - beta_hat)) + torch.log(1e-8 + delta2 / (beta_hat + 1e-8)) / 4.) + beta_hat / delta2 / 2.
+    return loss.mean()
+
+
+def phi_loss(net, X, diffusion_hyperparams, *, noise_source="reference", seed=0, iteration=0):
+    """The BDDM loss of the scheduling network (util.py:328-362); same positional signature.  Needs `net.noise_pred(x_t [B, L],
+    (beta_next [B, 1], delta^2 [B, 1]))` -- the network the reference calls but never defines, so with the stock module it
+    ends, there as here, in AttributeError after the denoiser evaluation; fastdiff_amd.NoisePredictor is one.  The denoiser evaluation
+    itself is FastDiff.forward: the inference kernels under no_grad, the autograd graph of fastdiff_amd/train.py otherwise.
+    Random draws in the reference's order: torch.randint for the steps, then std_normal for z.
+    Keyword-only: noise_source="device" draws the steps and z with the on-device Philox generator keyed by (seed, iteration)
+    (lvc_op.phi_draw), evaluates the denoiser under no_grad (theta is frozen in this loss) and the residual on the fixed-order HIP
+    sums: what fastdiff_amd.PhiStep runs per step, without the optimizer."""
     assert type(X) == tuple and len(X) == 2
     dh = diffusion_hyperparams
     T_train, alpha, tau = dh["T"], dh["alpha"], dh["tau"]
     mel_spectrogram, audio = X
     n_items = audio.shape[0]
+    if noise_source == "device":
+        from .lvc_op import phi_draw
+        draw = phi_draw(audio, alpha.to(audio.device), T_train, tau, seed=seed, iteration=iteration)
+        draw = (draw[0].view(audio.shape), draw[1].view(audio.shape)) + draw[2:]
+        # (net.noise_pred is looked up behind the denoiser evaluation: the stock module ends in AttributeError there, as on the default path)
+        return phi_loss_from_draw(net, lambda x, cond: net.noise_pred(x, cond), mel_spectrogram, draw)
+    assert noise_source == "reference", noise_source
     ts = torch.randint(tau, T_train - tau, size=(n_items,)).cuda()
     alpha = alpha.to(ts.device)
     alpha_cur = alpha.index_select(0, ts).view(n_items, 1, 1)
@@ -271,16 +305,54 @@ def phi_loss(net, X, diffusion_hyperparams):
     return (torch.mean(loss, -1, keepdim=True) + beta_est / delta ** 2 / 2.).mean()
 
 
-def noise_scheduling(net, size, diffusion_hyperparams, condition=None, ddim=False):
-    """Greedy search of an inference schedule with a learned noise predictor; same signature as util.py:237.
+def _noise_scheduling_device(net, x, dh, condition, ddim):
+    """noise_scheduling's loop (util.py:254-288) with its state in device memory (lvc_op.sched_begin / sched_update: fd_sched_*): the
+    step lookup, the accept / stop decisions and the update's scalars are computed by one-thread kernels from float32 values in the
+    reference's order of operations, so no iteration waits for the device.  The loop always runs N times; once the search has stopped
+    its launches change nothing (at most N wasted denoiser evaluations).  One read of the state at the end."""
+    from . import lvc_op
+    N, rho = int(dh["N"]), float(dh["rho"])
+    if N > lvc_op.SCHED_MAX_STEPS:
+        raise ValueError(f"noise_scheduling(search='device'): N={N} exceeds {lvc_op.SCHED_MAX_STEPS}")
+    if not (isinstance(net, FastDiff) and x.is_cuda):
+        raise RuntimeError("noise_scheduling(search='device') needs a fastdiff_amd.FastDiff on a HIP device (no CPU fallback)")
+    dev = x.device
+    alpha = dh["alpha"].detach().to(dev, torch.float32).contiguous()
+    x = x.contiguous().float()
+    state = lvc_op.new_sched_state(dev, float(dh["betaN"]), float(dh["alphaN"]))
+    steps = torch.zeros((x.shape[0], 1), device=dev, dtype=torch.float32)
+    cond = torch.tensor([float(dh["betaN"]), 1.0], dtype=torch.float32).to(dev)      # (read by noise_pred only behind a stop in iteration 0)
+    beta_hat = None
+    with torch.no_grad():
+        for _ in range(N):
+            lvc_op.sched_begin(state, beta_hat, rho, alpha, ddim, steps)
+            eps = net((x, condition, steps))
+            lvc_op.sched_update(state, x, eps.contiguous(), cond)
+            beta_hat = net.noise_pred(x.squeeze(1), (cond[0:1].view(1, 1), cond[1:2].view(1, 1)))
+            beta_hat = beta_hat.to(dev, torch.float32).contiguous().view(-1)      # (the last one is never accepted, as in the reference)
+    found = lvc_op.read_sched_state(state)["found"]
+    return torch.FloatTensor(found[::-1].copy()).cuda()
+
+
+def noise_scheduling(net, size, diffusion_hyperparams, condition=None, ddim=False, *, search="host"):
+    """Greedy search of an inference schedule with a learned noise predictor; same positional signature as util.py:237.
 
     Needs `net.noise_pred(x, (beta_next, 1 - alpha^2))`.  The reference's FastDiff class has no such method
     (SURVEY.md 3.5), so there -- as here -- the call ends in AttributeError right after the first denoiser
-    evaluation; with a net that provides it the search proceeds, the denoiser itself running on the HIP path."""
+    evaluation; with a net that provides it (fastdiff_amd.NoisePredictor attached as `net.noise_pred`) the search proceeds, the
+    denoiser itself running on the HIP path.
+    Keyword-only: search="device" keeps the search's state on the device (same schedule, bit for bit; the host form waits for the
+    device three times per iteration).  It needs a fastdiff_amd.FastDiff on a HIP device and a noise_pred that returns a device
+    tensor without synchronising -- a NoisePredictor, or any callable made of torch operations -- and N <= 64."""
     dh = diffusion_hyperparams
     N, rho, alpha = dh["N"], dh["rho"], dh["alpha"]
+    assert search in ("host", "device"), search
+    if search == "device" and N > 64:
+        raise ValueError(f"noise_scheduling(search='device'): N={N} exceeds 64")
     print('begin noise scheduling, maximum number of reverse steps = %d' % (N))
     x = std_normal(size)
+    if search == "device":
+        return _noise_scheduling_device(net, x, dh, condition, ddim)
     beta_cur = torch.full((1, 1, 1), float(dh["betaN"]), device=x.device)
     alpha_cur = torch.full((1, 1, 1), float(dh["alphaN"]), device=x.device)
     found = []

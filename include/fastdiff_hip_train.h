@@ -323,6 +323,75 @@ typedef struct fd_eval_state {
 FD_API int fd_eval_accumulate(fd_handle h, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,
                               fd_eval_state *acc, float *item_out, fd_train_state *advance, void *stream);
 
+/* The scheduling network and what surrounds it (fastdiff_amd/noisepred.py: NoisePredictor, phistep.py: PhiStep, sampler.noise_scheduling
+ * with search = "device").  The reference calls a `noise_pred` (util.py:284,356) that it never defines: the network below is
+ * this project's own, in BDDM's form beta_hat = min(beta_next, delta^2) * sigma_phi(x).  Sums as above in this section: runs of
+ * FD_STEP_RUN, a fixed tree, per-workgroup results in the handle's step scratch, one final workgroup; no workgroup touches two items, no
+ * floating-point atomics, two runs agree bit for bit.  Calls on one handle are ordered on one stream; the first call at a new size must
+ * not sit inside a graph capture.
+ *
+ * Band energies.  x [B, L] (16-byte aligned, L a multiple of 32, L >= 64), W [32, 64], b [32], F = L / 32 - 1 frames of 64 samples at
+ * stride 32, no padding:
+ *   y[b,c,f] = b[c] + sum_k W[c,k] x[b, 32 f + k]   (one sum of 64 products in tap order, then the bias)
+ *   feat[b,c] = log(1e-6 + mean_f y[b,c,f]^2)                                                                        feat [B, 32]
+ * x is read 16 bytes per lane.  The backward recomputes y:  dy = dfeat[b,c] 2 y / (F (1e-6 + mean y^2)),
+ * dW[c,k] = sum_{b,f} dy x[b, 32 f + k], db[c] = sum_{b,f} dy (items in order, frames in order).  No dx: x is data.  L < 2^31. */
+FD_API int fd_bandpool_forward(fd_handle h, const float *x, const float *W, const float *b, int B, int64_t L, float *feat, void *stream);
+FD_API int fd_bandpool_backward(fd_handle h, const float *x, const float *W, const float *b, const float *dfeat, int B, int64_t L, float *dW,
+                                float *db, void *stream);
+
+/* The head, one workgroup (thread j = hidden unit j; sums over items in item order):
+ *   in[b] = (feat[b, 0..31], ln beta_next[r], ln delta2[r])      r = b (R = B) or 0 (R = 1: the condition is broadcast)
+ *   h = swish(W1 in + b1)   u = W2 h + b2   ratio[b] = 1e-4 + (1 - 2e-4) sigmoid(u)         W1 [64, 34], b1 [64], W2 [1, 64], b2 [1]
+ *   R = B: beta_hat[b] = min(beta_next[b], delta2[b]) ratio[b];    R = 1: beta_hat[0] = min(beta_next, delta2) (sum_b ratio[b]) / B
+ * beta_hat [R], ratio [B].  The backward (R = B only) takes dbeta_hat [B] and writes dW1, db1, dW2, db2 and dfeat [B, 32]. */
+FD_API int fd_npred_head_forward(fd_handle h, const float *feat, const float *beta_next, const float *delta2, int R, const float *W1,
+                                 const float *b1, const float *W2, const float *b2, int B, float *beta_hat, float *ratio, void *stream);
+FD_API int fd_npred_head_backward(fd_handle h, const float *feat, const float *beta_next, const float *delta2, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, const float *dbeta_hat, int B, float *dW1, float *db1, float *dW2,
+                                  float *db2, float *dfeat, void *stream);
+
+/* The draws of phi_loss (util.py:340-350) on the device; arguments as fd_train_draw plus tau, T_train > 2 tau.  With `it` as there,
+ *   ts[b] = tau + ((w * (T_train - 2 tau)) >> 32), w = word b & 3 of Philox4x32-10 keyed (seed, stream 0xFFFFFFFA, position b >> 2, id it)
+ *   z[b,t] = component (b L + t) & 3 of the generator's normal4 keyed (seed, stream 0xFFFFFFF9, position (b L + t) >> 2, id it)
+ *   a = alpha[ts], a' = alpha[ts + tau]:  beta_nxt = 1 - (a' / a)^2,  delta = sqrt(1 - a^2),  delta2 = delta delta,  x_t = a x0 + delta z
+ * every operation rounded on its own.  steps, beta_nxt, delta, delta2: [B]. */
+FD_API int fd_phi_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int tau, int B, int64_t L, uint64_t seed,
+                       const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps, float *beta_nxt, float *delta,
+                       float *delta2, void *stream);
+
+/* The residual of phi_loss: with r = delta[b] z - (beta_hat[b] / delta[b]) eps, m[b] = mean_t r^2 and s[b] = mean_t r eps.  eps, z [B, L]
+ * (16-byte aligned, L a multiple of 4); delta, beta_hat, m, s [B].  d m[b] / d beta_hat[b] = (-2 / delta[b]) s[b]. */
+FD_API int fd_phi_residual_forward(fd_handle h, const float *eps, const float *z, const float *delta, const float *beta_hat, int B, int64_t L,
+                                   float *m, float *s, void *stream);
+
+/* The greedy schedule search (noise_scheduling, util.py:254-288) with its state in device memory: caller-owned, written only by kernels. */
+#define FD_SCHED_MAX_STEPS 64
+typedef struct fd_sched_state {
+    float alpha_cur, beta_cur;
+    int32_t stopped;                       /* 0 running, 1 alpha > 1, 2 beta < rho */
+    int32_t n_found;
+    float found[FD_SCHED_MAX_STEPS];       /* the accepted betas, in the order of the search (the schedule is their reverse) */
+    float step;                            /* the current step, as written to steps_out */
+    int32_t ddim;
+    float coef[4];                         /* DDPM: c, d;  "ddim": c1, c2, c3 */
+    float cond[2];                         /* (beta_cur, 1 - alpha_cur^2) as last written to cond_out */
+} fd_sched_state;
+/* state := (alphaN, betaN), running, nothing found. */
+FD_API int fd_sched_init(fd_handle h, fd_sched_state *state, float betaN, float alphaN, void *stream);
+/* One thread.  While running: a pending beta_hat [n_hat] (NULL: none) gives beta = (sum in order) / n_hat; (double) beta < rho stops the
+ * search (stopped = 2), else beta_cur = beta.  Still running: step = map_noise_scale_to_time_step(alpha_cur, alpha) (util.py:394-404: the
+ * clamps, the first bracket alpha[t+1] <= a <= alpha[t], frac as a float32 difference and quotient, (float)((double) t + (double) frac),
+ * -1 without a bracket); step >= 0 appends beta_cur to found; steps_out[0..B) = step; the update's coefficients as float32 scalars:
+ *   DDPM:   c = beta_cur / sqrt(1 - alpha_cur^2), d = sqrt(1 - beta_cur)
+ *   "ddim": a_next = alpha_cur / sqrt(1 - beta_cur), c1 = a_next / alpha_cur, c2 = -sqrt(1 - alpha_cur^2) c1, c3 = sqrt(1 - a_next^2) */
+FD_API int fd_sched_begin(fd_handle h, fd_sched_state *state, const float *beta_hat, int n_hat, double rho, const float *alpha, int T_train,
+                          int ddim, float *steps_out, int B, void *stream);
+/* While running: x = (x - c eps) / d  or  x = (c1 x + c2 eps) + c3 eps  over n elements (16 bytes per lane, every operation rounded on its
+ * own; n a multiple of 4), then in a launch of its own alpha_cur = alpha_cur / sqrt(1 - beta_cur); alpha_cur > 1 stops the search
+ * (stopped = 1), else cond_out = (beta_cur, 1 - alpha_cur^2).  Once stopped, x and cond_out are left untouched. */
+FD_API int fd_sched_update(fd_handle h, fd_sched_state *state, float *x, const float *eps, int64_t n, float *cond_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
