@@ -1010,6 +1010,7 @@ int fd_set_option(fd_handle h, const char *key, const char *value)
     static const struct { const char *key, *a, *b; void (*set)(fd_context *, bool); } choices[] = {
         {"gemm", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.gemm_f16 = a; }},
         {"gemm_form", "winograd", "direct", [](fd_context *c, bool a) { c->mode.gemm_wino = a; }},   // how the fp16x2 GEMM does its 3 taps
+        {"gemm_tile", "16", "32", [](fd_context *c, bool a) { c->mode.gemm_tile16 = a; }},           // rows of the Winograd form's matrix tiles
         {"lvc", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.lvc_f16 = a; }},
         {"conv", "f16x2", "fp32", [](fd_context *c, bool a) { c->mode.conv_f16 = a; }},
         {"lvc_h8", "mfma", "valu", [](fd_context *c, bool a) { c->mode.lvc_h8_mfma = a; }},

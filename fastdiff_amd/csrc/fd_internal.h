@@ -129,6 +129,8 @@ struct StepMode {
     bool fast[ST_COUNT] = {true, true, true, true, true, true, true, true};   // "kernels.<stage>" = fast | naive
     bool gemm_f16 = true;        // kp_gemm on the fp16 matrix pipe with the 2-piece operand split
     bool gemm_wino = true;       // option "gemm_form" = "winograd" | "direct": ... as Winograd F(2,3) over the frame axis (2/3 of the matrix work)
+    bool gemm_tile16 = true;     // option "gemm_tile" = "16" | "32": the Winograd form's item on 16x16x32 matrix tiles (two row tiles of 16 pairs; a
+                                 // row tile behind the utterance's end is skipped) or on 32x32x16 ones (k_kp_gemm_w<TILE>)
     bool lvc_f16 = true;         // LVC layers (hop 64, 256) likewise
     bool conv_f16 = true;        // DBlocks, ConvTranspose upsamplers and the predictor front likewise
     bool lvc_h8_mfma = true;     // option "lvc_h8" = "mfma": the hop-8 layers on 16x16x32 fp16 tiles (k_lvc_h8m) | "valu" (k_lvc_h8)
@@ -159,7 +161,7 @@ struct StepMode {
     {
         for (int i = 0; i < ST_COUNT; ++i)
             if (fast[i] != o.fast[i]) return false;
-        return gemm_f16 == o.gemm_f16 && gemm_wino == o.gemm_wino && lvc_f16 == o.lvc_f16 && conv_f16 == o.conv_f16 &&
+        return gemm_f16 == o.gemm_f16 && gemm_wino == o.gemm_wino && gemm_tile16 == o.gemm_tile16 && lvc_f16 == o.lvc_f16 && conv_f16 == o.conv_f16 &&
                lvc_h8_mfma == o.lvc_h8_mfma && fuse_final == o.fuse_final && fuse_up == o.fuse_up && fuse_advance == o.fuse_advance &&
                keep_taps == o.keep_taps && fp32_mask == o.fp32_mask && inline_fallback == o.inline_fallback && ragged == o.ragged &&
                hoist_np == o.hoist_np && hoist_chunk == o.hoist_chunk;

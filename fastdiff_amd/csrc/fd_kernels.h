@@ -12,6 +12,30 @@ constexpr int GW_PAIRS = 32;                      // Winograd form: pairs per it
 constexpr int GW_ROWB = 1024;                     // bytes per pair row: [4 j][2 pieces][64 ch] fp16
 __host__ __device__ inline int gx_rows(int T) { return ((T + GX_CT * 32 - 1) / (GX_CT * 32)) * (GX_CT * 32) + 2; }   // image rows per (block, utterance)
 __host__ __device__ inline int gw_pairs(int T) { return ((T + 2 * GW_PAIRS - 1) / (2 * GW_PAIRS)) * GW_PAIRS; }      // image rows (pairs) per (block, entry)
+
+// The Winograd form's item on 16 x 16 x 32 matrix tiles (k_kp_gemm_w<16>): an item is 2 row tiles (rt) of 16 pairs x 2 column tiles (ct) of
+// 16 record positions, a K = 64 product 2 steps (ks) of K = 32.  Lane = (r or n = lane & 15, g = lane >> 4).  The lane maps live here so
+// that tools/gemm16_index_check.cpp walks the very arithmetic the kernel runs.
+// A operand: byte offset of lane's 16 B inside the row tile's window, piece q, step ks (+ 16 rt GW_ROWB + 256 j for row tile and sub-row)
+__host__ __device__ inline int gw16_a_off(int lane, int q, int ks)
+{
+    const int r = lane & 15, g = lane >> 4;
+    return r * GW_ROWB + (((8 * q + 4 * ks + g) ^ r) << 4);
+}
+// B operand: float4 index into a block's gemm_w_pack ([ptile][piece][16 kg][lane = col + 32 hi][8]) for sub-row j, step ks, column tile ct
+__host__ __device__ inline int gw16_b_idx(int ptile, int q, int j, int ks, int ct, int lane)
+{
+    const int kh = 4 * ks + (lane >> 4);      // 8-value group of the K = 64 product: kg = 4 j + kh / 2, hi = kh % 2
+    return ((ptile * 2 + q) * 16 + 4 * j + (kh >> 1)) * 64 + 32 * (kh & 1) + 16 * ct + (lane & 15);
+}
+// D: register i of tile (rt, ct) holds pair row 16 rt + gw16_d_pair and position gw16_d_pos of the 32-column tile
+__host__ __device__ inline int gw16_d_pair(int lane, int i) { return 4 * (lane >> 4) + i; }
+__host__ __device__ inline int gw16_d_pos(int lane, int ct) { return 16 * ct + (lane & 15); }
+// Stores of a whole row tile.  The odd 16-lane rows of the ct = 0 register have changed places with the even rows of the ct = 1 register:
+// register i of part 0 (the former ct = 0 register) / part 1 then holds pair row 16 rt + 4 part + i + 8 (lane >> 5), position lane & 31.
+// Float offsets inside the item's 64 records: a per-lane part and a wave-uniform one.
+__host__ __device__ inline unsigned gw16_st_lane_off(int lane) { return (unsigned)(16 * (lane >> 5)) * (unsigned)fd::KREC + (unsigned)(lane & 31); }
+__host__ __device__ inline int gw16_st_row_off(int rt, int part, int i, int odd) { return (2 * (16 * rt + 4 * part + i) + odd) * fd::KREC; }
 }  // namespace fdk_fast
 
 namespace fdk {

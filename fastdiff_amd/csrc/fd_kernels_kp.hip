@@ -893,11 +893,136 @@ __device__ __forceinline__ void gw_item(char *lds, const GxItem &cur, bool more,
     __builtin_amdgcn_s_barrier();
 }
 
+// The same item on 16 x 16 x 32 tiles (option gemm_tile = 16, the default): two row tiles of 16 pairs, one after the other, each over two
+// column tiles of 16 positions.  Lane maps: fd_kernels.h (gw16_*).  Per row tile the chain of gw_item runs on acc / lo / keep of 2 x 4
+// registers instead of 16 each, against the same 128 registers of stationary weight pieces (held in this instruction's B order); a K = 64
+// product is 2 K = 32 steps of six matrix instructions, issued so that no two neighbours write the same accumulator.  What that buys:
+//   * a row tile that begins behind the utterance is skipped whole, and one that lies inside it stores the fast way: T % 64 == 32 (every
+//     second bucket length) no longer ends in a whole item's matrix work behind 512 predicated scalar stores and a vmcnt(0);
+//   * with 24 instead of 48 registers in the chain, the first operands of product s + 1 are requested under the last step of product s;
+//   * the 16-row tile shape itself (tools/ubench/clk_probe.hip: the clock the chip holds under either shape).
+// Stores: register i of tile (rt, ct) holds pair row 16 rt + 4 g + i, positions 16 ct + n -- 64-byte runs.  v_permlane16_swap exchanges
+// the odd 16-lane rows of the ct = 0 value with the even rows of the ct = 1 value, after which either register holds two whole 128-byte
+// runs (pair rows +0 and +8) and goes out as one buffer_store_dword, as in gw_item: 16 stores per row tile, 32 per whole item.
+// Vector-memory order per item: [DMA of the next window] [per stored row tile: 8 stores of the even frames, 8 of the odd ones]; the wait
+// behind the item counts the stores that were issued.
+typedef float gw_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ gw_f4 mfma16_f16(const float4 &a, const float4 &b, gw_f4 c)
+{
+    union { float4 f; f16x8 h; } ua, ub;
+    ua.f = a;
+    ub.f = b;
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(ua.h, ub.h, c, 0, 0, 0);
+}
+template <int BUF>
+__device__ __forceinline__ void gw16_item(char *lds, const GxItem &cur, bool more, const GxItem &nxt, const char *wx, float *kpack,
+                                          const float4 (&wq)[2][16] /*[piece][(2 j + ks) * 2 + ct]*/, const float (&bias_lo)[2],
+                                          const int (&aoff)[2][2], int B, int T, int P, int wave_u, int lane, int Tb)
+{
+    if (more) gw_dma(wx, lds + (BUF ^ 1) * GW_WINB, nxt, B, P, wave_u, lane);
+    const int t_begin = cur.chunk * (2 * GW_PAIRS);
+    float *krow = kpack + (((int64_t)cur.blk * B + cur.b) * T + t_begin) * fd::KREC + (cur.xg * 4 + wave_u) * 32;     // uniform
+    const unsigned loff = gw16_st_lane_off(lane);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(krow, 0, 2 * GW_PAIRS * fd::KREC * 4, 0x00020000);
+    const gw_f4 zero = {0.f, 0.f, 0.f, 0.f};
+    constexpr int ORDER[4] = {1, 2, 0, 3};
+    int n_fast = 0;           // row tiles stored through the descriptor (16 stores each)
+    bool counted = true;      // ... and nothing else behind the DMA
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+        const int t0 = t_begin + 32 * rt;
+        if (t0 >= Tb) continue;                      // the whole row tile lies behind the utterance (wave-uniform)
+        const bool whole = t0 + 32 <= Tb;            // else it straddles the utterance's end: predicated stores
+        const char *hb = lds + BUF * GW_WINB + rt * 16 * GW_ROWB;
+        gw_f4 acc[2], lo[2], keep[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) lo[ct] = gw_f4{bias_lo[ct], bias_lo[ct], bias_lo[ct], bias_lo[ct]};      // 2048 * bias, as in gw_item
+        float4 a1 = *reinterpret_cast<const float4 *>(hb + aoff[0][0] + ORDER[0] * 256);
+        float4 a2 = *reinterpret_cast<const float4 *>(hb + aoff[1][0] + ORDER[0] * 256);
+#ifdef FD_GW16_PIN
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#endif
+#pragma unroll
+        for (int step = 0; step < 8; ++step) {
+            const int s = step >> 1, ks = step & 1, j = ORDER[s], w = (2 * j + ks) * 2;
+            float4 n1 = a1, n2 = a2;
+            if (step + 1 < 8) {      // one step ahead, across products too: the next product's first operands fly under this one's last step
+                const int jn = ORDER[(step + 1) >> 1], kn = (step + 1) & 1;
+                n1 = *reinterpret_cast<const float4 *>(hb + aoff[0][kn] + jn * 256);
+                n2 = *reinterpret_cast<const float4 *>(hb + aoff[1][kn] + jn * 256);
+            }
+            const bool m3 = (step == 6);      // the m3 chain starts from d, its cross-term accumulator from 0
+            acc[0] = mfma16_f16(a1, wq[0][w], step == 0 ? zero : (m3 ? keep[0] : acc[0]));
+            lo[0] = mfma16_f16(a2, wq[0][w], m3 ? zero : lo[0]);
+            acc[1] = mfma16_f16(a1, wq[0][w + 1], step == 0 ? zero : (m3 ? keep[1] : acc[1]));
+            lo[1] = mfma16_f16(a2, wq[0][w + 1], m3 ? zero : lo[1]);
+            lo[0] = mfma16_f16(a1, wq[1][w], lo[0]);
+            lo[1] = mfma16_f16(a1, wq[1][w + 1], lo[1]);
+            a1 = n1;
+            a2 = n2;
+#ifdef FD_GW16_PIN      // probe (LABBOOK R17.1): pin the order the source asks for -- the next step's two reads, then this step's six matrix instructions
+            if (step + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+#endif
+            if (ks == 0) continue;
+            if (s == 0) {                // keep = m1 + bias
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) keep[ct][i] = fmaf(lo[ct][i], GX_INV_SCALE, acc[ct][i]);
+            } else if (s == 1) {         // keep = d = 2 (m1 + bias) - (m1 + m2 + bias)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) keep[ct][i] = fmaf(2.0f, keep[ct][i], -fmaf(lo[ct][i], GX_INV_SCALE, acc[ct][i]));
+            } else {                     // y[2p] = s + m0, then y[2p+1] = d + m3
+                const int odd = s == 3 ? 1 : 0;
+                float v[2][4];
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[ct][i] = fmaf(lo[ct][i], GX_INV_SCALE, acc[ct][i]);
+                if (whole) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[0][i]), __float_as_uint(v[1][i]), false, false);
+#pragma unroll
+                        for (int part = 0; part < 2; ++part)
+                            __builtin_amdgcn_raw_buffer_store_b32(x[part], rs, loff * 4u, gw16_st_row_off(rt, part, i, odd) * 4, FD_GX_STORE_AUX);
+                    }
+                } else {
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int f = 2 * (16 * rt + gw16_d_pair(lane, i)) + odd;
+                            if (t_begin + f < Tb) krow[f * fd::KREC + gw16_d_pos(lane, ct)] = v[ct][i];
+                        }
+                }
+            }
+        }
+        if (whole) ++n_fast;
+        else counted = false;
+    }
+    if (more) {      // the DMA has landed; this item's buffer stores may still fly
+        if (counted && n_fast == 2) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+        else if (counted && n_fast == 1) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+}
+
+#ifdef FD_GW_CLOCK      // probe (tools/ubench/gemm_bench.hip): core ticks and 10 ns ticks of every workgroup's item loop -> the clock it ran at
+__device__ long long fd_gwclk[2];
+#endif
+// TILE: rows of the matrix tiles an item is built from (option gemm_tile): 16 = gw16_item, 32 = gw_item
+template <int TILE>
 __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ wx /*[3][B][P][4][2][64] fp16*/, float *__restrict__ kpack,
                                                       const float4 *g0, const float4 *g1, const float4 *g2, const float *gb0,
                                                       const float *gb1, const float *gb2, const int *__restrict__ range_flag, int B,
                                                       int T, int P, int chunks_per_utt, int n_items, const int *__restrict__ lens)
 {
+    static_assert(TILE == 16 || TILE == 32, "k_kp_gemm_w: 16- or 32-row matrix tiles");
     __shared__ __attribute__((aligned(16))) char lds[2 * GW_WINB];     // 2 x 32 KB
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -907,17 +1032,24 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ w
     if (n_mine <= 0) return;
     int run = 0, left = walk.left0;
     GxItem cur = walk.first();
-    // byte offsets of the A-operand reads: pair row l31, slot = (8*piece + 2*k4 + hi) ^ (row & 15); the sub-row j adds the constant 256 j
-    int aoff[2][4];
+    // byte offsets of the A-operand reads.  32: pair row l31, slot = (8*piece + 2*k4 + hi) ^ (row & 15); 16: gw16_a_off.  The sub-row j
+    // (and the row tile) add constants
+    constexpr int NOFF = TILE == 16 ? 2 : 4;
+    int aoff[2][NOFF];
 #pragma unroll
     for (int q2 = 0; q2 < 2; ++q2)
 #pragma unroll
-        for (int k4 = 0; k4 < 4; ++k4) aoff[q2][k4] = l31 * GW_ROWB + (((q2 * 8 + k4 * 2 + hi) ^ (l31 & 15)) << 4);
+        for (int k4 = 0; k4 < NOFF; ++k4)
+            aoff[q2][k4] = TILE == 16 ? gw16_a_off(lane, q2, k4) : l31 * GW_ROWB + (((q2 * 8 + k4 * 2 + hi) ^ (l31 & 15)) << 4);
     gw_dma(wx, lds, cur, B, P, wave_u, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+#ifdef FD_GW_CLOCK
+    const long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
     float4 wq[2][16];
-    float bias_lo = 0.0f;      // 2048 * bias of this lane's column (one register: gw_item copies it into the accumulator twice per item)
+    // 2048 * bias of this lane's column(s) (32: one register, gw_item copies it into the accumulator twice per item; 16: one per column tile)
+    float bias_lo[2] = {0.0f, 0.0f};
     int have_blk = -1, have_xg = -1;
 #pragma unroll 1
     for (int i = 0; i < n_mine; i += 2) {
@@ -928,28 +1060,50 @@ __global__ void __launch_bounds__(256, 2) k_kp_gemm_w(const char *__restrict__ w
                 const float4 *gp = cur.blk == 0 ? g0 : (cur.blk == 1 ? g1 : g2);
                 const float *gb = cur.blk == 0 ? gb0 : (cur.blk == 1 ? gb1 : gb2);
                 const int ptile = cur.xg * 4 + wave_u;
+                if constexpr (TILE == 16) {
 #pragma unroll
-                for (int q2 = 0; q2 < 2; ++q2)
+                    for (int q2 = 0; q2 < 2; ++q2)
 #pragma unroll
-                    for (int kg = 0; kg < 16; ++kg) wq[q2][kg] = gp[(((int64_t)ptile * 2 + q2) * 16 + kg) * 64 + lane];
-                bias_lo = gb[ptile * 32 + l31] * GX_SCALE;
+                        for (int jk = 0; jk < 8; ++jk)
+#pragma unroll
+                            for (int ct = 0; ct < 2; ++ct) wq[q2][jk * 2 + ct] = gp[gw16_b_idx(ptile, q2, jk >> 1, jk & 1, ct, lane)];
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) bias_lo[ct] = gb[ptile * 32 + gw16_d_pos(lane, ct)] * GX_SCALE;
+                } else {
+#pragma unroll
+                    for (int q2 = 0; q2 < 2; ++q2)
+#pragma unroll
+                        for (int kg = 0; kg < 16; ++kg) wq[q2][kg] = gp[(((int64_t)ptile * 2 + q2) * 16 + kg) * 64 + lane];
+                    bias_lo[0] = gb[ptile * 32 + l31] * GX_SCALE;
+                }
                 have_blk = cur.blk; have_xg = cur.xg;
                 __builtin_amdgcn_s_waitcnt(0x0F70);
             }
             const bool more = (i + half + 1 < n_mine);
             GX_WALK_NEXT(walk, cur, more, nxt, run, left);
             const int Tb = frames_of(lens, cur.b, T);
-            const bool full = cur.chunk * (2 * GW_PAIRS) + 2 * GW_PAIRS <= Tb;
-            if (half == 0) {
-                if (full) gw_item<0, true>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
-                else gw_item<0, false>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
+            if constexpr (TILE == 16) {
+                if (half == 0) gw16_item<0>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
+                else gw16_item<1>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
             } else {
-                if (full) gw_item<1, true>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
-                else gw_item<1, false>(lds, cur, more, nxt, wx, kpack, wq, bias_lo, aoff, B, T, P, wave_u, lane, Tb);
+                const bool full = cur.chunk * (2 * GW_PAIRS) + 2 * GW_PAIRS <= Tb;
+                if (half == 0) {
+                    if (full) gw_item<0, true>(lds, cur, more, nxt, wx, kpack, wq, bias_lo[0], aoff, B, T, P, wave_u, lane, Tb);
+                    else gw_item<0, false>(lds, cur, more, nxt, wx, kpack, wq, bias_lo[0], aoff, B, T, P, wave_u, lane, Tb);
+                } else {
+                    if (full) gw_item<1, true>(lds, cur, more, nxt, wx, kpack, wq, bias_lo[0], aoff, B, T, P, wave_u, lane, Tb);
+                    else gw_item<1, false>(lds, cur, more, nxt, wx, kpack, wq, bias_lo[0], aoff, B, T, P, wave_u, lane, Tb);
+                }
             }
             cur = nxt;
         }
     }
+#ifdef FD_GW_CLOCK
+    if (tid == 0) {
+        atomicAdd((unsigned long long *)&fd_gwclk[0], (unsigned long long)(__builtin_amdgcn_s_memtime() - clk_t0));
+        atomicAdd((unsigned long long *)&fd_gwclk[1], (unsigned long long)(__builtin_amdgcn_s_memrealtime() - clk_r0));
+    }
+#endif
 }
 
 }  // namespace fdk_fast
@@ -1020,7 +1174,9 @@ hipError_t fast_kp_gemm(const Launch &L, int B, int T)
         const GemmGrid g = gemm_grid(c, B, P / GW_PAIRS);
         FD_LAUNCH(L, "h_wino", k_h_wino, dim3((8 * P + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
                   reinterpret_cast<char *>(c->ws.h_f16), c->ws.range_flag, B, T, P, lens);
-        FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_w, dim3(g.grid), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
+        const auto gemm_w = m.gemm_tile16 ? &k_kp_gemm_w<16> : &k_kp_gemm_w<32>;      // option gemm_tile
+        FD_LAUNCH(L, "kp_gemm_f16x2", gemm_w, dim3(g.grid), dim3(256), 0,
+                  reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[0]), reinterpret_cast<const float4 *>(w.gemm_w_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
                   (const int *)c->ws.range_flag, B, T, P, g.chunks, g.items, lens);

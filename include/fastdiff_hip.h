@@ -170,6 +170,8 @@ FD_API int fd_set_noise_streams(fd_handle h, const uint64_t *stream_ids, int B);
  *                          fp16 matrix pipe with 2-piece operands (22 significant bits, fp32 accumulation) or on the exact-fp32 one
  *   "gemm_form" = "winograd" | "direct"   the fp16x2 predictor GEMM evaluates kernel_conv's three taps as Winograd F(2,3) over the frame
  *                          axis (2/3 of the matrix work, same 2-piece arithmetic per product) or tap by tap
+ *   "gemm_tile" = "16" | "32"      the Winograd form's work item on 16x16x32 matrix tiles (two row tiles of 16 frame pairs; one that lies
+ *                          behind the utterance's end is skipped) or on 32x32x16 ones.  fp32 rounding points differ, not the arithmetic
  *   "fallback" = "host" | "graph"  what fd_sample does about an operand outside the fp16 range: see fd_sample
  *   "defer_check" = "0" | "1"      fallback = host: settle inside fd_sample | the pipelined form (fd_sample_check / _settle)
  *   "t_bucket" = "32" | frames     fd_sample's buffers and graphs are sized for T rounded up to a multiple of this (0 = exact T)

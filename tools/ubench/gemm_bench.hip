@@ -1,4 +1,6 @@
-// gemm_bench.hip -- standalone timing harness for k_kp_gemm
+// gemm_bench.hip -- standalone timing harness for k_kp_gemm, and (third argument w16 | w32) for k_h_wino + k_kp_gemm_w<16 | 32>, the two bodies
+// of the Winograd form side by side: gemm_bench 8 864 w32; gemm_bench 8 864 w16.  Built with -DFD_GW_CLOCK it also prints the clock the
+// workgroups of k_kp_gemm_w ran at (core ticks of s_memtime per 10 ns tick of s_memrealtime, summed over the workgroups' item loops).
 #include "../../fastdiff_amd/csrc/fd_kernels_kp.hip"
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +19,46 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < ng; ++i) v[i] = (float)((i * 2654435761u) % 2001) * 1e-3f - 1.0f;
     CK(hipMemcpy(g, v.data(), ng * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(h, v.data(), nh * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(gb, v.data(), fd::KREC * 4, hipMemcpyHostToDevice));
+    if (argc > 3 && argv[3][0] == 'w') {
+        const bool t16 = atoi(argv[3] + 1) == 16;
+        const int P = fdk_fast::gw_pairs(T), wchunks = P / fdk_fast::GW_PAIRS, items = 3 * (fd::KREC / 128) * B * wchunks, G = argc > 4 ? atoi(argv[4]) : 512;
+        const size_t nw = (size_t)776 * 2 * 16 * 64 * 4;      // floats of a block's fp16 piece pack
+        float *wx, *gw;
+        int *flag;
+        CK(hipMalloc(&flag, 256)); CK(hipMemset(flag, 0, 256));
+        CK(hipMalloc(&wx, (size_t)3 * B * P * fdk_fast::GW_ROWB)); CK(hipMalloc(&gw, nw * 4));
+        {   // fp16 weight pieces of plausible magnitude (2^-7 .. 2^-2), random sign and mantissa (as gemm_h2_bench.hip)
+            std::vector<unsigned short> w16(nw * 2);
+            unsigned x = 12345u;
+            for (auto &b : w16) { x = x * 1664525u + 1013904223u; b = (unsigned short)(((x >> 16) & 0x8000u) | ((8u + ((x >> 8) % 6u)) << 10) | ((x >> 20) & 0x3FFu)); }
+            CK(hipMemcpy(gw, w16.data(), nw * 4, hipMemcpyHostToDevice));
+        }
+        auto run = [&]() {
+            hipLaunchKernelGGL(fdk_fast::k_h_wino, dim3((8 * P + 255) / 256, 3 * B), dim3(256), 0, 0, (const float *)h, (char *)wx, flag, B, T, P, (const int *)nullptr);
+            if (t16) hipLaunchKernelGGL(fdk_fast::k_kp_gemm_w<16>, dim3(G), dim3(256), 0, 0, (const char *)wx, kp, (const float4 *)gw, (const float4 *)gw,
+                                        (const float4 *)gw, gb, gb, gb, (const int *)flag, B, T, P, wchunks, items, (const int *)nullptr);
+            else hipLaunchKernelGGL(fdk_fast::k_kp_gemm_w<32>, dim3(G), dim3(256), 0, 0, (const char *)wx, kp, (const float4 *)gw, (const float4 *)gw,
+                                    (const float4 *)gw, gb, gb, gb, (const int *)flag, B, T, P, wchunks, items, (const int *)nullptr);
+        };
+        hipEvent_t w0, w1; CK(hipEventCreate(&w0)); CK(hipEventCreate(&w1));
+        for (int i = 0; i < 2; ++i) run();
+        CK(hipDeviceSynchronize());
+#ifdef FD_GW_CLOCK
+        { long long z[2] = {0, 0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(fdk_fast::fd_gwclk), z, sizeof(z))); }
+#endif
+        const int wreps = 5;
+        CK(hipEventRecord(w0, 0));
+        for (int i = 0; i < wreps; ++i) run();
+        CK(hipEventRecord(w1, 0)); CK(hipEventSynchronize(w1));
+        float wms = 0; CK(hipEventElapsedTime(&wms, w0, w1));
+        int raised = 0; CK(hipMemcpy(&raised, flag, 4, hipMemcpyDeviceToHost));
+        printf("h_wino+kp_gemm_w<%d> B=%d T=%d grid=%d items=%d: %.1f us  (range flag %d)\n", t16 ? 16 : 32, B, T, G, items, wms * 1e3 / wreps, raised);
+#ifdef FD_GW_CLOCK
+        long long clk[2]; CK(hipMemcpyFromSymbol(clk, HIP_SYMBOL(fdk_fast::fd_gwclk), sizeof(clk)));
+        printf("   item loops ran at %.0f MHz (%lld core ticks / %lld x 10 ns)\n", (double)clk[0] / clk[1] * 100.0, clk[0], clk[1]);
+#endif
+        return 0;
+    }
     const int tiles_per_utt = (T + 31) / 32, chunks = (tiles_per_utt + fdk_fast::GEMM_CT - 1) / fdk_fast::GEMM_CT;
     const int chunk_tiles = (tiles_per_utt + chunks - 1) / chunks;
     const int n_items = 3 * (fd::KREC / 128) * B * chunks;
