@@ -81,7 +81,8 @@ class TrainCorpus:
     sums) are tensors on `device` (None: the HIP device if there is one, else the CPU); lengths / frame_off_host are their host copies.
     A corpus on the CPU does everything but feed the kernel: .to(device) uploads it."""
 
-    def __init__(self, items, hop_size=256, max_samples=25600, aux_context_window=0, device=None):
+    @staticmethod
+    def _geometry(hop_size, max_samples, aux_context_window):
         if aux_context_window != 0:
             raise NotImplementedError("TrainCorpus: aux_context_window = 0 only (base.yaml's value; the model takes wavs of exactly T * hop samples)")
         hop, F = int(hop_size), int(max_samples) // int(hop_size)
@@ -89,6 +90,10 @@ class TrainCorpus:
             raise ValueError(f"TrainCorpus: hop_size = {hop_size} must be a multiple of 4 (whatever the items)")
         if F < 1:
             raise ValueError(f"TrainCorpus: max_samples = {max_samples} is shorter than one frame of {hop} samples (whatever the items)")
+        return hop, F
+
+    def __init__(self, items, hop_size=256, max_samples=25600, aux_context_window=0, device=None):
+        hop, F = self._geometry(hop_size, max_samples, aux_context_window)
         mels, wavs, kept = [], [], []
         for i, item in enumerate(items):
             mel, wav = np.asarray(item["mel"]), np.asarray(item["wav"]).reshape(-1)
@@ -162,6 +167,48 @@ class TrainCorpus:
         corpus.kept = np.asarray(long_enough, np.int64)[corpus.kept]
         corpus.n_skipped = len(lengths) - corpus.n_items
         return corpus
+
+    @classmethod
+    def from_wav_dir(cls, model, wav_dir, sample_rate=22050, mel_variant="pwg", hop_size=256, max_samples=25600, aux_context_window=0,
+                     device=None):
+        """A corpus straight from recordings, without the reference's binarizer (which needs librosa): every *.wav below `wav_dir`, in
+        sorted order, goes through what process_utterance does per item (data_gen/tts/data_gen_utils.py:93-147), on the device of
+        `model` (a FastDiff on the GPU): any rate, sample type and channel count -> float mono at `sample_rate` (infer.wav_to_device:
+        FastDiff.resample), the mel of T = 1 + n // hop frames (FastDiff.mel_spectrogram), the wav zero-padded at its end to T * hop
+        samples and cut there (:138-140).  One recording at a time -- peak memory is one recording plus the arenas -- and nothing comes
+        back to the host.  Items the length rule drops are counted in n_skipped, `kept` lists the positions of the kept ones among the
+        sorted files."""
+        import glob
+        from scipy.io import wavfile
+        from . import infer
+        hop, F = cls._geometry(hop_size, max_samples, aux_context_window)
+        if hop != model.hop_length:
+            raise ValueError(f"TrainCorpus.from_wav_dir: hop_size = {hop_size}, the model's mel front-end has {model.hop_length}")
+        paths = sorted(glob.glob(f"{wav_dir}/*.wav"))
+        mels, wavs, kept = [], [], []
+        for i, path in enumerate(paths):
+            sr, pcm = wavfile.read(path)
+            wav = infer.wav_to_device(model, pcm, sr, sample_rate, path)
+            T = 1 + wav.shape[0] // hop
+            if T <= F:                                     # dataset_utils.py:68-72 would drop it: no mel computed
+                continue
+            mels.append(model.mel_spectrogram(wav, variant=mel_variant)[0].transpose(0, 1).contiguous())      # [T, 80] as the binarizer stores it
+            wavs.append(torch.nn.functional.pad(wav, (0, T * hop - wav.shape[0])))
+            kept.append(i)
+        if not kept:
+            raise ValueError(f"TrainCorpus.from_wav_dir: none of the {len(paths)} recordings below {wav_dir} is longer than {F} frames")
+        if len(kept) > MAX_ITEMS:
+            raise ValueError(f"TrainCorpus.from_wav_dir: {len(kept)} items (2^28 at most)")
+        self = object.__new__(cls)
+        self.n_skipped = len(paths) - len(kept)
+        self.hop_size, self.frames, self.max_samples = hop, F, int(max_samples)
+        self.kept = np.asarray(kept, np.int64)
+        self.lengths = np.asarray([m.shape[0] for m in mels], np.int64)
+        self.frame_off_host = np.concatenate([np.zeros(1, np.int64), np.cumsum(self.lengths)])
+        self.mel, self.wav = torch.cat(mels, dim=0), torch.cat(wavs)
+        self.frame_off = torch.from_numpy(self.frame_off_host.copy())
+        self._move(torch.device(device) if device is not None else self.wav.device)
+        return self
 
     def plan(self, iteration, batch_size, seed=0, rank=0, world_size=1):
         """(items [B], starts [B]) int64: what fd_train_collate picks for step `iteration` -- equal, not close.  Pure integer numpy."""

@@ -214,6 +214,7 @@ static void release_handle(fd_context *h)
         if (sl.done) hipEventDestroy(sl.done);
     }
     for (void *p : h->mel_allocs) hipFree(p);
+    for (auto &t : h->resample_tabs) hipFree(const_cast<float *>(t.dev));
     if (h->ev_switch) hipEventDestroy(h->ev_switch);
     if (h->cap_stream) hipStreamDestroy(h->cap_stream);
     delete h;

@@ -1,5 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h: the mel front-end in front of the vocoder and the int16
-// waveform epilogue behind it, taps, layout introspection, counters and per-kernel profiling.
+// waveform epilogue behind it, sample-rate conversion in front of and behind both (fd_resample), taps, layout
+// introspection, counters and per-kernel profiling.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -9,6 +10,7 @@
 
 #include "fd_kernels.h"
 #include "fd_host.h"
+#include "fd_resample.h"
 
 extern "C" {
 
@@ -186,6 +188,88 @@ int fd_peak_normalize_int16_ragged(fd_handle h, const float *wav, int B, int64_t
 int fd_peak_normalize_int16(fd_handle h, const float *wav, int B, int64_t len, int16_t *pcm, void *stream)
 {
     return fd_peak_normalize_int16_ragged(h, wav, B, len, nullptr, pcm, stream);
+}
+
+// Sample-rate conversion (fastdiff_hip_ext.h; the filter design: fd_resample.h, the kernels: fd_kernels_resample.hip) -----------------
+int64_t fd_resample_out_len(int64_t n, int sr_in, int sr_out)
+{
+    fdr::Ratio r;
+    if (n < 0 || !fdr::reduce(sr_in, sr_out, r)) return FD_ERR_INVALID;
+    if (std::max(r.up, r.down) > fdr::MAX_RATIO) return FD_ERR_UNSUPPORTED;
+    return fdr::out_len(n, r);
+}
+
+int fd_resample_taps(int sr_in, int sr_out, float *taps, int64_t capacity, int *up, int *down, int *half)
+{
+    fdr::Ratio r;
+    if (!fdr::reduce(sr_in, sr_out, r) || (taps && capacity < 0)) return FD_ERR_INVALID;
+    if (std::max(r.up, r.down) > fdr::MAX_RATIO) return FD_ERR_UNSUPPORTED;
+    if (up) *up = r.up;
+    if (down) *down = r.down;
+    if (half) *half = r.half;
+    const int n = 2 * r.half + 1;
+    if (taps) {
+        const std::vector<float> hp = fdr::taps(r);
+        memcpy(taps, hp.data(), sizeof(float) * (size_t)std::min<int64_t>(capacity, n));
+    }
+    return n;
+}
+
+// the device table of a ratio: built and uploaded at its first use (a synchronous copy from pageable memory: complete on return)
+static int resample_table(fd_handle h, const fdr::Ratio &r, hipStream_t stream, const float **dev)
+{
+    for (const auto &t : h->resample_tabs)
+        if (t.up == r.up && t.down == r.down) { *dev = t.dev; return FD_OK; }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        FD_FAIL(h, FD_ERR_STATE, "fd_resample: the table of ratio %d/%d is built at the first use of that ratio, which cannot happen inside a stream capture: call it once before",
+                r.up, r.down);
+    }
+    const std::vector<float> tab = fdr::table(r);
+    void *d = nullptr;
+    FD_HIP(h, hipMalloc(&d, tab.size() * sizeof(float)));
+    const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        FD_FAIL(h, FD_ERR_HIP, "fd_resample: table upload failed: %s", hipGetErrorString(e));
+    }
+    h->resample_tabs.push_back({r.up, r.down, static_cast<const float *>(d)});
+    *dev = static_cast<const float *>(d);
+    return FD_OK;
+}
+
+int fd_resample(fd_handle h, const void *src, int format, int channels, int B, int64_t n_in, int64_t src_pitch, const int64_t *valid_in,
+                int sr_in, int sr_out, float *dst, int64_t dst_pitch, void *stream)
+{
+    if (!h) return FD_ERR_INVALID;
+    if (!src || !dst) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: null %s", !src ? "src" : "dst");
+    if (format != FD_PCM_F32 && format != FD_PCM_S16 && format != FD_PCM_S32 && format != FD_PCM_U8)
+        FD_FAIL(h, FD_ERR_INVALID, "fd_resample: unknown sample format %d (FD_PCM_F32 / _S16 / _S32 / _U8)", format);
+    if (channels < 1 || channels > 8) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: %d channels, 1..8 are supported", channels);
+    if (B < 1 || n_in < 1) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: B = %d items of n_in = %lld frames", B, (long long)n_in);
+    if (n_in > (INT64_MAX >> 12) / channels) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: n_in = %lld is too long", (long long)n_in);
+    fdr::Ratio r;
+    if (!fdr::reduce(sr_in, sr_out, r)) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: sample rates %d -> %d", sr_in, sr_out);
+    if (std::max(r.up, r.down) > fdr::MAX_RATIO)
+        FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_resample: %d -> %d Hz reduces to %d/%d; ratios up to %d are supported", sr_in, sr_out, r.up, r.down, fdr::MAX_RATIO);
+    const int64_t n_out = fdr::out_len(n_in, r);
+    if (src_pitch < n_in * channels)
+        FD_FAIL(h, FD_ERR_INVALID, "fd_resample: src_pitch = %lld < n_in * channels = %lld", (long long)src_pitch, (long long)(n_in * channels));
+    if (dst_pitch < n_out) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: dst_pitch = %lld < out_len(n_in) = %lld", (long long)dst_pitch, (long long)n_out);
+    if (valid_in)
+        for (int b = 0; b < B; ++b)
+            if (valid_in[b] < 1 || valid_in[b] > n_in)
+                FD_FAIL(h, FD_ERR_INVALID, "fd_resample: valid_in[%d] = %lld outside [1, %lld]", b, (long long)valid_in[b], (long long)n_in);
+    FD_HIP(h, hipSetDevice(h->device));
+    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // the resampler touches no sampler state
+    if (rc != FD_OK) return rc;
+    const float *table = nullptr;
+    if (r.up != r.down && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
+    fdk::Launch L = {h, (hipStream_t)stream, false};
+    const hipError_t e = fdk::resample(L, src, format, channels, B, n_in, src_pitch, valid_in, r.up, r.down, r.half, r.K, r.Kp, n_out, table, dst, dst_pitch);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_resample: %s", hipGetErrorString(e));
+    return FD_OK;
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

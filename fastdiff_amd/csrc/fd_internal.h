@@ -281,6 +281,8 @@ struct fd_context {
     std::vector<float> mel_bank[MEL_VARIANTS];   // the dense [80][513] bank each front-end uses (host copy: fd_get_mel_filterbank)
     bool mel_bank_user[MEL_VARIANTS] = {false, false};   // supplied through fd_set_mel_filterbank (else the restated default)
     std::vector<void *> mel_allocs;           // device memory behind `mel` (built on first use, freed at fd_destroy)
+    struct ResampleTable { int up, down; const float *dev; };
+    std::vector<ResampleTable> resample_tabs; // fd_resample's polyphase tables, one per reduced ratio used so far (freed at fd_destroy)
     int last_B = 0, last_T = 0;
     hipStream_t cap_stream = nullptr;
     // Calls on one handle share the workspace, the embedding rows and the pending range check: they are ordered by the stream they run
@@ -456,6 +458,12 @@ hipError_t ring_append(const Launch &L, const fd_ring_chunk *chunks, int n, long
 hipError_t copy_rows(const Launch &L, float *dst, int64_t dpitch, const float *src, int64_t spitch, int width, int rows, int reps = 1,
                      int64_t rep_stride = 0);
 hipError_t peak_normalize_int16(const Launch &L, const float *wav, int B, int64_t len, int16_t *pcm, const long long *valid_dev);
+// fd_resample (fd_kernels_resample.hip).  The frames that count of up to RESAMPLE_ITEMS items are a kernel argument; a larger batch is
+// one launch per RESAMPLE_ITEMS items.  valid: HOST [B] or null; table: device [up][Kp] (csrc/fd_resample.h), unused for up = down = 1.
+constexpr int RESAMPLE_ITEMS = 64;
+struct ResampleLens { long long v[RESAMPLE_ITEMS]; };
+hipError_t resample(const Launch &L, const void *src, int format, int C, int B, int64_t n_in, int64_t src_pitch, const int64_t *valid,
+                    int up, int down, int half, int K, int Kp, int64_t n_out_max, const float *table, float *dst, int64_t dst_pitch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

@@ -13,10 +13,10 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
     The reference CLI runs B = 1 (config `max_sentences`); batching is this path's extension: the batch goes down with its
     `lens`, so every item is computed exactly as if it ran alone (and the padding costs nothing), then cropped to its length.
 
-Entry points: load_mel_inputs, load_wav_inputs (device mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
+Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
-(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt]`).
+(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--out_sample_rate R]`).
 """
 import argparse
 import glob
@@ -58,22 +58,38 @@ def pcm_to_float(pcm: np.ndarray, what: str = "wav") -> np.ndarray:
     raise ValueError(f"{what}: unsupported sample type {pcm.dtype}")
 
 
+def wav_to_device(model, pcm: np.ndarray, sr: int, sample_rate: int = 22050, what: str = "wav") -> torch.Tensor:
+    """The samples of a RIFF file ([n] or [n, C] as scipy.io.wavfile.read returns them, recorded at `sr`) as float32 mono at `sample_rate`
+    on the device, [n'] -- librosa.core.load(path, sr=sample_rate).  Mono at the model's rate: pcm_to_float and an upload.  Anything
+    else: the raw samples go up and FastDiff.resample converts, mixes down and resamples them there."""
+    if sr == sample_rate and pcm.ndim == 1:
+        return torch.from_numpy(pcm_to_float(pcm, what)).cuda()
+    if pcm.ndim not in (1, 2) or (pcm.ndim == 2 and not 1 <= pcm.shape[1] <= 8):
+        raise ValueError(f"{what}: expected [n] or [n, channels <= 8] samples, got shape {pcm.shape}")
+    if pcm.dtype in (np.float32, np.float64):
+        pcm = pcm_to_float(pcm, what)                      # float32, range checked
+    elif pcm.dtype not in (np.uint8, np.int16, np.int32):
+        raise ValueError(f"{what}: unsupported sample type {pcm.dtype}")
+    if pcm.shape[0] < 1:
+        raise ValueError(f"{what}: no samples")
+    raw = torch.from_numpy(np.ascontiguousarray(pcm)).cuda()
+    return model.resample(raw, sr, sample_rate, channels=1 if pcm.ndim == 1 else pcm.shape[1])[0]
+
+
 def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg") -> List[dict]:
     """Copy-synthesis inputs (`test_input_dir` with recordings, tasks/vocoder/dataset_utils.py:162-184): every *.wav below the
     directory, in sorted order, through the device mel front-end (`FastDiff.mel_spectrogram` = process_utterance of
     data_gen/tts/data_gen_utils.py:93-147, or with mel_variant="tacotron" the TacotronSTFT of vocoder_binarizer_tacotron.py:110-116
     for models trained on FastDiff_tacotron.yaml features).  Integer PCM is scaled by its full range as librosa.core.load does
-    (pcm_to_float); the sample rate must already be the model's (no resampler here)."""
+    (pcm_to_float).  A recording at another rate, or with several channels, first goes through the device resampler as the file holds
+    it (FastDiff.resample: sample type, down-mix and rate in one launch -- librosa.core.load(path, sr=sample_rate),
+    data_gen_utils.py:111); a mono recording at the model's rate takes the direct path, bit for bit as before."""
     from scipy.io import wavfile
     items = []
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
         sr, pcm = wavfile.read(path)
-        if sr != sample_rate:
-            raise ValueError(f"{path}: sample rate {sr}, expected {sample_rate}")
-        if pcm.ndim != 1:
-            raise ValueError(f"{path}: expected mono audio, got shape {pcm.shape}")
-        wav = pcm_to_float(pcm, path)
-        mel = model.mel_spectrogram(torch.from_numpy(wav).cuda(), variant=mel_variant)[0].transpose(0, 1).contiguous().cpu()      # [T, 80] as on disk
+        wav = wav_to_device(model, pcm, sr, sample_rate, path)
+        mel = model.mel_spectrogram(wav, variant=mel_variant)[0].transpose(0, 1).contiguous().cpu()      # [T, 80] as on disk
         items.append({"item_name": path[len(test_input_dir) + 1:].replace("/", "_"), "mel": mel, "len": mel.shape[0]})
     return items
 
@@ -177,14 +193,20 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
 
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
-               noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True) -> Dict[str, np.ndarray]:
+               noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
+               sample_rate: int = 22050) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
     waveform does not depend on the micro-batch, rank or world size that produced it.
     Mels may live on the host ([T, 80] tensors or arrays: collated in numpy straight into pinned memory) or on the GPU (collated
     there).  return_device: the values are int16 device tensors instead of host arrays (no device-to-host copy at all: what
-    synthesize_sharded hands to the RCCL gather).  sort=False: micro-batches in the order of arrival instead of longest first."""
+    synthesize_sharded hands to the RCCL gather).  sort=False: micro-batches in the order of arrival instead of longest first.
+    out_sample_rate = R (None: the model's `sample_rate`, every byte as without the argument): the float waveform of each micro-batch is
+    resampled on the device (FastDiff.resample, ragged: valid = lens * hop) and THEN peak-normalised over its out_len(lens * hop) samples,
+    so the filter's overshoot cannot clip; an item's PCM is what it would get alone."""
+    from . import resample as _resample
+    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
     # every call, as the reference does), the same rows then drive every micro-batch
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
@@ -193,13 +215,21 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     if not items:
         return out
     hop = model.hop_length
+    n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
+
+    def epilogue(wav, lens):
+        if R is None:
+            return model.peak_normalize_int16(wav, valid=[t * hop for t in lens])
+        y = model.resample(wav.reshape(wav.shape[0], -1), sample_rate, R, valid=[t * hop for t in lens])
+        return model.peak_normalize_int16(y, valid=[n_of(t) for t in lens])
+
     on_device = isinstance(items[0]["mel"], torch.Tensor) and items[0]["mel"].is_cuda
     t_max, b_max = max(lengths), min(max_batch, len(items))
     # pinned staging, two mel and two PCM buffers used alternately -- buffer k & 1 is free again once micro-batch k - 2 has been
     # collected, which happens in iteration k - 1.  Only the legs that cross PCIe need it.
     mel_pin = pcm_pin = mel_np = None
     if not (on_device and return_device):
-        mel_pin, pcm_pin = _pinned_staging(model, 0 if on_device else b_max * 80 * t_max, 0 if return_device else b_max * t_max * hop)
+        mel_pin, pcm_pin = _pinned_staging(model, 0 if on_device else b_max * 80 * t_max, 0 if return_device else b_max * n_of(t_max))
         mel_np = [m.numpy() for m in mel_pin]      # the collater writes the batch straight into the pinned buffer
     mel_up = [None, None]          # event behind the upload that last read mel_pin[i]: the collater waits for it before writing there again
     pending = None                 # (event, pinned PCM view, names, lens, ticket, wav) of the micro-batch still on its way to the host
@@ -213,18 +243,18 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         # next sample() has looked at it (no wait by then) and not at the end of the job
         ticket, wav, names, lens = p
         if model.settle(ticket):                     # run again on fp32: so is its epilogue
-            pcm = model.peak_normalize_int16(wav, valid=[t * hop for t in lens])
+            pcm = epilogue(wav, lens)
             for b, (name, t) in enumerate(zip(names, lens)):
-                out[name] = pcm[b, : t * hop]
+                out[name] = pcm[b, : n_of(t)]
 
     def collect(p):
         done, host, names, lens, ticket, wav = p
         done.synchronize()
         if host_check and model.settle(ticket):      # an operand left the fp16 range: the call was run again on fp32 -- so is its epilogue
-            host.copy_(model.peak_normalize_int16(wav, valid=[t * hop for t in lens]), non_blocking=True)
+            host.copy_(epilogue(wav, lens), non_blocking=True)
             torch.cuda.current_stream().synchronize()
         for b, (name, t) in enumerate(zip(names, lens)):
-            out[name] = host[b, : t * hop].numpy().copy()
+            out[name] = host[b, : n_of(t)].numpy().copy()
 
     k = 0
     for batch_idx in shard.micro_batches(range(len(items)), lengths, max_batch, sort=sort):
@@ -247,16 +277,16 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
             wav = model.sample(mels, rows, ddim=False, seed=seed, lens=lens, stream_ids=[uid_of[n] for n in names], defer_check=host_check)
         ticket = getattr(model, "last_ticket", 0)
         # one epilogue call and one asynchronous copy per micro-batch; the previous batch is unpacked on the host while this one runs
-        pcm = model.peak_normalize_int16(wav, valid=[t * hop for t in lens])
+        pcm = epilogue(wav, lens)
         if return_device:
             for b, (name, t) in enumerate(zip(names, lens)):
-                out[name] = pcm[b, : t * hop]
+                out[name] = pcm[b, : n_of(t)]
             if host_check and prev_dev is not None:
                 settle_on_device(prev_dev)
             prev_dev = (ticket, wav, names, lens)
             k += 1
             continue
-        host = pcm_pin[k & 1][: B * T * hop].view(B, T * hop)
+        host = pcm_pin[k & 1][: B * n_of(T)].view(B, n_of(T))
         host.copy_(pcm, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
@@ -272,7 +302,8 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
-                       device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time") -> Dict[str, np.ndarray]:
+                       device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
+                       sample_rate: int = 22050) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -288,7 +319,8 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     utterances, nothing is collected): each rank returns item_name -> PCM of ITS share, brought to its own host behind its own
     micro-batches; no message travels back and `src` does no work the other ranks do not do.
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
-    "frames": by frames alone (rounds 1-5)."""
+    "frames": by frames alone (rounds 1-5).
+    out_sample_rate: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate."""
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -296,7 +328,7 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     import torch.distributed as dist
     loop = int(force_collectives) if (dist.is_available() and dist.is_initialized() and dist.get_world_size() == 1) else 0
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and loop < 2):
-        return synthesize(model, items, n_steps, max_batch, seed, drop_last_frame)
+        return synthesize(model, items, n_steps, max_batch, seed, drop_last_frame, out_sample_rate=out_sample_rate, sample_rate=sample_rate)
     rank, world = dist.get_rank(), dist.get_world_size()
     meta = [None]
     if rank == src:      # the collater's view of every item: the on-disk [T', 80] rows with the last frame dropped (a view: no copy, no
@@ -310,11 +342,17 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     on_gpu = device is not None and torch.device(device).type == "cuda"
     local = [{"item_name": str(i), "mel": m, "len": m.shape[0], "uid": uids[i]} for i, m in mine]
     if gather == "none":      # the reference's own ending: this rank's waveforms on this rank's host, nothing sent back
-        pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False)
+        pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, out_sample_rate=out_sample_rate, sample_rate=sample_rate)
         return {names[i]: pcm[str(i)] for i, _ in mine}
-    pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, return_device=on_gpu)
+    pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, return_device=on_gpu, out_sample_rate=out_sample_rate,
+                     sample_rate=sample_rate)
     wavs = [(i, pcm[str(i)] if on_gpu else torch.from_numpy(pcm[str(i)])) for i, _ in mine]
-    out = shard.gather_waveforms(wavs, lens, parts, hop=model.hop_length, dst=src, device=device, dtype=torch.int16, loopback=bool(loop))
+    if out_sample_rate is None or int(out_sample_rate) == int(sample_rate):
+        sizes_of, unit = lens, model.hop_length
+    else:      # the gather sizes its messages as lens * hop: hand it the resampled sample counts with a hop of 1
+        from . import resample as _resample
+        sizes_of, unit = [_resample.out_len(t * model.hop_length, sample_rate, out_sample_rate) for t in lens], 1
+    out = shard.gather_waveforms(wavs, sizes_of, parts, hop=unit, dst=src, device=device, dtype=torch.int16, loopback=bool(loop))
     if rank != src:
         return {}
     if not on_gpu:
@@ -428,6 +466,8 @@ def main(argv=None):
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (state_dict under ['state_dict']['model'])")
     ap.add_argument("--max_batch", type=int, default=16, help="utterances per padded micro-batch (16: 6 % faster than 8 on a 64-utterance job)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--out_sample_rate", type=int, default=None, metavar="R",
+                    help="write the wavs at R Hz (e.g. 16000, 24000, 44100, 48000) instead of the model's 22050: resampled on the device, then normalised")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
@@ -446,10 +486,12 @@ def main(argv=None):
     items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.long_form:
+        if args.out_sample_rate is not None:
+            ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed)
     else:
-        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed)
-    paths = save_wavs(pcm, args.out_dir)
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate)
+    paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 
 

@@ -343,6 +343,16 @@ class FastDiff(nn.Module):
         _capi.check(lib, h, lib.fd_mel_spectrogram(h, wav.data_ptr(), B, n, mel.data_ptr(), T, self._stream(wav.device)), "fd_mel_spectrogram")
         return mel
 
+    def resample(self, x, sr_in, sr_out, valid=None, channels=1):
+        """Sample-rate conversion on the device (fastdiff_amd/resample.py; the reference's librosa.core.load(path, sr=...),
+        data_gen/tts/data_gen_utils.py:111): x [n] / [B, n], or interleaved [n, C] / [B, n, C] with channels = C, float32 / int16 /
+        int32 / uint8 as a RIFF file holds them -> float32 mono [B, out_len(n, sr_in, sr_out)].  valid: [B] frame counts of a
+        zero-padded batch; each item's result is what it gets alone, and 0 behind its own length."""
+        from . import resample as _resample
+        self._require_inference(x, x)
+        lib, h = self._ready(x.device)
+        return _resample._run(lib, h, self._stream(x.device), x, sr_in, sr_out, valid, channels)
+
     def set_mel_filterbank(self, fb, variant="pwg", device=None):
         """Use `fb` [80, 513] (numpy / tensor, float32; librosa.filters.mel's own layout) as the filter bank of front-end `variant`
         instead of the library's restated default -- what a deployment that has librosa passes

@@ -45,6 +45,53 @@ FD_API int fd_mel_spectrogram(fd_handle h, const float *wav, int B, int64_t n_sa
 FD_API int fd_set_mel_filterbank(fd_handle h, const float *fb, int n_mels, int n_bins);
 FD_API int fd_get_mel_filterbank(fd_handle h, float *fb_out, int n_mels, int n_bins);
 
+/* Sample-rate conversion around the vocoder: recordings of any rate and channel count in, waveforms of any rate out -- what the
+ * reference gets from librosa.core.load(wav_path, sr=sample_rate) at the first line of its front-end (data_gen/tts/data_gen_utils.py:111,
+ * :40-49; vocoders/pwg.py:132): down-mix to mono, resample to the model's rate.
+ *
+ * The operator.  up / down = sr_out / sr_in reduced by their gcd, q = max(up, down), half = Z q.  The prototype low-pass in double,
+ *     g[k] = sinc(rolloff (k - half) / q) * kaiser(k; 2 half + 1, beta),  k = 0 .. 2 half,  divided by its sum
+ * (= scipy.signal.firwin(2 half + 1, rolloff / q, window=("kaiser", beta))), h = up g rounded once to float32, and
+ *     y[i] = sum_j x[j] h[i down - j up + half],   x = 0 outside [0, n),   i = 0 .. n_out - 1,   n_out = ceil(n up / down)
+ * (= scipy.signal.resample_poly(x, up, down, window=g), sample for sample).  Z = 64 zero crossings, rolloff = 0.9475937167399596,
+ * beta = 14.769656459379492: the parameters resampy publishes for its "kaiser_best" filter, which the librosa of the reference's time
+ * used by default.  They are restated here, not checked against resampy / librosa (absent from the build image), and resampy
+ * interpolates a tabulated filter where this evaluates it at the exact tap positions: the same design, not the same bits.
+ * Taps per output: K = ceil((2 half + 1) / up) (48k -> 22.05k: 279; 16k -> 22.05k: 129).
+ *
+ * Summation order (fixed: an item's output is bit-identical alone, anywhere in a ragged batch, at any pitch or alignment): output i
+ * adds its products x[j] h[.] with j ASCENDING into one float32 accumulator that starts at +0, one fmaf per product; products whose x
+ * lies outside [0, n) are left out (they are exact zeros).  No atomics, no scratch of the handle.
+ *
+ * The polyphase table ([up][K rounded up to 4], every row in the order its output walks x) is built on the host in double, cached on
+ * the handle per reduced ratio and uploaded at the first use of that ratio -- never inside a stream capture, where a ratio that has
+ * not been used before is refused with FD_ERR_STATE. */
+#define FD_RESAMPLE_TILE 256      /* consecutive outputs of one item that one workgroup computes */
+#define FD_RESAMPLE_MAX_RATIO 1024 /* max(up, down) after reduction */
+enum { FD_PCM_F32 = 0, FD_PCM_S16 = 1, FD_PCM_S32 = 2, FD_PCM_U8 = 3 };
+
+/* n_out = ceil(n up / down) for n >= 0 (pure host code, no handle).  FD_ERR_INVALID: n < 0 or a rate < 1; FD_ERR_UNSUPPORTED:
+ * max(up, down) > 1024 after reduction.  Equal rates give n. */
+FD_API int64_t fd_resample_out_len(int64_t n, int sr_in, int sr_out);
+/* The float32 prototype h (2 half + 1 values; pure host code, no handle, like fd_pack_source).  Returns its length and writes the first
+ * min(capacity, length) values (taps NULL: sizes only); up / down / half receive the reduced ratio and half (each may be NULL).  Equal
+ * rates: up = down = 1, the filter a converter between two different rates would use (fd_resample itself then copies). */
+FD_API int fd_resample_taps(int sr_in, int sr_out, float *taps, int64_t capacity, int *up, int *down, int *half);
+/* src -> dst [B][out_len(n_in)] float mono at sr_out, asynchronous on `stream`, one launch per 64 items.
+ *   src        device; item b's frame j, channel c at element (b * src_pitch + j * channels + c) of the source type `format`:
+ *              FD_PCM_F32 as is, _S16 / 32768, _S32 float(v) / 2^31, _U8 (v - 128) / 128 (what librosa.core.load hands on); any alignment
+ *              the type allows
+ *   channels   1 .. 8 interleaved; summed in channel order in float32, then divided by `channels` (correctly rounded)
+ *   n_in       frames per item; src_pitch >= n_in * channels ELEMENTS between items
+ *   valid_in   HOST [B] or NULL: frames of each item that count, 1 .. n_in; its outputs behind out_len(valid_in[b]) up to out_len(n_in)
+ *              are written as 0
+ *   dst_pitch  floats between the rows of dst, >= out_len(n_in)
+ * Equal rates: conversion, down-mix and copy, no filter.
+ * FD_ERR_INVALID: a null pointer, channels outside 1..8, an unknown format, B < 1, n_in < 1, a pitch too short, valid_in[b] outside
+ * [1, n_in]; FD_ERR_UNSUPPORTED: max(up, down) > 1024.  Every refusal with a handle leaves its message in fd_last_error. */
+FD_API int fd_resample(fd_handle h, const void *src, int format, int channels, int B, int64_t n_in, int64_t src_pitch,
+                       const int64_t *valid_in, int sr_in, int sr_out, float *dst, int64_t dst_pitch, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
