@@ -75,6 +75,18 @@ def _cast_back(ctx, *grads):
     return tuple(None if g is None else g.to(t) for g, t in zip(grads, ctx.in_dtypes))
 
 
+def _flat(pairs):
+    """[a_1, b_1, a_2, b_2, ...] of the pairs (a_i, b_i): how the operators over many convolutions take their tensors (*args of apply)."""
+    return [t for pair in pairs for t in pair]
+
+
+def _out_grads(gout, shape, dev):
+    """The gradients of a node's outputs as contiguous float32 tensors; an output that took no part in the loss (None): zeros, one
+    tensor of `shape` shared by all of them."""
+    zero = torch.zeros(shape, device=dev, dtype=torch.float32) if any(t is None for t in gout) else None
+    return [(zero if t is None else t).contiguous().float() for t in gout]
+
+
 def _batch_strided(k):
     """True if k [B, Cin, Cout, ks, T] is contiguous apart from its batch stride (one layer's slice of a [B, layers, ...] tensor)."""
     _, ci, co, ks, T = k.shape
@@ -396,14 +408,7 @@ class _PredictorFronts(torch.autograd.Function):
         H = sv[2 * P + n * P:]
         B, _, T = xs[0].shape
         dev = xs[0].device
-        zero = None
-        g = []
-        for t in gout:      # a predictor whose output took no part in the loss: zeros
-            if t is None:
-                zero = torch.zeros((B, 64, T), device=dev, dtype=torch.float32) if zero is None else zero
-                t = zero
-            g.append(t.contiguous().float())
-        gtop = g
+        gtop = g = _out_grads(gout, (B, 64, T), dev)
         gs = [None] * n            # gs[j]: the gradients in front of pair j's activation (P tensors); the top pair's is masked in the kernels
         cur = g
         for j in range(n - 1, -1, -1):
@@ -441,12 +446,7 @@ def predictor_fronts(xs, input_convs, stacks, slope):
     """[leaky_relu(input_conv_p(x_p)) + stack_p(.) for p] for P predictors at once: xs = P tensors [B, 80, T]; input_convs = P pairs
     (weight [64, 80, 5], bias); stacks = P lists of n pairs (weight [64, 64, 3], bias); one launch per chain step for all P."""
     n = len(stacks[0])
-    flat = []
-    for (w, b), st in zip(input_convs, stacks):
-        flat += [w, b]
-        for wj, bj in st:
-            flat += [wj, bj]
-    return list(_PredictorFronts.apply(slope, n, *xs, *flat))
+    return list(_PredictorFronts.apply(slope, n, *xs, *_flat(pair for ic, st in zip(input_convs, stacks) for pair in (ic, *st))))
 
 
 class _KConvSide(torch.autograd.Function):
@@ -474,13 +474,7 @@ class _KConvSide(torch.autograd.Function):
         B, _, T = xs[0].shape
         M = ws[0].shape[0]
         dev = xs[0].device
-        zero = None
-        g = []
-        for t in gout:
-            if t is None:
-                zero = torch.zeros((B, M, T), device=dev, dtype=torch.float32) if zero is None else zero
-                t = zero
-            g.append(t.contiguous().float())
+        g = _out_grads(gout, (B, M, T), dev)
         DX = torch.empty((P, B, 64, T), device=dev, dtype=torch.float32) if any(ctx.needs_input_grad[:P]) else None
         if DX is not None:
             _call(dev, "fd_kconv_backward_x_multi", "fd_kconv_backward_x_multi", P, None, ws, None, g, B, M, T, 1.0, 1.0, DX.unbind(0))
@@ -496,19 +490,13 @@ class _KConvSide(torch.autograd.Function):
 def kernel_conv1d_side_by_side(xs, weights, biases):
     """[conv1d(x_p, w_p, b_p, padding=1) for p] for P <= 8 inputs [B, 64, T] and weights [M, 64, 3] of one shape (M <= 512), one launch
     per kernel for all P."""
-    flat = []
-    for w, b in zip(weights, biases):
-        flat += [w, b]
-    return list(_KConvSide.apply(*xs, *flat))
+    return list(_KConvSide.apply(*xs, *_flat(zip(weights, biases))))
 
 
 def kernel_conv_stack(x, weights, biases, slope):
     """leaky_relu(conv1d(., w_j, b_j, padding=1), slope) applied n times in a row to x [B, 64, T] (every w_j [64, 64, 3]) as one
     differentiable HIP operator: the predictor's residual stack without its Dropout(p = 0) modules."""
-    params = []
-    for w, b in zip(weights, biases):
-        params += [w, b]
-    return _KConvStack.apply(x, slope, *params)
+    return _KConvStack.apply(x, slope, *_flat(zip(weights, biases)))
 
 
 class _Conv7(torch.autograd.Function):
@@ -675,10 +663,7 @@ class _WeightNormAll(torch.autograd.Function):
 def weight_norm_all(pairs):
     """[torch._weight_norm(v, g, 0) for (v, g) in pairs] for float32 HIP tensors, all in one differentiable operator (one or two
     launches each way whatever the number of tensors)."""
-    flat = []
-    for v, g in pairs:
-        flat += [v, g]
-    return list(_WeightNormAll.apply(*flat))
+    return list(_WeightNormAll.apply(*_flat(pairs)))
 
 
 class _Conv32(torch.autograd.Function):

@@ -28,10 +28,7 @@ class PhiStep(TrainStep):
     def __init__(self, model, predictor, diffusion_hyperparams, lr=2e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, clip_grad_norm=1.0,
                  seed=0, *, corpus=None, batch_size=None, rank=0, world_size=1):
         self.model, self.predictor = model, predictor
-        self.params = list(predictor.parameters())
-        if not self.params or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params):
-            raise RuntimeError("fastdiff_amd.PhiStep needs the predictor's parameters as contiguous float32 tensors on a HIP device (no CPU fallback)")
-        self.device = self.params[0].device
+        self._init_optimizer(list(predictor.parameters()), lr, betas, eps, weight_decay, clip_grad_norm)
         if any(p.device != self.device for p in model.parameters()):
             raise RuntimeError(f"PhiStep: the denoiser and the predictor must lie on one device ({self.device})")
         dh = diffusion_hyperparams
@@ -40,28 +37,9 @@ class PhiStep(TrainStep):
             raise ValueError(f"PhiStep: T={self.T_train} must exceed 2 tau={2 * self.tau}")
         self.alpha = dh["alpha"].detach().to(self.device, torch.float32).contiguous()
         self.seed = int(seed)
-        self.hyper = dict(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), weight_decay=float(weight_decay),
-                          max_norm=float(clip_grad_norm or 0.0))
-        self._hyper_dev = torch.zeros(6, dtype=torch.float64, device=self.device)      # fd_adamw_hyper
-        self._write_hyper()
-        self._state = lvc_op.new_train_state(self.device)                               # fd_train_state
-        self._state_loss = self._state.view(torch.float32)[7:8]                         # its `loss` field
-        sizes = [p.numel() for p in self.params]
-        self._m, self._v = (torch.zeros(sum(sizes), device=self.device, dtype=torch.float32) for _ in range(2))
-        self.exp_avg = [t.view(p.shape) for t, p in zip(self._m.split(sizes), self.params)]
-        self.exp_avg_sq = [t.view(p.shape) for t, p in zip(self._v.split(sizes), self.params)]
-        self.ema = None
-        self._key = self.loss = None
-        self.corpus, self.batch_size, self.rank, self.world_size, self.picked = corpus, None, int(rank), int(world_size), None
-        if corpus is not None:
-            if batch_size is None or int(batch_size) < 1:
-                raise ValueError("PhiStep: a corpus needs batch_size")
-            if corpus.device != self.device:
-                raise RuntimeError(f"PhiStep: the corpus lies on {corpus.device}, the modules on {self.device} (corpus.to(device) uploads it)")
-            if not 0 <= self.rank < self.world_size:
-                raise ValueError(f"PhiStep: rank={rank} of world_size={world_size}")
-            self.batch_size = int(batch_size)
-            self.picked = torch.zeros((self.batch_size, 2), dtype=torch.int64, device=self.device)
+        self._state_loss = self._state.view(torch.float32)[7:8]                         # the `loss` field of the fd_train_state
+        self.ema = None                                                                  # (no average: state_dict() asks)
+        self._init_batch_source(corpus, batch_size, rank, world_size)
         self.mel = self.wav = self.draw = None      # the buffers of the current batch shape
 
     def _prepare(self, mel_shape, wav_shape):
@@ -81,22 +59,12 @@ class PhiStep(TrainStep):
         loss as a device tensor and does not synchronise.  No parameter of the denoiser is written."""
         if not torch.is_grad_enabled():
             raise RuntimeError("PhiStep.step needs gradients enabled")
-        collate = mels is None and wavs is None
-        if collate:
-            if self.corpus is None:
-                raise RuntimeError("PhiStep.step() without a batch needs a PhiStep built with corpus= and batch_size=")
-            B, F = self.batch_size, self.corpus.frames
-            shapes = ((B, 80, F), (B, 1, F * self.corpus.hop_size))
-        elif mels is None or wavs is None:
-            raise TypeError("PhiStep.step: mels and wavs, or neither")
-        else:
-            shapes = (tuple(mels.shape), tuple(wavs.shape))
+        collate, shapes = self._batch_of(mels, wavs)
         if shapes != self._key:
             self._prepare(*shapes)
             self._key = shapes
         if collate:
-            lvc_op.train_collate(self.corpus, self.batch_size, seed=self.seed, state=self._state, rank=self.rank, world_size=self.world_size,
-                                 out=(self.mel, self.wav, self.picked))
+            self._collate()
         else:
             self.mel.copy_(mels, non_blocking=True)
             self.wav.copy_(wavs, non_blocking=True)

@@ -38,14 +38,26 @@ class TrainStep:
     def __init__(self, model, diffusion_hyperparams, lr=2e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, clip_grad_norm=1.0, seed=0,
                  graph=True, *, ema_decay=None, ema_warmup=True, corpus=None, batch_size=None, rank=0, world_size=1):
         self.model = model
-        self.params = list(model.parameters())
-        if not self.params or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params):
-            raise RuntimeError("fastdiff_amd.TrainStep needs the module's parameters as contiguous float32 tensors on a HIP device (no CPU fallback)")
-        self.device = self.params[0].device
+        self._init_optimizer(list(model.parameters()), lr, betas, eps, weight_decay, clip_grad_norm)
         self.T_train = int(diffusion_hyperparams["T"])
         self.alpha = diffusion_hyperparams["alpha"].detach().to(self.device, torch.float32).contiguous()
         self.seed = int(seed)
         self.use_graph = bool(graph)
+        self._graph = None
+        self._init_batch_source(corpus, batch_size, rank, world_size)
+        self.mel = self.wav = self.x_t = self.z = self.steps = None      # the static buffers of the current batch shape
+        # the average of the parameters (None: off, and no launch of the step is about it)
+        self.ema = None
+        if ema_decay is not None:
+            from .ema import ParamEMA
+            self.ema = ParamEMA(model, decay=ema_decay, warmup=ema_warmup)
+
+    def _init_optimizer(self, params, lr, betas, eps, weight_decay, clip_grad_norm):
+        """AdamW's state over `params` on their device: the hyper-parameters, the fd_train_state, zeroed moments in two flat buffers."""
+        self.params = params
+        if not self.params or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params):
+            raise RuntimeError(f"fastdiff_amd.{type(self).__name__} needs its parameters as contiguous float32 tensors on a HIP device (no CPU fallback)")
+        self.device = self.params[0].device
         self.hyper = dict(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), weight_decay=float(weight_decay),
                           max_norm=float(clip_grad_norm or 0.0))
         self._hyper_dev = torch.zeros(6, dtype=torch.float64, device=self.device)      # fd_adamw_hyper
@@ -55,24 +67,21 @@ class TrainStep:
         self._m, self._v = (torch.zeros(sum(sizes), device=self.device, dtype=torch.float32) for _ in range(2))
         self.exp_avg = [t.view(p.shape) for t, p in zip(self._m.split(sizes), self.params)]
         self.exp_avg_sq = [t.view(p.shape) for t, p in zip(self._v.split(sizes), self.params)]
-        self._key = self._graph = self.loss = None
-        # the batch source of step(): rank / world_size only shape the plan (corpus.plan), the step itself stays single-process
+
+    def _init_batch_source(self, corpus, batch_size, rank, world_size):
+        """The batch source of step(): rank / world_size only shape the plan (corpus.plan), the step itself stays single-process."""
+        name = type(self).__name__
+        self._key = self.loss = None      # the batch shape the buffers are for; the last loss
         self.corpus, self.batch_size, self.rank, self.world_size, self.picked = corpus, None, int(rank), int(world_size), None
         if corpus is not None:
             if batch_size is None or int(batch_size) < 1:
-                raise ValueError("TrainStep: a corpus needs batch_size")
+                raise ValueError(f"{name}: a corpus needs batch_size")
             if corpus.device != self.device:
-                raise RuntimeError(f"TrainStep: the corpus lies on {corpus.device}, the module on {self.device} (corpus.to(device) uploads it)")
+                raise RuntimeError(f"{name}: the corpus lies on {corpus.device}, the parameters on {self.device} (corpus.to(device) uploads it)")
             if not 0 <= self.rank < self.world_size:
-                raise ValueError(f"TrainStep: rank={rank} of world_size={world_size}")
+                raise ValueError(f"{name}: rank={rank} of world_size={world_size}")
             self.batch_size = int(batch_size)
             self.picked = torch.zeros((self.batch_size, 2), dtype=torch.int64, device=self.device)      # (item, start frame) of the last batch
-        self.mel = self.wav = self.x_t = self.z = self.steps = None      # the static buffers of the current batch shape
-        # the average of the parameters (None: off, and no launch of the step is about it)
-        self.ema = None
-        if ema_decay is not None:
-            from .ema import ParamEMA
-            self.ema = ParamEMA(model, decay=ema_decay, warmup=ema_warmup)
 
     # ---- hyper-parameters and state ------------------------------------------------------------------------------------------------
     def _write_hyper(self):
@@ -192,6 +201,18 @@ class TrainStep:
         torch.cuda.current_stream(self.device).wait_stream(side)
         self.model.zero_grad(set_to_none=True)
 
+    def _batch_of(self, mels, wavs):
+        """(collate, (mel shape, wav shape)): which batch this call of step() is on -- cut from the corpus, or the caller's."""
+        name = type(self).__name__
+        if mels is None and wavs is None:
+            if self.corpus is None:
+                raise RuntimeError(f"{name}.step() without a batch needs a {name} built with corpus= and batch_size=")
+            B, F = self.batch_size, self.corpus.frames
+            return True, ((B, 80, F), (B, 1, F * self.corpus.hop_size))
+        if mels is None or wavs is None:
+            raise TypeError(f"{name}.step: mels and wavs, or neither")
+        return False, (tuple(mels.shape), tuple(wavs.shape))
+
     def _prepare(self, mel_shape, wav_shape):
         B, L = wav_shape[0], wav_shape[-1]
         if len(wav_shape) != 3 or wav_shape[1] != 1 or L % 4 != 0:
@@ -209,16 +230,7 @@ class TrainStep:
         frames, corpus.plan(state()["iter"], batch_size, seed, rank, world_size) says the same beforehand): a replay and nothing else."""
         if not (self.model.training and torch.is_grad_enabled()):
             raise RuntimeError("TrainStep.step needs the module in train() mode and gradients enabled")
-        collate = mels is None and wavs is None
-        if collate:
-            if self.corpus is None:
-                raise RuntimeError("TrainStep.step() without a batch needs a TrainStep built with corpus= and batch_size=")
-            B, F = self.batch_size, self.corpus.frames
-            shapes = ((B, 80, F), (B, 1, F * self.corpus.hop_size))
-        elif mels is None or wavs is None:
-            raise TypeError("TrainStep.step: mels and wavs, or neither")
-        else:
-            shapes = (tuple(mels.shape), tuple(wavs.shape))
+        collate, shapes = self._batch_of(mels, wavs)
         key = shapes + (collate,)
         if key != self._key:
             self._prepare(*shapes)

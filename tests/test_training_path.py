@@ -101,16 +101,19 @@ def test_inference_entry_points_still_refuse_autograd_inputs_on_cpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("frames", [True, False])
-def test_training_step_on_the_hip_operator_matches_the_reference_backward(monkeypatch, frames):
-    """frames: kernel_conv hands the LVC operator its frame-major operands directly (the product path); False: through the reference's
-    [B, layers, 32, 64, 3, T] tensor -- same kernels plus the transposes, kept for A/B runs (module._train_frames)."""
+@pytest.mark.parametrize("off", [None, "frames", "fuse_act", "skip_fan", "stack", "wn_all", "fronts"])
+def test_training_step_on_the_hip_operator_matches_the_reference_backward(monkeypatch, off):
+    """off: the one switch of the product path set to False (module._train_<off>: that piece runs as its predecessor, kept for A/B
+    runs), None: the product path as it ships.  frames on: kernel_conv hands the LVC operator its frame-major operands directly; off:
+    through the reference's [B, layers, 32, 64, 3, T] tensor -- same kernels plus the transposes."""
     import fastdiff_amd
     from fastdiff_amd import sampler
     g = load_golden("theta_grad")
     sched = load_golden("schedule")
     m = _module().cuda().train()
-    m._train_frames = frames
+    frames = off != "frames"
+    if off is not None:
+        setattr(m, "_train_" + off, False)
     monkeypatch.setattr(sampler, "std_normal", lambda size: torch.from_numpy(g["z"].copy()).view(*size).cuda())
     monkeypatch.setattr(torch, "randint", lambda *a, **k: torch.from_numpy(g["ts"].copy()))
     dh = {"T": 1000, "alpha": torch.from_numpy(sched["train_alpha"]).cuda()}
