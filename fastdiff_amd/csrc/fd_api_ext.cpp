@@ -1,5 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h: the mel front-end in front of the vocoder and the int16
-// waveform epilogue behind it, sample-rate conversion in front of and behind both (fd_resample), taps, layout
+// waveform epilogue behind it, sample-rate conversion (fd_resample) and BS.1770 loudness (fd_loudness_*) in
+// front of and behind both, taps, layout
 // introspection, counters and per-kernel profiling.
 #include <math.h>
 #include <stddef.h>
@@ -270,6 +271,81 @@ int fd_resample(fd_handle h, const void *src, int format, int channels, int B, i
     const hipError_t e = fdk::resample(L, src, format, channels, B, n_in, src_pitch, valid_in, r.up, r.down, r.half, r.K, r.Kp, n_out, table, dst, dst_pitch);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_resample: %s", hipGetErrorString(e));
     return FD_OK;
+}
+
+// BS.1770 loudness (fastdiff_hip_ext.h; the filter design: fd_loudness.h, the kernels: fd_kernels_loudness.hip) ------------------------
+int fd_loudness_design(int rate, double *coef10)
+{
+    if (!coef10 || !fdl::rate_ok(rate)) return FD_ERR_INVALID;
+    fdl::design(rate, coef10);
+    return FD_OK;
+}
+
+int64_t fd_loudness_blocks(int64_t n, int rate)
+{
+    if (n < 0 || !fdl::rate_ok(rate)) return FD_ERR_INVALID;
+    return fdl::blocks(n, rate);
+}
+
+static int loudness_call(fd_handle h, const char *who, const float *wav, int B, int64_t L, const int64_t *valid, int rate, bool normalize,
+                         double target, float *out_f32, int16_t *out_pcm, fd_loudness *rec_dev, void *stream)
+{
+    if (!h) return FD_ERR_INVALID;
+    if (!wav) FD_FAIL(h, FD_ERR_INVALID, "%s: null wav", who);
+    if (B < 1 || B > 4096 || L < 1 || L > ((int64_t)1 << 40)) FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d utterances (1 .. 4096) of L = %lld samples", who, B, (long long)L);
+    if (!fdl::rate_ok(rate)) FD_FAIL(h, FD_ERR_INVALID, "%s: sample rate %d outside %d .. %d", who, rate, fdl::RATE_MIN, fdl::RATE_MAX);
+    if (normalize && !out_f32 && !out_pcm) FD_FAIL(h, FD_ERR_INVALID, "%s: neither out_f32 nor out_pcm", who);
+    if (normalize && !isfinite(target)) FD_FAIL(h, FD_ERR_INVALID, "%s: the target is not finite", who);
+    if (!normalize && !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null rec_dev", who);
+    if (valid)
+        for (int b = 0; b < B; ++b)
+            if (valid[b] < 1 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [1, %lld]", who, b, (long long)valid[b], (long long)L);
+    FD_HIP(h, hipSetDevice(h->device));
+    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the peak epilogue: provisional with a lazily checked call
+    if (rc != FD_OK) return rc;
+    const size_t need = fdk::loudness_scratch_bytes(B, L, rate);
+    Scratch &s = h->loud_scratch;
+    if (s.bytes < need) {      // grown at the first call that needs more; hipFree waits for the calls that still use the old one
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes for B = %d, L = %lld, which cannot happen inside a stream capture: call it once before",
+                    who, need, B, (long long)L);
+        }
+        if (s.p) FD_HIP(h, hipFree(s.p));
+        s = Scratch{};
+        void *p = nullptr;
+        FD_HIP(h, hipMalloc(&p, need));
+        s.p = static_cast<float *>(p);
+        s.bytes = need;
+    }
+    const long long *valid_dev = nullptr;
+    if (valid) {
+        fd_context::StageSlot *sl = nullptr;
+        if ((rc = fd_stage_acquire(h, sizeof(long long) * B, &sl)) != FD_OK) return rc;
+        for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = valid[b];
+        long long *dst = fdk::loudness_valid_slot(s.p, B, L, rate);
+        FD_HIP(h, hipMemcpyAsync(dst, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, (hipStream_t)stream));
+        if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
+        valid_dev = dst;
+    }
+    fdk::LoudnessFilter F;
+    fdl::make_filter(rate, F);
+    fdk::Launch La = {h, (hipStream_t)stream, false};
+    const hipError_t e = fdk::loudness(La, wav, B, L, valid_dev, rate, F, normalize, target, rec_dev, out_f32, out_pcm, s.p);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FD_OK;
+}
+
+int fd_loudness_measure(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, fd_loudness *rec_dev, void *stream)
+{
+    return loudness_call(h, "fd_loudness_measure", wav, B, L, valid, rate, false, 0.0, nullptr, nullptr, rec_dev, stream);
+}
+
+int fd_loudness_normalize(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, double target_lufs, float *out_f32,
+                          int16_t *out_pcm, fd_loudness *rec_dev, void *stream)
+{
+    return loudness_call(h, "fd_loudness_normalize", wav, B, L, valid, rate, true, target_lufs, out_f32, out_pcm, rec_dev, stream);
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

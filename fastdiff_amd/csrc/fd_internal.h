@@ -11,6 +11,7 @@
 #include "../../include/fastdiff_hip.h"
 #include "../../include/fastdiff_hip_ext.h"
 #include "../../include/fastdiff_hip_train.h"
+#include "fd_loudness.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -368,6 +369,7 @@ struct fd_context {
     Scratch span_scratch;                    // a window batch of fd_sample_span / fd_sample_spans: window records, mel, injected x_T / z, x_0
     Scratch ring_scratch;                    // fd_mel_ring_append's chunk records
     long long n_span_batches = 0, n_span_windows = 0;   // fd_get_counter: fd_sample calls / windows made by the span entry points
+    Scratch loud_scratch;                    // fd_loudness_measure / _normalize: peak words, lengths, tile states, partial sums, block powers
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -464,6 +466,15 @@ constexpr int RESAMPLE_ITEMS = 64;
 struct ResampleLens { long long v[RESAMPLE_ITEMS]; };
 hipError_t resample(const Launch &L, const void *src, int format, int C, int B, int64_t n_in, int64_t src_pitch, const int64_t *valid,
                     int up, int down, int half, int K, int Kp, int64_t n_out_max, const float *table, float *dst, int64_t dst_pitch);
+// fd_loudness_measure / fd_loudness_normalize (fd_kernels_loudness.hip).  scratch: loudness_scratch_bytes(B, L, rate) bytes of the handle's
+// loudness buffer; valid_dev: null or loudness_valid_slot() of that buffer, filled by the caller; rec: device [B] or null (a slot of the
+// buffer); the filter and its powers (csrc/fd_loudness.h) are kernel arguments.
+constexpr int LOUDNESS_SEGS = 24;      // 100 ms segments a tile can touch: 16384 / 799 + 2 at the lowest rate, 8000 Hz
+using LoudnessFilter = fdl::Filter;
+size_t loudness_scratch_bytes(int B, int64_t L, int rate);
+long long *loudness_valid_slot(void *scratch, int B, int64_t L, int rate);
+hipError_t loudness(const Launch &L_, const float *wav, int B, int64_t L, const long long *valid_dev, int rate, const LoudnessFilter &F,
+                    bool normalize, double target, fd_loudness *rec, float *out_f32, int16_t *out_pcm, void *scratch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

@@ -16,7 +16,8 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
 Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
-(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--out_sample_rate R]`).
+(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
+[--loudness LUFS]`).
 """
 import argparse
 import glob
@@ -76,19 +77,41 @@ def wav_to_device(model, pcm: np.ndarray, sr: int, sample_rate: int = 22050, wha
     return model.resample(raw, sr, sample_rate, channels=1 if pcm.ndim == 1 else pcm.shape[1])[0]
 
 
-def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg") -> List[dict]:
+LOUD_NORM_LUFS = -22.0      # process_utterance(loud_norm=True): pyln.normalize.loudness(wav, loudness, -22.0) (data_gen_utils.py:118)
+
+
+def loud_norm_wav(model, wav: torch.Tensor, sample_rate: int = 22050, what: str = "wav") -> torch.Tensor:
+    """The loud_norm branch of process_utterance (data_gen/tts/data_gen_utils.py:115-120) on a device waveform [n]: normalised to
+    -22 LUFS in float32, or divided by its new peak where that would exceed 1.  Shorter than one 400 ms block: ValueError, as
+    pyloudnorm raises; nothing to measure (silence): left unchanged, with a warning."""
+    from . import loudness as _loudness
+    y, rec = model.loudness_normalize(wav, LOUD_NORM_LUFS, sample_rate=sample_rate, out="float", return_record=True)
+    status = int(rec["status"][0])
+    if status == _loudness.SHORT:
+        raise ValueError(f"{what}: {wav.shape[-1]} samples at {sample_rate} Hz are shorter than one 400 ms block: loudness cannot be measured")
+    if status == _loudness.SILENT:
+        import warnings
+        warnings.warn(f"{what}: no block passes the loudness gates (silence?): left as it is", stacklevel=2)
+    return y
+
+
+def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg", loud_norm: bool = False) -> List[dict]:
     """Copy-synthesis inputs (`test_input_dir` with recordings, tasks/vocoder/dataset_utils.py:162-184): every *.wav below the
     directory, in sorted order, through the device mel front-end (`FastDiff.mel_spectrogram` = process_utterance of
     data_gen/tts/data_gen_utils.py:93-147, or with mel_variant="tacotron" the TacotronSTFT of vocoder_binarizer_tacotron.py:110-116
     for models trained on FastDiff_tacotron.yaml features).  Integer PCM is scaled by its full range as librosa.core.load does
     (pcm_to_float).  A recording at another rate, or with several channels, first goes through the device resampler as the file holds
     it (FastDiff.resample: sample type, down-mix and rate in one launch -- librosa.core.load(path, sr=sample_rate),
-    data_gen_utils.py:111); a mono recording at the model's rate takes the direct path, bit for bit as before."""
+    data_gen_utils.py:111); a mono recording at the model's rate takes the direct path, bit for bit as before.
+    loud_norm: the reference's `loud_norm: true` configurations -- every recording is brought to -22 LUFS before its mel is taken
+    (loud_norm_wav: FastDiff.loudness_normalize)."""
     from scipy.io import wavfile
     items = []
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
         sr, pcm = wavfile.read(path)
         wav = wav_to_device(model, pcm, sr, sample_rate, path)
+        if loud_norm:
+            wav = loud_norm_wav(model, wav, sample_rate, path)
         mel = model.mel_spectrogram(wav, variant=mel_variant)[0].transpose(0, 1).contiguous().cpu()      # [T, 80] as on disk
         items.append({"item_name": path[len(test_input_dir) + 1:].replace("/", "_"), "mel": mel, "len": mel.shape[0]})
     return items
@@ -194,7 +217,7 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
-               sample_rate: int = 22050) -> Dict[str, np.ndarray]:
+               sample_rate: int = 22050, loudness: float = None) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
@@ -204,7 +227,11 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     synthesize_sharded hands to the RCCL gather).  sort=False: micro-batches in the order of arrival instead of longest first.
     out_sample_rate = R (None: the model's `sample_rate`, every byte as without the argument): the float waveform of each micro-batch is
     resampled on the device (FastDiff.resample, ragged: valid = lens * hop) and THEN peak-normalised over its out_len(lens * hop) samples,
-    so the filter's overshoot cannot clip; an item's PCM is what it would get alone."""
+    so the filter's overshoot cannot clip; an item's PCM is what it would get alone.
+    loudness = LUFS (None: peak normalisation, every byte as without the argument): the loudness epilogue instead of the peak epilogue
+    (FastDiff.loudness_normalize, out="int16"): every utterance is measured as it is delivered -- after the resampling, at that rate,
+    over its own samples -- and scaled to that BS.1770 loudness; one that cannot be measured, or that the gain would clip, is
+    peak-normalised as before."""
     from . import resample as _resample
     R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
@@ -217,11 +244,16 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     hop = model.hop_length
     n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
 
+    def to_pcm(wav, valid, rate):
+        if loudness is None:
+            return model.peak_normalize_int16(wav, valid=valid)
+        return model.loudness_normalize(wav.reshape(wav.shape[0], -1), float(loudness), valid=valid, sample_rate=rate, out="int16")
+
     def epilogue(wav, lens):
         if R is None:
-            return model.peak_normalize_int16(wav, valid=[t * hop for t in lens])
+            return to_pcm(wav, [t * hop for t in lens], sample_rate)
         y = model.resample(wav.reshape(wav.shape[0], -1), sample_rate, R, valid=[t * hop for t in lens])
-        return model.peak_normalize_int16(y, valid=[n_of(t) for t in lens])
+        return to_pcm(y, [n_of(t) for t in lens], R)
 
     on_device = isinstance(items[0]["mel"], torch.Tensor) and items[0]["mel"].is_cuda
     t_max, b_max = max(lengths), min(max_batch, len(items))
@@ -303,7 +335,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
-                       sample_rate: int = 22050) -> Dict[str, np.ndarray]:
+                       sample_rate: int = 22050, loudness: float = None) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -320,7 +352,7 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     micro-batches; no message travels back and `src` does no work the other ranks do not do.
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
     "frames": by frames alone (rounds 1-5).
-    out_sample_rate: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate."""
+    out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate."""
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -328,7 +360,7 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     import torch.distributed as dist
     loop = int(force_collectives) if (dist.is_available() and dist.is_initialized() and dist.get_world_size() == 1) else 0
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and loop < 2):
-        return synthesize(model, items, n_steps, max_batch, seed, drop_last_frame, out_sample_rate=out_sample_rate, sample_rate=sample_rate)
+        return synthesize(model, items, n_steps, max_batch, seed, drop_last_frame, out_sample_rate=out_sample_rate, sample_rate=sample_rate, loudness=loudness)
     rank, world = dist.get_rank(), dist.get_world_size()
     meta = [None]
     if rank == src:      # the collater's view of every item: the on-disk [T', 80] rows with the last frame dropped (a view: no copy, no
@@ -342,10 +374,10 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     on_gpu = device is not None and torch.device(device).type == "cuda"
     local = [{"item_name": str(i), "mel": m, "len": m.shape[0], "uid": uids[i]} for i, m in mine]
     if gather == "none":      # the reference's own ending: this rank's waveforms on this rank's host, nothing sent back
-        pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, out_sample_rate=out_sample_rate, sample_rate=sample_rate)
+        pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, out_sample_rate=out_sample_rate, sample_rate=sample_rate, loudness=loudness)
         return {names[i]: pcm[str(i)] for i, _ in mine}
     pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, return_device=on_gpu, out_sample_rate=out_sample_rate,
-                     sample_rate=sample_rate)
+                     sample_rate=sample_rate, loudness=loudness)
     wavs = [(i, pcm[str(i)] if on_gpu else torch.from_numpy(pcm[str(i)])) for i, _ in mine]
     if out_sample_rate is None or int(out_sample_rate) == int(sample_rate):
         sizes_of, unit = lens, model.hop_length
@@ -410,11 +442,13 @@ LONG_FORM_GROUP_FRAMES = 1 << 16      # mel frames per sample_long_batch call: 6
 
 
 def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
-                    diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES) -> Dict[str, np.ndarray]:
+                    diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES, loudness: float = None,
+                    sample_rate: int = 22050) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM through FastDiff.sample_long_batch (windowed: any length, device memory of one window batch): the
     utterances are taken in order in groups of up to group_frames mel frames, so their outputs fit, and the windows of a group share the
     sampler's batches.  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same,
-    byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110)."""
+    byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
+    loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is."""
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -425,7 +459,11 @@ def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 
             wavs = model.sample_long_batch([m for _, _, m in group], rows, ddim=False, seed=seed, stream_ids=[u for _, u, _ in group],
                                            window_frames=window_frames)
         for (name, _, m), wav in zip(group, wavs):
-            out[name] = model.peak_normalize_int16(wav)[0, : m.shape[-1] * hop].cpu().numpy()
+            if loudness is None:
+                pcm = model.peak_normalize_int16(wav)
+            else:
+                pcm = model.loudness_normalize(wav.reshape(1, -1), float(loudness), sample_rate=sample_rate, out="int16")
+            out[name] = pcm[0, : m.shape[-1] * hop].cpu().numpy()
 
     for i, it in enumerate(items):
         c = torch.as_tensor(it["mel"])
@@ -468,6 +506,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--out_sample_rate", type=int, default=None, metavar="R",
                     help="write the wavs at R Hz (e.g. 16000, 24000, 44100, 48000) instead of the model's 22050: resampled on the device, then normalised")
+    ap.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                    help="normalise every wav to this BS.1770 integrated loudness (e.g. -23) on the device instead of to its peak; an utterance "
+                         "too short or too quiet to measure, or that the gain would clip, is peak-normalised")
+    ap.add_argument("--loud_norm", action="store_true",
+                    help="with --from_wav: bring every recording to -22 LUFS before its mel is taken (the reference's loud_norm: true)")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
@@ -483,14 +526,14 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"]["model"], strict=True)
     if args.mel_basis:
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
-    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
-        pcm = synthesize_long(model, mine, args.N, args.seed)
+        pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
-        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate)
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness)
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 

@@ -353,6 +353,27 @@ class FastDiff(nn.Module):
         lib, h = self._ready(x.device)
         return _resample._run(lib, h, self._stream(x.device), x, sr_in, sr_out, valid, channels)
 
+    def loudness(self, wav, valid=None, sample_rate=22050):
+        """BS.1770 integrated loudness on the device (fastdiff_amd/loudness.py; the reference's pyloudnorm.Meter(rate), data_gen/tts/
+        data_gen_utils.py:115-117): wav [n] / [B, n] / [B, 1, n] float32 -> a dict of numpy arrays over the batch: lufs, gain (1 here),
+        peak, blocks, gated, status (loudness.OK / SHORT / SILENT / CLIPPED).  valid: [B] sample counts of a padded batch.  Synchronises
+        once, for the records."""
+        from . import loudness as _loudness
+        self._require_inference(wav, wav)
+        lib, h = self._ready(wav.device)
+        return _loudness._measure(lib, h, self._stream(wav.device), wav, valid, sample_rate)
+
+    def loudness_normalize(self, wav, target, valid=None, sample_rate=22050, out="float", return_record=False):
+        """wav scaled to `target` LUFS on the device (pyloudnorm.normalize.loudness with the reference's guard, data_gen_utils.py:118-120):
+        out="float": float32 in the shape of wav; out="int16": PCM [B, n] = (int16)(wav gain 32767).  An utterance that cannot be
+        measured (SHORT, SILENT) or whose peak the gain would push over 1 (CLIPPED) is peak-normalised instead in int16 mode, bit for bit
+        as peak_normalize_int16 does it; in float mode it is left unchanged (SHORT, SILENT) or divided by its peak (CLIPPED).
+        return_record: (output, record as FastDiff.loudness returns it, with the gain applied); without it nothing synchronises."""
+        from . import loudness as _loudness
+        self._require_inference(wav, wav)
+        lib, h = self._ready(wav.device)
+        return _loudness._normalize(lib, h, self._stream(wav.device), wav, target, valid, sample_rate, out, return_record)
+
     def set_mel_filterbank(self, fb, variant="pwg", device=None):
         """Use `fb` [80, 513] (numpy / tensor, float32; librosa.filters.mel's own layout) as the filter bank of front-end `variant`
         instead of the library's restated default -- what a deployment that has librosa passes

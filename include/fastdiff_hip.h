@@ -149,7 +149,7 @@ FD_API int fd_sample(fd_handle h, const float *mel, int B, int T, const int *len
  *                                the last 16 redone calls report 0).
  * The next fd_sample (schedules of up to 8 steps) enqueues its own work first and looks at the previous call's flags afterwards, so
  * the host's wait falls on a busy GPU.  fd_forward, fd_commit_weights, fd_set_option, fd_read_tap and fd_destroy settle a pending
- * call first; fd_peak_normalize_int16[_ragged] and fd_mel_spectrogram do not.  Schedules longer than 8 steps are checked every 8
+ * call first; fd_peak_normalize_int16[_ragged], fd_loudness_measure / _normalize, fd_resample and fd_mel_spectrogram do not.  Schedules longer than 8 steps are checked every 8
  * steps inside fd_sample in either mode.  Without the option, and with fallback = "graph", nothing is ever pending: fd_sample_check and
  * fd_sample_settle return 0. */
 FD_API int fd_sample_check(fd_handle h);

@@ -92,6 +92,72 @@ FD_API int fd_resample_taps(int sr_in, int sr_out, float *taps, int64_t capacity
 FD_API int fd_resample(fd_handle h, const void *src, int format, int channels, int B, int64_t n_in, int64_t src_pitch,
                        const int64_t *valid_in, int sr_in, int sr_out, float *dst, int64_t dst_pitch, void *stream);
 
+/* BS.1770 loudness: measure a waveform's integrated loudness and normalise it to a target, on the device -- the level control behind the
+ * vocoder next to the peak epilogue, and the reference's process_utterance(loud_norm=True) in front of the mel
+ * (data_gen/tts/data_gen_utils.py:115-120: pyloudnorm.Meter(rate) with its defaults, one channel, -22 LUFS; :42-47: -20 LUFS).
+ *
+ * The measurement.  K-weighting = two biquads in series, RBJ forms divided by a0, w0 = 2 pi fc / rate, alpha = sin w0 / (2 Q):
+ *   high shelf  G = 4 dB, Q = 1/sqrt 2, fc = 1500, A = 10^(G/40), c = cos w0, s = 2 sqrt(A) alpha:
+ *     b = [A((A+1)+(A-1)c+s), -2A((A-1)+(A+1)c), A((A+1)+(A-1)c-s)],  a = [(A+1)-(A-1)c+s, 2((A-1)-(A+1)c), (A+1)-(A-1)c-s]
+ *   high pass   Q = 0.5, fc = 38:  b = [(1+c)/2, -(1+c), (1+c)/2],  a = [1+alpha, -2c, 1-alpha]
+ * from zero state.  These are pyloudnorm's filters, NOT the 48 kHz coefficient table of ITU-R BS.1770: a full-scale 997 Hz sine reads
+ * -3.052 / -3.066 / -3.083 LUFS at 48000 / 22050 / 16000 Hz where the ITU table gives -3.01.  The reference depends on pyloudnorm, so
+ * that is what is followed.  Blocks of T_g = 0.4 s every 0.1 s: nb = int(round((n / rate - 0.4) / 0.1) + 1) (round half to even),
+ * block j = samples [int(0.4 (0.25 j) rate), int(0.4 (0.25 j + 1) rate)) cut to n, z_j = sum y^2 / (0.4 rate),
+ * l_j = -0.691 + 10 log10 z_j.  Absolute gate J = {l_j >= -70}; relative threshold = -0.691 + 10 log10(mean_J z) - 10;
+ * J' = {l_j > threshold and l_j > -70}; LUFS = -0.691 + 10 log10(mean_J' z).  gain = 10^((target - LUFS) / 20); where peak gain > 1
+ * the reference divides by the new peak instead (:119-120), which is peak normalisation of that utterance.
+ *
+ * Status of an utterance: FD_LOUDNESS_SHORT  n < int(0.4 rate) (pyloudnorm raises), FD_LOUDNESS_SILENT  J or J' empty,
+ * FD_LOUDNESS_CLIPPED  the gain was replaced by 1 / peak, else FD_LOUDNESS_OK.
+ *
+ * The filter is a linear recurrence and is computed exactly, not with a warm-up: an utterance is cut into tiles of FD_LOUDNESS_TILE
+ * samples (one workgroup each: the grid is tiles x B, so one long waveform fills the device), a tile into 256 runs of 64 samples, one
+ * per lane.  With the cascade written as s' = A s + B x (4 states), pass 1 runs every run from zero state and combines the end states
+ * with A^64, A^128, ... A^8192 (computed on the host in double, passed by value) into the tile's zero-state end state; a carry step
+ * propagates the true state across tiles with A^16384; pass 2 runs every run again from its true incoming state and sums y^2 per
+ * 100 ms segment (block j is segments j .. j + 3: both borders are the same double expression).  The filtered signal never reaches
+ * memory.  State, powers and sums are float64.  Summation order is fixed -- a lane adds its samples in ascending order, a run that
+ * straddles a segment border gives two partials, a tile's partials are added over lanes in a fixed order, a segment's over tiles in tile
+ * order, no floating-point atomics (the peak is an atomicMax on non-negative float bits, which has no order) -- so an utterance's record
+ * and output are bit-identical alone, anywhere in a ragged batch and from call to call.  Samples behind valid[b] are never read as signal.
+ * Coefficients and powers travel as kernel arguments: nothing is uploaded, the calls can be captured (with `valid`, its B lengths go
+ * through the handle's staging ring as in fd_peak_normalize_int16_ragged).  Tile states and partial sums live in a buffer of the handle
+ * that grows at the first call that needs more -- never inside a stream capture, where such a call is refused with FD_ERR_STATE.  A
+ * graph that holds a captured call points into that buffer: capture after the largest shape has been seen, or capture again. */
+#define FD_LOUDNESS_TILE 16384      /* samples of one utterance that one workgroup filters */
+enum { FD_LOUDNESS_OK = 0, FD_LOUDNESS_SHORT = 1, FD_LOUDNESS_SILENT = 2, FD_LOUDNESS_CLIPPED = 3 };
+typedef struct fd_loudness {
+    double lufs;           /* integrated loudness; -inf for SHORT and SILENT */
+    float gain;            /* what fd_loudness_normalize scales with: 10^((target - lufs) / 20), 1 / peak if CLIPPED, 1 if SHORT / SILENT
+                              (and always 1 from fd_loudness_measure) */
+    float peak;            /* max |wav| over the utterance's own samples */
+    int32_t blocks;        /* nb (0 if SHORT) */
+    int32_t gated;         /* |J'|: the blocks the result is the mean of */
+    int32_t status;        /* FD_LOUDNESS_* */
+    int32_t reserved;      /* 0 */
+} fd_loudness;
+
+/* The ten coefficients, divided by a0: shelf b0 b1 b2 a1 a2, high pass b0 b1 b2 a1 a2 (pure host code, no handle).
+ * FD_ERR_INVALID: coef10 NULL or a rate outside 8000 .. 192000. */
+FD_API int fd_loudness_design(int rate, double *coef10);
+/* nb for n samples at `rate`, 0 if n < int(0.4 rate) (SHORT); pure host code.  FD_ERR_INVALID: n < 0 or a rate outside 8000 .. 192000. */
+FD_API int64_t fd_loudness_blocks(int64_t n, int rate);
+/* wav [B][L] device float -> rec_dev [B] device records, asynchronous on `stream`.  valid: HOST [B] or NULL = samples of each
+ * utterance that count (1 .. L).  B <= 4096, rate 8000 .. 192000. */
+FD_API int fd_loudness_measure(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, fd_loudness *rec_dev,
+                               void *stream);
+/* Measure, then scale to target_lufs.  out_f32 [B][L] and / or out_pcm [B][L] (device; at least one), rec_dev [B] device or NULL.
+ *   out_f32: wav gain; CLIPPED: wav / peak; SHORT and SILENT: wav unchanged
+ *   out_pcm: v = wav gain in float32, (int16_t)(v * 32767.0f); SHORT, SILENT and CLIPPED: exactly what
+ *            fd_peak_normalize_int16_ragged writes (wav / peak, then * 32767), bit for bit
+ * Both are 0 behind valid[b].  Like the peak epilogue and fd_mel_spectrogram, neither call settles a pending lazily checked fd_sample
+ * (fastdiff_hip.h: fd_sample_check): their result is provisional with it.
+ * FD_ERR_INVALID: a null pointer, B outside 1 .. 4096, L < 1, a rate outside 8000 .. 192000, valid[b] outside [1, L], a target that
+ * is not finite; FD_ERR_STATE: the scratch buffer would have to grow inside a stream capture. */
+FD_API int fd_loudness_normalize(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, double target_lufs,
+                                 float *out_f32, int16_t *out_pcm, fd_loudness *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
