@@ -19,10 +19,12 @@ FastDiff.sample_long / stream vocode one utterance of any length window by windo
 fastdiff_amd.resample / FastDiff.resample convert sample rate, sample type and channel count on the device, so recordings of any rate
 feed the mel front-end and TrainCorpus.from_wav_dir, and infer.synthesize writes PCM at any rate (fastdiff_amd/resample.py);
 fastdiff_amd.loudness / FastDiff.loudness / loudness_normalize measure BS.1770 loudness and normalise to a target on the device: the
-reference's loud_norm in front of the mel, and infer.synthesize(loudness=-23) behind the vocoder (fastdiff_amd/loudness.py).
+reference's loud_norm in front of the mel, and infer.synthesize(loudness=-23) behind the vocoder (fastdiff_amd/loudness.py);
+fastdiff_amd.stoi / FastDiff.stoi score a vocoded waveform against its recording with STOI and ESTOI on the device, Validator(stoi=True)
+does so for every held-out window and infer.synthesize(stoi=True) / --stoi in copy synthesis (fastdiff_amd/stoi.py).
 """
 from .model import FastDiff  # noqa: F401
-from . import sampler, schedules, resample, loudness  # noqa: F401
+from . import sampler, schedules, resample, loudness, stoi  # noqa: F401
 from . import sampler as util  # noqa: F401  (the reference module is called util)
 from .lvc_op import location_variable_convolution, gated_residual, kernel_conv1d, conv32  # noqa: F401
 from .trainstep import TrainStep  # noqa: F401
@@ -35,5 +37,5 @@ from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

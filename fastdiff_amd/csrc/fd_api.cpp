@@ -207,7 +207,7 @@ static void release_handle(fd_context *h)
     if (h->refresh_bad) hipHostFree(h->refresh_bad);
     if (h->refresh_done) hipEventDestroy(h->refresh_done);
     if (h->scratch) hipFree(h->scratch);
-    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->ring_scratch, &h->step_scratch, &h->loud_scratch})
+    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->ring_scratch, &h->step_scratch, &h->loud_scratch, &h->stoi_scratch})
         if (s->p) hipFree(s->p);
     for (auto &sl : h->stage) {
         if (sl.host) hipHostFree(sl.host);
@@ -215,6 +215,7 @@ static void release_handle(fd_context *h)
     }
     for (void *p : h->mel_allocs) hipFree(p);
     for (auto &t : h->resample_tabs) hipFree(const_cast<float *>(t.dev));
+    if (h->stoi_tab) hipFree(const_cast<float *>(h->stoi_tab));
     if (h->ev_switch) hipEventDestroy(h->ev_switch);
     if (h->cap_stream) hipStreamDestroy(h->cap_stream);
     delete h;

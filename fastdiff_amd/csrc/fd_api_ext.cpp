@@ -1,6 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h: the mel front-end in front of the vocoder and the int16
 // waveform epilogue behind it, sample-rate conversion (fd_resample) and BS.1770 loudness (fd_loudness_*) in
-// front of and behind both, taps, layout
+// front of and behind both, STOI / ESTOI of a vocoded waveform against its recording (fd_stoi_*), taps, layout
 // introspection, counters and per-kernel profiling.
 #include <math.h>
 #include <stddef.h>
@@ -346,6 +346,104 @@ int fd_loudness_normalize(fd_handle h, const float *wav, int B, int64_t L, const
                           int16_t *out_pcm, fd_loudness *rec_dev, void *stream)
 {
     return loudness_call(h, "fd_loudness_normalize", wav, B, L, valid, rate, true, target_lufs, out_f32, out_pcm, rec_dev, stream);
+}
+
+// STOI / ESTOI (fastdiff_hip_ext.h; constants, band table and counts: fd_stoi.h, the kernels: fd_kernels_stoi.hip) --------------------
+int fd_stoi_bands(int *lo15, int *hi15)
+{
+    if (!lo15 || !hi15) return FD_ERR_INVALID;
+    fds::bands(lo15, hi15);
+    return FD_OK;
+}
+
+int64_t fd_stoi_frames(int64_t n10k)
+{
+    if (n10k < 0) return FD_ERR_INVALID;
+    return fds::frames(n10k);
+}
+
+int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid, int rate, fd_stoi *rec_dev,
+                    void *stream)
+{
+    const char *who = "fd_stoi_measure";
+    if (!h) return FD_ERR_INVALID;
+    if (!clean || !degraded || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !clean ? "clean" : (!degraded ? "degraded" : "rec_dev"));
+    if (B < 1 || B > 4096 || L < 1) FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d pairs (1 .. 4096) of L = %lld samples", who, B, (long long)L);
+    if (rate < fds::RATE_MIN || rate > fds::RATE_MAX) FD_FAIL(h, FD_ERR_INVALID, "%s: sample rate %d outside %d .. %d", who, rate, fds::RATE_MIN, fds::RATE_MAX);
+    const bool resampled = rate != fds::RATE;
+    fdr::Ratio r;
+    if (resampled) {
+        if (!fdr::reduce(rate, fds::RATE, r)) FD_FAIL(h, FD_ERR_INVALID, "%s: sample rates %d -> %d", who, rate, fds::RATE);
+        if (std::max(r.up, r.down) > fdr::MAX_RATIO)
+            FD_FAIL(h, FD_ERR_UNSUPPORTED, "%s: %d -> %d Hz reduces to %d/%d; ratios up to %d are supported", who, rate, fds::RATE, r.up, r.down, fdr::MAX_RATIO);
+        if (L > (INT64_MAX >> 12)) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is too long", who, (long long)L);
+    }
+    const int64_t n10 = resampled ? fdr::out_len(L, r) : L;
+    if (n10 > ((int64_t)1 << 30)) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is %lld samples at 10 kHz, at most 2^30 are supported", who, (long long)L, (long long)n10);
+    if (valid)
+        for (int b = 0; b < B; ++b)
+            if (valid[b] < 1 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [1, %lld]", who, b, (long long)valid[b], (long long)L);
+    FD_HIP(h, hipSetDevice(h->device));
+    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the loudness meter: provisional with a lazily checked call
+    if (rc != FD_OK) return rc;
+    const size_t need = fdk::stoi_scratch_bytes(B, n10, resampled);
+    Scratch &s = h->stoi_scratch;
+    if (s.bytes < need || !h->stoi_tab) {      // grown at the first call that needs more; hipFree waits for the calls that still use the old one
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes for B = %d, L = %lld, which cannot happen inside a stream capture: call it once before",
+                    who, need, B, (long long)L);
+        }
+        if (!h->stoi_tab) {      // a synchronous copy from pageable memory: complete on return
+            float tab[fds::TAB_FLOATS];
+            fds::tables(tab);
+            void *d = nullptr;
+            FD_HIP(h, hipMalloc(&d, sizeof(tab)));
+            const hipError_t e = hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                hipFree(d);
+                FD_FAIL(h, FD_ERR_HIP, "%s: table upload failed: %s", who, hipGetErrorString(e));
+            }
+            h->stoi_tab = static_cast<const float *>(d);
+        }
+        if (s.bytes < need) {
+            if (s.p) FD_HIP(h, hipFree(s.p));
+            s = Scratch{};
+            void *p = nullptr;
+            FD_HIP(h, hipMalloc(&p, need));
+            s.p = static_cast<float *>(p);
+            s.bytes = need;
+        }
+    }
+    const float *table = nullptr;
+    if (resampled && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
+    const fdk::StoiSlots sl10 = fdk::stoi_slots(s.p, B, n10, resampled);
+    const long long *lens_dev = nullptr;
+    if (valid) {      // each pair's own length at 10 kHz, through the staging ring as the loudness meter's lengths
+        fd_context::StageSlot *sl = nullptr;
+        if ((rc = fd_stage_acquire(h, sizeof(long long) * B, &sl)) != FD_OK) return rc;
+        for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = resampled ? fdr::out_len(valid[b], r) : valid[b];
+        FD_HIP(h, hipMemcpyAsync(sl10.lens, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, (hipStream_t)stream));
+        if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
+        lens_dev = sl10.lens;
+    }
+    fdk::Launch La = {h, (hipStream_t)stream, false};
+    const float *x = clean, *y = degraded;
+    long long pitch = L;
+    if (resampled) {
+        for (int k = 0; k < 2; ++k) {
+            const hipError_t e = fdk::resample(La, k ? degraded : clean, FD_PCM_F32, 1, B, L, L, valid, r.up, r.down, r.half, r.K, r.Kp, n10, table,
+                                               k ? sl10.y10 : sl10.x10, sl10.pitch10);
+            if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+        }
+        x = sl10.x10; y = sl10.y10; pitch = sl10.pitch10;
+    }
+    fdk::StoiBands bd;
+    fds::bands(bd.lo, bd.hi);
+    const hipError_t e = fdk::stoi(La, x, y, pitch, B, n10, lens_dev, h->stoi_tab, bd, rec_dev, s.p, resampled);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FD_OK;
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

@@ -12,6 +12,7 @@
 #include "../../include/fastdiff_hip_ext.h"
 #include "../../include/fastdiff_hip_train.h"
 #include "fd_loudness.h"
+#include "fd_stoi.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -370,6 +371,8 @@ struct fd_context {
     Scratch ring_scratch;                    // fd_mel_ring_append's chunk records
     long long n_span_batches = 0, n_span_windows = 0;   // fd_get_counter: fd_sample calls / windows made by the span entry points
     Scratch loud_scratch;                    // fd_loudness_measure / _normalize: peak words, lengths, tile states, partial sums, block powers
+    Scratch stoi_scratch;                    // fd_stoi_measure: lengths, the 10 kHz signals, frame energies, src, band amplitudes, segment partials
+    const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call, freed at fd_destroy
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -475,6 +478,15 @@ size_t loudness_scratch_bytes(int B, int64_t L, int rate);
 long long *loudness_valid_slot(void *scratch, int B, int64_t L, int rate);
 hipError_t loudness(const Launch &L_, const float *wav, int B, int64_t L, const long long *valid_dev, int rate, const LoudnessFilter &F,
                     bool normalize, double target, fd_loudness *rec, float *out_f32, int16_t *out_pcm, void *scratch);
+// fd_stoi_measure (fd_kernels_stoi.hip).  x, y: [B] rows `pitch` floats apart AT 10 kHz (the caller's, or the x10 / y10 slots of the
+// scratch buffer after the internal resample); n10: the longest row; lens_dev: null (every row n10 samples) or the lens slot, filled by
+// the caller with each row's own 10 kHz length; tab: device copy of fds::tables; rec: device [B].
+struct StoiBands { int lo[fds::BANDS], hi[fds::BANDS]; };
+struct StoiSlots { long long *lens; float *x10, *y10; long long pitch10; };
+size_t stoi_scratch_bytes(int B, int64_t n10, bool resampled);
+StoiSlots stoi_slots(void *scratch, int B, int64_t n10, bool resampled);
+hipError_t stoi(const Launch &L_, const float *x, const float *y, long long pitch, int B, int64_t n10, const long long *lens_dev,
+                const float *tab, const StoiBands &bd, fd_stoi *rec, void *scratch, bool resampled);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

@@ -17,7 +17,7 @@ Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS]`).
+[--loudness LUFS] [--stoi]`).
 """
 import argparse
 import glob
@@ -95,7 +95,8 @@ def loud_norm_wav(model, wav: torch.Tensor, sample_rate: int = 22050, what: str 
     return y
 
 
-def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg", loud_norm: bool = False) -> List[dict]:
+def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg", loud_norm: bool = False,
+                    keep_wav: bool = False) -> List[dict]:
     """Copy-synthesis inputs (`test_input_dir` with recordings, tasks/vocoder/dataset_utils.py:162-184): every *.wav below the
     directory, in sorted order, through the device mel front-end (`FastDiff.mel_spectrogram` = process_utterance of
     data_gen/tts/data_gen_utils.py:93-147, or with mel_variant="tacotron" the TacotronSTFT of vocoder_binarizer_tacotron.py:110-116
@@ -104,7 +105,9 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     it (FastDiff.resample: sample type, down-mix and rate in one launch -- librosa.core.load(path, sr=sample_rate),
     data_gen_utils.py:111); a mono recording at the model's rate takes the direct path, bit for bit as before.
     loud_norm: the reference's `loud_norm: true` configurations -- every recording is brought to -22 LUFS before its mel is taken
-    (loud_norm_wav: FastDiff.loudness_normalize)."""
+    (loud_norm_wav: FastDiff.loudness_normalize).
+    keep_wav: every item also carries "wav", its device waveform [n] at the model's rate as the mel was taken from it (what
+    synthesize(stoi=True) scores the vocoded waveform against)."""
     from scipy.io import wavfile
     items = []
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
@@ -114,6 +117,8 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
             wav = loud_norm_wav(model, wav, sample_rate, path)
         mel = model.mel_spectrogram(wav, variant=mel_variant)[0].transpose(0, 1).contiguous().cpu()      # [T, 80] as on disk
         items.append({"item_name": path[len(test_input_dir) + 1:].replace("/", "_"), "mel": mel, "len": mel.shape[0]})
+        if keep_wav:
+            items[-1]["wav"] = wav.reshape(-1)
     return items
 
 
@@ -217,7 +222,7 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
-               sample_rate: int = 22050, loudness: float = None) -> Dict[str, np.ndarray]:
+               sample_rate: int = 22050, loudness: float = None, stoi: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
@@ -231,8 +236,15 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     loudness = LUFS (None: peak normalisation, every byte as without the argument): the loudness epilogue instead of the peak epilogue
     (FastDiff.loudness_normalize, out="int16"): every utterance is measured as it is delivered -- after the resampling, at that rate,
     over its own samples -- and scaled to that BS.1770 loudness; one that cannot be measured, or that the gain would clip, is
-    peak-normalised as before."""
+    peak-normalised as before.
+    stoi=True (copy synthesis: every item carries "wav", its recording on the device at `sample_rate`, load_wav_inputs(keep_wav=True)):
+    returns (pcm, report) with report[name] = {"stoi", "estoi", "status"} (FastDiff.stoi; status by name, the values NaN unless "OK"),
+    measured on the float waveform of each micro-batch before the level epilogue and before any out_sample_rate, the recording cut to
+    the vocoded length (lens * hop)."""
     from . import resample as _resample
+    if stoi and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+        raise ValueError("synthesize: stoi=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    report: Dict[str, dict] = {}
     R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
     # every call, as the reference does), the same rows then drive every micro-batch
@@ -240,7 +252,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     lengths = [it["len"] for it in items]
     out: Dict[str, np.ndarray] = {}
     if not items:
-        return out
+        return (out, report) if stoi else out
     hop = model.hop_length
     n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
 
@@ -270,12 +282,28 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     host_check = getattr(model, "_options", {}).get("fallback") == "host"
     prev_dev = None                # return_device: (ticket, wav, names, lens) of the micro-batch nobody has settled yet
 
+    def score(wav, names, lens):
+        # the recordings of the micro-batch next to its float waveform: one padded batch, one call, one record read
+        from . import stoi as _stoi
+        wav_of = {it["item_name"]: it["wav"] for it in items}
+        B, n = wav.shape[0], wav.shape[-1]
+        clean = torch.zeros((B, n), device=wav.device, dtype=torch.float32)
+        for b, (name, t) in enumerate(zip(names, lens)):
+            if wav_of[name].numel() < t * hop:
+                raise ValueError(f"synthesize: the recording of {name} has {wav_of[name].numel()} samples, fewer than the {t * hop} vocoded")
+            clean[b, : t * hop] = wav_of[name][: t * hop]
+        rec = model.stoi(clean, wav.reshape(B, n), valid=[t * hop for t in lens], sample_rate=sample_rate)
+        for b, name in enumerate(names):
+            report[name] = {"stoi": float(rec["stoi"][b]), "estoi": float(rec["estoi"][b]), "status": _stoi.STATUS[int(rec["status"][b])]}
+
     def settle_on_device(p):
         # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
         # next sample() has looked at it (no wait by then) and not at the end of the job
         ticket, wav, names, lens = p
         if model.settle(ticket):                     # run again on fp32: so is its epilogue
             pcm = epilogue(wav, lens)
+            if stoi:
+                score(wav, names, lens)
             for b, (name, t) in enumerate(zip(names, lens)):
                 out[name] = pcm[b, : n_of(t)]
 
@@ -285,6 +313,8 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         if host_check and model.settle(ticket):      # an operand left the fp16 range: the call was run again on fp32 -- so is its epilogue
             host.copy_(epilogue(wav, lens), non_blocking=True)
             torch.cuda.current_stream().synchronize()
+            if stoi:
+                score(wav, names, lens)
         for b, (name, t) in enumerate(zip(names, lens)):
             out[name] = host[b, : n_of(t)].numpy().copy()
 
@@ -310,6 +340,8 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         ticket = getattr(model, "last_ticket", 0)
         # one epilogue call and one asynchronous copy per micro-batch; the previous batch is unpacked on the host while this one runs
         pcm = epilogue(wav, lens)
+        if stoi:
+            score(wav, names, lens)
         if return_device:
             for b, (name, t) in enumerate(zip(names, lens)):
                 out[name] = pcm[b, : n_of(t)]
@@ -330,12 +362,12 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         collect(pending)
     if host_check and prev_dev is not None:
         settle_on_device(prev_dev)
-    return out
+    return (out, report) if stoi else out
 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
-                       sample_rate: int = 22050, loudness: float = None) -> Dict[str, np.ndarray]:
+                       sample_rate: int = 22050, loudness: float = None, stoi: bool = False) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -352,7 +384,10 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     micro-batches; no message travels back and `src` does no work the other ranks do not do.
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
     "frames": by frames alone (rounds 1-5).
-    out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate."""
+    out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate.
+    stoi=True is refused: the recordings are not scattered (score with synthesize(stoi=True))."""
+    if stoi:
+        raise ValueError("synthesize_sharded: stoi=True is not available (the recordings are not scattered): use synthesize(stoi=True)")
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -443,12 +478,15 @@ LONG_FORM_GROUP_FRAMES = 1 << 16      # mel frames per sample_long_batch call: 6
 
 def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
                     diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES, loudness: float = None,
-                    sample_rate: int = 22050) -> Dict[str, np.ndarray]:
+                    sample_rate: int = 22050, stoi: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM through FastDiff.sample_long_batch (windowed: any length, device memory of one window batch): the
     utterances are taken in order in groups of up to group_frames mel frames, so their outputs fit, and the windows of a group share the
     sampler's batches.  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same,
     byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
-    loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is."""
+    loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is.
+    stoi=True is refused (score the result with FastDiff.stoi, which takes any length)."""
+    if stoi:
+        raise ValueError("synthesize_long: stoi=True is not available: score the waveforms with FastDiff.stoi")
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -511,9 +549,16 @@ def main(argv=None):
                          "too short or too quiet to measure, or that the gain would clip, is peak-normalised")
     ap.add_argument("--loud_norm", action="store_true",
                     help="with --from_wav: bring every recording to -22 LUFS before its mel is taken (the reference's loud_norm: true)")
+    ap.add_argument("--stoi", action="store_true",
+                    help="with --from_wav (copy synthesis): score every vocoded waveform against its recording with STOI and ESTOI on the "
+                         "device, print the table and write <out_dir>/stoi.tsv")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
+    if args.stoi and not args.from_wav:
+        ap.error("--stoi scores the vocoded waveform against its recording: it needs --from_wav")
+    if args.stoi and args.long_form:
+        ap.error("--stoi is not available with --long_form")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -526,14 +571,22 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"]["model"], strict=True)
     if args.mel_basis:
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
-    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=args.stoi) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
-        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness)
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi)
+    if args.stoi:
+        pcm, report = pcm
+        os.makedirs(args.out_dir, exist_ok=True)
+        lines = ["name\tstoi\testoi\tstatus"] + [f"{it['item_name']}\t{report[it['item_name']]['stoi']:.6f}\t{report[it['item_name']]['estoi']:.6f}\t"
+                                                 f"{report[it['item_name']]['status']}" for it in mine if it["item_name"] in report]
+        print("\n".join(lines))
+        with open(os.path.join(args.out_dir, "stoi.tsv" if world == 1 else f"stoi.rank{rank}.tsv"), "w") as f:
+            f.write("\n".join(lines) + "\n")
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 

@@ -374,6 +374,16 @@ class FastDiff(nn.Module):
         lib, h = self._ready(wav.device)
         return _loudness._normalize(lib, h, self._stream(wav.device), wav, target, valid, sample_rate, out, return_record)
 
+    def stoi(self, clean, degraded, valid=None, sample_rate=22050):
+        """STOI and ESTOI of `degraded` against `clean` on the device (fastdiff_amd/stoi.py; what people run pystoi for over the reference's
+        *_gt.wav / *_pred.wav pairs, FastDiff.py:113-117): two tensors [n] / [B, n] / [B, 1, n] of one shape at `sample_rate` -> a dict of
+        numpy arrays over the batch: stoi, estoi (NaN unless OK), frames, kept, segments, status (stoi.OK / SHORT / SILENT).  valid: [B]
+        sample counts of a padded batch.  Synchronises once, for the records."""
+        from . import stoi as _stoi
+        self._require_inference(clean, degraded)
+        lib, h = self._ready(clean.device)
+        return _stoi._measure(lib, h, self._stream(clean.device), clean, degraded, valid, sample_rate)
+
     def set_mel_filterbank(self, fb, variant="pwg", device=None):
         """Use `fb` [80, 513] (numpy / tensor, float32; librosa.filters.mel's own layout) as the filter bank of front-end `variant`
         instead of the library's restated default -- what a deployment that has librosa passes

@@ -21,6 +21,8 @@ With sample_schedule (an inference noise schedule, e.g. schedules.noise_schedule
 (FastDiff.sample with the item ids as noise streams: an item's noise does not depend on the batch size) and compared with the ground
 truth as the mean |difference| of the two log-mel spectrograms, both from the library's own front end ('pwg' variant), so that edge
 frames affect the two alike.  sample() looks at its range check before returning: this mode waits for the device once per batch.
+With stoi=True on top of it, the vocoded window is also scored against the ground truth with STOI and ESTOI (FastDiff.stoi's kernels,
+fastdiff_amd/stoi.py) at the corpus' sample rate: the records of every batch stay on the device until result() reads them.
 
 The default seed differs from TrainStep's (0), so that batch j of a pass does not repeat the noise of training step j.  The operators
 share the per-device step scratch with TrainStep (lvc_op._handle): a pass asks for far less of it than an optimizer step over the
@@ -36,7 +38,7 @@ DEFAULT_SEED = 0x56414C      # "VAL"
 
 
 class Validator:
-    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None):
+    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None, stoi=False, sample_rate=22050):
         if int(batch_size) < 1:
             raise ValueError(f"Validator: batch_size={batch_size} (at least 1)")
         if not 1 <= int(bins) <= lvc_op.EVAL_MAX_BINS:
@@ -76,6 +78,13 @@ class Validator:
         self.eps = self.sampled = self.mel_sampled = self.mel_target = None
         self.values_mel = torch.empty(B, device=dev, dtype=torch.float32) if self.table is not None else None
         self.item_mel_l1 = torch.zeros(corpus.n_items, device=dev, dtype=torch.float32) if self.table is not None else None
+        self._stoi_rec = None
+        if stoi:
+            if self.table is None:
+                raise ValueError("Validator: stoi=True scores the vocoded windows, which needs sample_schedule")
+            from . import stoi as _stoi
+            self.sample_rate = int(sample_rate)                # the rate of the corpus' waveforms (fd_stoi_measure resamples to 10 kHz)
+            self._stoi_rec = torch.zeros((self.n_batches * B, _stoi.RECORD.itemsize), device=dev, dtype=torch.uint8)      # slot b of batch j
 
     def state(self):
         """The pass's fd_train_state as a dict (`iter` = batches done).  Synchronises."""
@@ -102,6 +111,10 @@ class Validator:
             self.mel_target = m.mel_spectrogram(self.wav.view(B, -1), n_frames=F, variant="pwg")
             lvc_op.item_distance(self.mel_sampled, self.mel_target, 1, out=self.values_mel)
             lvc_op.eval_accumulate(self.values_mel, self.picked, self._acc_mel, item_out=self.item_mel_l1)
+            if self._stoi_rec is not None:
+                from . import stoi as _stoi
+                lib, h = m._ready(self.device)
+                _stoi._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, self.sample_rate, rec=self._stoi_rec[j * B: (j + 1) * B])
         # last: it advances the batch index, behind every read of it
         lvc_op.eval_accumulate(self.values, self.picked, self._acc, steps=self.steps, T_train=self.T_train, bins=self.bins,
                                item_out=self.item_loss, advance=self._state)
@@ -126,7 +139,8 @@ class Validator:
 
     def result(self):
         """{"loss", "items", "nonfinite", "loss_by_t" [bins], "count_by_t" [bins], "item_loss" [n]} of the last pass, plus "mel_l1" and
-        "item_mel_l1" [n] with sample_schedule.  loss = the mean over the items (the reference's validation_end averages batch means:
+        "item_mel_l1" [n] with sample_schedule, plus "stoi", "estoi" (the means over the items with status OK), "item_stoi", "item_estoi"
+        [n] (NaN where not OK) and "stoi_skipped" (the items not OK) with stoi=True.  loss = the mean over the items (the reference's validation_end averages batch means:
         the two differ only through a short last batch); loss_by_t[k] = the mean over the items whose step fell into
         [k T / bins, (k + 1) T / bins), NaN where none did.  Synchronises once."""
         acc = lvc_op.read_eval_state(self._acc, self.bins)
@@ -137,4 +151,14 @@ class Validator:
             mel = lvc_op.read_eval_state(self._acc_mel, 1)
             out["mel_l1"] = mel["sum"] / mel["count"] if mel["count"] else float("nan")
             out["item_mel_l1"] = self.item_mel_l1.cpu().numpy()
+        if self._stoi_rec is not None:
+            from . import stoi as _stoi
+            rec = _stoi._record(self._stoi_rec)              # slot b of batch j is item j B + b: the first n rows are the items
+            n = self.corpus.n_items
+            ok = rec["status"][:n] == _stoi.OK
+            for key in ("stoi", "estoi"):
+                item = np.where(ok, rec[key][:n], np.nan)
+                out["item_" + key] = item
+                out[key] = float(item[ok].mean()) if ok.any() else float("nan")
+            out["stoi_skipped"] = int(n - ok.sum())
         return out

@@ -158,6 +158,70 @@ FD_API int fd_loudness_measure(fd_handle h, const float *wav, int B, int64_t L, 
 FD_API int fd_loudness_normalize(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, double target_lufs,
                                  float *out_f32, int16_t *out_pcm, fd_loudness *rec_dev, void *stream);
 
+/* STOI and ESTOI: how intelligible a degraded waveform is against the clean one (Taal, Hendriks, Heusdens, Jensen 2011; Jensen and Taal
+ * 2016) -- the objective score next to MOS and PESQ in the FastDiff paper's table, which the reference has no code for: people run pystoi
+ * over the *_gt.wav / *_pred.wav pairs that test_step writes (FastDiff.py:113-117).  pystoi is not in the build image, so THIS TEXT defines
+ * the measurement; it follows pystoi's conventions AS RECALLED, NOT AS CHECKED against its source, and tests/stoi_ref.py restates it in
+ * float64 numpy.  A deployment that has pystoi should expect agreement to about the third decimal, from the two deviations stated below.
+ *
+ * Inputs: a clean waveform x and a degraded one y of the same length n and rate.
+ *  1. Resample.  If the rate is not 10000, both go through fd_resample to 10000 Hz: n' = fd_resample_out_len(n, rate, 10000) samples.
+ *     DEVIATION: pystoi uses an Octave-compatible polyphase filter here; this is the library's own kaiser_best design.
+ *  2. Frames.  w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0 .. 255 (hanning(258)[1:-1]).  Frame i covers samples
+ *     [128 i, 128 i + 256), i = 0 .. F0 - 1, F0 = ceil((n' - 256) / 128) for n' > 256, else 0 (pystoi's range(0, len - 256, 128): the
+ *     last full frame is left out when n' - 256 is a multiple of 128).
+ *  3. Silent frames.  E_i = sum (w x_i)^2 on the clean signal only; frame i is kept iff E_i > 1e-4 max_i E_i (40 dB on the frame norm;
+ *     pystoi's "+ eps" inside its log matters only for an all-zero signal, which is SILENT here).  The kept frames in order,
+ *     k = 0 .. K - 1 with source index src[k], windowed by w, are overlap-added at hop 128 into x_s and y_s of 128 (K - 1) + 256 samples
+ *     each; the same mask serves y.  The hop is half a frame, so every sample of x_s is the sum of at most two windowed source
+ *     samples: a gather.
+ *  4. STFT.  M = K - 1 frames of x_s and y_s (rule 2 again: pystoi drops the last frame here too), each windowed by w again and
+ *     zero-padded to 512; P[k] = |X[k]|^2, k = 0 .. 256.
+ *  5. Bands.  A[j][m] = sqrt(sum_{k = lo[j]}^{hi[j] - 1} P[k]), j = 0 .. 14, with
+ *       lo = 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174,   hi = 9 11 14 17 22 27 34 43 55 69 87 109 138 174 219:
+ *     the bins nearest to 150 * 2^((2j -+ 1) / 6) Hz on the grid k * 10000 / 512 (fd_stoi_bands computes them from that rule).
+ *  6. Segments.  Segment s = 0 .. J - 1 holds frames [s, s + 30) (384 ms), J = M - 29.
+ *  7. STOI.  Per segment and band over the 30 frames: c = ||X|| / (||Y|| + eps), eps = 2^-52; Y' = min(c Y, (1 + 10^(15/20)) X); the
+ *     means of X and Y' removed, each divided by its norm plus eps; d = sum X Y' / (15 J).
+ *  8. ESTOI.  Per segment on the 15 x 30 matrices of X and Y separately: each row (a band over time) mean removed and divided by its
+ *     norm plus eps, then each column (a frame over bands) likewise; d_e = sum X Y / (30 J).
+ *     DEVIATION: pystoi adds eps-scaled random noise before each normalisation; that is left out.
+ *  9. Status.  FD_STOI_SHORT: F0 = 0, or K < 31 (M < 30: not one segment; pystoi returns 1e-5 with a warning);  FD_STOI_SILENT: F0 > 0 and
+ *     max E_i == 0;  else FD_STOI_OK.  stoi and estoi are NaN unless OK.
+ *
+ * On the device: frame energies in float32 (one wavefront per frame; the maximum by atomicMax on non-negative float bits, which has no
+ * order), the mask and an exclusive scan over tiles of FD_STOI_SCAN_TILE frames with a carry across tiles (any frame count) that writes
+ * src[] and K, then one workgroup per STFT frame and signal (gather, window, a 16 x 32 split 512-point transform in LDS, 15 float32
+ * band amplitudes), then the segment stage in float64, FD_STOI_SEG_TILE segments per workgroup, and per-segment partials added in
+ * segment order.  Every sum has a fixed order and there are no floating-point atomics: an utterance's record is bit-identical alone,
+ * anywhere in a ragged batch with anything behind it, and from call to call.  Samples behind valid[b] are never read as signal.
+ * Scratch (energies, src, band amplitudes, partials, the two 10 kHz signals) lives in a buffer of the handle that grows at the first call
+ * that needs more -- never inside a stream capture, where such a call is refused with FD_ERR_STATE; the window and twiddle table is
+ * uploaded at the first call; the internal resample inherits fd_resample's rule about a ratio first seen inside a capture.  A graph that
+ * holds a captured call points into that buffer: capture after the largest shape has been seen, or capture again. */
+#define FD_STOI_SCAN_TILE 1024      /* frames of one utterance per workgroup of the compaction scan */
+#define FD_STOI_SEG_TILE 16         /* segments of one utterance per workgroup of the segment stage */
+enum { FD_STOI_OK = 0, FD_STOI_SHORT = 1, FD_STOI_SILENT = 2 };
+typedef struct fd_stoi {
+    double stoi, estoi;    /* NaN unless status is FD_STOI_OK */
+    int32_t frames;        /* F0 */
+    int32_t kept;          /* K */
+    int32_t segments;      /* J (0 unless OK) */
+    int32_t status;        /* FD_STOI_* */
+} fd_stoi;                 /* 32 bytes */
+
+/* The band table of step 5, computed from its rule: lo15[j], hi15[j] (pure host code, no handle).  FD_ERR_INVALID: a null pointer. */
+FD_API int fd_stoi_bands(int *lo15, int *hi15);
+/* F0 for n10k samples at 10 kHz (pure host code).  FD_ERR_INVALID: n10k < 0. */
+FD_API int64_t fd_stoi_frames(int64_t n10k);
+/* clean, degraded [B][L] device float at `rate` -> rec_dev [B] device records, asynchronous on `stream`.  valid: HOST [B] or NULL =
+ * samples of each pair that count (1 .. L), as in fd_loudness_measure.  B 1 .. 4096, rate 8000 .. 192000, at most 2^30 samples at 10 kHz.
+ * Like fd_loudness_measure it does not settle a pending lazily checked fd_sample: its result is provisional with it.
+ * FD_ERR_INVALID: a null pointer, B, L, rate or valid[b] out of range; FD_ERR_STATE: the scratch buffer (or a resampling table) would
+ * have to be built inside a stream capture. */
+FD_API int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid, int rate,
+                           fd_stoi *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
