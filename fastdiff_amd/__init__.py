@@ -21,10 +21,13 @@ feed the mel front-end and TrainCorpus.from_wav_dir, and infer.synthesize writes
 fastdiff_amd.loudness / FastDiff.loudness / loudness_normalize measure BS.1770 loudness and normalise to a target on the device: the
 reference's loud_norm in front of the mel, and infer.synthesize(loudness=-23) behind the vocoder (fastdiff_amd/loudness.py);
 fastdiff_amd.stoi / FastDiff.stoi score a vocoded waveform against its recording with STOI and ESTOI on the device, Validator(stoi=True)
-does so for every held-out window and infer.synthesize(stoi=True) / --stoi in copy synthesis (fastdiff_amd/stoi.py).
+does so for every held-out window and infer.synthesize(stoi=True) / --stoi in copy synthesis (fastdiff_amd/stoi.py);
+fastdiff_amd.pitch / FastDiff.pitch track F0 with YIN on the mel frame grid and score the vocoded pitch against the recording's (F0 RMSE in
+cents, gross pitch error, voicing decision error), Validator(pitch=True) and infer.synthesize(pitch=True) / --pitch likewise
+(fastdiff_amd/pitch.py).
 """
 from .model import FastDiff  # noqa: F401
-from . import sampler, schedules, resample, loudness, stoi  # noqa: F401
+from . import sampler, schedules, resample, loudness, stoi, pitch  # noqa: F401
 from . import sampler as util  # noqa: F401  (the reference module is called util)
 from .lvc_op import location_variable_convolution, gated_residual, kernel_conv1d, conv32  # noqa: F401
 from .trainstep import TrainStep  # noqa: F401
@@ -37,5 +40,5 @@ from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

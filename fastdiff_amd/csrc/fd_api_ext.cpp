@@ -1,6 +1,7 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h: the mel front-end in front of the vocoder and the int16
 // waveform epilogue behind it, sample-rate conversion (fd_resample) and BS.1770 loudness (fd_loudness_*) in
-// front of and behind both, STOI / ESTOI of a vocoded waveform against its recording (fd_stoi_*), taps, layout
+// front of and behind both, STOI / ESTOI (fd_stoi_*) and F0 tracking with the pitch scores (fd_pitch_*) of a vocoded waveform against its
+// recording, taps, layout
 // introspection, counters and per-kernel profiling.
 #include <math.h>
 #include <stddef.h>
@@ -442,6 +443,111 @@ int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int 
     fdk::StoiBands bd;
     fds::bands(bd.lo, bd.hi);
     const hipError_t e = fdk::stoi(La, x, y, pitch, B, n10, lens_dev, h->stoi_tab, bd, rec_dev, s.p, resampled);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FD_OK;
+}
+
+// F0 tracking and the pitch scores (fastdiff_hip_ext.h; constants, lags and counts: fd_pitch.h, the kernels: fd_kernels_pitch.hip) ------
+int fd_pitch_default_config(fd_pitch_config *cfg)
+{
+    if (!cfg) return FD_ERR_INVALID;
+    fdp::defaults(cfg);
+    return FD_OK;
+}
+
+int fd_pitch_lags(const fd_pitch_config *cfg, int *tau_min, int *tau_max)
+{
+    fdp::Lags lg;
+    if (!cfg || fdp::lags(*cfg, lg)) return FD_ERR_INVALID;
+    if (tau_min) *tau_min = lg.tau_min;
+    if (tau_max) *tau_max = lg.tau_max;
+    return FD_OK;
+}
+
+int64_t fd_pitch_frames(int64_t n, int hop)
+{
+    if (n < 0 || hop < 1) return FD_ERR_INVALID;
+    return fdp::frames(n, hop);
+}
+
+// the host counts [B] of a pitch call -> slot `which` (0: fd_pitch_track's valid, 1: fd_pitch_compare's frames) of the handle's
+// pitch scratch, through the staging ring as the STOI lengths; *dev = null when counts is null
+static int pitch_counts(fd_handle h, const char *who, const int64_t *counts, int B, int which, hipStream_t stream, const long long **dev)
+{
+    *dev = nullptr;
+    if (!counts) return FD_OK;
+    const size_t slot = (sizeof(long long) * 4096 + 255) & ~(size_t)255, need = 2 * slot;      // B <= 4096
+    Scratch &s = h->pitch_scratch;
+    if (s.bytes < need) {      // allocated at the first call that passes counts; never inside a capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes, which cannot happen inside a stream capture: call it once before", who, need);
+        }
+        if (s.p) FD_HIP(h, hipFree(s.p));
+        s = Scratch{};
+        void *p = nullptr;
+        FD_HIP(h, hipMalloc(&p, need));
+        s.p = static_cast<float *>(p);
+        s.bytes = need;
+    }
+    long long *dst = reinterpret_cast<long long *>(reinterpret_cast<char *>(s.p) + which * slot);
+    fd_context::StageSlot *sl = nullptr;
+    int rc = fd_stage_acquire(h, sizeof(long long) * B, &sl);
+    if (rc != FD_OK) return rc;
+    for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = counts[b];
+    FD_HIP(h, hipMemcpyAsync(dst, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, stream));
+    if ((rc = fd_stage_commit(h, sl, stream)) != FD_OK) return rc;
+    *dev = dst;
+    return FD_OK;
+}
+
+int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_pitch_config *cfg, float *f0_dev,
+                   float *aper_dev, int64_t out_pitch, void *stream)
+{
+    const char *who = "fd_pitch_track";
+    if (!h) return FD_ERR_INVALID;
+    if (!wav || !cfg || !f0_dev || !aper_dev)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !wav ? "wav" : (!cfg ? "cfg" : (!f0_dev ? "f0_dev" : "aper_dev")));
+    fdp::Lags lg;
+    if (const char *why = fdp::lags(*cfg, lg)) FD_FAIL(h, FD_ERR_INVALID, "%s: configuration refused: %s", who, why);
+    if (B < 1 || B > 4096 || L < 1) FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d utterances (1 .. 4096) of L = %lld samples", who, B, (long long)L);
+    const int64_t F = fdp::frames(L, cfg->hop);
+    if (F > fdp::MAX_FRAMES) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is %lld frames, at most 2^30 are supported", who, (long long)L, (long long)F);
+    if (out_pitch < std::max<int64_t>(F, 1))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: out_pitch = %lld is less than the %lld frames of L = %lld", who, (long long)out_pitch, (long long)F, (long long)L);
+    if (valid)
+        for (int b = 0; b < B; ++b)
+            if (valid[b] < 0 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [0, %lld]", who, b, (long long)valid[b], (long long)L);
+    FD_HIP(h, hipSetDevice(h->device));
+    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the STOI call: provisional with a lazily checked call
+    if (rc != FD_OK) return rc;
+    const long long *lens_dev = nullptr;
+    if ((rc = pitch_counts(h, who, valid, B, 0, (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
+    fdk::Launch La = {h, (hipStream_t)stream, false};
+    const hipError_t e = fdk::pitch_track(La, wav, L, B, L, lens_dev, *cfg, lg, f0_dev, aper_dev, out_pitch);
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FD_OK;
+}
+
+int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int B, int64_t pitch, const int64_t *frames, fd_pitch *rec_dev,
+                     void *stream)
+{
+    const char *who = "fd_pitch_compare";
+    if (!h) return FD_ERR_INVALID;
+    if (!f0_ref || !f0_deg || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !f0_ref ? "f0_ref" : (!f0_deg ? "f0_deg" : "rec_dev"));
+    if (B < 1 || B > 4096 || pitch < 1 || pitch > fdp::MAX_FRAMES)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d tracks (1 .. 4096) of pitch = %lld frames (1 .. 2^30)", who, B, (long long)pitch);
+    if (frames)
+        for (int b = 0; b < B; ++b)
+            if (frames[b] < 0 || frames[b] > pitch)
+                FD_FAIL(h, FD_ERR_INVALID, "%s: frames[%d] = %lld outside [0, %lld]", who, b, (long long)frames[b], (long long)pitch);
+    FD_HIP(h, hipSetDevice(h->device));
+    const long long *frames_dev = nullptr;
+    int rc = pitch_counts(h, who, frames, B, 1, (hipStream_t)stream, &frames_dev);
+    if (rc != FD_OK) return rc;
+    fdk::Launch La = {h, (hipStream_t)stream, false};
+    const hipError_t e = fdk::pitch_compare(La, f0_ref, f0_deg, pitch, B, frames_dev, rec_dev);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return FD_OK;
 }

@@ -13,6 +13,7 @@
 #include "../../include/fastdiff_hip_train.h"
 #include "fd_loudness.h"
 #include "fd_stoi.h"
+#include "fd_pitch.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -373,6 +374,7 @@ struct fd_context {
     Scratch loud_scratch;                    // fd_loudness_measure / _normalize: peak words, lengths, tile states, partial sums, block powers
     Scratch stoi_scratch;                    // fd_stoi_measure: lengths, the 10 kHz signals, frame energies, src, band amplitudes, segment partials
     const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call, freed at fd_destroy
+    Scratch pitch_scratch;                   // fd_pitch_track / _compare: the device copies of valid [B] and frames [B]
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -487,6 +489,12 @@ size_t stoi_scratch_bytes(int B, int64_t n10, bool resampled);
 StoiSlots stoi_slots(void *scratch, int B, int64_t n10, bool resampled);
 hipError_t stoi(const Launch &L_, const float *x, const float *y, long long pitch, int B, int64_t n10, const long long *lens_dev,
                 const float *tab, const StoiBands &bd, fd_stoi *rec, void *scratch, bool resampled);
+// fd_pitch_track / fd_pitch_compare (fd_kernels_pitch.hip).  lens_dev / frames_dev: null (every row L samples / `pitch` frames) or device
+// [B]; lg: fdp::lags of cfg, which the caller has validated.
+hipError_t pitch_track(const Launch &L_, const float *wav, long long pitch, int B, int64_t L, const long long *lens_dev,
+                       const fd_pitch_config &cfg, const fdp::Lags &lg, float *f0, float *aper, long long out_pitch);
+hipError_t pitch_compare(const Launch &L_, const float *f0_ref, const float *f0_deg, long long pitch, int B, const long long *frames_dev,
+                         fd_pitch *rec);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

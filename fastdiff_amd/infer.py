@@ -17,7 +17,7 @@ Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi]`).
+[--loudness LUFS] [--stoi] [--pitch]`).
 """
 import argparse
 import glob
@@ -107,7 +107,7 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     loud_norm: the reference's `loud_norm: true` configurations -- every recording is brought to -22 LUFS before its mel is taken
     (loud_norm_wav: FastDiff.loudness_normalize).
     keep_wav: every item also carries "wav", its device waveform [n] at the model's rate as the mel was taken from it (what
-    synthesize(stoi=True) scores the vocoded waveform against)."""
+    synthesize(stoi=True) and synthesize(pitch=True) score the vocoded waveform against)."""
     from scipy.io import wavfile
     items = []
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
@@ -222,7 +222,7 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
-               sample_rate: int = 22050, loudness: float = None, stoi: bool = False) -> Dict[str, np.ndarray]:
+               sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
@@ -240,10 +240,15 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     stoi=True (copy synthesis: every item carries "wav", its recording on the device at `sample_rate`, load_wav_inputs(keep_wav=True)):
     returns (pcm, report) with report[name] = {"stoi", "estoi", "status"} (FastDiff.stoi; status by name, the values NaN unless "OK"),
     measured on the float waveform of each micro-batch before the level epilogue and before any out_sample_rate, the recording cut to
-    the vocoded length (lens * hop)."""
+    the vocoded length (lens * hop).
+    pitch=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"f0_rmse_cents", "gpe", "vde",
+    "pitch_status"} (FastDiff.pitch at `sample_rate`, one F0 per mel frame; status by name), measured on the same waveforms as STOI.
+    With stoi=True as well, report[name] holds both sets of keys."""
     from . import resample as _resample
-    if stoi and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
-        raise ValueError("synthesize: stoi=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    for flag, what in ((stoi, "stoi"), (pitch, "pitch")):
+        if flag and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+            raise ValueError(f"synthesize: {what}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    scored = stoi or pitch
     report: Dict[str, dict] = {}
     R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
@@ -252,7 +257,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     lengths = [it["len"] for it in items]
     out: Dict[str, np.ndarray] = {}
     if not items:
-        return (out, report) if stoi else out
+        return (out, report) if scored else out
     hop = model.hop_length
     n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
 
@@ -292,9 +297,17 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
             if wav_of[name].numel() < t * hop:
                 raise ValueError(f"synthesize: the recording of {name} has {wav_of[name].numel()} samples, fewer than the {t * hop} vocoded")
             clean[b, : t * hop] = wav_of[name][: t * hop]
-        rec = model.stoi(clean, wav.reshape(B, n), valid=[t * hop for t in lens], sample_rate=sample_rate)
-        for b, name in enumerate(names):
-            report[name] = {"stoi": float(rec["stoi"][b]), "estoi": float(rec["estoi"][b]), "status": _stoi.STATUS[int(rec["status"][b])]}
+        valid = [t * hop for t in lens]
+        if stoi:
+            rec = model.stoi(clean, wav.reshape(B, n), valid=valid, sample_rate=sample_rate)
+            for b, name in enumerate(names):
+                report[name] = {"stoi": float(rec["stoi"][b]), "estoi": float(rec["estoi"][b]), "status": _stoi.STATUS[int(rec["status"][b])]}
+        if pitch:
+            from . import pitch as _pitch
+            rec = model.pitch(clean, wav.reshape(B, n), valid=valid, rate=sample_rate, hop=hop)
+            for b, name in enumerate(names):
+                report.setdefault(name, {}).update({"f0_rmse_cents": float(rec["rmse_cents"][b]), "gpe": float(rec["gpe"][b]), "vde": float(rec["vde"][b]),
+                                                    "pitch_status": _pitch.STATUS[int(rec["status"][b])]})
 
     def settle_on_device(p):
         # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
@@ -302,7 +315,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         ticket, wav, names, lens = p
         if model.settle(ticket):                     # run again on fp32: so is its epilogue
             pcm = epilogue(wav, lens)
-            if stoi:
+            if scored:
                 score(wav, names, lens)
             for b, (name, t) in enumerate(zip(names, lens)):
                 out[name] = pcm[b, : n_of(t)]
@@ -313,7 +326,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         if host_check and model.settle(ticket):      # an operand left the fp16 range: the call was run again on fp32 -- so is its epilogue
             host.copy_(epilogue(wav, lens), non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            if stoi:
+            if scored:
                 score(wav, names, lens)
         for b, (name, t) in enumerate(zip(names, lens)):
             out[name] = host[b, : n_of(t)].numpy().copy()
@@ -340,7 +353,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         ticket = getattr(model, "last_ticket", 0)
         # one epilogue call and one asynchronous copy per micro-batch; the previous batch is unpacked on the host while this one runs
         pcm = epilogue(wav, lens)
-        if stoi:
+        if scored:
             score(wav, names, lens)
         if return_device:
             for b, (name, t) in enumerate(zip(names, lens)):
@@ -362,12 +375,12 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         collect(pending)
     if host_check and prev_dev is not None:
         settle_on_device(prev_dev)
-    return (out, report) if stoi else out
+    return (out, report) if scored else out
 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
-                       sample_rate: int = 22050, loudness: float = None, stoi: bool = False) -> Dict[str, np.ndarray]:
+                       sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -385,9 +398,11 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
     "frames": by frames alone (rounds 1-5).
     out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate.
-    stoi=True is refused: the recordings are not scattered (score with synthesize(stoi=True))."""
+    stoi=True and pitch=True are refused: the recordings are not scattered (score with synthesize(stoi=True, pitch=True))."""
     if stoi:
         raise ValueError("synthesize_sharded: stoi=True is not available (the recordings are not scattered): use synthesize(stoi=True)")
+    if pitch:
+        raise ValueError("synthesize_sharded: pitch=True is not available (the recordings are not scattered): use synthesize(pitch=True)")
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -478,15 +493,17 @@ LONG_FORM_GROUP_FRAMES = 1 << 16      # mel frames per sample_long_batch call: 6
 
 def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
                     diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES, loudness: float = None,
-                    sample_rate: int = 22050, stoi: bool = False) -> Dict[str, np.ndarray]:
+                    sample_rate: int = 22050, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM through FastDiff.sample_long_batch (windowed: any length, device memory of one window batch): the
     utterances are taken in order in groups of up to group_frames mel frames, so their outputs fit, and the windows of a group share the
     sampler's batches.  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same,
     byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
     loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is.
-    stoi=True is refused (score the result with FastDiff.stoi, which takes any length)."""
+    stoi=True and pitch=True are refused (score the result with FastDiff.stoi and FastDiff.pitch, which take any length)."""
     if stoi:
         raise ValueError("synthesize_long: stoi=True is not available: score the waveforms with FastDiff.stoi")
+    if pitch:
+        raise ValueError("synthesize_long: pitch=True is not available: score the waveforms with FastDiff.pitch")
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -552,6 +569,9 @@ def main(argv=None):
     ap.add_argument("--stoi", action="store_true",
                     help="with --from_wav (copy synthesis): score every vocoded waveform against its recording with STOI and ESTOI on the "
                          "device, print the table and write <out_dir>/stoi.tsv")
+    ap.add_argument("--pitch", action="store_true",
+                    help="with --from_wav (copy synthesis): track F0 of every recording and vocoded waveform with YIN on the device and score "
+                         "the pitch (F0 RMSE in cents, gross pitch error, voicing decision error), print the table and write <out_dir>/pitch.tsv")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
@@ -559,6 +579,10 @@ def main(argv=None):
         ap.error("--stoi scores the vocoded waveform against its recording: it needs --from_wav")
     if args.stoi and args.long_form:
         ap.error("--stoi is not available with --long_form")
+    if args.pitch and not args.from_wav:
+        ap.error("--pitch scores the vocoded pitch against its recording's: it needs --from_wav")
+    if args.pitch and args.long_form:
+        ap.error("--pitch is not available with --long_form")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -571,22 +595,28 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"]["model"], strict=True)
     if args.mel_basis:
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
-    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=args.stoi) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=args.stoi or args.pitch) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
-        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi)
-    if args.stoi:
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi, pitch=args.pitch)
+    if args.stoi or args.pitch:
         pcm, report = pcm
         os.makedirs(args.out_dir, exist_ok=True)
-        lines = ["name\tstoi\testoi\tstatus"] + [f"{it['item_name']}\t{report[it['item_name']]['stoi']:.6f}\t{report[it['item_name']]['estoi']:.6f}\t"
-                                                 f"{report[it['item_name']]['status']}" for it in mine if it["item_name"] in report]
-        print("\n".join(lines))
-        with open(os.path.join(args.out_dir, "stoi.tsv" if world == 1 else f"stoi.rank{rank}.tsv"), "w") as f:
-            f.write("\n".join(lines) + "\n")
+        rows = [(it["item_name"], report[it["item_name"]]) for it in mine if it["item_name"] in report]
+        tables = []
+        if args.stoi:
+            tables.append(("stoi", ["name\tstoi\testoi\tstatus"] + [f"{name}\t{r['stoi']:.6f}\t{r['estoi']:.6f}\t{r['status']}" for name, r in rows]))
+        if args.pitch:
+            tables.append(("pitch", ["name\tf0_rmse_cents\tgpe\tvde\tstatus"] +
+                           [f"{name}\t{r['f0_rmse_cents']:.3f}\t{r['gpe']:.6f}\t{r['vde']:.6f}\t{r['pitch_status']}" for name, r in rows]))
+        for what, lines in tables:
+            print("\n".join(lines))
+            with open(os.path.join(args.out_dir, f"{what}.tsv" if world == 1 else f"{what}.rank{rank}.tsv"), "w") as f:
+                f.write("\n".join(lines) + "\n")
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 

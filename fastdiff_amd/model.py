@@ -384,6 +384,24 @@ class FastDiff(nn.Module):
         lib, h = self._ready(clean.device)
         return _stoi._measure(lib, h, self._stream(clean.device), clean, degraded, valid, sample_rate)
 
+    def pitch(self, clean, degraded, valid=None, **cfg):
+        """The pitch scores of `degraded` against `clean` on the device (fastdiff_amd/pitch.py): both are tracked with YIN on the mel
+        frame grid (one F0 per hop, where the reference's data_gen_utils.get_pitch runs Praat / WORLD) and the tracks compared.  Two
+        tensors [n] / [B, n] / [B, 1, n] of one shape -> a dict of numpy arrays over the batch: rmse_cents, gpe (NaN unless OK), vde,
+        frames, both_voiced, ref_voiced, deg_voiced, status (pitch.OK / SHORT / UNVOICED).  valid: [B] sample counts of a padded batch;
+        cfg: rate, hop, win, f0_min, f0_max, threshold.  Synchronises once, for the records."""
+        from . import pitch as _pitch
+        self._require_inference(clean, degraded)
+        lib, h = self._ready(clean.device)
+        return _pitch._measure(lib, h, self._stream(clean.device), clean, degraded, valid, cfg)
+
+    def pitch_track(self, wav, valid=None, **cfg):
+        """(f0, aper) of `wav` on the device, float32 [B, n // hop] (fastdiff_amd/pitch.py: track); does not synchronise."""
+        from . import pitch as _pitch
+        self._require_inference(wav, wav)
+        lib, h = self._ready(wav.device)
+        return _pitch._track(lib, h, self._stream(wav.device), wav, valid, cfg)
+
     def set_mel_filterbank(self, fb, variant="pwg", device=None):
         """Use `fb` [80, 513] (numpy / tensor, float32; librosa.filters.mel's own layout) as the filter bank of front-end `variant`
         instead of the library's restated default -- what a deployment that has librosa passes

@@ -23,6 +23,8 @@ truth as the mean |difference| of the two log-mel spectrograms, both from the li
 frames affect the two alike.  sample() looks at its range check before returning: this mode waits for the device once per batch.
 With stoi=True on top of it, the vocoded window is also scored against the ground truth with STOI and ESTOI (FastDiff.stoi's kernels,
 fastdiff_amd/stoi.py) at the corpus' sample rate: the records of every batch stay on the device until result() reads them.
+With pitch=True on top of it, both are tracked with YIN on the mel frame grid and the vocoded pitch is scored against the ground truth's
+(FastDiff.pitch's kernels, fastdiff_amd/pitch.py: F0 RMSE in cents, gross pitch error, voicing decision error), likewise.
 
 The default seed differs from TrainStep's (0), so that batch j of a pass does not repeat the noise of training step j.  The operators
 share the per-device step scratch with TrainStep (lvc_op._handle): a pass asks for far less of it than an optimizer step over the
@@ -38,7 +40,8 @@ DEFAULT_SEED = 0x56414C      # "VAL"
 
 
 class Validator:
-    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None, stoi=False, sample_rate=22050):
+    def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None, stoi=False, sample_rate=22050,
+                 pitch=False):
         if int(batch_size) < 1:
             raise ValueError(f"Validator: batch_size={batch_size} (at least 1)")
         if not 1 <= int(bins) <= lvc_op.EVAL_MAX_BINS:
@@ -85,6 +88,15 @@ class Validator:
             from . import stoi as _stoi
             self.sample_rate = int(sample_rate)                # the rate of the corpus' waveforms (fd_stoi_measure resamples to 10 kHz)
             self._stoi_rec = torch.zeros((self.n_batches * B, _stoi.RECORD.itemsize), device=dev, dtype=torch.uint8)      # slot b of batch j
+        self._pitch_rec = None
+        if pitch:
+            if self.table is None:
+                raise ValueError("Validator: pitch=True scores the vocoded windows, which needs sample_schedule")
+            from . import pitch as _pitch
+            self.sample_rate = int(sample_rate)
+            self._pitch_cfg = _pitch._config({"rate": self.sample_rate, "hop": corpus.hop_size})      # one F0 per mel frame; refused now, not inside a pass
+            _pitch.lags({"rate": self.sample_rate, "hop": corpus.hop_size})
+            self._pitch_rec = torch.zeros((self.n_batches * B, _pitch.RECORD.itemsize), device=dev, dtype=torch.uint8)     # slot b of batch j
 
     def state(self):
         """The pass's fd_train_state as a dict (`iter` = batches done).  Synchronises."""
@@ -115,6 +127,10 @@ class Validator:
                 from . import stoi as _stoi
                 lib, h = m._ready(self.device)
                 _stoi._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, self.sample_rate, rec=self._stoi_rec[j * B: (j + 1) * B])
+            if self._pitch_rec is not None:
+                from . import pitch as _pitch
+                lib, h = m._ready(self.device)
+                _pitch._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, self._pitch_cfg, rec=self._pitch_rec[j * B: (j + 1) * B])
         # last: it advances the batch index, behind every read of it
         lvc_op.eval_accumulate(self.values, self.picked, self._acc, steps=self.steps, T_train=self.T_train, bins=self.bins,
                                item_out=self.item_loss, advance=self._state)
@@ -140,7 +156,9 @@ class Validator:
     def result(self):
         """{"loss", "items", "nonfinite", "loss_by_t" [bins], "count_by_t" [bins], "item_loss" [n]} of the last pass, plus "mel_l1" and
         "item_mel_l1" [n] with sample_schedule, plus "stoi", "estoi" (the means over the items with status OK), "item_stoi", "item_estoi"
-        [n] (NaN where not OK) and "stoi_skipped" (the items not OK) with stoi=True.  loss = the mean over the items (the reference's validation_end averages batch means:
+        [n] (NaN where not OK) and "stoi_skipped" (the items not OK) with stoi=True, plus "f0_rmse_cents", "gpe" (the means over the items
+        with status OK), "vde" (over the items OK or UNVOICED), "item_f0_rmse_cents", "item_gpe", "item_vde" [n] (NaN where not measured) and
+        "pitch_skipped" (the items not OK) with pitch=True.  loss = the mean over the items (the reference's validation_end averages batch means:
         the two differ only through a short last batch); loss_by_t[k] = the mean over the items whose step fell into
         [k T / bins, (k + 1) T / bins), NaN where none did.  Synchronises once."""
         acc = lvc_op.read_eval_state(self._acc, self.bins)
@@ -161,4 +179,14 @@ class Validator:
                 out["item_" + key] = item
                 out[key] = float(item[ok].mean()) if ok.any() else float("nan")
             out["stoi_skipped"] = int(n - ok.sum())
+        if self._pitch_rec is not None:
+            from . import pitch as _pitch
+            rec = _pitch._record(self._pitch_rec)            # slot b of batch j is item j B + b, as above
+            n = self.corpus.n_items
+            ok = rec["status"][:n] == _pitch.OK
+            for key, name, use in (("rmse_cents", "f0_rmse_cents", ok), ("gpe", "gpe", ok), ("vde", "vde", ok | (rec["status"][:n] == _pitch.UNVOICED))):
+                item = np.where(use, rec[key][:n], np.nan)
+                out["item_" + name] = item
+                out[name] = float(item[use].mean()) if use.any() else float("nan")
+            out["pitch_skipped"] = int(n - ok.sum())
         return out

@@ -222,6 +222,87 @@ FD_API int64_t fd_stoi_frames(int64_t n10k);
 FD_API int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid, int rate,
                            fd_stoi *rec_dev, void *stream);
 
+/* F0 tracking (YIN: de Cheveigne and Kawahara 2002) and the pitch scores of a vocoded waveform against its recording: F0 RMSE in cents,
+ * gross pitch error, voicing decision error.  The reference's data pipeline extracts one F0 per mel frame with Praat or WORLD
+ * (data_gen/tts/data_gen_utils.py: get_pitch, 80 .. 750 Hz, one value per hop); neither is in the build image, so THIS TEXT defines the
+ * measurement and tests/pitch_ref.py restates it in float64 numpy.  It is YIN, not Praat's autocorrelation method and not WORLD: the
+ * values differ from the reference's binarised F0, the frame grid is the same.
+ *
+ * Parameters (fd_pitch_config; fd_pitch_default_config fills the values in brackets): rate [22050], hop [256], win [1024], f0_min [80],
+ * f0_max [750], threshold [0.15].  Derived (fd_pitch_lags):
+ *     tau_min = floor(rate / f0_max),  tau_max = ceil(rate / f0_min),  L = tau_max + 2 (the lags 0 .. tau_max + 1: one past tau_max for
+ *     the interpolation),  span = win + tau_max + 1.
+ * A configuration is refused (FD_ERR_INVALID) when tau_min < 2, tau_max <= tau_min, L > FD_PITCH_MAX_LAGS, win < 64, win > 2048, hop < 1,
+ * or threshold is not inside (0, 1); also when rate < 1, f0_min or f0_max is not positive, or `reserved` is not 0.
+ *
+ * One utterance of n valid samples, at its own rate (nothing is resampled):
+ *  1. Frames.  F = n / hop (integer division; the mel frame count for n = T * hop; fd_pitch_frames).  Frame i reads `span` samples from
+ *     s_i = i * hop + hop / 2 - span / 2 (integer divisions); samples outside [0, n) read as zero.
+ *  2. Difference function.  d(tau) = sum_{j = 0}^{win - 1} (x[s + j] - x[s + j + tau])^2, tau = 0 .. tau_max + 1: the direct form, not
+ *     e(0) + e(tau) - 2 r(tau), whose cancellation at the minima is exactly where the answer is read.
+ *  3. Cumulative mean normalised difference.  d'(0) = 1;  d'(tau) = d(tau) tau / sum_{j = 1}^{tau} d(j);  where that sum is 0,
+ *     d'(tau) = 1 (silence is unvoiced).
+ *  4. Decision.  k0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold.  None: the frame is unvoiced, f0 = 0 and aper = the
+ *     minimum of d' over [tau_min, tau_max].  Otherwise walk down from k0:  k = k0;  while k + 1 <= tau_max and d'(k + 1) < d'(k): ++k.
+ *  5. Refinement.  a, b, c = d'(k - 1), d'(k), d'(k + 1);  den = a - 2 b + c;  off = 0.5 (a - c) / den if den > 0, else 0, clamped to
+ *     [-1, 1];  f0 = rate / (k + off),  aper = d'(k).
+ * Outputs: f0 (0 where unvoiced) and aper, float32 [B][out_pitch], F values per row.  Frames of a row behind its own F up to the F of
+ * the longest row (L / hop) are written as f0 = 0, aper = 1.
+ *
+ * Comparison of two tracks of one utterance over F frames (fd_pitch_compare; a frame is voiced when its f0 > 0):
+ *     rmse_cents = sqrt(mean over the both-voiced frames of (1200 log2(f_deg / f_ref))^2)
+ *     gpe        = the share of the both-voiced frames with |f_deg / f_ref - 1| > 0.2
+ *     vde        = the share of all F frames whose voicing differs
+ * Status.  FD_PITCH_SHORT: F = 0, all three are NaN;  FD_PITCH_UNVOICED: F > 0 and no frame is voiced in both, vde is valid and the other
+ * two are NaN;  FD_PITCH_OK otherwise.
+ *
+ * On the device.  fd_pitch_track: one workgroup per FD_PITCH_FRAME_TILE consecutive frames of one utterance stages their samples in LDS
+ * once (they overlap by span - hop); where a large hop would not let the tile fit into FD_PITCH_STAGE_FLOATS samples, g frames at a
+ * time, g = min(FD_PITCH_FRAME_TILE, 1 + (FD_PITCH_STAGE_FLOATS - span) / hop) (integer division; a span alone always fits).  A wavefront takes one (frame, chunk of FD_PITCH_LAG_CHUNK lags) after the other, a lane per lag:
+ * x[s + j] is an LDS broadcast, x[s + j + tau] is conflict-free across the lanes.  d(tau) is summed in float32 into four accumulators
+ * (j mod 4) that are added as (a0 + a1) + (a2 + a3): an order that depends on nothing but win.  Steps 3-5 run in float64 from the float32
+ * sums, a wavefront per frame: the lanes own consecutive runs of lags, the running sum is a scan over the lanes, k0 and k are minimum
+ * reductions over lag indices (the lowest index, no atomics).  fd_pitch_compare: one workgroup per utterance, float64 partials over 256
+ * consecutive runs of frames added in run order.  Every sum has a fixed order that depends on the utterance alone: a row is bit-identical
+ * alone, anywhere in a ragged batch with anything behind it, at any row pitch and from call to call.  Nothing at or behind valid[b] is
+ * read.  The only scratch is the device copy of valid / frames, in a buffer of the handle that grows at the first call that needs more --
+ * never inside a stream capture, where such a call is refused with FD_ERR_STATE. */
+#define FD_PITCH_MAX_LAGS 1024      /* the largest L = tau_max + 2 */
+#define FD_PITCH_FRAME_TILE 4       /* consecutive frames of one utterance per workgroup of the tracker */
+#define FD_PITCH_LAG_CHUNK 64       /* lags of one frame per wavefront pass of the tracker */
+#define FD_PITCH_STAGE_FLOATS 6144  /* samples of a tile's frames that are staged in LDS together */
+enum { FD_PITCH_OK = 0, FD_PITCH_SHORT = 1, FD_PITCH_UNVOICED = 2 };
+typedef struct fd_pitch_config {
+    int32_t rate, hop, win, reserved;      /* reserved: 0 */
+    double f0_min, f0_max, threshold;
+} fd_pitch_config;                         /* 40 bytes */
+typedef struct fd_pitch {
+    double rmse_cents, gpe;    /* NaN unless status is FD_PITCH_OK */
+    double vde;                /* NaN when status is FD_PITCH_SHORT */
+    int32_t frames;            /* F */
+    int32_t both_voiced, ref_voiced, deg_voiced;
+    int32_t status;            /* FD_PITCH_* */
+    int32_t reserved;          /* 0 */
+} fd_pitch;                    /* 48 bytes */
+
+/* The bracketed defaults (pure host code).  FD_ERR_INVALID: a null pointer. */
+FD_API int fd_pitch_default_config(fd_pitch_config *cfg);
+/* tau_min and tau_max of a configuration (pure host code; either pointer may be NULL).  FD_ERR_INVALID: a null or refused configuration. */
+FD_API int fd_pitch_lags(const fd_pitch_config *cfg, int *tau_min, int *tau_max);
+/* F for n samples (pure host code).  FD_ERR_INVALID (< 0): n < 0 or hop < 1. */
+FD_API int64_t fd_pitch_frames(int64_t n, int hop);
+/* wav [B][L] device float -> f0_dev, aper_dev [B][out_pitch] device float, asynchronous on `stream`.  valid: HOST [B] or NULL = samples of
+ * each row that count (0 .. L).  B 1 .. 4096, L >= 1 with L / hop <= 2^30, out_pitch >= max(L / hop, 1).  Like fd_stoi_measure it does not
+ * settle a pending lazily checked fd_sample.  FD_ERR_INVALID: a null pointer, a refused configuration, B, L, out_pitch or valid[b] out of
+ * range; FD_ERR_STATE: the scratch buffer would have to grow inside a stream capture. */
+FD_API int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_pitch_config *cfg, float *f0_dev,
+                          float *aper_dev, int64_t out_pitch, void *stream);
+/* f0_ref, f0_deg [B][pitch] device float (two tracks of fd_pitch_track) -> rec_dev [B] device records, asynchronous on `stream`.
+ * frames: HOST [B] or NULL = frames of each row that count (0 .. pitch; NULL: pitch).  B 1 .. 4096, pitch 1 .. 2^30.
+ * FD_ERR_INVALID: a null pointer, B, pitch or frames[b] out of range; FD_ERR_STATE: as above. */
+FD_API int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int B, int64_t pitch, const int64_t *frames,
+                            fd_pitch *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
