@@ -213,9 +213,7 @@ static void release_handle(fd_context *h)
         if (sl.host) hipHostFree(sl.host);
         if (sl.done) hipEventDestroy(sl.done);
     }
-    for (void *p : h->mel_allocs) hipFree(p);
-    for (auto &t : h->resample_tabs) hipFree(const_cast<float *>(t.dev));
-    if (h->stoi_tab) hipFree(const_cast<float *>(h->stoi_tab));
+    for (void *p : h->tables) hipFree(p);
     if (h->ev_switch) hipEventDestroy(h->ev_switch);
     if (h->cap_stream) hipStreamDestroy(h->cap_stream);
     delete h;
@@ -455,6 +453,16 @@ int fd_stage_commit(fd_handle h, fd_context::StageSlot *sl, hipStream_t stream)
 {
     FD_HIP(h, hipEventRecord(sl->done, stream));
     return FD_OK;
+}
+// host bytes -> the device array `dev` through one slot (the call does not wait for the copy)
+int fd_stage_upload(fd_handle h, const void *src, size_t bytes, void *dev, hipStream_t stream)
+{
+    fd_context::StageSlot *sl = nullptr;
+    const int rc = fd_stage_acquire(h, bytes, &sl);
+    if (rc != FD_OK) return rc;
+    memcpy(sl->host, src, bytes);
+    FD_HIP(h, hipMemcpyAsync(dev, sl->host, bytes, hipMemcpyHostToDevice, stream));
+    return fd_stage_commit(h, sl, stream);
 }
 
 // One stream at a time per handle: a call on another stream than the previous one first settles what is pending there and then makes

@@ -1,8 +1,7 @@
-// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h: the mel front-end in front of the vocoder and the int16
-// waveform epilogue behind it, sample-rate conversion (fd_resample) and BS.1770 loudness (fd_loudness_*) in
-// front of and behind both, STOI / ESTOI (fd_stoi_*) and F0 tracking with the pitch scores (fd_pitch_*) of a vocoded waveform against its
-// recording, taps, layout
-// introspection, counters and per-kernel profiling.
+// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
+// sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
+// waveform against its recording: STOI / ESTOI (fd_stoi_*) and F0 tracking with the pitch scores (fd_pitch_*).  Then taps, layout
+// introspection, counters and per-kernel profiling.  
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -15,6 +14,73 @@
 #include "fd_resample.h"
 
 extern "C" {
+
+// The host path the waveform tools below share ("One host path under these tools"): check_counts, enter, reserve, upload_table,
+// upload_counts, and run (fd_host.h) ----------------------------------------------------------------------------------------------
+static_assert(sizeof(long long) == sizeof(int64_t), "the kernels read the callers' int64_t counts as long long");
+
+// the caller's counts [B] (null: every row whole) lie in [lo, hi]; checked before the call touches the device or the handle
+static int check_counts(fd_handle h, const char *who, const char *name, const int64_t *counts, int B, int64_t lo, int64_t hi)
+{
+    for (int b = 0; counts && b < B; ++b)
+        if (counts[b] < lo || counts[b] > hi)
+            FD_FAIL(h, FD_ERR_INVALID, "%s: %s[%d] = %lld outside [%lld, %lld]", who, name, b, (long long)counts[b], (long long)lo, (long long)hi);
+    return FD_OK;
+}
+
+// the handle's device, and a pending sampler call settled unless it is lazily checked: these tools touch no sampler state, and their
+// result is provisional with such a call
+static int enter(fd_handle h)
+{
+    FD_HIP(h, hipSetDevice(h->device));
+    return (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);
+}
+
+static bool capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return false;
+    (void)hipGetLastError();
+    return true;
+}
+
+// a tool's own scratch holds at least `need` bytes: grown at the first call that needs more (hipFree waits for the calls that still use
+// the old one), never inside a capture, whose graph would keep the old pointers
+static int reserve(fd_handle h, const char *who, Scratch &s, size_t need, hipStream_t stream)
+{
+    if (s.bytes >= need) return FD_OK;
+    if (capturing(stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes, which cannot happen inside a stream capture: call it once before", who, need);
+    if (s.p) FD_HIP(h, hipFree(s.p));
+    s = Scratch{};
+    void *p = nullptr;
+    FD_HIP(h, hipMalloc(&p, need));
+    s.p = static_cast<float *>(p);
+    s.bytes = need;
+    return FD_OK;
+}
+
+// a constant table -> device memory the handle owns until fd_destroy (a replaced table stays valid for launches still in flight); a
+// synchronous copy from pageable memory: complete on return.  Whether this may happen inside a capture is the caller's decision.
+static int upload_table(fd_handle h, const char *who, const void *src, size_t bytes, const void **dst)
+{
+    void *d = nullptr;
+    FD_HIP(h, hipMalloc(&d, bytes));
+    const hipError_t e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        FD_FAIL(h, FD_ERR_HIP, "%s: table upload failed: %s", who, hipGetErrorString(e));
+    }
+    h->tables.push_back(d);
+    *dst = d;
+    return FD_OK;
+}
+
+// host counts [B] -> `dst` on the device through the pinned staging ring (null counts: nothing to do)
+static int upload_counts(fd_handle h, const int64_t *counts, int B, long long *dst, hipStream_t stream)
+{
+    return counts ? fd_stage_upload(h, counts, sizeof(long long) * B, dst, stream) : FD_OK;
+}
 
 // The DEFAULT filter bank of a front-end, dense [80][513]: librosa.filters.mel(22050, 1024, 80, fmin, fmax) restated in double
 // precision (Slaney mel scale, triangular weights on the FFT bin centres, each filter scaled by 2 / (f[m+2] - f[m])) for 'pwg' (fmin
@@ -45,15 +111,7 @@ static std::vector<float> default_mel_bank(int variant)
     return fb;
 }
 
-static int mel_upload(fd_handle h, const void *src, size_t bytes, const void **dst)
-{
-    void *d = nullptr;
-    FD_HIP(h, hipMalloc(&d, bytes));
-    h->mel_allocs.push_back(d);        // freed at fd_destroy: a replaced table stays valid for launches still in flight
-    FD_HIP(h, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    *dst = d;
-    return FD_OK;
-}
+static int mel_upload(fd_handle h, const void *src, size_t bytes, const void **dst) { return upload_table(h, "mel tables", src, bytes, dst); }
 
 // A dense bank [80][513] as the kernel reads it: per filter the first non-zero bin, the span up to the last non-zero one, and the
 // weights of that span exactly as given (k_mel_frontend adds w[k] * |X_k| over the span in ascending k; a zero inside it adds zero).
@@ -149,42 +207,23 @@ int fd_mel_spectrogram(fd_handle h, const float *wav, int B, int64_t n_samples, 
     if (T < 1 || T > 1 + n_samples / 256) FD_FAIL(h, FD_ERR_INVALID, "fd_mel_spectrogram: T=%d outside 1..1+n_samples/256=%lld", T, (long long)(1 + n_samples / 256));
     if (h->mel_variant == MEL_TACOTRON && n_samples <= 512)      // F.pad(mode='reflect') needs pad < length (tacotron/stft.py:84-88)
         FD_FAIL(h, FD_ERR_INVALID, "fd_mel_spectrogram: reflect padding of 512 needs more than 512 samples, got %lld", (long long)n_samples);
-    FD_HIP(h, hipSetDevice(h->device));
-    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // the front-end touches no sampler state
+    int rc = enter(h);
     if (rc != FD_OK) return rc;
     rc = ensure_mel_tables(h);
     if (rc != FD_OK) return rc;
-    fdk::Launch L = {h, (hipStream_t)stream, false};
-    hipError_t e = fdk::mel_frontend(L, wav, B, n_samples, mel, T);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_mel_spectrogram: %s", hipGetErrorString(e));
-    return FD_OK;
+    return run(h, stream, "fd_mel_spectrogram", [&](const fdk::Launch &L) { return fdk::mel_frontend(L, wav, B, n_samples, mel, T); });
 }
 
 int fd_peak_normalize_int16_ragged(fd_handle h, const float *wav, int B, int64_t len, const int64_t *valid, int16_t *pcm, void *stream)
 {
     if (!h || !wav || !pcm || B <= 0 || len <= 0 || B > 4096) return FD_ERR_INVALID;
-    FD_HIP(h, hipSetDevice(h->device));
-    if (!(h->pending.active && h->pending.lazy)) {      // a lazily checked call stays pending: the epilogue's result is provisional with it
-        const int rcs = fd_settle(h);
-        if (rcs != FD_OK) return rcs;
-    }
-    const long long *valid_dev = nullptr;
-    if (valid) {
-        for (int b = 0; b < B; ++b)
-            if (valid[b] < 1 || valid[b] > len) FD_FAIL(h, FD_ERR_INVALID, "fd_peak_normalize_int16_ragged: valid[%d] = %lld outside [1, %lld]", b, (long long)valid[b], (long long)len);
-        fd_context::StageSlot *sl = nullptr;
-        int rc = fd_stage_acquire(h, sizeof(long long) * B, &sl);
-        if (rc != FD_OK) return rc;
-        for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = valid[b];
-        long long *dst = reinterpret_cast<long long *>(reinterpret_cast<char *>(h->scratch) + 32768);      // behind the abs-max words
-        FD_HIP(h, hipMemcpyAsync(dst, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, (hipStream_t)stream));
-        if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
-        valid_dev = dst;
-    }
-    fdk::Launch L = {h, (hipStream_t)stream, false};
-    hipError_t e = fdk::peak_normalize_int16(L, wav, B, len, pcm, valid_dev);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_peak_normalize_int16: %s", hipGetErrorString(e));
-    return FD_OK;
+    int rc = enter(h);      // (this entry point has always settled before it looks at the counts)
+    if (rc != FD_OK) return rc;
+    if ((rc = check_counts(h, "fd_peak_normalize_int16_ragged", "valid", valid, B, 1, len)) != FD_OK) return rc;
+    long long *valid_dev = reinterpret_cast<long long *>(reinterpret_cast<char *>(h->scratch) + 32768);      // behind the abs-max words
+    if ((rc = upload_counts(h, valid, B, valid_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, "fd_peak_normalize_int16",
+               [&](const fdk::Launch &L) { return fdk::peak_normalize_int16(L, wav, B, len, pcm, valid ? valid_dev : nullptr); });
 }
 
 int fd_peak_normalize_int16(fd_handle h, const float *wav, int B, int64_t len, int16_t *pcm, void *stream)
@@ -217,28 +256,18 @@ int fd_resample_taps(int sr_in, int sr_out, float *taps, int64_t capacity, int *
     return n;
 }
 
-// the device table of a ratio: built and uploaded at its first use (a synchronous copy from pageable memory: complete on return)
+// the device table of a ratio: built and uploaded at its first use
 static int resample_table(fd_handle h, const fdr::Ratio &r, hipStream_t stream, const float **dev)
 {
     for (const auto &t : h->resample_tabs)
         if (t.up == r.up && t.down == r.down) { *dev = t.dev; return FD_OK; }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
+    if (capturing(stream))
         FD_FAIL(h, FD_ERR_STATE, "fd_resample: the table of ratio %d/%d is built at the first use of that ratio, which cannot happen inside a stream capture: call it once before",
                 r.up, r.down);
-    }
     const std::vector<float> tab = fdr::table(r);
-    void *d = nullptr;
-    FD_HIP(h, hipMalloc(&d, tab.size() * sizeof(float)));
-    const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d);
-        FD_FAIL(h, FD_ERR_HIP, "fd_resample: table upload failed: %s", hipGetErrorString(e));
-    }
-    h->resample_tabs.push_back({r.up, r.down, static_cast<const float *>(d)});
-    *dev = static_cast<const float *>(d);
-    return FD_OK;
+    const int rc = upload_table(h, "fd_resample", tab.data(), tab.size() * sizeof(float), reinterpret_cast<const void **>(dev));
+    if (rc == FD_OK) h->resample_tabs.push_back({r.up, r.down, *dev});
+    return rc;
 }
 
 int fd_resample(fd_handle h, const void *src, int format, int channels, int B, int64_t n_in, int64_t src_pitch, const int64_t *valid_in,
@@ -259,19 +288,13 @@ int fd_resample(fd_handle h, const void *src, int format, int channels, int B, i
     if (src_pitch < n_in * channels)
         FD_FAIL(h, FD_ERR_INVALID, "fd_resample: src_pitch = %lld < n_in * channels = %lld", (long long)src_pitch, (long long)(n_in * channels));
     if (dst_pitch < n_out) FD_FAIL(h, FD_ERR_INVALID, "fd_resample: dst_pitch = %lld < out_len(n_in) = %lld", (long long)dst_pitch, (long long)n_out);
-    if (valid_in)
-        for (int b = 0; b < B; ++b)
-            if (valid_in[b] < 1 || valid_in[b] > n_in)
-                FD_FAIL(h, FD_ERR_INVALID, "fd_resample: valid_in[%d] = %lld outside [1, %lld]", b, (long long)valid_in[b], (long long)n_in);
-    FD_HIP(h, hipSetDevice(h->device));
-    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // the resampler touches no sampler state
-    if (rc != FD_OK) return rc;
+    int rc = check_counts(h, "fd_resample", "valid_in", valid_in, B, 1, n_in);
+    if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
     const float *table = nullptr;
     if (r.up != r.down && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
-    fdk::Launch L = {h, (hipStream_t)stream, false};
-    const hipError_t e = fdk::resample(L, src, format, channels, B, n_in, src_pitch, valid_in, r.up, r.down, r.half, r.K, r.Kp, n_out, table, dst, dst_pitch);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_resample: %s", hipGetErrorString(e));
-    return FD_OK;
+    return run(h, stream, "fd_resample", [&](const fdk::Launch &La) {
+        return fdk::resample(La, src, format, channels, B, n_in, src_pitch, valid_in, r.up, r.down, r.half, r.K, r.Kp, n_out, table, dst, dst_pitch);
+    });
 }
 
 // BS.1770 loudness (fastdiff_hip_ext.h; the filter design: fd_loudness.h, the kernels: fd_kernels_loudness.hip) ------------------------
@@ -298,44 +321,17 @@ static int loudness_call(fd_handle h, const char *who, const float *wav, int B, 
     if (normalize && !out_f32 && !out_pcm) FD_FAIL(h, FD_ERR_INVALID, "%s: neither out_f32 nor out_pcm", who);
     if (normalize && !isfinite(target)) FD_FAIL(h, FD_ERR_INVALID, "%s: the target is not finite", who);
     if (!normalize && !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null rec_dev", who);
-    if (valid)
-        for (int b = 0; b < B; ++b)
-            if (valid[b] < 1 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [1, %lld]", who, b, (long long)valid[b], (long long)L);
-    FD_HIP(h, hipSetDevice(h->device));
-    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the peak epilogue: provisional with a lazily checked call
-    if (rc != FD_OK) return rc;
-    const size_t need = fdk::loudness_scratch_bytes(B, L, rate);
+    int rc = check_counts(h, who, "valid", valid, B, 1, L);
+    if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
     Scratch &s = h->loud_scratch;
-    if (s.bytes < need) {      // grown at the first call that needs more; hipFree waits for the calls that still use the old one
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes for B = %d, L = %lld, which cannot happen inside a stream capture: call it once before",
-                    who, need, B, (long long)L);
-        }
-        if (s.p) FD_HIP(h, hipFree(s.p));
-        s = Scratch{};
-        void *p = nullptr;
-        FD_HIP(h, hipMalloc(&p, need));
-        s.p = static_cast<float *>(p);
-        s.bytes = need;
-    }
-    const long long *valid_dev = nullptr;
-    if (valid) {
-        fd_context::StageSlot *sl = nullptr;
-        if ((rc = fd_stage_acquire(h, sizeof(long long) * B, &sl)) != FD_OK) return rc;
-        for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = valid[b];
-        long long *dst = fdk::loudness_valid_slot(s.p, B, L, rate);
-        FD_HIP(h, hipMemcpyAsync(dst, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, (hipStream_t)stream));
-        if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
-        valid_dev = dst;
-    }
+    if ((rc = reserve(h, who, s, fdk::loudness_scratch_bytes(B, L, rate), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *valid_dev = fdk::loudness_valid_slot(s.p, B, L, rate);
+    if ((rc = upload_counts(h, valid, B, valid_dev, (hipStream_t)stream)) != FD_OK) return rc;
     fdk::LoudnessFilter F;
     fdl::make_filter(rate, F);
-    fdk::Launch La = {h, (hipStream_t)stream, false};
-    const hipError_t e = fdk::loudness(La, wav, B, L, valid_dev, rate, F, normalize, target, rec_dev, out_f32, out_pcm, s.p);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FD_OK;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::loudness(La, wav, B, L, valid ? valid_dev : nullptr, rate, F, normalize, target, rec_dev, out_f32, out_pcm, s.p);
+    });
 }
 
 int fd_loudness_measure(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int rate, fd_loudness *rec_dev, void *stream)
@@ -381,70 +377,41 @@ int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int 
     }
     const int64_t n10 = resampled ? fdr::out_len(L, r) : L;
     if (n10 > ((int64_t)1 << 30)) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is %lld samples at 10 kHz, at most 2^30 are supported", who, (long long)L, (long long)n10);
-    if (valid)
-        for (int b = 0; b < B; ++b)
-            if (valid[b] < 1 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [1, %lld]", who, b, (long long)valid[b], (long long)L);
-    FD_HIP(h, hipSetDevice(h->device));
-    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the loudness meter: provisional with a lazily checked call
-    if (rc != FD_OK) return rc;
-    const size_t need = fdk::stoi_scratch_bytes(B, n10, resampled);
-    Scratch &s = h->stoi_scratch;
-    if (s.bytes < need || !h->stoi_tab) {      // grown at the first call that needs more; hipFree waits for the calls that still use the old one
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes for B = %d, L = %lld, which cannot happen inside a stream capture: call it once before",
-                    who, need, B, (long long)L);
-        }
-        if (!h->stoi_tab) {      // a synchronous copy from pageable memory: complete on return
-            float tab[fds::TAB_FLOATS];
-            fds::tables(tab);
-            void *d = nullptr;
-            FD_HIP(h, hipMalloc(&d, sizeof(tab)));
-            const hipError_t e = hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                hipFree(d);
-                FD_FAIL(h, FD_ERR_HIP, "%s: table upload failed: %s", who, hipGetErrorString(e));
-            }
-            h->stoi_tab = static_cast<const float *>(d);
-        }
-        if (s.bytes < need) {
-            if (s.p) FD_HIP(h, hipFree(s.p));
-            s = Scratch{};
-            void *p = nullptr;
-            FD_HIP(h, hipMalloc(&p, need));
-            s.p = static_cast<float *>(p);
-            s.bytes = need;
-        }
+    int rc = check_counts(h, who, "valid", valid, B, 1, L);
+    if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
+    if (!h->stoi_tab) {
+        if (capturing((hipStream_t)stream))
+            FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table is uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
+        float tab[fds::TAB_FLOATS];
+        fds::tables(tab);
+        if ((rc = upload_table(h, who, tab, sizeof(tab), reinterpret_cast<const void **>(&h->stoi_tab))) != FD_OK) return rc;
     }
+    Scratch &s = h->stoi_scratch;
+    if ((rc = reserve(h, who, s, fdk::stoi_scratch_bytes(B, n10, resampled), (hipStream_t)stream)) != FD_OK) return rc;
     const float *table = nullptr;
     if (resampled && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
     const fdk::StoiSlots sl10 = fdk::stoi_slots(s.p, B, n10, resampled);
-    const long long *lens_dev = nullptr;
-    if (valid) {      // each pair's own length at 10 kHz, through the staging ring as the loudness meter's lengths
-        fd_context::StageSlot *sl = nullptr;
-        if ((rc = fd_stage_acquire(h, sizeof(long long) * B, &sl)) != FD_OK) return rc;
-        for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = resampled ? fdr::out_len(valid[b], r) : valid[b];
-        FD_HIP(h, hipMemcpyAsync(sl10.lens, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, (hipStream_t)stream));
-        if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
-        lens_dev = sl10.lens;
+    std::vector<int64_t> lens10;      // each pair's own length at 10 kHz
+    if (valid && resampled) {
+        lens10.resize(B);
+        for (int b = 0; b < B; ++b) lens10[b] = fdr::out_len(valid[b], r);
     }
-    fdk::Launch La = {h, (hipStream_t)stream, false};
-    const float *x = clean, *y = degraded;
-    long long pitch = L;
-    if (resampled) {
-        for (int k = 0; k < 2; ++k) {
-            const hipError_t e = fdk::resample(La, k ? degraded : clean, FD_PCM_F32, 1, B, L, L, valid, r.up, r.down, r.half, r.K, r.Kp, n10, table,
-                                               k ? sl10.y10 : sl10.x10, sl10.pitch10);
-            if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-        }
-        x = sl10.x10; y = sl10.y10; pitch = sl10.pitch10;
-    }
+    if ((rc = upload_counts(h, lens10.empty() ? valid : lens10.data(), B, sl10.lens, (hipStream_t)stream)) != FD_OK) return rc;
     fdk::StoiBands bd;
     fds::bands(bd.lo, bd.hi);
-    const hipError_t e = fdk::stoi(La, x, y, pitch, B, n10, lens_dev, h->stoi_tab, bd, rec_dev, s.p, resampled);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FD_OK;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        const float *x = clean, *y = degraded;
+        long long pitch = L;
+        if (resampled) {
+            for (int k = 0; k < 2; ++k) {
+                const hipError_t e = fdk::resample(La, k ? degraded : clean, FD_PCM_F32, 1, B, L, L, valid, r.up, r.down, r.half, r.K, r.Kp, n10, table,
+                                                   k ? sl10.y10 : sl10.x10, sl10.pitch10);
+                if (e != hipSuccess) return e;
+            }
+            x = sl10.x10; y = sl10.y10; pitch = sl10.pitch10;
+        }
+        return fdk::stoi(La, x, y, pitch, B, n10, valid ? sl10.lens : nullptr, h->stoi_tab, bd, rec_dev, s.p, resampled);
+    });
 }
 
 // F0 tracking and the pitch scores (fastdiff_hip_ext.h; constants, lags and counts: fd_pitch.h, the kernels: fd_kernels_pitch.hip) ------
@@ -470,36 +437,18 @@ int64_t fd_pitch_frames(int64_t n, int hop)
     return fdp::frames(n, hop);
 }
 
-// the host counts [B] of a pitch call -> slot `which` (0: fd_pitch_track's valid, 1: fd_pitch_compare's frames) of the handle's
-// pitch scratch, through the staging ring as the STOI lengths; *dev = null when counts is null
+// the host counts [B] of a pitch call -> slot `which` (0: fd_pitch_track's valid, 1: fd_pitch_compare's frames) of the handle's pitch
+// scratch, allocated at the first call that passes counts; *dev = null when counts is null
 static int pitch_counts(fd_handle h, const char *who, const int64_t *counts, int B, int which, hipStream_t stream, const long long **dev)
 {
     *dev = nullptr;
     if (!counts) return FD_OK;
-    const size_t slot = (sizeof(long long) * 4096 + 255) & ~(size_t)255, need = 2 * slot;      // B <= 4096
-    Scratch &s = h->pitch_scratch;
-    if (s.bytes < need) {      // allocated at the first call that passes counts; never inside a capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes, which cannot happen inside a stream capture: call it once before", who, need);
-        }
-        if (s.p) FD_HIP(h, hipFree(s.p));
-        s = Scratch{};
-        void *p = nullptr;
-        FD_HIP(h, hipMalloc(&p, need));
-        s.p = static_cast<float *>(p);
-        s.bytes = need;
-    }
-    long long *dst = reinterpret_cast<long long *>(reinterpret_cast<char *>(s.p) + which * slot);
-    fd_context::StageSlot *sl = nullptr;
-    int rc = fd_stage_acquire(h, sizeof(long long) * B, &sl);
+    const size_t slot = (sizeof(long long) * 4096 + 255) & ~(size_t)255;      // B <= 4096
+    const int rc = reserve(h, who, h->pitch_scratch, 2 * slot, stream);
     if (rc != FD_OK) return rc;
-    for (int b = 0; b < B; ++b) reinterpret_cast<long long *>(sl->host)[b] = counts[b];
-    FD_HIP(h, hipMemcpyAsync(dst, sl->host, sizeof(long long) * B, hipMemcpyHostToDevice, stream));
-    if ((rc = fd_stage_commit(h, sl, stream)) != FD_OK) return rc;
+    long long *dst = reinterpret_cast<long long *>(reinterpret_cast<char *>(h->pitch_scratch.p) + which * slot);
     *dev = dst;
-    return FD_OK;
+    return upload_counts(h, counts, B, dst, stream);
 }
 
 int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_pitch_config *cfg, float *f0_dev,
@@ -516,18 +465,11 @@ int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const int64_
     if (F > fdp::MAX_FRAMES) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is %lld frames, at most 2^30 are supported", who, (long long)L, (long long)F);
     if (out_pitch < std::max<int64_t>(F, 1))
         FD_FAIL(h, FD_ERR_INVALID, "%s: out_pitch = %lld is less than the %lld frames of L = %lld", who, (long long)out_pitch, (long long)F, (long long)L);
-    if (valid)
-        for (int b = 0; b < B; ++b)
-            if (valid[b] < 0 || valid[b] > L) FD_FAIL(h, FD_ERR_INVALID, "%s: valid[%d] = %lld outside [0, %lld]", who, b, (long long)valid[b], (long long)L);
-    FD_HIP(h, hipSetDevice(h->device));
-    int rc = (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);      // like the STOI call: provisional with a lazily checked call
-    if (rc != FD_OK) return rc;
+    int rc = check_counts(h, who, "valid", valid, B, 0, L);
+    if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
     const long long *lens_dev = nullptr;
     if ((rc = pitch_counts(h, who, valid, B, 0, (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
-    fdk::Launch La = {h, (hipStream_t)stream, false};
-    const hipError_t e = fdk::pitch_track(La, wav, L, B, L, lens_dev, *cfg, lg, f0_dev, aper_dev, out_pitch);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FD_OK;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::pitch_track(La, wav, L, B, L, lens_dev, *cfg, lg, f0_dev, aper_dev, out_pitch); });
 }
 
 int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int B, int64_t pitch, const int64_t *frames, fd_pitch *rec_dev,
@@ -538,18 +480,12 @@ int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int 
     if (!f0_ref || !f0_deg || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !f0_ref ? "f0_ref" : (!f0_deg ? "f0_deg" : "rec_dev"));
     if (B < 1 || B > 4096 || pitch < 1 || pitch > fdp::MAX_FRAMES)
         FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d tracks (1 .. 4096) of pitch = %lld frames (1 .. 2^30)", who, B, (long long)pitch);
-    if (frames)
-        for (int b = 0; b < B; ++b)
-            if (frames[b] < 0 || frames[b] > pitch)
-                FD_FAIL(h, FD_ERR_INVALID, "%s: frames[%d] = %lld outside [0, %lld]", who, b, (long long)frames[b], (long long)pitch);
-    FD_HIP(h, hipSetDevice(h->device));
-    const long long *frames_dev = nullptr;
-    int rc = pitch_counts(h, who, frames, B, 1, (hipStream_t)stream, &frames_dev);
+    int rc = check_counts(h, who, "frames", frames, B, 0, pitch);
     if (rc != FD_OK) return rc;
-    fdk::Launch La = {h, (hipStream_t)stream, false};
-    const hipError_t e = fdk::pitch_compare(La, f0_ref, f0_deg, pitch, B, frames_dev, rec_dev);
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FD_OK;
+    FD_HIP(h, hipSetDevice(h->device));      // no settle: the tracks are the caller's, and the scores touch no sampler state
+    const long long *frames_dev = nullptr;
+    if ((rc = pitch_counts(h, who, frames, B, 1, (hipStream_t)stream, &frames_dev)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::pitch_compare(La, f0_ref, f0_deg, pitch, B, frames_dev, rec_dev); });
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

@@ -137,17 +137,6 @@ int span_reserve(fd_handle h, size_t need)
     return FD_OK;
 }
 
-// host records -> the device array `dev`, through the pinned staging ring (the call does not wait for the copy)
-int upload_records(fd_handle h, const void *recs, size_t bytes, void *dev, hipStream_t stream)
-{
-    fd_context::StageSlot *sl = nullptr;
-    const int rc = fd_stage_acquire(h, bytes, &sl);
-    if (rc != FD_OK) return rc;
-    memcpy(sl->host, recs, bytes);
-    FD_HIP(h, hipMemcpyAsync(dev, sl->host, bytes, hipMemcpyHostToDevice, stream));
-    return fd_stage_commit(h, sl, stream);
-}
-
 int sample_spans(fd_handle h, const char *who, const fd_span *spans, int n_spans, const fd_step *table, int N, int ddim, uint64_t seed,
                  int window_frames, void *stream_)
 {
@@ -192,7 +181,7 @@ int sample_spans(fd_handle h, const char *who, const fd_span *spans, int n_spans
             ids.push_back((unsigned long long)s.stream_id);
             max_clen = std::max(max_clen, (int)w.clen);
         }
-        if ((rc = upload_records(h, recs, sizeof(fdk::SpanRec) * n, rec_dev, stream)) != FD_OK) return rc;
+        if ((rc = fd_stage_upload(h, recs, sizeof(fdk::SpanRec) * n, rec_dev, stream)) != FD_OK) return rc;
         hipError_t e = fdk::spans_gather(Lc, rec_dev, n, Wp, mel_w);
         if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: window gather failed: %s", who, hipGetErrorString(e));
         h->noise_ids = ids;
@@ -332,7 +321,7 @@ int fd_mel_ring_append(fd_handle h, const fd_ring_chunk *chunks, int n, void *st
         FD_HIP(h, hipMalloc(reinterpret_cast<void **>(&s.p), cap));
         s.bytes = cap;
     }
-    if ((rc = upload_records(h, chunks, bytes, s.p, stream)) != FD_OK) return rc;
+    if ((rc = fd_stage_upload(h, chunks, bytes, s.p, stream)) != FD_OK) return rc;
     const fdk::Launch Lc = {h, stream, false, nullptr};
     const hipError_t e = fdk::ring_append(Lc, reinterpret_cast<const fd_ring_chunk *>(s.p), n, longest);
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_mel_ring_append: launch failed: %s", hipGetErrorString(e));

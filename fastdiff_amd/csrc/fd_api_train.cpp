@@ -36,17 +36,6 @@ static hipError_t grow(Scratch &s, size_t floats)
     return e;
 }
 
-// What every entry point ends with once its arguments are checked: the handle's device, one Launch on `stream`, and a failure of
-// `launch` (a scratch allocation included) reported as "<who>: <HIP error>".
-template <class F>
-static int run(fd_handle h, void *stream, const char *who, F &&launch)
-{
-    FD_HIP(h, hipSetDevice(h->device));
-    const hipError_t e = launch(fdk::Launch{h, (hipStream_t)stream, false});
-    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FD_OK;
-}
-
 static bool slope_ok(float s) { return s > 0.0f && s <= 1.0f; }      // a leaky-relu slope: (0, 1], 1 = no activation
 
 static int check_batch(fd_handle h, int B, const char *who)

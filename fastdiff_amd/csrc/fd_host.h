@@ -1,5 +1,5 @@
-// fd_host.h -- shared by the host translation units of libfastdiff_hip.so (fd_api.cpp, fd_weights.cpp, fd_api_ext.cpp, fd_api_train.cpp):
-// the error macros and the few helpers of the core that the others call.
+// fd_host.h -- shared by the host translation units of libfastdiff_hip.so (fd_api.cpp, fd_weights.cpp, fd_api_ext.cpp, fd_api_span.cpp,
+// fd_api_train.cpp): the error macros and the few helpers of the core that the others call.
 #pragma once
 #include <stdio.h>
 
@@ -35,8 +35,21 @@ void drop_graph(fd_context *c);
 // the copies that read it
 int fd_stage_acquire(fd_handle h, size_t bytes, fd_context::StageSlot **out);
 int fd_stage_commit(fd_handle h, fd_context::StageSlot *sl, hipStream_t stream);
+// host bytes -> the device array `dev` through one slot of that ring (the call does not wait for the copy)
+int fd_stage_upload(fd_handle h, const void *src, size_t bytes, void *dev, hipStream_t stream);
 // one stream at a time per handle: a call on another stream first waits for the tail of the handle's last call; ... and the tail's mark
 int fd_follow_stream(fd_handle h, hipStream_t s);
 int fd_mark_tail(fd_handle h, hipStream_t s);
 }
 void fd_prof_drain(fd_context *c);
+
+// What an entry point ends with once its arguments are checked: the handle's device, one Launch on `stream`, and a failure of
+// `launch` (a scratch allocation inside it included) reported as "<who>: <HIP error>".
+template <class F>
+static int run(fd_handle h, void *stream, const char *who, F &&launch)
+{
+    FD_HIP(h, hipSetDevice(h->device));
+    const hipError_t e = launch(fdk::Launch{h, (hipStream_t)stream, false});
+    if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FD_OK;
+}

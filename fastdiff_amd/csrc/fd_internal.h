@@ -283,9 +283,9 @@ struct fd_context {
     int mel_variant = MEL_PWG;               // option "mel"
     std::vector<float> mel_bank[MEL_VARIANTS];   // the dense [80][513] bank each front-end uses (host copy: fd_get_mel_filterbank)
     bool mel_bank_user[MEL_VARIANTS] = {false, false};   // supplied through fd_set_mel_filterbank (else the restated default)
-    std::vector<void *> mel_allocs;           // device memory behind `mel` (built on first use, freed at fd_destroy)
+    std::vector<void *> tables;               // every constant table uploaded so far (mel, resampler, STOI): owned here, freed at fd_destroy
     struct ResampleTable { int up, down; const float *dev; };
-    std::vector<ResampleTable> resample_tabs; // fd_resample's polyphase tables, one per reduced ratio used so far (freed at fd_destroy)
+    std::vector<ResampleTable> resample_tabs; // fd_resample's polyphase tables, one per reduced ratio used so far (`dev` is in `tables`)
     int last_B = 0, last_T = 0;
     hipStream_t cap_stream = nullptr;
     // Calls on one handle share the workspace, the embedding rows and the pending range check: they are ordered by the stream they run
@@ -373,7 +373,7 @@ struct fd_context {
     long long n_span_batches = 0, n_span_windows = 0;   // fd_get_counter: fd_sample calls / windows made by the span entry points
     Scratch loud_scratch;                    // fd_loudness_measure / _normalize: peak words, lengths, tile states, partial sums, block powers
     Scratch stoi_scratch;                    // fd_stoi_measure: lengths, the 10 kHz signals, frame energies, src, band amplitudes, segment partials
-    const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call, freed at fd_destroy
+    const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call (in `tables`)
     Scratch pitch_scratch;                   // fd_pitch_track / _compare: the device copies of valid [B] and frames [B]
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;

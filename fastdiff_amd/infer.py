@@ -27,7 +27,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import schedules, shard
+from . import _scores, schedules, shard
 from .sampler import InferenceSchedule
 
 
@@ -245,10 +245,9 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     "pitch_status"} (FastDiff.pitch at `sample_rate`, one F0 per mel frame; status by name), measured on the same waveforms as STOI.
     With stoi=True as well, report[name] holds both sets of keys."""
     from . import resample as _resample
-    for flag, what in ((stoi, "stoi"), (pitch, "pitch")):
-        if flag and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
-            raise ValueError(f"synthesize: {what}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
-    scored = stoi or pitch
+    scored = _scores.enabled(stoi=stoi, pitch=pitch)
+    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+        raise ValueError(f"synthesize: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
     report: Dict[str, dict] = {}
     R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
@@ -288,8 +287,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     prev_dev = None                # return_device: (ticket, wav, names, lens) of the micro-batch nobody has settled yet
 
     def score(wav, names, lens):
-        # the recordings of the micro-batch next to its float waveform: one padded batch, one call, one record read
-        from . import stoi as _stoi
+        # the recordings of the micro-batch next to its float waveform: one padded batch, one call and one record read per score
         wav_of = {it["item_name"]: it["wav"] for it in items}
         B, n = wav.shape[0], wav.shape[-1]
         clean = torch.zeros((B, n), device=wav.device, dtype=torch.float32)
@@ -298,16 +296,11 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
                 raise ValueError(f"synthesize: the recording of {name} has {wav_of[name].numel()} samples, fewer than the {t * hop} vocoded")
             clean[b, : t * hop] = wav_of[name][: t * hop]
         valid = [t * hop for t in lens]
-        if stoi:
-            rec = model.stoi(clean, wav.reshape(B, n), valid=valid, sample_rate=sample_rate)
+        for sc in scored:
+            rec = getattr(model, sc.name)(clean, wav.reshape(B, n), valid=valid, **sc.kwargs(sample_rate, hop))
             for b, name in enumerate(names):
-                report[name] = {"stoi": float(rec["stoi"][b]), "estoi": float(rec["estoi"][b]), "status": _stoi.STATUS[int(rec["status"][b])]}
-        if pitch:
-            from . import pitch as _pitch
-            rec = model.pitch(clean, wav.reshape(B, n), valid=valid, rate=sample_rate, hop=hop)
-            for b, name in enumerate(names):
-                report.setdefault(name, {}).update({"f0_rmse_cents": float(rec["rmse_cents"][b]), "gpe": float(rec["gpe"][b]), "vde": float(rec["vde"][b]),
-                                                    "pitch_status": _pitch.STATUS[int(rec["status"][b])]})
+                report.setdefault(name, {}).update({key: float(rec[col][b]) for col, key, _, _ in sc.columns})
+                report[name][sc.status_key] = sc.module.STATUS[int(rec["status"][b])]
 
     def settle_on_device(p):
         # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
@@ -399,10 +392,7 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     "frames": by frames alone (rounds 1-5).
     out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate.
     stoi=True and pitch=True are refused: the recordings are not scattered (score with synthesize(stoi=True, pitch=True))."""
-    if stoi:
-        raise ValueError("synthesize_sharded: stoi=True is not available (the recordings are not scattered): use synthesize(stoi=True)")
-    if pitch:
-        raise ValueError("synthesize_sharded: pitch=True is not available (the recordings are not scattered): use synthesize(pitch=True)")
+    _scores.refuse("synthesize_sharded", " (the recordings are not scattered): use synthesize({name}=True)", stoi=stoi, pitch=pitch)
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -500,10 +490,7 @@ def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 
     byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
     loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is.
     stoi=True and pitch=True are refused (score the result with FastDiff.stoi and FastDiff.pitch, which take any length)."""
-    if stoi:
-        raise ValueError("synthesize_long: stoi=True is not available: score the waveforms with FastDiff.stoi")
-    if pitch:
-        raise ValueError("synthesize_long: pitch=True is not available: score the waveforms with FastDiff.pitch")
+    _scores.refuse("synthesize_long", ": score the waveforms with FastDiff.{name}", stoi=stoi, pitch=pitch)
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -575,14 +562,12 @@ def main(argv=None):
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
-    if args.stoi and not args.from_wav:
-        ap.error("--stoi scores the vocoded waveform against its recording: it needs --from_wav")
-    if args.stoi and args.long_form:
-        ap.error("--stoi is not available with --long_form")
-    if args.pitch and not args.from_wav:
-        ap.error("--pitch scores the vocoded pitch against its recording's: it needs --from_wav")
-    if args.pitch and args.long_form:
-        ap.error("--pitch is not available with --long_form")
+    scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch)
+    for sc in scored:
+        if not args.from_wav:
+            ap.error(f"--{sc.name} scores the vocoded waveform against its recording: it needs --from_wav")
+        if args.long_form:
+            ap.error(f"--{sc.name} is not available with --long_form")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -595,7 +580,7 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"]["model"], strict=True)
     if args.mel_basis:
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
-    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=args.stoi or args.pitch) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored)) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.long_form:
         if args.out_sample_rate is not None:
@@ -603,19 +588,15 @@ def main(argv=None):
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
         pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi, pitch=args.pitch)
-    if args.stoi or args.pitch:
+    if scored:
         pcm, report = pcm
         os.makedirs(args.out_dir, exist_ok=True)
         rows = [(it["item_name"], report[it["item_name"]]) for it in mine if it["item_name"] in report]
-        tables = []
-        if args.stoi:
-            tables.append(("stoi", ["name\tstoi\testoi\tstatus"] + [f"{name}\t{r['stoi']:.6f}\t{r['estoi']:.6f}\t{r['status']}" for name, r in rows]))
-        if args.pitch:
-            tables.append(("pitch", ["name\tf0_rmse_cents\tgpe\tvde\tstatus"] +
-                           [f"{name}\t{r['f0_rmse_cents']:.3f}\t{r['gpe']:.6f}\t{r['vde']:.6f}\t{r['pitch_status']}" for name, r in rows]))
-        for what, lines in tables:
+        for sc in scored:
+            lines = ["\t".join(["name"] + [key for _, key, _, _ in sc.columns] + ["status"])]
+            lines += ["\t".join([name] + [format(r[key], fmt) for _, key, _, fmt in sc.columns] + [r[sc.status_key]]) for name, r in rows]
             print("\n".join(lines))
-            with open(os.path.join(args.out_dir, f"{what}.tsv" if world == 1 else f"{what}.rank{rank}.tsv"), "w") as f:
+            with open(os.path.join(args.out_dir, f"{sc.name}.tsv" if world == 1 else f"{sc.name}.rank{rank}.tsv"), "w") as f:
                 f.write("\n".join(lines) + "\n")
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")

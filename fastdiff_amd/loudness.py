@@ -17,12 +17,10 @@ A record is a dict of numpy arrays over the batch: lufs (float64; -inf for SHORT
 status (int32).  SHORT: shorter than one block (pyloudnorm raises); SILENT: no block passes the gates; CLIPPED: peak gain > 1, so the
 utterance was divided by its peak instead (data_gen_utils.py:119-120); OK otherwise.
 """
-import ctypes as ct
-
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _wave
 
 TILE = _capi.FD_LOUDNESS_TILE
 OK, SHORT, SILENT, CLIPPED = _capi.FD_LOUDNESS_OK, _capi.FD_LOUDNESS_SHORT, _capi.FD_LOUDNESS_SILENT, _capi.FD_LOUDNESS_CLIPPED
@@ -49,27 +47,12 @@ def blocks(n, rate):
 
 
 def _prepare(wav, valid, who):
-    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
-        raise ValueError(f"{who}: a tensor on the HIP device is expected (there is no CPU path)")
-    wav = wav.contiguous().float()
-    if wav.dim() == 1:
-        wav = wav.unsqueeze(0)
-    B = wav.shape[0]
-    L = wav.numel() // max(B, 1)
-    if B < 1 or L < 1:
-        raise ValueError(f"{who}: empty input of shape {list(wav.shape)}")
-    varr = None
-    if valid is not None:
-        if len(valid) != B:
-            raise ValueError(f"{who}: valid has {len(valid)} entries for {B} utterances")
-        varr = (ct.c_int64 * B)(*[int(v) for v in valid])
-    return wav, B, L, varr
+    wav, B, L = _wave.rows(wav, who)
+    return wav, B, L, _wave.counts(valid, B, who)
 
 
 def _record(rec):
-    """The device records [B, 32] uint8 -> dict of numpy arrays (one synchronising copy)."""
-    r = rec.cpu().numpy().view(RECORD).reshape(-1)
-    return {k: r[k].copy() for k in ("lufs", "gain", "peak", "blocks", "gated", "status")}
+    return _wave.records(rec, RECORD, ("lufs", "gain", "peak", "blocks", "gated", "status"))
 
 
 def _measure(lib, handle, stream, wav, valid, sample_rate):
@@ -99,9 +82,7 @@ def measure(wav, valid=None, sample_rate=22050):
     """wav: device tensor [n] / [B, n] / [B, 1, n] -> record of its B utterances (one synchronisation).  valid: [B] sample counts of a
     padded batch; what lies behind them is not read.  Runs on the current stream, on the per-device handle of the operators (lvc_op);
     FastDiff.loudness uses the module's own."""
-    from . import lvc_op
-    lib, h = lvc_op._handle(wav.device)
-    return _measure(lib, h, lvc_op._stream(wav.device), wav, valid, sample_rate)
+    return _measure(*_wave.default_handle(wav), wav, valid, sample_rate)
 
 
 def normalize(wav, target, valid=None, sample_rate=22050, out="float", return_record=False):
@@ -109,6 +90,4 @@ def normalize(wav, target, valid=None, sample_rate=22050, out="float", return_re
     by their peak), out="int16" PCM [B, n] = (int16)(wav gain 32767) (SHORT, SILENT and CLIPPED ones exactly as peak_normalize_int16
     converts them); 0 behind valid[b].  An utterance's result does not depend on the batch it is in.  return_record: (output, record),
     which synchronises; without it the call is asynchronous."""
-    from . import lvc_op
-    lib, h = lvc_op._handle(wav.device)
-    return _normalize(lib, h, lvc_op._stream(wav.device), wav, target, valid, sample_rate, out, return_record)
+    return _normalize(*_wave.default_handle(wav), wav, target, valid, sample_rate, out, return_record)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _wave
 
 
 class _DBlockParams(nn.Module):
@@ -310,14 +310,10 @@ class FastDiff(nn.Module):
         """wav [B,1,L] float32 -> int16 PCM [B,L]: wav/abs(wav).max() * 32767 (FastDiff.py:110; utils/audio.py:11-16).
         valid (optional, [B] sample counts of a zero-padded batch): each utterance's peak is searched over its own samples only
         and the PCM behind them is 0 -- one call and one device-to-host copy per micro-batch instead of one per utterance."""
-        self._require_inference(wav, wav)
-        wav = wav.contiguous().float()
-        B = wav.shape[0]
-        L = wav.numel() // B
+        lib, h, stream = self._wave_call(wav)
+        wav, B, L = _wave.rows(wav, "peak_normalize_int16")
         pcm = torch.empty((B, L), device=wav.device, dtype=torch.int16)
-        lib, h = self._ready(wav.device)
-        varr = None if valid is None else (ct.c_int64 * B)(*[int(v) for v in valid])
-        rc = lib.fd_peak_normalize_int16_ragged(h, wav.data_ptr(), B, L, varr, pcm.data_ptr(), self._stream(wav.device))
+        rc = lib.fd_peak_normalize_int16_ragged(h, wav.data_ptr(), B, L, _wave.counts(valid, B, "peak_normalize_int16"), pcm.data_ptr(), stream)
         _capi.check(lib, h, rc, "fd_peak_normalize_int16")
         return pcm
 
@@ -349,9 +345,7 @@ class FastDiff(nn.Module):
         int32 / uint8 as a RIFF file holds them -> float32 mono [B, out_len(n, sr_in, sr_out)].  valid: [B] frame counts of a
         zero-padded batch; each item's result is what it gets alone, and 0 behind its own length."""
         from . import resample as _resample
-        self._require_inference(x, x)
-        lib, h = self._ready(x.device)
-        return _resample._run(lib, h, self._stream(x.device), x, sr_in, sr_out, valid, channels)
+        return _resample._run(*self._wave_call(x), x, sr_in, sr_out, valid, channels)
 
     def loudness(self, wav, valid=None, sample_rate=22050):
         """BS.1770 integrated loudness on the device (fastdiff_amd/loudness.py; the reference's pyloudnorm.Meter(rate), data_gen/tts/
@@ -359,9 +353,7 @@ class FastDiff(nn.Module):
         peak, blocks, gated, status (loudness.OK / SHORT / SILENT / CLIPPED).  valid: [B] sample counts of a padded batch.  Synchronises
         once, for the records."""
         from . import loudness as _loudness
-        self._require_inference(wav, wav)
-        lib, h = self._ready(wav.device)
-        return _loudness._measure(lib, h, self._stream(wav.device), wav, valid, sample_rate)
+        return _loudness._measure(*self._wave_call(wav), wav, valid, sample_rate)
 
     def loudness_normalize(self, wav, target, valid=None, sample_rate=22050, out="float", return_record=False):
         """wav scaled to `target` LUFS on the device (pyloudnorm.normalize.loudness with the reference's guard, data_gen_utils.py:118-120):
@@ -370,9 +362,7 @@ class FastDiff(nn.Module):
         as peak_normalize_int16 does it; in float mode it is left unchanged (SHORT, SILENT) or divided by its peak (CLIPPED).
         return_record: (output, record as FastDiff.loudness returns it, with the gain applied); without it nothing synchronises."""
         from . import loudness as _loudness
-        self._require_inference(wav, wav)
-        lib, h = self._ready(wav.device)
-        return _loudness._normalize(lib, h, self._stream(wav.device), wav, target, valid, sample_rate, out, return_record)
+        return _loudness._normalize(*self._wave_call(wav), wav, target, valid, sample_rate, out, return_record)
 
     def stoi(self, clean, degraded, valid=None, sample_rate=22050):
         """STOI and ESTOI of `degraded` against `clean` on the device (fastdiff_amd/stoi.py; what people run pystoi for over the reference's
@@ -380,9 +370,7 @@ class FastDiff(nn.Module):
         numpy arrays over the batch: stoi, estoi (NaN unless OK), frames, kept, segments, status (stoi.OK / SHORT / SILENT).  valid: [B]
         sample counts of a padded batch.  Synchronises once, for the records."""
         from . import stoi as _stoi
-        self._require_inference(clean, degraded)
-        lib, h = self._ready(clean.device)
-        return _stoi._measure(lib, h, self._stream(clean.device), clean, degraded, valid, sample_rate)
+        return _stoi._measure(*self._wave_call(clean, degraded), clean, degraded, valid, sample_rate)
 
     def pitch(self, clean, degraded, valid=None, **cfg):
         """The pitch scores of `degraded` against `clean` on the device (fastdiff_amd/pitch.py): both are tracked with YIN on the mel
@@ -391,16 +379,12 @@ class FastDiff(nn.Module):
         frames, both_voiced, ref_voiced, deg_voiced, status (pitch.OK / SHORT / UNVOICED).  valid: [B] sample counts of a padded batch;
         cfg: rate, hop, win, f0_min, f0_max, threshold.  Synchronises once, for the records."""
         from . import pitch as _pitch
-        self._require_inference(clean, degraded)
-        lib, h = self._ready(clean.device)
-        return _pitch._measure(lib, h, self._stream(clean.device), clean, degraded, valid, cfg)
+        return _pitch._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
 
     def pitch_track(self, wav, valid=None, **cfg):
         """(f0, aper) of `wav` on the device, float32 [B, n // hop] (fastdiff_amd/pitch.py: track); does not synchronise."""
         from . import pitch as _pitch
-        self._require_inference(wav, wav)
-        lib, h = self._ready(wav.device)
-        return _pitch._track(lib, h, self._stream(wav.device), wav, valid, cfg)
+        return _pitch._track(*self._wave_call(wav), wav, valid, cfg)
 
     def set_mel_filterbank(self, fb, variant="pwg", device=None):
         """Use `fb` [80, 513] (numpy / tensor, float32; librosa.filters.mel's own layout) as the filter bank of front-end `variant`
@@ -486,6 +470,12 @@ class FastDiff(nn.Module):
         if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
             raise NotImplementedError("this entry point is the inference pipeline (no saved activations): only FastDiff.forward "
                                       "records an autograd graph (fastdiff_amd/train.py)")
+
+    def _wave_call(self, *tensors):
+        """(lib, handle, stream) of a waveform method: the tensors lie on one device and carry no autograd graph, the weights are synced."""
+        self._require_inference(*tensors)
+        device = tensors[0].device
+        return (*self._ready(device), self._stream(device))
 
     def _prep_condition(self, c, B, device):
         c = c.to(device=device, dtype=torch.float32)

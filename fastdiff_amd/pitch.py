@@ -24,7 +24,7 @@ import ctypes as ct
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _wave
 
 MAX_LAGS, FRAME_TILE, LAG_CHUNK, STAGE_FLOATS = _capi.FD_PITCH_MAX_LAGS, _capi.FD_PITCH_FRAME_TILE, _capi.FD_PITCH_LAG_CHUNK, _capi.FD_PITCH_STAGE_FLOATS
 OK, SHORT, UNVOICED = _capi.FD_PITCH_OK, _capi.FD_PITCH_SHORT, _capi.FD_PITCH_UNVOICED
@@ -76,28 +76,11 @@ def frames(n, hop=256):
     return int(r)
 
 
-def _rows(wav, valid, what="wav"):
-    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
-        raise ValueError("pitch: tensors on the HIP device are expected (there is no CPU path)")
-    wav = wav.contiguous().float()
-    if wav.dim() == 1:
-        wav = wav.unsqueeze(0)
-    B = wav.shape[0]
-    L = wav.numel() // max(B, 1)
-    if B < 1 or L < 1:
-        raise ValueError(f"pitch: empty {what} of shape {list(wav.shape)}")
-    varr = None
-    if valid is not None:
-        if len(valid) != B:
-            raise ValueError(f"pitch: {len(valid)} counts for {B} rows")
-        varr = (ct.c_int64 * B)(*[int(v) for v in valid])
-    return wav.reshape(B, L), B, L, varr
-
-
 def _track(lib, handle, stream, wav, valid, cfg):
     """fd_pitch_track on the stream -> (f0, aper) device [B, F]; nothing synchronises."""
     c = cfg if isinstance(cfg, FdPitchConfig) else _config(cfg)
-    wav, B, L, varr = _rows(wav, valid)
+    wav, B, L = _wave.rows(wav, "pitch")
+    varr = _wave.counts(valid, B, "pitch")
     F = L // max(int(c.hop), 1)
     out = torch.zeros((2, B, max(F, 1)), device=wav.device, dtype=torch.float32)
     rc = lib.fd_pitch_track(handle, wav.data_ptr(), B, L, varr, ct.byref(c), out[0].data_ptr(), out[1].data_ptr(), max(F, 1), stream)
@@ -106,9 +89,7 @@ def _track(lib, handle, stream, wav, valid, cfg):
 
 
 def _record(rec):
-    """The device records [B, 48] uint8 -> dict of numpy arrays (one synchronising copy)."""
-    r = rec.cpu().numpy().view(RECORD).reshape(-1)
-    return {k: r[k].copy() for k in FIELDS}
+    return _wave.records(rec, RECORD, FIELDS)
 
 
 def _compare(lib, handle, stream, f0_ref, f0_deg, nframes=None, rec=None):
@@ -121,8 +102,9 @@ def _compare(lib, handle, stream, f0_ref, f0_deg, nframes=None, rec=None):
         nframes = [F] * B
     if F == 0:      # (the views of _track's buffer: one column stands behind them, but a caller's empty tensor has none)
         f0_ref = f0_deg = torch.zeros((B, 1), device=f0_ref.device, dtype=torch.float32)
-    a, B, pitch, farr = _rows(f0_ref, nframes, "track")
-    g = _rows(f0_deg, None, "track")[0]
+    a, B, pitch = _wave.rows(f0_ref, "pitch", "track")
+    g = _wave.rows(f0_deg, "pitch", "track")[0]
+    farr = _wave.counts(nframes, B, "pitch")
     if rec is None:
         rec = torch.empty((B, RECORD.itemsize), device=a.device, dtype=torch.uint8)
     assert rec.is_cuda and rec.dtype == torch.uint8 and rec.is_contiguous() and rec.numel() == B * RECORD.itemsize
@@ -148,18 +130,12 @@ def _measure(lib, handle, stream, clean, degraded, valid, cfg):
     return _record(_enqueue(lib, handle, stream, clean, degraded, valid, cfg))
 
 
-def _default_handle(t):
-    from . import lvc_op
-    lib, h = lvc_op._handle(t.device)
-    return lib, h, lvc_op._stream(t.device)
-
-
 def track(wav, valid=None, **cfg):
     """wav: device tensor [n] / [B, n] / [B, 1, n] -> (f0, aper), device float32 [B, n // hop]: f0 in Hz, 0 where unvoiced; aper = d' at
     the chosen lag (its minimum over the lag range where unvoiced).  valid: [B] sample counts of a padded batch; what lies behind them
     is not read, and the frames behind valid[b] // hop are (0, 1).  cfg: rate, hop, win, f0_min, f0_max, threshold.  Runs on the current
     stream, on the per-device handle of the operators (lvc_op); FastDiff.pitch_track uses the module's own.  Does not synchronise."""
-    lib, h, stream = _default_handle(wav)
+    lib, h, stream = _wave.default_handle(wav)
     return _track(lib, h, stream, wav, valid, cfg)
 
 
@@ -167,11 +143,11 @@ def compare(f0_ref, f0_deg, frames=None):
     """Two device tracks [B, F] (or [F]) -> record (one synchronisation).  frames: [B] frame counts of a padded batch."""
     if f0_ref.dim() == 1:
         f0_ref, f0_deg = f0_ref.unsqueeze(0), f0_deg.unsqueeze(0)
-    lib, h, stream = _default_handle(f0_ref)
+    lib, h, stream = _wave.default_handle(f0_ref)
     return _record(_compare(lib, h, stream, f0_ref, f0_deg, frames))
 
 
 def measure(clean, degraded, valid=None, **cfg):
     """clean, degraded: device tensors [n] / [B, n] / [B, 1, n] of one shape -> record of the B pairs (one synchronisation)."""
-    lib, h, stream = _default_handle(clean)
+    lib, h, stream = _wave.default_handle(clean)
     return _measure(lib, h, stream, clean, degraded, valid, cfg)

@@ -25,7 +25,7 @@ from math import gcd
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _wave
 
 ZEROS = 64
 ROLLOFF = 0.9475937167399596
@@ -122,11 +122,7 @@ def _run(lib, handle, stream, x, sr_in, sr_out, valid, channels):
     pitch = x.stride(0) if B > 1 else n * C
     n_out = out_len(n, sr_in, sr_out)
     y = torch.empty((B, n_out), device=x.device, dtype=torch.float32)
-    varr = None
-    if valid is not None:
-        if len(valid) != B:
-            raise ValueError(f"resample: valid has {len(valid)} entries for {B} items")
-        varr = (ct.c_int64 * B)(*[int(v) for v in valid])
+    varr = _wave.counts(valid, B, "resample")
     rc = lib.fd_resample(handle, x.data_ptr(), _FORMATS[x.dtype], C, B, n, pitch, varr, int(sr_in), int(sr_out), y.data_ptr(), n_out, stream)
     _capi.check(lib, handle, rc, "fd_resample")
     return y
@@ -138,6 +134,4 @@ def resample(x, sr_in, sr_out, valid=None, channels=1):
     valid (optional, [B] frame counts of a zero-padded batch): item b is resampled as if it were valid[b] frames long, and its row is 0
     behind out_len(valid[b]).  An item's result does not depend on the batch it is in.  Equal rates: conversion and down-mix only.
     Runs on the current stream, on the per-device handle of the operators (lvc_op); FastDiff.resample uses the module's own."""
-    from . import lvc_op
-    lib, h = lvc_op._handle(x.device)
-    return _run(lib, h, lvc_op._stream(x.device), x, sr_in, sr_out, valid, channels)
+    return _run(*_wave.default_handle(x), x, sr_in, sr_out, valid, channels)

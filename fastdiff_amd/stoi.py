@@ -15,12 +15,10 @@ A record is a dict of numpy arrays over the batch: stoi, estoi (float64; NaN unl
 SHORT: fewer than 31 frames survive the silence removal, so there is not one segment (pystoi returns 1e-5 with a warning); SILENT: the
 clean signal is all zeros; OK otherwise.
 """
-import ctypes as ct
-
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _wave
 
 SCAN_TILE, SEG_TILE = _capi.FD_STOI_SCAN_TILE, _capi.FD_STOI_SEG_TILE
 OK, SHORT, SILENT = _capi.FD_STOI_OK, _capi.FD_STOI_SHORT, _capi.FD_STOI_SILENT
@@ -47,32 +45,15 @@ def frames(n):
 
 
 def _prepare(clean, degraded, valid):
-    for t in (clean, degraded):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("stoi: tensors on the HIP device are expected (there is no CPU path)")
-    clean, degraded = clean.contiguous().float(), degraded.contiguous().float()
-    if clean.dim() == 1:
-        clean = clean.unsqueeze(0)
-    if degraded.dim() == 1:
-        degraded = degraded.unsqueeze(0)
-    B = clean.shape[0]
-    L = clean.numel() // max(B, 1)
-    if B < 1 or L < 1:
-        raise ValueError(f"stoi: empty input of shape {list(clean.shape)}")
-    if degraded.shape[0] != B or degraded.numel() != clean.numel() or degraded.device != clean.device:
+    clean, B, L = _wave.rows(clean, "stoi", "clean")
+    degraded, Bd, Ld = _wave.rows(degraded, "stoi", "degraded")
+    if (Bd, Ld) != (B, L) or degraded.device != clean.device:
         raise ValueError(f"stoi: clean {list(clean.shape)} and degraded {list(degraded.shape)} must be the same batch of waveforms on one device")
-    varr = None
-    if valid is not None:
-        if len(valid) != B:
-            raise ValueError(f"stoi: valid has {len(valid)} entries for {B} utterances")
-        varr = (ct.c_int64 * B)(*[int(v) for v in valid])
-    return clean, degraded, B, L, varr
+    return clean, degraded, B, L, _wave.counts(valid, B, "stoi")
 
 
 def _record(rec):
-    """The device records [B, 32] uint8 -> dict of numpy arrays (one synchronising copy)."""
-    r = rec.cpu().numpy().view(RECORD).reshape(-1)
-    return {k: r[k].copy() for k in RECORD.names}
+    return _wave.records(rec, RECORD, RECORD.names)
 
 
 def _enqueue(lib, handle, stream, clean, degraded, valid, sample_rate, rec=None):
@@ -94,6 +75,4 @@ def measure(clean, degraded, valid=None, sample_rate=22050):
     """clean, degraded: device tensors [n] / [B, n] / [B, 1, n] of one shape -> record of the B pairs (one synchronisation).  valid: [B]
     sample counts of a padded batch; what lies behind them is not read.  Runs on the current stream, on the per-device handle of the
     operators (lvc_op); FastDiff.stoi uses the module's own."""
-    from . import lvc_op
-    lib, h = lvc_op._handle(clean.device)
-    return _measure(lib, h, lvc_op._stream(clean.device), clean, degraded, valid, sample_rate)
+    return _measure(*_wave.default_handle(clean), clean, degraded, valid, sample_rate)

@@ -34,7 +34,7 @@ followed by that TrainStep's own warm-up, which happens outside its capture.
 import numpy as np
 import torch
 
-from . import lvc_op
+from . import _scores, lvc_op
 
 DEFAULT_SEED = 0x56414C      # "VAL"
 
@@ -81,22 +81,13 @@ class Validator:
         self.eps = self.sampled = self.mel_sampled = self.mel_target = None
         self.values_mel = torch.empty(B, device=dev, dtype=torch.float32) if self.table is not None else None
         self.item_mel_l1 = torch.zeros(corpus.n_items, device=dev, dtype=torch.float32) if self.table is not None else None
-        self._stoi_rec = None
-        if stoi:
+        self.sample_rate = int(sample_rate)                    # the rate of the corpus' waveforms
+        self._scored = []                                      # (score, its configuration, its records: slot b of batch j is row j B + b)
+        for sc in _scores.enabled(stoi=stoi, pitch=pitch):
             if self.table is None:
-                raise ValueError("Validator: stoi=True scores the vocoded windows, which needs sample_schedule")
-            from . import stoi as _stoi
-            self.sample_rate = int(sample_rate)                # the rate of the corpus' waveforms (fd_stoi_measure resamples to 10 kHz)
-            self._stoi_rec = torch.zeros((self.n_batches * B, _stoi.RECORD.itemsize), device=dev, dtype=torch.uint8)      # slot b of batch j
-        self._pitch_rec = None
-        if pitch:
-            if self.table is None:
-                raise ValueError("Validator: pitch=True scores the vocoded windows, which needs sample_schedule")
-            from . import pitch as _pitch
-            self.sample_rate = int(sample_rate)
-            self._pitch_cfg = _pitch._config({"rate": self.sample_rate, "hop": corpus.hop_size})      # one F0 per mel frame; refused now, not inside a pass
-            _pitch.lags({"rate": self.sample_rate, "hop": corpus.hop_size})
-            self._pitch_rec = torch.zeros((self.n_batches * B, _pitch.RECORD.itemsize), device=dev, dtype=torch.uint8)     # slot b of batch j
+                raise ValueError(f"Validator: {sc.name}=True scores the vocoded windows, which needs sample_schedule")
+            cfg = sc.config(self.sample_rate, corpus.hop_size)      # refused now, not inside a pass
+            self._scored.append((sc, cfg, torch.zeros((self.n_batches * B, sc.module.RECORD.itemsize), device=dev, dtype=torch.uint8)))
 
     def state(self):
         """The pass's fd_train_state as a dict (`iter` = batches done).  Synchronises."""
@@ -123,14 +114,9 @@ class Validator:
             self.mel_target = m.mel_spectrogram(self.wav.view(B, -1), n_frames=F, variant="pwg")
             lvc_op.item_distance(self.mel_sampled, self.mel_target, 1, out=self.values_mel)
             lvc_op.eval_accumulate(self.values_mel, self.picked, self._acc_mel, item_out=self.item_mel_l1)
-            if self._stoi_rec is not None:
-                from . import stoi as _stoi
+            for sc, cfg, rec in self._scored:
                 lib, h = m._ready(self.device)
-                _stoi._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, self.sample_rate, rec=self._stoi_rec[j * B: (j + 1) * B])
-            if self._pitch_rec is not None:
-                from . import pitch as _pitch
-                lib, h = m._ready(self.device)
-                _pitch._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, self._pitch_cfg, rec=self._pitch_rec[j * B: (j + 1) * B])
+                sc.module._enqueue(lib, h, m._stream(self.device), self.wav, self.sampled, None, cfg, rec=rec[j * B: (j + 1) * B])
         # last: it advances the batch index, behind every read of it
         lvc_op.eval_accumulate(self.values, self.picked, self._acc, steps=self.steps, T_train=self.T_train, bins=self.bins,
                                item_out=self.item_loss, advance=self._state)
@@ -169,24 +155,14 @@ class Validator:
             mel = lvc_op.read_eval_state(self._acc_mel, 1)
             out["mel_l1"] = mel["sum"] / mel["count"] if mel["count"] else float("nan")
             out["item_mel_l1"] = self.item_mel_l1.cpu().numpy()
-        if self._stoi_rec is not None:
-            from . import stoi as _stoi
-            rec = _stoi._record(self._stoi_rec)              # slot b of batch j is item j B + b: the first n rows are the items
-            n = self.corpus.n_items
-            ok = rec["status"][:n] == _stoi.OK
-            for key in ("stoi", "estoi"):
-                item = np.where(ok, rec[key][:n], np.nan)
-                out["item_" + key] = item
-                out[key] = float(item[ok].mean()) if ok.any() else float("nan")
-            out["stoi_skipped"] = int(n - ok.sum())
-        if self._pitch_rec is not None:
-            from . import pitch as _pitch
-            rec = _pitch._record(self._pitch_rec)            # slot b of batch j is item j B + b, as above
-            n = self.corpus.n_items
-            ok = rec["status"][:n] == _pitch.OK
-            for key, name, use in (("rmse_cents", "f0_rmse_cents", ok), ("gpe", "gpe", ok), ("vde", "vde", ok | (rec["status"][:n] == _pitch.UNVOICED))):
+        n = self.corpus.n_items
+        for sc, _, dev_rec in self._scored:
+            rec = sc.module._record(dev_rec)                 # slot b of batch j is item j B + b: the first n rows are the items
+            status = rec["status"][:n]
+            for key, name, measured, _ in sc.columns:
+                use = np.isin(status, measured)
                 item = np.where(use, rec[key][:n], np.nan)
                 out["item_" + name] = item
                 out[name] = float(item[use].mean()) if use.any() else float("nan")
-            out["pitch_skipped"] = int(n - ok.sum())
+            out[sc.name + "_skipped"] = int(n - (status == sc.module.OK).sum())
         return out

@@ -246,6 +246,28 @@ def test_null_arguments_are_refused():
     assert lib.fd_pitch_compare(None, None, None, 1, 3, None, None, None) == _capi.FD_ERR_INVALID
 
 
+def test_a_null_handle_is_refused_by_every_waveform_entry_point():
+    """Every other argument is in order (host memory stands in for the device pointers, which nothing may touch): the shared host path
+    -- the counts check, the settle, the scratch and the staging ring -- is not reached without a handle."""
+    lib = _capi.load()
+    n = 9000
+    buf = (ct.c_float * n)()
+    p = ct.addressof(buf)
+    one = (ct.c_int64 * 1)(n)
+    cfg = pt._config(None)
+    calls = {
+        "fd_resample": lambda: lib.fd_resample(None, p, _capi.FD_PCM_F32, 1, 1, 4000, 4000, (ct.c_int64 * 1)(4000), 22050, 16000, p, n, None),
+        "fd_loudness_measure": lambda: lib.fd_loudness_measure(None, p, 1, n, one, 22050, p, None),
+        "fd_loudness_normalize": lambda: lib.fd_loudness_normalize(None, p, 1, n, one, 22050, -23.0, p, None, None, None),
+        "fd_stoi_measure": lambda: lib.fd_stoi_measure(None, p, p, 1, n, one, 22050, p, None),
+        "fd_pitch_track": lambda: lib.fd_pitch_track(None, p, 1, n, one, ct.byref(cfg), p, p, 64, None),
+        "fd_pitch_compare": lambda: lib.fd_pitch_compare(None, p, p, 1, 35, (ct.c_int64 * 1)(35), p, None),
+        "fd_peak_normalize_int16_ragged": lambda: lib.fd_peak_normalize_int16_ragged(None, p, 1, n, one, p, None),
+    }
+    for name, call in calls.items():
+        assert call() == _capi.FD_ERR_INVALID, name
+
+
 def test_the_oracles_record():
     a = np.array([100.0, 0.0, 200.0, 0.0, 150.0, 300.0], np.float32)
     b = np.array([103.0, 50.0, 0.0, 0.0, 300.0, 300.0], np.float32)
@@ -486,6 +508,27 @@ def test_refusals_leave_a_message(model):
     with pytest.raises(Exception, match="win"):
         model.pitch_track(x, win=63)
     torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_the_counts_buffer_cannot_be_allocated_inside_a_capture():
+    """A handle of its own, so that no earlier test has allocated the buffer of the counts: the first call that passes `valid` is
+    refused inside a capture, and the handle works on afterwards."""
+    import gpu_common
+    m = gpu_common.make_model()
+    x = torch.zeros(1, 9000, device="cuda")
+    m._ready(torch.device("cuda"))                         # the handle and its weights exist; no pitch call has run on it
+    torch.cuda.synchronize()
+    refused = torch.cuda.CUDAGraph()
+    with pytest.raises(_capi.FastDiffHipError, match="stream capture"):
+        with torch.cuda.graph(refused):
+            x.mul_(1.0)                                    # (so that the abandoned capture is not empty)
+            m.pitch_track(x, valid=[9000])
+    torch.cuda.synchronize()
+    f0, aper = m.pitch_track(x, valid=[9000])
+    whole = m.pitch_track(x)
+    assert f0.shape == (1, 35)
+    assert f0.cpu().numpy().tobytes() == whole[0].cpu().numpy().tobytes() and aper.cpu().numpy().tobytes() == whole[1].cpu().numpy().tobytes()
 
 
 @pytest.fixture(scope="module")
