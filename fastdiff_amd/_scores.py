@@ -1,7 +1,7 @@
 """The scores of a vocoded waveform against its recording, as infer.py and validate.py offer them: one entry per keyword argument."""
 from collections import namedtuple
 
-from . import pitch, stoi
+from . import pitch, spectral, stoi
 
 # name: the keyword argument, the FastDiff method, the command-line flag and the TSV file; module: its OK / STATUS / RECORD / _enqueue /
 # _record; columns: (record key, report and result key, the statuses with which the value counts as measured, TSV format);
@@ -22,11 +22,14 @@ SCORES = (
     Score("pitch", pitch, (("rmse_cents", "f0_rmse_cents", (pitch.OK,), ".3f"), ("gpe", "gpe", (pitch.OK,), ".6f"),
                            ("vde", "vde", (pitch.OK, pitch.UNVOICED), ".6f")), "pitch_status",
           lambda rate, hop: {"rate": rate, "hop": hop}, _pitch_config),
+    Score("spectral", spectral, (("mr_sc", "mr_sc", (spectral.OK,), ".6f"), ("mr_logmag", "mr_logmag", (spectral.OK,), ".6f"),
+                                 ("lsd_db", "lsd_db", (spectral.OK,), ".4f")), "spectral_status",
+          lambda rate, hop: {}, lambda rate, hop: spectral._config(None)),      # the resolutions are in samples, whatever the rate
 )
 
 
 def enabled(**flags):
-    """The entries whose keyword argument is true, in the table's order: enabled(stoi=stoi, pitch=pitch)."""
+    """The entries whose keyword argument is true, in the table's order: enabled(stoi=stoi, pitch=pitch, spectral=spectral)."""
     return [s for s in SCORES if flags.get(s.name)]
 
 

@@ -1,6 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
 // sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
-// waveform against its recording: STOI / ESTOI (fd_stoi_*) and F0 tracking with the pitch scores (fd_pitch_*).  Then taps, layout
+// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  Then taps, layout
 // introspection, counters and per-kernel profiling.  
 #include <math.h>
 #include <stddef.h>
@@ -486,6 +486,60 @@ int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int 
     const long long *frames_dev = nullptr;
     if ((rc = pitch_counts(h, who, frames, B, 1, (hipStream_t)stream, &frames_dev)) != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::pitch_compare(La, f0_ref, f0_deg, pitch, B, frames_dev, rec_dev); });
+}
+
+// Multi-resolution STFT distances (fastdiff_hip_ext.h; constants, refusals, counts and tables: fd_spectral.h, the kernels:
+// fd_kernels_spectral.hip) ---------------------------------------------------------------------------------------------------------
+int fd_spectral_default_config(fd_spectral_config *cfg)
+{
+    if (!cfg) return FD_ERR_INVALID;
+    fdx::defaults(cfg);
+    return FD_OK;
+}
+
+int64_t fd_spectral_frames(int64_t n, int hop)
+{
+    if (n < 0 || hop < 1) return FD_ERR_INVALID;
+    return fdx::frames(n, hop);
+}
+
+int fd_spectral_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid,
+                        const fd_spectral_config *cfg, fd_spectral *rec_dev, void *stream)
+{
+    // (the arguments first: their refusals need no handle, and without one the text is left where fd_last_error(NULL) reads it)
+    const char *who = "fd_spectral_measure";
+    if (!clean || !degraded || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !clean ? "clean" : (!degraded ? "degraded" : "rec_dev"));
+    if (B < 1 || B > 4096 || L < 1 || L > fdx::MAX_SAMPLES)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d pairs (1 .. 4096) of L = %lld samples (1 .. 2^30)", who, B, (long long)L);
+    fd_spectral_config c;
+    if (cfg) c = *cfg; else fdx::defaults(&c);
+    char why[fdx::MSG];
+    if (fdx::refusal(c, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: configuration refused: %s", who, why);
+    int rc = check_counts(h, who, "valid", valid, B, 1, L);
+    if (rc != FD_OK) return rc;
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    if ((rc = enter(h)) != FD_OK) return rc;
+    const float *tabs[fdx::MAX_RES] = {nullptr, nullptr, nullptr, nullptr};
+    for (int r = 0; r < c.n_res; ++r) {
+        const float *&slot = h->spectral_tabs[{c.nfft[r], c.win[r]}];
+        if (!slot) {
+            if (capturing((hipStream_t)stream))
+                FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table of nfft = %d, win = %d is uploaded at the first call that uses it, which cannot happen inside a stream capture: call it once before", who, c.nfft[r], c.win[r]);
+            std::vector<float> tab(fdx::table_floats(c.nfft[r]));
+            fdx::tables(c.nfft[r], c.win[r], tab.data());
+            const void *dev = nullptr;
+            if ((rc = upload_table(h, who, tab.data(), tab.size() * sizeof(float), &dev)) != FD_OK) return rc;      // (a null slot counts as none)
+            slot = static_cast<const float *>(dev);
+        }
+        tabs[r] = slot;
+    }
+    Scratch &s = h->spectral_scratch;
+    if ((rc = reserve(h, who, s, fdk::spectral_scratch_bytes(B, L, c), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *lens_dev = fdk::spectral_lens_slot(s.p);
+    if ((rc = upload_counts(h, valid, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::spectral(La, clean, degraded, L, B, L, valid ? lens_dev : nullptr, c, tabs, rec_dev, s.p);
+    });
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

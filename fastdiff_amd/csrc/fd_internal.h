@@ -14,6 +14,7 @@
 #include "fd_loudness.h"
 #include "fd_stoi.h"
 #include "fd_pitch.h"
+#include "fd_spectral.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -283,7 +284,7 @@ struct fd_context {
     int mel_variant = MEL_PWG;               // option "mel"
     std::vector<float> mel_bank[MEL_VARIANTS];   // the dense [80][513] bank each front-end uses (host copy: fd_get_mel_filterbank)
     bool mel_bank_user[MEL_VARIANTS] = {false, false};   // supplied through fd_set_mel_filterbank (else the restated default)
-    std::vector<void *> tables;               // every constant table uploaded so far (mel, resampler, STOI): owned here, freed at fd_destroy
+    std::vector<void *> tables;               // every constant table uploaded so far (mel, resampler, STOI, spectral): owned here, freed at fd_destroy
     struct ResampleTable { int up, down; const float *dev; };
     std::vector<ResampleTable> resample_tabs; // fd_resample's polyphase tables, one per reduced ratio used so far (`dev` is in `tables`)
     int last_B = 0, last_T = 0;
@@ -375,6 +376,8 @@ struct fd_context {
     Scratch stoi_scratch;                    // fd_stoi_measure: lengths, the 10 kHz signals, frame energies, src, band amplitudes, segment partials
     const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call (in `tables`)
     Scratch pitch_scratch;                   // fd_pitch_track / _compare: the device copies of valid [B] and frames [B]
+    Scratch spectral_scratch;                // fd_spectral_measure: lengths, then the frame partials of every resolution
+    std::map<std::pair<int, int>, const float *> spectral_tabs;      // its window and twiddles by (nfft, win) (csrc/fd_spectral.h: tables), each uploaded at the first call that uses it (in `tables`)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -495,6 +498,12 @@ hipError_t pitch_track(const Launch &L_, const float *wav, long long pitch, int 
                        const fd_pitch_config &cfg, const fdp::Lags &lg, float *f0, float *aper, long long out_pitch);
 hipError_t pitch_compare(const Launch &L_, const float *f0_ref, const float *f0_deg, long long pitch, int B, const long long *frames_dev,
                          fd_pitch *rec);
+// fd_spectral_measure (fd_kernels_spectral.hip).  x, y: [B] rows `pitch` floats apart; lens_dev: null (every row L samples) or the lens
+// slot of the scratch buffer; c: a configuration the caller has validated (fdx::refusal); tabs[r]: device copy of fdx::tables(nfft[r], win[r]).
+size_t spectral_scratch_bytes(int B, int64_t L, const fd_spectral_config &c);
+long long *spectral_lens_slot(void *scratch);
+hipError_t spectral(const Launch &L_, const float *x, const float *y, long long pitch, int B, int64_t L, const long long *lens_dev,
+                    const fd_spectral_config &c, const float *const *tabs, fd_spectral *rec, void *scratch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

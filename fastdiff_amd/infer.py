@@ -17,7 +17,7 @@ Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch]`).
+[--loudness LUFS] [--stoi] [--pitch] [--spectral]`).
 """
 import argparse
 import glob
@@ -107,7 +107,7 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     loud_norm: the reference's `loud_norm: true` configurations -- every recording is brought to -22 LUFS before its mel is taken
     (loud_norm_wav: FastDiff.loudness_normalize).
     keep_wav: every item also carries "wav", its device waveform [n] at the model's rate as the mel was taken from it (what
-    synthesize(stoi=True) and synthesize(pitch=True) score the vocoded waveform against)."""
+    synthesize(stoi=True), synthesize(pitch=True) and synthesize(spectral=True) score the vocoded waveform against)."""
     from scipy.io import wavfile
     items = []
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
@@ -222,7 +222,8 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
-               sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
+               sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
+               spectral: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
@@ -243,9 +244,12 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     the vocoded length (lens * hop).
     pitch=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"f0_rmse_cents", "gpe", "vde",
     "pitch_status"} (FastDiff.pitch at `sample_rate`, one F0 per mel frame; status by name), measured on the same waveforms as STOI.
-    With stoi=True as well, report[name] holds both sets of keys."""
+    With stoi=True as well, report[name] holds both sets of keys.
+    spectral=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"mr_sc", "mr_logmag", "lsd_db",
+    "spectral_status"} (FastDiff.spectral at the default resolutions: the means over them of the spectral convergence, the log-magnitude
+    distance in nepers and the log-spectral distance in dB; status by name), measured on the same waveforms, next to the other sets."""
     from . import resample as _resample
-    scored = _scores.enabled(stoi=stoi, pitch=pitch)
+    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
     if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
         raise ValueError(f"synthesize: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
     report: Dict[str, dict] = {}
@@ -373,7 +377,8 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
-                       sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
+                       sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
+                       spectral: bool = False) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -391,8 +396,9 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
     "frames": by frames alone (rounds 1-5).
     out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate.
-    stoi=True and pitch=True are refused: the recordings are not scattered (score with synthesize(stoi=True, pitch=True))."""
-    _scores.refuse("synthesize_sharded", " (the recordings are not scattered): use synthesize({name}=True)", stoi=stoi, pitch=pitch)
+    stoi=True, pitch=True and spectral=True are refused: the recordings are not scattered (score with synthesize(stoi=True, pitch=True,
+    spectral=True))."""
+    _scores.refuse("synthesize_sharded", " (the recordings are not scattered): use synthesize({name}=True)", stoi=stoi, pitch=pitch, spectral=spectral)
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -483,14 +489,15 @@ LONG_FORM_GROUP_FRAMES = 1 << 16      # mel frames per sample_long_batch call: 6
 
 def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
                     diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES, loudness: float = None,
-                    sample_rate: int = 22050, stoi: bool = False, pitch: bool = False) -> Dict[str, np.ndarray]:
+                    sample_rate: int = 22050, stoi: bool = False, pitch: bool = False, spectral: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM through FastDiff.sample_long_batch (windowed: any length, device memory of one window batch): the
     utterances are taken in order in groups of up to group_frames mel frames, so their outputs fit, and the windows of a group share the
     sampler's batches.  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same,
     byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
     loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is.
-    stoi=True and pitch=True are refused (score the result with FastDiff.stoi and FastDiff.pitch, which take any length)."""
-    _scores.refuse("synthesize_long", ": score the waveforms with FastDiff.{name}", stoi=stoi, pitch=pitch)
+    stoi=True, pitch=True and spectral=True are refused (score the result with FastDiff.stoi, FastDiff.pitch and FastDiff.spectral, which
+    take any length)."""
+    _scores.refuse("synthesize_long", ": score the waveforms with FastDiff.{name}", stoi=stoi, pitch=pitch, spectral=spectral)
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -559,10 +566,14 @@ def main(argv=None):
     ap.add_argument("--pitch", action="store_true",
                     help="with --from_wav (copy synthesis): track F0 of every recording and vocoded waveform with YIN on the device and score "
                          "the pitch (F0 RMSE in cents, gross pitch error, voicing decision error), print the table and write <out_dir>/pitch.tsv")
+    ap.add_argument("--spectral", action="store_true",
+                    help="with --from_wav (copy synthesis): measure the multi-resolution STFT distances of every vocoded waveform against its "
+                         "recording on the device (spectral convergence, log-magnitude distance, log-spectral distance in dB; the means over "
+                         "512 / 1024 / 2048-point transforms), print the table and write <out_dir>/spectral.tsv")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
-    scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch)
+    scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch, spectral=args.spectral)
     for sc in scored:
         if not args.from_wav:
             ap.error(f"--{sc.name} scores the vocoded waveform against its recording: it needs --from_wav")
@@ -587,7 +598,8 @@ def main(argv=None):
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
-        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi, pitch=args.pitch)
+        pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi, pitch=args.pitch,
+                         spectral=args.spectral)
     if scored:
         pcm, report = pcm
         os.makedirs(args.out_dir, exist_ok=True)

@@ -381,6 +381,15 @@ class FastDiff(nn.Module):
         from . import pitch as _pitch
         return _pitch._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
 
+    def spectral(self, clean, degraded, valid=None, **cfg):
+        """The multi-resolution STFT distances of `degraded` against `clean` on the device (fastdiff_amd/spectral.py; what people compute
+        with torch.stft over the reference's *_gt.wav / *_pred.wav pairs): two tensors [n] / [B, n] / [B, 1, n] of one shape -> a dict of
+        numpy arrays over the batch: sc, logmag, lsd [B, 4] per resolution, their means mr_sc, mr_logmag, lsd_db (NaN unless OK), frames
+        [B, 4], n_res, status (spectral.OK / SHORT).  valid: [B] sample counts of a padded batch; cfg: resolutions, floor.  Synchronises
+        once, for the records."""
+        from . import spectral as _spectral
+        return _spectral._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
+
     def pitch_track(self, wav, valid=None, **cfg):
         """(f0, aper) of `wav` on the device, float32 [B, n // hop] (fastdiff_amd/pitch.py: track); does not synchronise."""
         from . import pitch as _pitch

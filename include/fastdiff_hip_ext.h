@@ -303,6 +303,81 @@ FD_API int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const
 FD_API int fd_pitch_compare(fd_handle h, const float *f0_ref, const float *f0_deg, int B, int64_t pitch, const int64_t *frames,
                             fd_pitch *rec_dev, void *stream);
 
+/* Multi-resolution STFT distances: how close the spectrum of a vocoded waveform is to the recording's -- spectral convergence and
+ * log-magnitude distance at several window sizes (the multi-resolution STFT error of Parallel WaveGAN, Yamamoto, Song, Kim 2020) and the
+ * log-spectral distance.  The reference ships modules/parallel_wavegan without its STFT loss and utils/torch_stft.py without a caller;
+ * people compute these offline with torch over the *_gt.wav / *_pred.wav pairs that test_step writes.  THIS TEXT defines the measurement;
+ * tests/spectral_ref.py restates it in float64 numpy, and torch.stft on the CPU confirms that restatement.
+ *
+ * Inputs: a recording x and a vocoded waveform y of the same length n.  A configuration (fd_spectral_config; fd_spectral_default_config
+ * fills the values in brackets) holds n_res resolutions, 1 .. FD_SPECTRAL_MAX_RES, each (nfft, hop, win) in samples whatever the rate
+ * [3: (512, 50, 240), (1024, 120, 600), (2048, 240, 1200)], and a power floor [1e-7].  Accepted: nfft in {512, 1024, 2048},
+ * 2 <= win <= nfft, 16 <= hop <= nfft, floor > 0 (and finite), reserved = 0.
+ *
+ * Per resolution, with the conventions of torch.stft(center=True, pad_mode="reflect", window=hann_window(win, periodic=True)):
+ *  1. Padding.  The signal is reflected by nfft / 2 on both sides: position p < 0 reads s[-p], p >= n reads s[2 (n - 1) - p].  Only the
+ *     signal's own n samples are read: nothing at or behind valid[b].
+ *  2. Frames.  F = 1 + n / hop (integer division; fd_spectral_frames).  Frame f covers padded positions f hop - nfft / 2 + i,
+ *     i = 0 .. nfft - 1.
+ *  3. Window.  w[i] = 0.5 - 0.5 cos(2 pi i / win), i = 0 .. win - 1, at offset (nfft - win) / 2 (integer division) inside the nfft frame
+ *     and zero elsewhere.
+ *  4. Magnitudes.  For k = 0 .. nfft / 2:  X[f][k] = sqrt(max(re^2 + im^2, floor)) of the nfft-point transform of the windowed frame of
+ *     x; Y[f][k] likewise of y.
+ *  5. sc = sqrt(sum (X - Y)^2 / sum X^2) over all frames and bins: the spectral convergence.
+ *  6. logmag = mean |ln X - ln Y| over all frames and bins, in nepers.
+ *  7. lsd_db = mean_f sqrt(mean_k (20 log10 X - 20 log10 Y)^2): the log-spectral distance in dB.
+ * The record holds the three values per resolution, their means over the n_res resolutions (mr_sc, mr_logmag, lsd_db), frames[r], n_res
+ * and the status.  FD_SPECTRAL_SHORT: n <= max_r nfft / 2, where the reflection is undefined: every value is NaN (frames[r] is still
+ * F).  FD_SPECTRAL_OK otherwise; the floor keeps sum X^2 > 0, so silence is measured like anything else.  The values of the unused
+ * resolutions r >= n_res are NaN and their frames 0.
+ *
+ * On the device.  Transform stage, one launch per resolution: one workgroup takes FD_SPECTRAL_FRAME_TILE consecutive frames of one pair,
+ * one after the other, and for each frame first x, then y THROUGH THE SAME CODE: the windowed frame (only the win samples under the
+ * window are read) is staged in LDS and transformed in float32 as a split N1 x N2 transform (16 x 32, 32 x 32, 32 x 64 for 512, 1024,
+ * 2048; n = N2 n1 + n2, k = k1 + N1 k2):
+ *     A[n2][k1] = sum_n1 xw[N2 n1 + n2] W_N1^(n1 k1);   B = A W_nfft^(n2 k1);   X[k1 + N1 k2] = sum_n2 B[n2][k1] W_N2^(n2 k2)
+ * with the twiddles read from one table of cos and sin of 2 pi m / nfft, rounded once from double, at exact integer indices (no
+ * recurrences); only the bins 0 .. nfft / 2 are computed.  The powers of x stay in registers until the same thread has the power of y
+ * at the same bin; then, in float64, the floor, the root and the logarithms, and the frame's four partial sums -- sum (X - Y)^2,
+ * sum X^2, sum |d|, sum d^2 with d = ln X - ln Y -- each thread over its own bins in ascending order, the 256 threads by a fixed tree.
+ * They are written to the handle's scratch, four doubles per frame: no spectrogram reaches memory.  Identical signals go through identical
+ * arithmetic, so a copy scores exactly 0.  Finalise stage, one workgroup per pair: per resolution, thread t adds the partials of the
+ * frames t, t + FD_SPECTRAL_SUM_CHUNK, ... in ascending order (sum d^2 after the root of its mean), thread 0 adds the
+ * FD_SPECTRAL_SUM_CHUNK sums in thread order, takes the roots and means and writes the record.  No order depends on B or on where the
+ * pair lies in the batch, and there are no floating-point atomics: a pair's record is bit-identical alone, anywhere in a ragged batch with
+ * anything behind it, at any row pitch and from call to call.  The window and twiddle table of each distinct (nfft, win) is uploaded at
+ * the first call that uses it and kept on the handle; the partials live in a buffer of the handle that grows at the first call that needs
+ * more.  Neither can happen inside a stream capture, where such a call is refused with FD_ERR_STATE: call it once before.  A graph that
+ * holds a captured call points into that buffer: capture after the largest shape has been seen, or capture again. */
+#define FD_SPECTRAL_MAX_RES 4       /* resolutions of one configuration */
+#define FD_SPECTRAL_FRAME_TILE 4    /* consecutive frames of one pair per workgroup of the transform stage */
+#define FD_SPECTRAL_SUM_CHUNK 256   /* interleaved runs of frames the finaliser adds before it adds the runs */
+enum { FD_SPECTRAL_OK = 0, FD_SPECTRAL_SHORT = 1 };
+typedef struct fd_spectral_config {
+    int32_t n_res, reserved;               /* reserved: 0 */
+    int32_t nfft[FD_SPECTRAL_MAX_RES], hop[FD_SPECTRAL_MAX_RES], win[FD_SPECTRAL_MAX_RES];
+    double floor;                          /* on the power re^2 + im^2 */
+} fd_spectral_config;                      /* 64 bytes */
+typedef struct fd_spectral {
+    double sc[FD_SPECTRAL_MAX_RES], logmag[FD_SPECTRAL_MAX_RES], lsd[FD_SPECTRAL_MAX_RES];      /* per resolution; lsd in dB */
+    double mr_sc, mr_logmag, lsd_db;       /* their means over the n_res resolutions */
+    int32_t frames[FD_SPECTRAL_MAX_RES];   /* F per resolution (0 for r >= n_res) */
+    int32_t n_res;
+    int32_t status;                        /* FD_SPECTRAL_* */
+} fd_spectral;                             /* 144 bytes */
+
+/* The bracketed defaults (pure host code).  FD_ERR_INVALID: a null pointer. */
+FD_API int fd_spectral_default_config(fd_spectral_config *cfg);
+/* F for n samples at `hop` (pure host code).  FD_ERR_INVALID (< 0): n < 0 or hop < 1. */
+FD_API int64_t fd_spectral_frames(int64_t n, int hop);
+/* clean, degraded [B][L] device float -> rec_dev [B] device records, asynchronous on `stream`.  valid: HOST [B] or NULL = samples of each
+ * pair that count (1 .. L).  cfg: NULL = the default.  B 1 .. 4096, L 1 .. 2^30.  Like fd_stoi_measure it does not settle a pending lazily
+ * checked fd_sample.  The arguments are checked before the handle is looked at, so a refusal's text is left with fd_last_error(NULL)
+ * when the handle is NULL.  FD_ERR_INVALID: a null handle or pointer, B, L, valid[b] or a configuration value out of range (the message
+ * names the value); FD_ERR_STATE: a table or the scratch buffer would have to be made inside a stream capture. */
+FD_API int fd_spectral_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid,
+                               const fd_spectral_config *cfg, fd_spectral *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
