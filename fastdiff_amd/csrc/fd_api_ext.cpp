@@ -149,11 +149,8 @@ static int ensure_mel_tables(fd_handle h)
     const int NF = 1024;
     const double pi = 3.14159265358979323846;
     std::vector<float> tab(3 * NF);
-    for (int i = 0; i < NF; ++i) {
-        tab[i] = (float)cos(2.0 * pi * i / NF);
-        tab[NF + i] = (float)sin(2.0 * pi * i / NF);
-        tab[2 * NF + i] = (float)(0.5 - 0.5 * cos(2.0 * pi * i / NF));
-    }
+    fdt::twiddles(NF, tab.data(), tab.data() + NF);
+    for (int i = 0; i < NF; ++i) tab[2 * NF + i] = (float)(0.5 - 0.5 * cos(2.0 * pi * i / NF));
     const float *tab_dev = nullptr;
     int rc;
     if ((rc = mel_upload(h, tab.data(), tab.size() * sizeof(float), reinterpret_cast<const void **>(&tab_dev))) != FD_OK) return rc;

@@ -474,6 +474,9 @@ constexpr int RESAMPLE_ITEMS = 64;
 struct ResampleLens { long long v[RESAMPLE_ITEMS]; };
 hipError_t resample(const Launch &L, const void *src, int format, int C, int B, int64_t n_in, int64_t src_pitch, const int64_t *valid,
                     int up, int down, int half, int K, int Kp, int64_t n_out_max, const float *table, float *dst, int64_t dst_pitch);
+// How the tools below lay out their scratch buffers: slots one after the other, each starting on a 256-byte border.
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Carve { size_t at = 0; size_t take(size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; } };      // at: bytes taken so far
 // fd_loudness_measure / fd_loudness_normalize (fd_kernels_loudness.hip).  scratch: loudness_scratch_bytes(B, L, rate) bytes of the handle's
 // loudness buffer; valid_dev: null or loudness_valid_slot() of that buffer, filled by the caller; rec: device [B] or null (a slot of the
 // buffer); the filter and its powers (csrc/fd_loudness.h) are kernel arguments.

@@ -47,6 +47,10 @@ __device__ __forceinline__ float f4c(const float4 &v, int r) { return r == 0 ? v
 // at the end of a signal, tiles behind it are skipped.  Inside [0, lens[b]) the result is bit-identical to running the
 // utterance alone (tests/test_gpu_parity.py); what the output buffers hold behind it is unspecified.
 __device__ __forceinline__ int frames_of(const int *lens, int b, int T) { return lens ? lens[b] : T; }
+// The same for the waveform tools' rows (`lens`: each row's own samples or frames, n_all: those of a whole row), and what their records
+// hold in a field that does not apply (from the bits: the library is built with -fno-honor-nans).
+__device__ __forceinline__ long long own_len(const long long *lens, int b, long long n_all) { return lens ? lens[b] : n_all; }
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 
 // Range flags (Workspace::range_flag): word i = "an operand of fp16-pipe launch i did not fit in this step", word 32 + i = the
 // same for the previous step of the sampler (copied by k_advance).  A launch whose flag was raised in the previous step does
@@ -168,4 +172,5 @@ __device__ __forceinline__ int lvc_tile_of_workgroup()
 }
 
 }  // namespace fdk_fast
+namespace fdk { using fdk_fast::own_len; using fdk_fast::quiet_nan; }      // the waveform tools' kernels live in fdk
 #endif /* FD_KERNELS_COMMON_H */

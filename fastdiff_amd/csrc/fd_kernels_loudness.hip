@@ -22,6 +22,7 @@
 // nothing of them is summed), so an utterance's numbers are the same alone and in a ragged batch.
 #include "fd_internal.h"
 #include "fd_kernels.h"
+#include "fd_kernels_common.h"
 
 namespace fdk {
 
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(256) k_loud_pass(const float *__restrict__ wav
     __shared__ int sq[LD_LANES];
     __shared__ float wm[4];
     const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    const long long n = valid ? valid[b] : L;
+    const long long n = own_len(valid, b, L);
     const long long t0 = (long long)t * LD_TILE;
     if (t0 >= n) return;                                   // (the whole workgroup) a tile behind the utterance: nothing reads its slots
     const float *__restrict__ row = wav + (long long)b * L;
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(64) k_loud_carry(double *__restrict__ state, l
 {
     __shared__ double buf[4 * 256], outb[4 * 256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const long long n = valid ? valid[b] : L;
+    const long long n = own_len(valid, b, L);
     const int nt = (int)((n + LD_TILE - 1) / LD_TILE);
     double *st = state + (long long)b * tiles * 4;
     LdState cur = {0.0, 0.0, 0.0, 0.0};
@@ -225,7 +226,7 @@ __global__ void __launch_bounds__(256) k_loud_gate(long long L, const long long 
 {
     __shared__ double sc[512];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const long long n = valid ? valid[b] : L;
+    const long long n = own_len(valid, b, L);
     const float peak = __uint_as_float(peakbits[b]);
     fd_loudness r;
     r.lufs = -__builtin_huge_val(); r.gain = 1.0f; r.peak = peak; r.blocks = 0; r.gated = 0; r.status = FD_LOUDNESS_SHORT; r.reserved = 0;
@@ -297,7 +298,7 @@ __global__ void k_loud_apply(const float *__restrict__ wav, long long L, const l
 {
     constexpr bool PCM = sizeof(OUT) == 2;
     const int b = blockIdx.y;
-    const long long n = valid ? valid[b] : L;
+    const long long n = own_len(valid, b, L);
     const int status = rec[b].status;
     const float gain = rec[b].gain, m = rec[b].peak;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (long long)gridDim.x * blockDim.x) {
@@ -313,8 +314,6 @@ __global__ void k_loud_apply(const float *__restrict__ wav, long long L, const l
     }
 }
 
-static size_t ld_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the scratch buffer: peak words [B], valid [B], records [B], tile states [B][tiles][4], partials [B][tiles][LD_SEGS], segment sums and block powers [B][zpitch]
 struct LdLayout { size_t peak, valid, rec, state, part, z, total; int tiles; long long zpitch, zoff; };
 static LdLayout ld_layout(int B, int64_t L, int rate)
@@ -324,14 +323,14 @@ static LdLayout ld_layout(int B, int64_t L, int rate)
     const int64_t nb = fdl::blocks(L, rate);
     o.zoff = nb + 4;                                       // per utterance: segment sums [nb + 3], then block powers [nb]
     o.zpitch = o.zoff + nb + 4;
-    size_t at = 0;
-    o.peak = at; at = ld_align(at + sizeof(unsigned int) * B);
-    o.valid = at; at = ld_align(at + sizeof(long long) * B);
-    o.rec = at; at = ld_align(at + sizeof(fd_loudness) * B);
-    o.state = at; at = ld_align(at + sizeof(double) * 4 * (size_t)B * o.tiles);
-    o.part = at; at = ld_align(at + sizeof(double) * LD_SEGS * (size_t)B * o.tiles);
-    o.z = at; at = ld_align(at + sizeof(double) * (size_t)B * (size_t)o.zpitch);
-    o.total = at;
+    Carve c;
+    o.peak = c.take(sizeof(unsigned int) * B);
+    o.valid = c.take(sizeof(long long) * B);
+    o.rec = c.take(sizeof(fd_loudness) * B);
+    o.state = c.take(sizeof(double) * 4 * (size_t)B * o.tiles);
+    o.part = c.take(sizeof(double) * LD_SEGS * (size_t)B * o.tiles);
+    o.z = c.take(sizeof(double) * (size_t)B * (size_t)o.zpitch);
+    o.total = c.at;
     return o;
 }
 

@@ -2,18 +2,17 @@
 //
 // Reference: data_gen/tts/data_gen_utils.py:93-147 (process_utterance, vocoder='pwg'):
 //   librosa.stft(n_fft=1024, hop=256, win=1024, window="hann", center, pad_mode="constant") -> |.| -> librosa.filters.mel(22050, 1024,
-//   80, 80, 7600) @ . -> log10(max(1e-6, .)).   One workgroup = one frame.  The 1024-point DFT is done as 32 x 32 (Cooley-Tukey, one
-// split): n = 32 n1 + n2, k = k1 + 32 k2,
-//     A[n2][k1] = sum_n1 x[32 n1 + n2] W32^(n1 k1);   B = A * W1024^(n2 k1);   X[k1 + 32 k2] = sum_n2 B[n2][k1] W32^(n2 k2)
-// two passes of 32-term sums through LDS (every table index is an exact integer product mod 32 / 1024; no recurrences), ~700 FMAs per
-// thread instead of the ~4000 LDS-bound ones of a direct DFT (0.16 ms for the B=8 x 864-frame benchmark batch).  The 513 magnitudes go
-// back to LDS and 80 threads apply their triangular filter and the log.
+//   80, 80, 7600) @ . -> log10(max(1e-6, .)).   One workgroup = one frame.  The 1024-point DFT is the split transform of
+// fd_kernels_dft.h (32 x 32): two passes of 32-term sums through LDS, ~700 FMAs per thread instead of the ~4000 LDS-bound ones of a
+// direct DFT (0.16 ms for the B=8 x 864-frame benchmark batch).  The 513 magnitudes go back to LDS and 80 threads apply their
+// triangular filter and the log.
 //
 // TACO = the Tacotron front-end (data_gen/tts/tacotron/layers.py:42-80 TacotronSTFT.mel_spectrogram over tacotron/stft.py:78-104
 // STFT.transform, driven by vocoder_binarizer_tacotron.py:110-116): the same transform with the signal REFLECT-padded by 512
 // (stft.py:84-88), filters.mel(22050, 1024, 80, 0, 8000) and ln(clamp(., 1e-5)) (audio_processing.py:78-84).
 #include "fd_internal.h"
 #include "fd_kernels.h"
+#include "fd_kernels_dft.h"
 
 namespace fdk {
 
@@ -23,7 +22,9 @@ __global__ void __launch_bounds__(256) k_mel_frontend(const float *__restrict__ 
                                                       const int *__restrict__ fb_off, const float *__restrict__ fb_w, int64_t n_samples,
                                                       int T)
 {
-    __shared__ float ct[1024], st[1024], xw[1024], br[1024], bi[1024], mag[544];
+    constexpr int N = 1024;
+    static_assert(fdt::split_n1(N) == 32 && fdt::split_n2(N) == 32, "the bins below are cut as 32 x 32");
+    __shared__ float ct[N], st[N], xw[N], br[32 * fdt::row(N)], bi[32 * fdt::row(N)], mag[544];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lo5 = tid & 31, g = tid >> 5;
     const float *w = wav + (int64_t)b * n_samples;
 #pragma unroll
@@ -36,46 +37,18 @@ __global__ void __launch_bounds__(256) k_mel_frontend(const float *__restrict__ 
         xw[n] = (p >= 0 && p < n_samples) ? w[p] * tab[2048 + n] : 0.0f;      // periodic Hann window
     }
     __syncthreads();
-    // pass 1: thread = (n2 = lo5, k1 = 4g .. 4g+3); W32^m = (ct, -st)[32 m]
-    {
-        float re[4] = {0.f, 0.f, 0.f, 0.f}, im[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-        for (int n1 = 0; n1 < 32; ++n1) {
-            const float x = xw[32 * n1 + lo5];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int m = ((n1 * (4 * g + j)) & 31) << 5;
-                re[j] = fmaf(x, ct[m], re[j]);
-                im[j] = fmaf(-x, st[m], im[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                  // twiddle W1024^(n2 k1) = (c, -s)
-            const int k1 = 4 * g + j, m = lo5 * k1;                     // <= 31 * 31
-            const float c = ct[m], sn = st[m];
-            br[lo5 * 32 + k1] = re[j] * c + im[j] * sn;
-            bi[lo5 * 32 + k1] = im[j] * c - re[j] * sn;
-        }
-    }
+    dft_pass1<N>(xw, ct, st, 0, 32, br, bi, tid);
     __syncthreads();
     // pass 2: thread = (k1 = lo5, k2 in {g, g + 8, 16 (g == 0)}); only k <= 512 is kept
     {
-        float re[3] = {0.f, 0.f, 0.f}, im[3] = {0.f, 0.f, 0.f};
+        float re[3], im[3];
         const int k2s[3] = {g, g + 8, 16};
-#pragma unroll 8
-        for (int n2 = 0; n2 < 32; ++n2) {
-            const float xr = br[n2 * 32 + lo5], xi = bi[n2 * 32 + lo5];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int m = ((n2 * k2s[j]) & 31) << 5;
-                const float c = ct[m], sn = st[m];                       // times (c - i s)
-                re[j] = fmaf(xr, c, fmaf(xi, sn, re[j]));
-                im[j] = fmaf(xi, c, fmaf(-xr, sn, im[j]));
-            }
-        }
-        mag[lo5 + 32 * g] = sqrtf(re[0] * re[0] + im[0] * im[0]);
-        mag[lo5 + 32 * (g + 8)] = sqrtf(re[1] * re[1] + im[1] * im[1]);
-        if (g == 0 && lo5 == 0) mag[512] = sqrtf(re[2] * re[2] + im[2] * im[2]);
+        dft_pass2<N, 8>(br, bi, ct, st, lo5, k2s, re, im);
+        // |X| = sqrt(re re + im im), rounded the way this kernel has always been compiled -- the two bins of every thread contracted to
+        // fmaf(im, im, re re), bin 512 not contracted -- and written out, so that the compiler's choice no longer decides a mel value
+        mag[lo5 + 32 * g] = sqrtf(fmaf(im[0], im[0], __fmul_rn(re[0], re[0])));
+        mag[lo5 + 32 * (g + 8)] = sqrtf(fmaf(im[1], im[1], __fmul_rn(re[1], re[1])));
+        if (g == 0 && lo5 == 0) mag[512] = sqrtf(__fadd_rn(__fmul_rn(re[2], re[2]), __fmul_rn(im[2], im[2])));
     }
     __syncthreads();
     if (tid < 80) {

@@ -23,6 +23,7 @@
 
 #include "fd_internal.h"
 #include "fd_kernels.h"
+#include "fd_kernels_common.h"
 
 namespace fdk {
 
@@ -41,7 +42,7 @@ __global__ void __launch_bounds__(256) k_pitch_track(const float *__restrict__ x
     float *xs = reinterpret_cast<float *>(pt_lds);         // [stage]: the samples of a stage group; afterwards 4 x [L] doubles of d'
     float *dsum = xs + P.stage;                            // [PT_FT][L]
     const int b = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const long long n = lens ? lens[b] : n_all;
+    const long long n = own_len(lens, b, n_all);
     const int F = (int)(n / P.hop);                        // <= F_all
     const int i0 = blockIdx.x * PT_FT;
     const int nf = F - i0 < PT_FT ? (F - i0 > 0 ? F - i0 : 0) : PT_FT;      // frames of this tile that exist
@@ -150,7 +151,7 @@ __global__ void __launch_bounds__(256) k_pitch_compare(const float *__restrict__
     __shared__ double ssum[256];
     __shared__ int scnt[256][5];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int F = (int)(frames ? frames[b] : F_all);
+    const int F = (int)own_len(frames, b, F_all);
     const float *__restrict__ r = fr + (long long)b * pitch, *__restrict__ g = fd + (long long)b * pitch;
     const int run = (F + 255) / 256;
     double sum = 0.0;
@@ -178,7 +179,7 @@ __global__ void __launch_bounds__(256) k_pitch_compare(const float *__restrict__
     }
     // the three doubles go out as 64-bit integers: the NaN of a field that does not apply is a bit pattern chosen from the counts, which
     // no reading of -fno-honor-nans can turn into something else
-    const long long nan_bits = 0x7FF8000000000000LL;
+    const long long nan_bits = __double_as_longlong(quiet_nan());
     const int status = F == 0 ? FD_PITCH_SHORT : (both == 0 ? FD_PITCH_UNVOICED : FD_PITCH_OK);
     long long rmse_bits = nan_bits, gpe_bits = nan_bits, vde_bits = nan_bits;
     if (status == FD_PITCH_OK) {

@@ -5,12 +5,9 @@
 //
 //   k_spectral_frames<nfft>     grid (frame tiles, B), one launch per resolution: SP_TILE consecutive frames of one pair per workgroup, one
 //                     after the other; per frame x, then y, through the same code: the win samples under the window (reflected at the
-//                     pair's own ends) times the window into LDS, then the nfft = N1 N2 point transform in float32 as in
-//                     fd_kernels_stoi.hip (n = N2 n1 + n2, k = k1 + N1 k2):
-//                         A[n2][k1] = sum_n1 xw[N2 n1 + n2] W_N1^(n1 k1);  B = A W_nfft^(n2 k1);  X[k1 + N1 k2] = sum_n2 B[n2][k1] W_N2^(n2 k2)
-//                     pass 1: thread = (n2, k1 = g + G q), only the n1 that can lie under the window; pass 2: thread = bins tid,
-//                     tid + 256, ... < nfft / 2 (the same k1, so B is read once for all of them), thread 0 also the bin nfft / 2.  All table
-//                     indices are exact integer products.  The power of x at a bin waits in a register for the power of y; then in
+//                     pair's own ends) times the window into LDS, then the nfft-point transform of fd_kernels_dft.h: pass 1 over the
+//                     n1 that can lie under the window only; pass 2: thread = bins tid, tid + 256, ... < nfft / 2 (the same k1, so one
+//                     call), thread 0 also the bin nfft / 2.  The power of x at a bin waits in a register for the power of y; then in
 //                     float64 the floor, X - Y and d = (ln Px - ln Py) / 2, the thread's bins in ascending order, and a fixed tree over
 //                     the 256 threads -> four doubles per frame in the scratch: sum (X - Y)^2, sum X^2, sum |d|, sum d^2.
 //   k_spectral_finish one workgroup per pair: per resolution thread t adds the frames t, t + 256, ... in ascending order (sum d^2 after
@@ -21,6 +18,8 @@
 // a copy scores exactly 0.  Nothing at or behind a pair's own length is read.
 #include "fd_internal.h"
 #include "fd_kernels.h"
+#include "fd_kernels_common.h"
+#include "fd_kernels_dft.h"
 
 namespace fdk {
 
@@ -30,8 +29,6 @@ static_assert(fdx::THREADS == 256 && SP_CHUNK == 256, "256-thread workgroups thr
 static_assert(sizeof(fd_spectral) == 144 && sizeof(fd_spectral_config) == 64, "the sizes the header states");
 static_assert(fdx::lds_bytes(2048) <= fdx::LDS_WORKGROUP_MAX && fdx::lds_bytes(1024) <= fdx::LDS_WORKGROUP_MAX && fdx::lds_bytes(512) <= fdx::LDS_WORKGROUP_MAX,
               "a transform workgroup's LDS");
-
-__device__ __forceinline__ double sp_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 
 // sums the four doubles of every thread in a fixed tree; the result is in red[q][0]
 __device__ __forceinline__ void sp_reduce(double (*red)[256], int tid, const double *a)
@@ -65,15 +62,14 @@ __global__ void __launch_bounds__(256) k_spectral_frames(const float *__restrict
                                                          const long long *__restrict__ lens, long long n_all, const float *__restrict__ tab,
                                                          int hop, int win, int short_n, double floor_, double *__restrict__ part, int Fp)
 {
-    constexpr int N1 = fdx::split_n1(N), N2 = fdx::split_n2(N), ROW = N1 + 1;
-    constexpr int G = 256 / N2, Q = N1 / G;                // pass 1: thread = (n2, k1 = g + G q), q < Q
-    constexpr int J = N / 512, K2S = 256 / N1;             // pass 2: thread = bins tid + 256 j, j < J: k1 = tid % N1, k2 = tid / N1 + K2S j
-    static_assert(N1 * N2 == N && 256 % N2 == 0 && N1 % G == 0 && 256 % N1 == 0 && J >= 1, "the split");
+    constexpr int N1 = fdt::split_n1(N), N2 = fdt::split_n2(N), ROW = fdt::row(N);
+    constexpr int J = N / 512, K2S = 256 / N1;             // pass 2: thread = bins tid + 256 j, j < J
+    static_assert(256 % N1 == 0 && J >= 1, "whole bins per thread");
     __shared__ float ct[N], sn[N], xw[N], ar[N2 * ROW], ai[N2 * ROW];
     __shared__ double red[4][256];
     static_assert(sizeof(float) * (3 * N + 2 * N2 * ROW) + sizeof(double) * 4 * 256 == fdx::lds_bytes(N), "fd_spectral.h states this workgroup's LDS");
     const int b = blockIdx.y, tid = threadIdx.x;
-    const long long n = lens ? lens[b] : n_all;
+    const long long n = own_len(lens, b, n_all);
     if (n <= short_n) return;                              // (the whole workgroup) SHORT: the reflection is undefined
     const long long F = 1 + n / hop;
     const long long f0 = (long long)blockIdx.x * SP_TILE;
@@ -99,58 +95,23 @@ __global__ void __launch_bounds__(256) k_spectral_frames(const float *__restrict
                 xw[i] = v;
             }
             __syncthreads();
-            {   // pass 1; W_N1^q = (ct, -sn)[N2 q]
-                const int n2 = tid % N2, g = tid / N2;
-                float re[Q], im[Q];
-#pragma unroll
-                for (int q = 0; q < Q; ++q) re[q] = im[q] = 0.0f;
-                for (int n1 = n1_lo; n1 < n1_hi; ++n1) {
-                    const float xv = xw[N2 * n1 + n2];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) {
-                        const int t = ((n1 * (g + G * q)) & (N1 - 1)) * N2;
-                        re[q] = fmaf(xv, ct[t], re[q]);
-                        im[q] = fmaf(-xv, sn[t], im[q]);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {              // twiddle W_N^(n2 k1) = (c, -s); n2 k1 <= (N2 - 1)(N1 - 1) < N
-                    const int k1 = g + G * q, t = n2 * k1;
-                    const float c = ct[t], sv = sn[t];
-                    ar[n2 * ROW + k1] = re[q] * c + im[q] * sv;
-                    ai[n2 * ROW + k1] = im[q] * c - re[q] * sv;
-                }
-            }
+            dft_pass1<N>(xw, ct, sn, n1_lo, n1_hi, ar, ai, tid);
             __syncthreads();
             float pw[J], pwn = 0.0f;
-            {   // pass 2; W_N2^q = (ct, -sn)[N1 q]
-                const int k1 = tid % N1, k2 = tid / N1;
+            {   // this thread's bins tid + 256 j: k1 = tid % N1, k2 = tid / N1 + K2S j
+                int k2[J];
                 float re[J], im[J];
 #pragma unroll
-                for (int j = 0; j < J; ++j) re[j] = im[j] = 0.0f;
-#pragma unroll 4
-                for (int n2 = 0; n2 < N2; ++n2) {
-                    const float xr = ar[n2 * ROW + k1], xi = ai[n2 * ROW + k1];
-#pragma unroll
-                    for (int j = 0; j < J; ++j) {
-                        const int t = ((n2 * (k2 + K2S * j)) & (N2 - 1)) * N1;
-                        const float c = ct[t], sv = sn[t];
-                        re[j] = fmaf(xr, c, fmaf(xi, sv, re[j]));
-                        im[j] = fmaf(xi, c, fmaf(-xr, sv, im[j]));
-                    }
-                }
+                for (int j = 0; j < J; ++j) k2[j] = tid / N1 + K2S * j;
+                dft_pass2<N>(ar, ai, ct, sn, tid % N1, k2, re, im);
 #pragma unroll
                 for (int j = 0; j < J; ++j) pw[j] = fmaf(re[j], re[j], im[j] * im[j]);
                 if (tid == 0) {                            // bin N / 2: k1 = 0, k2 = N2 / 2
-                    float rn = 0.0f, in = 0.0f;
-                    for (int n2 = 0; n2 < N2; ++n2) {
-                        const float xr = ar[n2 * ROW], xi = ai[n2 * ROW];
-                        const int t = ((n2 * (N2 / 2)) & (N2 - 1)) * N1;
-                        const float c = ct[t], sv = sn[t];
-                        rn = fmaf(xr, c, fmaf(xi, sv, rn));
-                        in = fmaf(xi, c, fmaf(-xr, sv, in));
-                    }
-                    pwn = fmaf(rn, rn, in * in);
+                    const int kn[1] = {N2 / 2};
+                    float rn[1], in[1];
+                    // (one wavefront while three wait; unrolled by 32 at N2 = 64 the 2048-point kernel is 2 % slower, LABBOOK R25.1)
+                    dft_pass2<N, (N2 == 32 ? 32 : 8)>(ar, ai, ct, sn, 0, kn, rn, in);
+                    pwn = fmaf(rn[0], rn[0], in[0] * in[0]);
                 }
             }
             if (sig == 0) {
@@ -175,15 +136,15 @@ __global__ void __launch_bounds__(256) k_spectral_finish(const long long *__rest
 {
     __shared__ double red[4][256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const long long n = lens ? lens[b] : n_all;
+    const long long n = own_len(lens, b, n_all);
     const bool ok = n > pl.short_n;
     fd_spectral r;
-    r.mr_sc = r.mr_logmag = r.lsd_db = sp_nan();
+    r.mr_sc = r.mr_logmag = r.lsd_db = quiet_nan();
     r.n_res = pl.n_res;
     r.status = ok ? FD_SPECTRAL_OK : FD_SPECTRAL_SHORT;
     double m_sc = 0.0, m_lm = 0.0, m_lsd = 0.0;
     for (int q = 0; q < SP_RES; ++q) {                     // (every thread passes every barrier)
-        r.sc[q] = r.logmag[q] = r.lsd[q] = sp_nan();
+        r.sc[q] = r.logmag[q] = r.lsd[q] = quiet_nan();
         r.frames[q] = 0;
         if (q >= pl.n_res) continue;
         const long long F = 1 + n / pl.hop[q];
@@ -213,20 +174,18 @@ __global__ void __launch_bounds__(256) k_spectral_finish(const long long *__rest
     rec[b] = r;
 }
 
-static size_t sp_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the scratch buffer: lengths [B], then per resolution the frame partials [B][Fp][4] doubles
 struct SpLayout { size_t lens, part[SP_RES], total; int Fp[SP_RES]; };
 static SpLayout sp_layout(int B, int64_t L, const fd_spectral_config &c)
 {
     SpLayout o{};
-    size_t at = 0;
-    o.lens = at; at = sp_align(at + sizeof(long long) * (size_t)B);
+    Carve cv;
+    o.lens = cv.take(sizeof(long long) * (size_t)B);
     for (int r = 0; r < c.n_res; ++r) {
         o.Fp[r] = (int)fdx::frames(L, c.hop[r]);
-        o.part[r] = at; at = sp_align(at + sizeof(double) * 4 * (size_t)B * (size_t)o.Fp[r]);
+        o.part[r] = cv.take(sizeof(double) * 4 * (size_t)B * (size_t)o.Fp[r]);
     }
-    o.total = at;
+    o.total = cv.at;
     return o;
 }
 

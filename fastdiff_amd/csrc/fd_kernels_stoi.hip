@@ -11,10 +11,9 @@
 //   k_stoi_compact    the tile's flags again, an exclusive scan over its 256 threads (4 consecutive frames each), src[k] = i.
 //   k_stoi_bands      grid (M, B, 2 signals), one workgroup per STFT frame: sample j of frame m of the silence-free signal is the sum of
 //                     at most two windowed source samples (kept frames m - 1 | m for j < 128, m | m + 1 above: a gather); windowed
-//                     again, 512-point DFT of the 256 samples as 16 x 32 in LDS (n = 32 n1 + n2, n1 < 8 non-zero; k = k1 + 16 k2):
-//                         A[n2][k1] = sum_n1 x[32 n1 + n2] W16^(n1 k1);  B = A W512^(n2 k1);  X[k1 + 16 k2] = sum_n2 B[n2][k1] W32^(n2 k2)
-//                     with exact integer table indices and no recurrences (as fd_kernels_mel.hip), only k2 < 14 (bins 0 .. 223; the bands
-//                     cover 7 .. 218); 15 threads add their band's |X|^2 in ascending k and write the root.
+//                     again, 512-point DFT of the 256 samples by the split transform of fd_kernels_dft.h (16 x 32, n1 < 8 non-zero),
+//                     only k2 < 14 (bins 0 .. 223; the bands cover 7 .. 218); 15 threads add their band's |X|^2 in ascending k and
+//                     write the root.
 //   k_stoi_segments   grid (segment tiles, B), float64: ST_SEGS segments per workgroup, their 45 frames staged in LDS.  STOI: one
 //                     thread per (segment, band), the 15 bands then added in band order.  ESTOI: one wavefront per segment (four
 //                     segments one after the other): rows, then columns, then 30 column sums added in frame order.
@@ -25,6 +24,8 @@
 // alone, anywhere in a ragged batch and from call to call.  Nothing at or behind an utterance's own length is read.
 #include "fd_internal.h"
 #include "fd_kernels.h"
+#include "fd_kernels_common.h"
+#include "fd_kernels_dft.h"
 
 namespace fdk {
 
@@ -44,7 +45,7 @@ __global__ void __launch_bounds__(256) k_stoi_energy(const float *__restrict__ x
 {
     __shared__ float wm[4];
     const int b = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int F0 = st_frames(lens ? lens[b] : n_all);
+    const int F0 = st_frames(own_len(lens, b, n_all));
     const int i = blockIdx.x * 4 + wv;
     float e = 0.0f;
     if (i < F0) {                                          // (the whole wavefront)
@@ -93,7 +94,7 @@ __global__ void __launch_bounds__(256) k_stoi_count(const float *__restrict__ E,
 {
     __shared__ int sc[256];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int F0 = st_frames(lens ? lens[b] : n_all);
+    const int F0 = st_frames(own_len(lens, b, n_all));
     int bits;
     const int c = st_flags(E + (long long)b * Fp, F0, __uint_as_float(maxbits[b]), blockIdx.x * ST_SCAN + tid * 4, bits);
     const int incl = st_scan256(sc, tid, c);
@@ -105,7 +106,7 @@ __global__ void __launch_bounds__(256) k_stoi_offsets(const long long *__restric
 {
     __shared__ int sc[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int F0 = st_frames(lens ? lens[b] : n_all);
+    const int F0 = st_frames(own_len(lens, b, n_all));
     const int nb = (F0 + ST_SCAN - 1) / ST_SCAN;           // <= nblk
     int *__restrict__ row = blk + (long long)b * nblk;
     int carry = 0;
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(256) k_stoi_compact(const float *__restrict__ 
 {
     __shared__ int sc[256];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int F0 = st_frames(lens ? lens[b] : n_all);
+    const int F0 = st_frames(own_len(lens, b, n_all));
     const int i0 = blockIdx.x * ST_SCAN + tid * 4;
     int bits;
     const int c = st_flags(E + (long long)b * Fp, F0, __uint_as_float(maxbits[b]), i0, bits);
@@ -144,7 +145,8 @@ __global__ void __launch_bounds__(256) k_stoi_bands(const float *__restrict__ x,
                                                     const float *__restrict__ tab, const int *__restrict__ src, int Fp,
                                                     const int *__restrict__ kept, StoiBands bd, float *__restrict__ bands, int B, int Mp)
 {
-    __shared__ float ct[ST_NFFT], sn[ST_NFFT], xw[ST_FRAME], ar[32 * 16], ai[32 * 16], pw[224];
+    static_assert(fdt::split_n1(ST_NFFT) == 16 && fdt::split_n2(ST_NFFT) == 32, "the bins below are cut as 16 x 32");
+    __shared__ float ct[ST_NFFT], sn[ST_NFFT], xw[ST_FRAME], ar[32 * fdt::row(ST_NFFT)], ai[32 * fdt::row(ST_NFFT)], pw[224];
     const int m = blockIdx.x, b = blockIdx.y, sig = blockIdx.z, tid = threadIdx.x;
     if (m >= kept[b] - 1) return;                          // (the whole workgroup) M = K - 1 frames
     const float *__restrict__ w = tab;
@@ -161,41 +163,14 @@ __global__ void __launch_bounds__(256) k_stoi_bands(const float *__restrict__ x,
         xw[j] = __fmul_rn(v, w[j]);
     }
     __syncthreads();
-    {   // pass 1: thread = (n2, k1 in {2g, 2g + 1}); W16^q = (ct, -sn)[32 q]
-        const int n2 = tid & 31, g = tid >> 5;
-        float re[2] = {0.f, 0.f}, im[2] = {0.f, 0.f};
-#pragma unroll
-        for (int n1 = 0; n1 < 8; ++n1) {
-            const float xv = xw[32 * n1 + n2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int t = ((n1 * (2 * g + q)) & 15) << 5;
-                re[q] = fmaf(xv, ct[t], re[q]);
-                im[q] = fmaf(-xv, sn[t], im[q]);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {                      // twiddle W512^(n2 k1) = (c, -s); n2 k1 <= 31 * 15
-            const int k1 = 2 * g + q, t = n2 * k1;
-            const float c = ct[t], s = sn[t];
-            ar[n2 * 16 + k1] = re[q] * c + im[q] * s;
-            ai[n2 * 16 + k1] = im[q] * c - re[q] * s;
-        }
-    }
+    dft_pass1<ST_NFFT>(xw, ct, sn, 0, ST_FRAME / 32, ar, ai, tid);      // the frame's 256 samples: n1 < 8
     __syncthreads();
-    {   // pass 2: thread = (k1, k2 < 14); W32^q = (ct, -sn)[16 q]
-        const int k1 = tid & 15, k2 = tid >> 4;
-        if (k2 < 14) {
-            float re = 0.f, im = 0.f;
-#pragma unroll 8
-            for (int n2 = 0; n2 < 32; ++n2) {
-                const float xr = ar[n2 * 16 + k1], xi = ai[n2 * 16 + k1];
-                const int t = ((n2 * k2) & 31) << 4;
-                const float c = ct[t], s = sn[t];
-                re = fmaf(xr, c, fmaf(xi, s, re));
-                im = fmaf(xi, c, fmaf(-xr, s, im));
-            }
-            pw[k1 + 16 * k2] = fmaf(re, re, im * im);
+    {   // pass 2: thread = (k1, k2 < 14)
+        const int k1 = tid & 15, k2[1] = {tid >> 4};
+        if (k2[0] < 14) {
+            float re[1], im[1];
+            dft_pass2<ST_NFFT, 8>(ar, ai, ct, sn, k1, k2, re, im);
+            pw[k1 + 16 * k2[0]] = fmaf(re[0], re[0], im[0] * im[0]);
         }
     }
     __syncthreads();
@@ -317,10 +292,10 @@ __global__ void __launch_bounds__(256) k_stoi_finish(const long long *__restrict
 {
     __shared__ double sa[256], sb[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int F0 = st_frames(lens ? lens[b] : n_all);
+    const int F0 = st_frames(own_len(lens, b, n_all));
     const int K = kept[b], J = K - ST_SEG;
     fd_stoi r;
-    r.stoi = r.estoi = __longlong_as_double(0x7FF8000000000000LL);
+    r.stoi = r.estoi = quiet_nan();
     r.frames = F0; r.kept = K; r.segments = 0;
     r.status = F0 == 0 ? FD_STOI_SHORT : (maxbits[b] == 0u ? FD_STOI_SILENT : (J < 1 ? FD_STOI_SHORT : FD_STOI_OK));
     if (r.status != FD_STOI_OK) {
@@ -342,8 +317,6 @@ __global__ void __launch_bounds__(256) k_stoi_finish(const long long *__restrict
     rec[b] = r;
 }
 
-static size_t st_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the scratch buffer: lengths [B], max words [B] + K [B], the two 10 kHz signals [B][pitch10] (only when resampled), energies [B][Fp],
 // tile counts / offsets [B][nblk], src [B][Fp], band amplitudes [2][B][Mp][16], per-segment partials [B][Jp][2]
 struct StLayout { size_t lens, words, x10, y10, E, blk, src, bands, part, total; long long pitch10; int F0, Fp, nblk, M, Mp, J, Jp; };
@@ -358,17 +331,17 @@ static StLayout st_layout(int B, int64_t n10, bool resampled)
     o.J = (int)fds::segments(o.F0);
     o.Jp = o.J > 0 ? o.J : 1;
     o.pitch10 = resampled ? (long long)((n10 + 3) & ~(int64_t)3) : 0;
-    size_t at = 0;
-    o.lens = at; at = st_align(at + sizeof(long long) * B);
-    o.words = at; at = st_align(at + sizeof(int) * 2 * (size_t)B);
-    o.x10 = at; at = st_align(at + sizeof(float) * (size_t)B * (size_t)o.pitch10);
-    o.y10 = at; at = st_align(at + sizeof(float) * (size_t)B * (size_t)o.pitch10);
-    o.E = at; at = st_align(at + sizeof(float) * (size_t)B * o.Fp);
-    o.blk = at; at = st_align(at + sizeof(int) * (size_t)B * o.nblk);
-    o.src = at; at = st_align(at + sizeof(int) * (size_t)B * o.Fp);
-    o.bands = at; at = st_align(at + sizeof(float) * 32 * (size_t)B * o.Mp);
-    o.part = at; at = st_align(at + sizeof(double) * 2 * (size_t)B * o.Jp);
-    o.total = at;
+    Carve c;
+    o.lens = c.take(sizeof(long long) * B);
+    o.words = c.take(sizeof(int) * 2 * (size_t)B);
+    o.x10 = c.take(sizeof(float) * (size_t)B * (size_t)o.pitch10);
+    o.y10 = c.take(sizeof(float) * (size_t)B * (size_t)o.pitch10);
+    o.E = c.take(sizeof(float) * (size_t)B * o.Fp);
+    o.blk = c.take(sizeof(int) * (size_t)B * o.nblk);
+    o.src = c.take(sizeof(int) * (size_t)B * o.Fp);
+    o.bands = c.take(sizeof(float) * 32 * (size_t)B * o.Mp);
+    o.part = c.take(sizeof(double) * 2 * (size_t)B * o.Jp);
+    o.total = c.at;
     return o;
 }
 

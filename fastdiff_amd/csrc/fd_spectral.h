@@ -1,6 +1,6 @@
 // fd_spectral.h -- host side of the multi-resolution STFT distances (include/fastdiff_hip_ext.h: "Multi-resolution STFT distances"): the
 // constants that decide which workgroup and thread handles which frame and bin, the accepted configurations with their refusals, the
-// frame counts, the tables the kernels read (window, twiddles) and the LDS sizing.
+// frame counts, the tables the kernels read (window, twiddles) and the LDS sizing.  The transform itself is described by fd_dft.h.
 // Plain C++ without the HIP runtime, so a stand-alone host program can include it.  tests/spectral_ref.py is the float64 oracle.
 #pragma once
 #include <math.h>
@@ -10,13 +10,14 @@
 #include <string.h>
 
 #include "../../include/fastdiff_hip_ext.h"
+#include "fd_dft.h"
 
 namespace fdx {
 
 constexpr int MAX_RES = 4;                                    // FD_SPECTRAL_MAX_RES
 constexpr int FRAME_TILE = 4;                                 // FD_SPECTRAL_FRAME_TILE: consecutive frames per workgroup of the transform stage
 constexpr int SUM_CHUNK = 256;                                // FD_SPECTRAL_SUM_CHUNK: interleaved runs of frames in the finaliser
-constexpr int THREADS = 256;                                  // every workgroup
+constexpr int THREADS = fdt::THREADS;                         // every workgroup
 constexpr int NFFT_MIN = 512, NFFT_MAX = 2048;
 constexpr int HOP_MIN = 16, WIN_MIN = 2;
 constexpr int64_t MAX_SAMPLES = (int64_t)1 << 30;
@@ -34,10 +35,6 @@ inline void defaults(fd_spectral_config *c)
     c->floor = 1e-7;
 }
 
-// the split nfft = N1 x N2 of the transform (n = N2 n1 + n2, k = k1 + N1 k2); 0 for an nfft that is not accepted
-constexpr int split_n1(int nfft) { return nfft == 512 ? 16 : (nfft == 1024 || nfft == 2048 ? 32 : 0); }
-constexpr int split_n2(int nfft) { return split_n1(nfft) ? nfft / split_n1(nfft) : 0; }
-
 // neither infinite nor NaN, read from the bits (the library is built without NaN-honouring comparisons)
 inline bool finite(double v)
 {
@@ -53,7 +50,7 @@ inline const char *refusal(const fd_spectral_config &c, char (&msg)[MSG])
     if (c.n_res < 1 || c.n_res > MAX_RES) { snprintf(msg, MSG, "n_res = %d outside 1 .. %d", (int)c.n_res, MAX_RES); return msg; }
     if (!finite(c.floor) || !(c.floor > 0.0)) { snprintf(msg, MSG, "floor = %g is not a positive finite number", c.floor); return msg; }
     for (int r = 0; r < c.n_res; ++r) {
-        if (!split_n1(c.nfft[r])) { snprintf(msg, MSG, "nfft[%d] = %d is not 512, 1024 or 2048", r, (int)c.nfft[r]); return msg; }
+        if (!fdt::split_n1(c.nfft[r])) { snprintf(msg, MSG, "nfft[%d] = %d is not 512, 1024 or 2048", r, (int)c.nfft[r]); return msg; }
         if (c.win[r] < WIN_MIN || c.win[r] > c.nfft[r]) {
             snprintf(msg, MSG, "win[%d] = %d outside %d .. nfft = %d", r, (int)c.win[r], WIN_MIN, (int)c.nfft[r]);
             return msg;
@@ -81,7 +78,7 @@ inline int win_offset(int nfft, int win) { return (nfft - win) / 2; }
 // the n1 of the first pass that can hold a sample under the window: [lo, hi)
 inline void n1_range(int nfft, int win, int *lo, int *hi)
 {
-    const int n2 = split_n2(nfft), off = win_offset(nfft, win);
+    const int n2 = fdt::split_n2(nfft), off = win_offset(nfft, win);
     *lo = off / n2;
     *hi = (off + win - 1) / n2 + 1;
 }
@@ -94,18 +91,11 @@ inline void tables(int nfft, int win, float *tab)
     const int off = win_offset(nfft, win);
     for (int i = 0; i < nfft; ++i) tab[i] = 0.0f;
     for (int i = 0; i < win; ++i) tab[off + i] = (float)(0.5 - 0.5 * cos(2.0 * pi * i / win));
-    for (int m = 0; m < nfft; ++m) {
-        tab[nfft + m] = (float)cos(2.0 * pi * m / nfft);
-        tab[2 * nfft + m] = (float)sin(2.0 * pi * m / nfft);
-    }
+    fdt::twiddles(nfft, tab + nfft, tab + 2 * nfft);
 }
 
-// static LDS of the transform workgroup: cos, sin, the windowed frame [nfft] each; the first pass' result, re and im, rows of N1 padded
-// by one against bank conflicts [N2][N1 + 1]; the reduction's four doubles per thread
-constexpr size_t lds_bytes(int nfft)
-{
-    return sizeof(float) * (3 * (size_t)nfft + 2 * (size_t)split_n2(nfft) * (split_n1(nfft) + 1)) + sizeof(double) * 4 * THREADS;
-}
+// static LDS of the transform workgroup: the transform's own floats and the reduction's four doubles per thread
+constexpr size_t lds_bytes(int nfft) { return sizeof(float) * fdt::lds_floats(nfft) + sizeof(double) * 4 * THREADS; }
 constexpr size_t LDS_WORKGROUP_MAX = 64 * 1024;               // what one workgroup takes without asking; two of the largest fit a CU's 160 KiB
 
 }  // namespace fdx

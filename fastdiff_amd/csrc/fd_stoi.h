@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fd_dft.h"
+
 namespace fds {
 
 constexpr int RATE = 10000;                                   // the rate the measure is defined at
@@ -39,10 +41,7 @@ inline void tables(float *tab)
 {
     const double pi = 3.14159265358979323846;
     for (int i = 0; i < FRAME; ++i) tab[i] = (float)(0.5 - 0.5 * cos(2.0 * pi * (i + 1) / (FRAME + 1)));
-    for (int m = 0; m < NFFT; ++m) {
-        tab[FRAME + m] = (float)cos(2.0 * pi * m / NFFT);
-        tab[FRAME + NFFT + m] = (float)sin(2.0 * pi * m / NFFT);
-    }
+    fdt::twiddles(NFFT, tab + FRAME, tab + FRAME + NFFT);
 }
 
 }  // namespace fds

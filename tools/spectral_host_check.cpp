@@ -4,7 +4,10 @@
 //   * frames(), short_len(), win_offset(), n1_range(): every sample under the window lies in an n1 the first pass visits;
 //   * tables(): built for EVERY accepted (nfft, win) into a buffer of exactly table_floats(nfft) floats -- the window is zero outside
 //     [offset, offset + win) and within [0, 1] inside, cos^2 + sin^2 = 1 to float32 rounding;
-//   * the table indices the kernel forms (W_N1^(n1 k1), W_nfft^(n2 k1), W_N2^(n2 k2)) stay inside the table;
+//   * the table indices the kernel forms (W_N1^(n1 k1), W_nfft^(n2 k1), W_N2^(n2 k2)) stay inside the table, through fd_dft.h, which
+//     describes the transform the kernel shares with the mel front-end and STOI -- so also over the ranges those two use;
+//   * every table that goes through fdt::twiddles (fdx::tables for every accepted (nfft, win), fds::tables, the mel front-end's cos and
+//     sin) equals, bit for bit, the formula each builder spelled out before they shared it, restated here;
 //   * the reflection rule of k_spectral_frames, walked for every frame and every sample under the window over signals of n samples
 //     (n from short_len + 1 upwards) held in a buffer of exactly n floats: nothing at or behind n is read;
 //   * lds_bytes(): within LDS_WORKGROUP_MAX, two of the largest within a CU's 160 KiB.
@@ -18,6 +21,7 @@
 #include <vector>
 
 #include "fd_spectral.h"
+#include "fd_stoi.h"
 
 static long checks = 0;
 #define CHECK(cond)                                                                 \
@@ -25,6 +29,35 @@ static long checks = 0;
         ++checks;                                                                   \
         if (!(cond)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); exit(1); } \
     } while (0)
+
+static const double PI = 3.14159265358979323846;
+
+static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof(a)) == 0; }
+
+// cos and sin [nfft] hold, bit for bit, what every table builder computed before fdt::twiddles: the formula restated
+static bool parents_twiddles(int nfft, const float *c, const float *s)
+{
+    for (int m = 0; m < nfft; ++m)
+        if (!same_bits(c[m], (float)cos(2.0 * PI * m / nfft)) || !same_bits(s[m], (float)sin(2.0 * PI * m / nfft))) return false;
+    return true;
+}
+
+// every index that the shared transform (fd_kernels_dft.h) forms over the n1 in [n1_lo, n1_hi) and the k2 <= k2_max of a caller whose
+// frame holds frame_floats floats: inside the frame, the cos / sin table and the padded first-pass result
+static void transform_indices(int nfft, int n1_lo, int n1_hi, int k2_max, int frame_floats)
+{
+    const int N1 = fdt::split_n1(nfft), N2 = fdt::split_n2(nfft), ROW = fdt::row(nfft);
+    CHECK(N1 * N2 == nfft && ROW >= N1 && fdt::lds_floats(nfft) == 3 * (size_t)nfft + 2 * (size_t)N2 * ROW);
+    CHECK(0 <= n1_lo && n1_lo < n1_hi && n1_hi <= N1 && k2_max < N2);
+    for (int n1 = n1_lo; n1 < n1_hi; ++n1) {
+        for (int n2 = 0; n2 < N2; ++n2) CHECK(N2 * n1 + n2 < frame_floats);
+        for (int k1 = 0; k1 < N1; ++k1) CHECK(((n1 * k1) & (N1 - 1)) * N2 < nfft);
+    }
+    for (int n2 = 0; n2 < N2; ++n2) {
+        for (int k1 = 0; k1 < N1; ++k1) CHECK(n2 * k1 < nfft && n2 * ROW + k1 < N2 * ROW);
+        for (int k2 = 0; k2 <= k2_max; ++k2) CHECK(((n2 * k2) & (N2 - 1)) * N1 < nfft);
+    }
+}
 
 static fd_spectral_config one(int nfft, int hop, int win, double floor_ = 1e-7)
 {
@@ -50,7 +83,7 @@ int main()
     CHECK(sizeof(fd_spectral) == 144 && sizeof(fd_spectral) % 8 == 0 && sizeof(fd_spectral_config) == 64);
     const int nffts[3] = {512, 1024, 2048};
     for (int nfft : nffts) {
-        const int N1 = fdx::split_n1(nfft), N2 = fdx::split_n2(nfft);
+        const int N1 = fdt::split_n1(nfft), N2 = fdt::split_n2(nfft);
         CHECK(N1 * N2 == nfft && 256 % N2 == 0 && 256 % N1 == 0);
         CHECK(fdx::lds_bytes(nfft) <= fdx::LDS_WORKGROUP_MAX && 2 * fdx::lds_bytes(nfft) <= 160 * 1024);
         // the borders of the accepted range, and one step outside
@@ -59,16 +92,12 @@ int main()
         CHECK(refused(one(nfft, 50, 1), "win[0] = 1") && refused(one(nfft, 50, nfft + 1), "win[0] = "));
         CHECK(refused(one(nfft + 256, 50, 240), "nfft[0] = ") && refused(one(nfft, 50, 240, 0.0), "floor = 0") && refused(one(nfft, 50, 240, -1.0), "floor = -1"));
         CHECK(refused(one(nfft, 50, 240, NAN), "floor = ") && refused(one(nfft, 50, 240, INFINITY), "floor = inf"));
-        // the kernel's table indices
-        for (int n1 = 0; n1 < N1; ++n1)
-            for (int k1 = 0; k1 < N1; ++k1) CHECK(((n1 * k1) & (N1 - 1)) * N2 < nfft);
-        for (int n2 = 0; n2 < N2; ++n2) {
-            for (int k1 = 0; k1 < N1; ++k1) CHECK(n2 * k1 < nfft);
-            for (int k2 = 0; k2 <= N2 / 2; ++k2) CHECK(((n2 * k2) & (N2 - 1)) * N1 < nfft);
-        }
+        transform_indices(nfft, 0, N1, N2 / 2, nfft);       // the kernel's table and LDS indices
         for (int win = fdx::WIN_MIN; win <= nfft; ++win) {
             std::vector<float> tab(fdx::table_floats(nfft));      // exactly: the sanitizer sees a write behind it
             fdx::tables(nfft, win, tab.data());
+            for (int i = 0; i < win; ++i) CHECK(same_bits(tab[(nfft - win) / 2 + i], (float)(0.5 - 0.5 * cos(2.0 * PI * i / win))));
+            CHECK(parents_twiddles(nfft, tab.data() + nfft, tab.data() + 2 * nfft));
             const int off = fdx::win_offset(nfft, win);
             int lo, hi;
             fdx::n1_range(nfft, win, &lo, &hi);
@@ -107,6 +136,17 @@ int main()
                 }
             }
         }
+    }
+    // the other two callers of the shared transform: the mel front-end (all 32 n1, k2 <= 16) and STOI (256 samples: n1 < 8; k2 < 14)
+    transform_indices(1024, 0, 32, 16, 1024);
+    transform_indices(fds::NFFT, 0, fds::FRAME / fdt::split_n2(fds::NFFT), 13, fds::FRAME);
+    {   // their tables: cos, sin (mel; its window is built next to the upload in fd_api_ext.cpp) and window [256], cos, sin (STOI)
+        std::vector<float> mel(2 * 1024), st(fds::TAB_FLOATS);
+        fdt::twiddles(1024, mel.data(), mel.data() + 1024);
+        CHECK(parents_twiddles(1024, mel.data(), mel.data() + 1024));
+        fds::tables(st.data());
+        for (int i = 0; i < fds::FRAME; ++i) CHECK(same_bits(st[i], (float)(0.5 - 0.5 * cos(2.0 * PI * (i + 1) / (fds::FRAME + 1)))));
+        CHECK(parents_twiddles(fds::NFFT, st.data() + fds::FRAME, st.data() + fds::FRAME + fds::NFFT));
     }
     // the other refusals
     d.n_res = 0; CHECK(refused(d, "n_res = 0"));
