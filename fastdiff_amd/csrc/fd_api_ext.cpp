@@ -15,8 +15,8 @@
 
 extern "C" {
 
-// The host path the waveform tools below share ("One host path under these tools"): check_counts, enter, reserve, upload_table,
-// upload_counts, and run (fd_host.h) ----------------------------------------------------------------------------------------------
+// The host path the waveform tools below share ("One host path under these tools"): check_counts, enter, upload_table,
+// upload_counts, and reserve and run (fd_host.h) ----------------------------------------------------------------------------------------------
 static_assert(sizeof(long long) == sizeof(int64_t), "the kernels read the callers' int64_t counts as long long");
 
 // the caller's counts [B] (null: every row whole) lie in [lo, hi]; checked before the call touches the device or the handle
@@ -34,30 +34,6 @@ static int enter(fd_handle h)
 {
     FD_HIP(h, hipSetDevice(h->device));
     return (h->pending.active && h->pending.lazy) ? FD_OK : fd_settle(h);
-}
-
-static bool capturing(hipStream_t stream)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return false;
-    (void)hipGetLastError();
-    return true;
-}
-
-// a tool's own scratch holds at least `need` bytes: grown at the first call that needs more (hipFree waits for the calls that still use
-// the old one), never inside a capture, whose graph would keep the old pointers
-static int reserve(fd_handle h, const char *who, Scratch &s, size_t need, hipStream_t stream)
-{
-    if (s.bytes >= need) return FD_OK;
-    if (capturing(stream))
-        FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes, which cannot happen inside a stream capture: call it once before", who, need);
-    if (s.p) FD_HIP(h, hipFree(s.p));
-    s = Scratch{};
-    void *p = nullptr;
-    FD_HIP(h, hipMalloc(&p, need));
-    s.p = static_cast<float *>(p);
-    s.bytes = need;
-    return FD_OK;
 }
 
 // a constant table -> device memory the handle owns until fd_destroy (a replaced table stays valid for launches still in flight); a

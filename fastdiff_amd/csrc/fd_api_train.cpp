@@ -18,23 +18,8 @@
     } while (0)
 
 // The backward passes add up partial sums, and the LVC operator's matrix-pipe kernels read the predicted kernels frame-major, through
-// scratch buffers kept on the handle (fd_context: lvc_scratch, kconv_scratch, cconv_scratch) and grown when a call needs more (hipFree
-// waits for the device, so work in flight on the old buffer is safe).  Calls on one handle share them: they must be ordered on one
-// stream, as torch.autograd orders a forward and its backward.
-static hipError_t grow(Scratch &s, size_t floats)
-{
-    const size_t bytes = sizeof(float) * floats;
-    if (s.bytes >= bytes) return hipSuccess;
-    if (s.p) {
-        const hipError_t e = hipFree(s.p);
-        if (e != hipSuccess) return e;
-    }
-    s = Scratch{};
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&s.p), bytes);
-    if (e == hipSuccess) s.bytes = bytes;
-    else s.p = nullptr;
-    return e;
-}
+// scratch buffers kept on the handle (fd_context: lvc_scratch, kconv_scratch, cconv_scratch, step_scratch), reserved by run_scratch
+// (fd_host.h) before the launch: grown when a call needs more, which is refused inside a stream capture.
 
 static bool slope_ok(float s) { return s > 0.0f && s <= 1.0f; }      // a leaky-relu slope: (0, 1], 1 = no activation
 
@@ -77,14 +62,11 @@ static int check_lvc_op(fd_handle h, int B, int Cin, int Cout, int ks, int T, in
     return FD_OK;
 }
 
-// The operator's frame-major copy of the predicted kernels (B*T*Cin*Cout*ks floats), for the shapes whose kernels read one; else null
-static hipError_t lvc_scratch(fd_handle h, int B, int Cin, int Cout, int ks, int T, int hop, float **out)
+// The operator's frame-major copy of the predicted kernels (B*T*Cin*Cout*ks floats), for the shapes whose kernels read one; else 0 floats
+// and a null pointer
+static size_t lvc_scratch_floats(int B, int Cin, int Cout, int ks, int T, int hop)
 {
-    *out = nullptr;
-    if (!fdk::lvc_op_needs_scratch(Cin, Cout, ks, hop)) return hipSuccess;
-    const hipError_t e = grow(h->lvc_scratch, (size_t)B * T * Cin * Cout * ks);
-    *out = h->lvc_scratch.p;
-    return e;
+    return fdk::lvc_op_needs_scratch(Cin, Cout, ks, hop) ? (size_t)B * T * Cin * Cout * ks : 0;
 }
 
 // a batch stride of the operator's kernel / dkernel: 0 or the tensor's own size, or, for the model's shape, anything beyond that
@@ -102,10 +84,9 @@ int fd_lvc_forward_strided(fd_handle h, const float *x, const float *kernel, int
     FD_TRY(check_lvc_op(h, B, Cin, Cout, ks, T, hop, "fd_lvc_forward"));
     if (!lvc_stride_ok(kernel_bstride, Cin, Cout, ks, T, hop))
         FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_lvc_forward: a batch-strided kernel (stride %lld) needs the model's shape (32 -> 64, k3, hop 8 / 64 / 256)", (long long)kernel_bstride);
-    return run(h, stream, "fd_lvc_forward", [&](const fdk::Launch &L) {
-        float *scratch;
-        const hipError_t e = lvc_scratch(h, B, Cin, Cout, ks, T, hop, &scratch);
-        return e != hipSuccess ? e : fdk::lvc_op_forward(L, x, kernel, bias, out, B, Cin, Cout, ks, T, hop, scratch, kernel_bstride);
+    const size_t floats = lvc_scratch_floats(B, Cin, Cout, ks, T, hop);
+    return run_scratch(h, stream, "fd_lvc_forward", h->lvc_scratch, floats, [&](const fdk::Launch &L, float *scratch) {
+        return fdk::lvc_op_forward(L, x, kernel, bias, out, B, Cin, Cout, ks, T, hop, floats ? scratch : nullptr, kernel_bstride);
     });
 }
 
@@ -124,11 +105,9 @@ int fd_lvc_backward_strided(fd_handle h, const float *x, const float *kernel, in
     for (int64_t st : {kernel_bstride, dkernel_bstride})
         if (!lvc_stride_ok(st, Cin, Cout, ks, T, hop))
             FD_FAIL(h, FD_ERR_UNSUPPORTED, "fd_lvc_backward: a batch-strided kernel / dkernel (stride %lld) needs the model's shape (32 -> 64, k3, hop 8 / 64 / 256)", (long long)st);
-    return run(h, stream, "fd_lvc_backward", [&](const fdk::Launch &L) {
-        float *scratch;
-        const hipError_t e = lvc_scratch(h, B, Cin, Cout, ks, T, hop, &scratch);
-        return e != hipSuccess ? e
-                               : fdk::lvc_op_backward(L, x, kernel, dout, dx, dkernel, dbias, B, Cin, Cout, ks, T, hop, scratch, kernel_bstride, dkernel_bstride);
+    const size_t floats = lvc_scratch_floats(B, Cin, Cout, ks, T, hop);
+    return run_scratch(h, stream, "fd_lvc_backward", h->lvc_scratch, floats, [&](const fdk::Launch &L, float *scratch) {
+        return fdk::lvc_op_backward(L, x, kernel, dout, dx, dkernel, dbias, B, Cin, Cout, ks, T, hop, floats ? scratch : nullptr, kernel_bstride, dkernel_bstride);
     });
 }
 
@@ -181,11 +160,8 @@ int fd_kconv_backward_act(fd_handle h, const float *x, const float *weight, cons
     if (post_slope != 1.0f && !y) FD_FAIL(h, FD_ERR_INVALID, "fd_kconv_backward: a fused activation needs the forward's output y");
     if (!slope_ok(in_slope)) FD_FAIL(h, FD_ERR_INVALID, "fd_kconv_backward: in_slope must lie in (0, 1], got %g", in_slope);
     if (in_slope != 1.0f && dx && !x) FD_FAIL(h, FD_ERR_INVALID, "fd_kconv_backward: in_slope needs x");
-    return run(h, stream, "fd_kconv_backward", [&](const fdk::Launch &L) {
-        const hipError_t e = grow(h->kconv_scratch, fdk::kconv_scratch_floats(B, M, T));
-        return e != hipSuccess ? e
-                               : fdk::kconv_backward(L, x, weight, dout, dx, dweight, dbias, B, M, T, h->kconv_scratch.p, false,
-                                                     post_slope != 1.0f ? y : nullptr, post_slope, in_slope);
+    return run_scratch(h, stream, "fd_kconv_backward", h->kconv_scratch, fdk::kconv_scratch_floats(B, M, T), [&](const fdk::Launch &L, float *scratch) {
+        return fdk::kconv_backward(L, x, weight, dout, dx, dweight, dbias, B, M, T, scratch, false, post_slope != 1.0f ? y : nullptr, post_slope, in_slope);
     });
 }
 
@@ -205,9 +181,8 @@ int fd_kconv_backward_w_multi(fd_handle h, int n, const float *const *x, const f
     FD_TRY(check_small(h, M, T, who));
     FD_TRY(check_act(h, M, T, post_slope, who));
     FD_TRY(check_lists(h, n, {x, dout}, who));
-    return run(h, stream, who, [&](const fdk::Launch &L) {
-        const hipError_t e = grow(h->kconv_scratch, fdk::kconv_w_multi_scratch_floats(n, B, M));
-        return e != hipSuccess ? e : fdk::kconv_backward_w_multi(L, n, x, dout, y, post_slope, B, M, T, dweight, dbias, h->kconv_scratch.p);
+    return run_scratch(h, stream, who, h->kconv_scratch, fdk::kconv_w_multi_scratch_floats(n, B, M), [&](const fdk::Launch &L, float *scratch) {
+        return fdk::kconv_backward_w_multi(L, n, x, dout, y, post_slope, B, M, T, dweight, dbias, scratch);
     });
 }
 
@@ -233,11 +208,8 @@ int fd_kconv_backward_x_multi(fd_handle h, int n, const float *const *x, const f
     if (!slope_ok(in_slope)) FD_FAIL(h, FD_ERR_INVALID, "%s: in_slope must lie in (0, 1], got %g", who, in_slope);
     if (in_slope != 1.0f) FD_TRY(check_lists(h, n, {x}, who));
     if (post_slope != 1.0f && !y) FD_FAIL(h, FD_ERR_INVALID, "%s: a fused activation needs the forward's outputs y", who);
-    return run(h, stream, who, [&](const fdk::Launch &L) {
-        const hipError_t e = grow(h->kconv_scratch, fdk::kconv_x_multi_scratch_floats(n, B, M, T));
-        return e != hipSuccess ? e
-                               : fdk::kconv_backward_x_multi(L, n, x, weight, post_slope != 1.0f ? y : nullptr, dout, dx, B, M, T, post_slope, in_slope,
-                                                             h->kconv_scratch.p);
+    return run_scratch(h, stream, who, h->kconv_scratch, fdk::kconv_x_multi_scratch_floats(n, B, M, T), [&](const fdk::Launch &L, float *scratch) {
+        return fdk::kconv_backward_x_multi(L, n, x, weight, post_slope != 1.0f ? y : nullptr, dout, dx, B, M, T, post_slope, in_slope, scratch);
     });
 }
 
@@ -262,9 +234,8 @@ static int input_conv_forward(fd_handle h, int n, const float *const *x, const f
 static int input_conv_backward(fd_handle h, int n, const float *const *x, const float *const *weight, const float *const *y, const float *const *dout,
                                int B, int T, float post_slope, float *const *dx, float *const *dweight, float *const *dbias, void *stream, const char *who)
 {
-    return run(h, stream, who, [&](const fdk::Launch &L) {
-        const hipError_t e = grow(h->kconv_scratch, fdk::input_conv_multi_scratch_floats(n, B));
-        return e != hipSuccess ? e : fdk::input_conv_backward_multi(L, n, x, weight, y, dout, dx, dweight, dbias, B, T, post_slope, h->kconv_scratch.p);
+    return run_scratch(h, stream, who, h->kconv_scratch, fdk::input_conv_multi_scratch_floats(n, B), [&](const fdk::Launch &L, float *scratch) {
+        return fdk::input_conv_backward_multi(L, n, x, weight, y, dout, dx, dweight, dbias, B, T, post_slope, scratch);
     });
 }
 
@@ -404,9 +375,8 @@ int fd_kconv_backward_frames(fd_handle h, const float *x, const float *weight, c
     if (!h) return FD_ERR_INVALID;
     if (!dframes || ((dweight || dbias) && !x) || (dx && !weight)) FD_FAIL(h, FD_ERR_INVALID, "fd_kconv_backward_frames: null pointer");
     FD_TRY(check_kconv_frames(h, B, M, T, "fd_kconv_backward_frames"));
-    return run(h, stream, "fd_kconv_backward_frames", [&](const fdk::Launch &L) {
-        const hipError_t e = grow(h->kconv_scratch, fdk::kconv_scratch_floats(B, M, T));
-        return e != hipSuccess ? e : fdk::kconv_backward(L, x, weight, dframes, dx, dweight, dbias, B, M, T, h->kconv_scratch.p, true);
+    return run_scratch(h, stream, "fd_kconv_backward_frames", h->kconv_scratch, fdk::kconv_scratch_floats(B, M, T), [&](const fdk::Launch &L, float *scratch) {
+        return fdk::kconv_backward(L, x, weight, dframes, dx, dweight, dbias, B, M, T, scratch, true);
     });
 }
 
@@ -445,12 +415,10 @@ int fd_lvc_backward_frames(fd_handle h, const float *x, const float *kernel_fram
     if (dx) FD_TRY(check_frames_stride(h, kernel_bstride, T, "fd_lvc_backward_frames"));
     if (dkernel_frames) FD_TRY(check_frames_stride(h, dkernel_bstride, T, "fd_lvc_backward_frames"));
     if (dbias && dbias_bstride != 0 && dbias_bstride < (int64_t)64 * T) FD_FAIL(h, FD_ERR_INVALID, "fd_lvc_backward_frames: dbias stride %lld < 64 * T", (long long)dbias_bstride);
-    return run(h, stream, "fd_lvc_backward_frames", [&](const fdk::Launch &L) {
-        float *scratch = nullptr;      // option lvc_dx = copy: the dx kernel's operand order
-        const hipError_t e = dx && !h->lvc_dx_gather ? lvc_scratch(h, B, 32, 64, 3, T, hop, &scratch) : hipSuccess;
-        return e != hipSuccess ? e
-                               : fdk::lvc_op_backward(L, x, kernel_frames, dout, dx, dkernel_frames, dbias, B, 32, 64, 3, T, hop, scratch, kernel_bstride,
-                                                      dkernel_bstride, true, dbias_bstride);
+    const size_t floats = dx && !h->lvc_dx_gather ? lvc_scratch_floats(B, 32, 64, 3, T, hop) : 0;      // option lvc_dx = copy: the dx kernel's operand order
+    return run_scratch(h, stream, "fd_lvc_backward_frames", h->lvc_scratch, floats, [&](const fdk::Launch &L, float *scratch) {
+        return fdk::lvc_op_backward(L, x, kernel_frames, dout, dx, dkernel_frames, dbias, B, 32, 64, 3, T, hop, floats ? scratch : nullptr,
+                                    kernel_bstride, dkernel_bstride, true, dbias_bstride);
     });
 }
 
@@ -484,10 +452,8 @@ int fd_conv32_backward(fd_handle h, const float *xs, const float *y, const float
     if (!h) return FD_ERR_INVALID;
     if (!xs || !y || !weight || !dy) FD_FAIL(h, FD_ERR_INVALID, "fd_conv32_backward: null pointer");
     FD_TRY(check_conv32(h, B, L, dilation, pre_slope, post_slope, "fd_conv32_backward"));
-    return run(h, stream, "fd_conv32_backward", [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->cconv_scratch, fdk::cconv_scratch_floats(La, dilation, B, L));
-        return e != hipSuccess ? e
-                               : fdk::cconv_backward(La, xs, y, weight, dy, gxs, dxs, dweight, dbias, B, L, dilation, pre_slope, post_slope, h->cconv_scratch.p);
+    return run_scratch(h, stream, "fd_conv32_backward", h->cconv_scratch, fdk::cconv_scratch_floats({h, nullptr, false}, dilation, B, L), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::cconv_backward(La, xs, y, weight, dy, gxs, dxs, dweight, dbias, B, L, dilation, pre_slope, post_slope, scratch);
     });
 }
 
@@ -512,9 +478,8 @@ int fd_conv7_backward(fd_handle h, int which, const float *x, const float *weigh
     if (!h) return FD_ERR_INVALID;
     if (!x || !weight || !dy) FD_FAIL(h, FD_ERR_INVALID, "fd_conv7_backward: null pointer");
     FD_TRY(check_conv7(h, which, B, L, "fd_conv7_backward"));
-    return run(h, stream, "fd_conv7_backward", [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->cconv_scratch, fdk::conv7_scratch_floats(La, B, L));
-        return e != hipSuccess ? e : fdk::conv7_backward(La, which, x, weight, dy, dx, dweight, dbias, B, L, h->cconv_scratch.p);
+    return run_scratch(h, stream, "fd_conv7_backward", h->cconv_scratch, fdk::conv7_scratch_floats({h, nullptr, false}, B, L), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::conv7_backward(La, which, x, weight, dy, dx, dweight, dbias, B, L, scratch);
     });
 }
 
@@ -539,9 +504,8 @@ int fd_upsample_backward(fd_handle h, const float *x, const float *weight, const
     if (!h) return FD_ERR_INVALID;
     if (!x || !weight || !dy) FD_FAIL(h, FD_ERR_INVALID, "fd_upsample_backward: null pointer");
     FD_TRY(check_upsample(h, B, Lin, ratio, "fd_upsample_backward"));
-    return run(h, stream, "fd_upsample_backward", [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->cconv_scratch, fdk::convt_scratch_floats(La, ratio, B, Lin));
-        return e != hipSuccess ? e : fdk::convt_backward(La, x, weight, dy, dx, dweight, dbias, B, Lin, ratio, h->cconv_scratch.p);
+    return run_scratch(h, stream, "fd_upsample_backward", h->cconv_scratch, fdk::convt_scratch_floats({h, nullptr, false}, ratio, B, Lin), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::convt_backward(La, x, weight, dy, dx, dweight, dbias, B, Lin, ratio, scratch);
     });
 }
 
@@ -571,37 +535,52 @@ int fd_gate_backward(fd_handle h, const float *y, const float *dout, int B, int 
 // per-step scalars live in the step scratch buffer.
 static bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// B rows of L floats that the kernels read 16 bytes per lane
+static int check_len4(fd_handle h, int B, int64_t L, const char *who)
+{
+    FD_TRY(check_batch(h, B, who));
+    if (L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 4)", who, (long long)L);
+    return FD_OK;
+}
+
 int fd_train_draw(fd_handle h, const float *x0, const float *alpha, int T_train, int B, int64_t L, uint64_t seed, const fd_train_state *state,
                   uint64_t iter_host, float *x_t, float *z, float *steps, void *stream)
 {
     const char *who = "fd_train_draw";
     if (!h) return FD_ERR_INVALID;
     if (!x0 || !alpha || !x_t || !z || !steps) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
-    FD_TRY(check_batch(h, B, who));
-    if (T_train < 1 || L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36))
-        FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d, L=%lld (a multiple of 4)", who, T_train, (long long)L);
+    if (T_train < 1) FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d", who, T_train);
+    FD_TRY(check_len4(h, B, L, who));
     if (!aligned(x0, 16) || !aligned(x_t, 16) || !aligned(z, 16) || !aligned(state, 8))
         FD_FAIL(h, FD_ERR_INVALID, "%s: x0, x_t and z must be 16-byte aligned, state 8-byte aligned", who);
     return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::train_draw(La, x0, alpha, T_train, B, L, seed, state, iter_host, x_t, z, steps); });
 }
 
-int fd_train_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
-                     uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs, float *mels,
-                     int64_t *picked, void *stream)
+// fd_train_collate, and fd_eval_collate (eval: the batch in item order; rank / world neither checked nor read)
+static int collate(fd_handle h, const char *who, bool eval, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
+                   int hop, int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs, float *mels,
+                   int64_t *picked, void *stream)
 {
-    const char *who = "fd_train_collate";
     if (!h) return FD_ERR_INVALID;
     if (!wav_arena || !mel_arena || !frame_off || !wavs || !mels || !picked) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
     FD_TRY(check_batch(h, B, who));
     if (n_items < 1 || n_items > ((int64_t)1 << 28)) FD_FAIL(h, FD_ERR_INVALID, "%s: n_items=%lld (1..2^28)", who, (long long)n_items);
     if (hop < 4 || hop % 4 != 0 || F < 1 || (int64_t)F * hop >= ((int64_t)1 << 31))
         FD_FAIL(h, FD_ERR_INVALID, "%s: hop=%d (a multiple of 4), F=%d", who, hop, F);
-    if (world < 1 || rank < 0 || rank >= world) FD_FAIL(h, FD_ERR_INVALID, "%s: rank=%d of world=%d", who, rank, world);
+    if (!eval && (world < 1 || rank < 0 || rank >= world)) FD_FAIL(h, FD_ERR_INVALID, "%s: rank=%d of world=%d", who, rank, world);
     if (!aligned(wav_arena, 16) || !aligned(wavs, 16) || !aligned(frame_off, 8) || !aligned(picked, 8) || !aligned(state, 8))
         FD_FAIL(h, FD_ERR_INVALID, "%s: wav_arena and wavs must be 16-byte aligned, frame_off, picked and state 8-byte aligned", who);
     return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::train_collate(La, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, rank, world, wavs, mels, picked);
+        return fdk::collate(La, eval, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, rank, world, wavs, mels, picked);
     });
+}
+
+int fd_train_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
+                     uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs, float *mels,
+                     int64_t *picked, void *stream)
+{
+    return collate(h, "fd_train_collate", false, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, rank, world, wavs, mels,
+                   picked, stream);
 }
 
 static int check_mse(fd_handle h, int64_t n, const char *who)
@@ -616,9 +595,8 @@ int fd_mse_forward(fd_handle h, const float *eps, const float *z, int64_t n, flo
     if (!h) return FD_ERR_INVALID;
     if (!eps || !z || !loss || !aligned(state, 8)) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer (or a state that is not 8-byte aligned)", who);
     FD_TRY(check_mse(h, n, who));
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats(fdk::mse_blocks(n)));
-        return e != hipSuccess ? e : fdk::mse_forward(La, eps, z, n, loss, state, h->step_scratch.p);
+    return run_scratch(h, stream, who, h->step_scratch, fdk::step_scratch_floats(fdk::mse_blocks(n)), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::mse_forward(La, eps, z, n, loss, state, scratch);
     });
 }
 
@@ -645,9 +623,8 @@ int fd_adamw_multi(fd_handle h, const fd_adamw_item *items, int n, const fd_adam
     }
     if (fdk::adamw_blocks(items, n) > ((int64_t)1 << 24))      // (workgroup indices are int; 2^36 elements is far beyond any model here)
         FD_FAIL(h, FD_ERR_UNSUPPORTED, "%s: more than 2^24 workgroups of %d elements in one call", who, FD_STEP_RUN * 256);
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats(fdk::adamw_blocks(items, n)));
-        return e != hipSuccess ? e : fdk::adamw_multi(La, items, n, hyper, state, h->step_scratch.p);
+    return run_scratch(h, stream, who, h->step_scratch, fdk::step_scratch_floats(fdk::adamw_blocks(items, n)), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::adamw_multi(La, items, n, hyper, state, scratch);
     });
 }
 
@@ -671,18 +648,7 @@ int fd_ema_multi(fd_handle h, const fd_ema_item *items, int n, const fd_ema_hype
 int fd_eval_collate(fd_handle h, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop, int F, int B,
                     uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked, void *stream)
 {
-    const char *who = "fd_eval_collate";
-    if (!h) return FD_ERR_INVALID;
-    if (!wav_arena || !mel_arena || !frame_off || !wavs || !mels || !picked) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
-    FD_TRY(check_batch(h, B, who));
-    if (n_items < 1 || n_items > ((int64_t)1 << 28)) FD_FAIL(h, FD_ERR_INVALID, "%s: n_items=%lld (1..2^28)", who, (long long)n_items);
-    if (hop < 4 || hop % 4 != 0 || F < 1 || (int64_t)F * hop >= ((int64_t)1 << 31))
-        FD_FAIL(h, FD_ERR_INVALID, "%s: hop=%d (a multiple of 4), F=%d", who, hop, F);
-    if (!aligned(wav_arena, 16) || !aligned(wavs, 16) || !aligned(frame_off, 8) || !aligned(picked, 8) || !aligned(state, 8))
-        FD_FAIL(h, FD_ERR_INVALID, "%s: wav_arena and wavs must be 16-byte aligned, frame_off, picked and state 8-byte aligned", who);
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::eval_collate(La, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, wavs, mels, picked);
-    });
+    return collate(h, "fd_eval_collate", true, wav_arena, mel_arena, frame_off, n_items, hop, F, B, seed, state, iter_host, 0, 1, wavs, mels, picked, stream);
 }
 
 int fd_item_distance(fd_handle h, const float *a, const float *b, int B, int64_t n, int kind, float *out, void *stream)
@@ -694,9 +660,9 @@ int fd_item_distance(fd_handle h, const float *a, const float *b, int B, int64_t
     if (n < 1 || (int64_t)B * n >= ((int64_t)1 << 36) || (kind != 0 && kind != 1))
         FD_FAIL(h, FD_ERR_INVALID, "%s: n=%lld, kind=%d (0 squared, 1 absolute)", who, (long long)n, kind);
     if (!aligned(a, 16) || !aligned(b, 16)) FD_FAIL(h, FD_ERR_INVALID, "%s: a and b must be 16-byte aligned", who);
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, fdk::step_scratch_floats((int64_t)B * fdk::item_distance_blocks(n)));
-        return e != hipSuccess ? e : fdk::item_distance(La, a, b, B, n, kind, out, h->step_scratch.p);
+    const size_t floats = fdk::step_scratch_floats((int64_t)B * fdk::item_distance_blocks(n));
+    return run_scratch(h, stream, who, h->step_scratch, floats, [&](const fdk::Launch &La, float *scratch) {
+        return fdk::item_distance(La, a, b, B, n, kind, out, scratch);
     });
 }
 
@@ -738,9 +704,8 @@ int fd_bandpool_forward(fd_handle h, const float *x, const float *W, const float
     if (!h) return FD_ERR_INVALID;
     if (!x || !W || !b || !feat) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
     FD_TRY(check_bandpool(h, x, B, L, who));
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, fdk::bandpool_scratch_floats(B, L, false));
-        return e != hipSuccess ? e : fdk::bandpool_forward(La, x, W, b, B, L, feat, h->step_scratch.p);
+    return run_scratch(h, stream, who, h->step_scratch, fdk::bandpool_scratch_floats(B, L, false), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::bandpool_forward(La, x, W, b, B, L, feat, scratch);
     });
 }
 
@@ -751,9 +716,8 @@ int fd_bandpool_backward(fd_handle h, const float *x, const float *W, const floa
     if (!h) return FD_ERR_INVALID;
     if (!x || !W || !b || !dfeat || !dW || !db) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
     FD_TRY(check_bandpool(h, x, B, L, who));
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, fdk::bandpool_scratch_floats(B, L, true));
-        return e != hipSuccess ? e : fdk::bandpool_backward(La, x, W, b, dfeat, B, L, dW, db, h->step_scratch.p);
+    return run_scratch(h, stream, who, h->step_scratch, fdk::bandpool_scratch_floats(B, L, true), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::bandpool_backward(La, x, W, b, dfeat, B, L, dW, db, scratch);
     });
 }
 
@@ -787,9 +751,8 @@ int fd_phi_draw(fd_handle h, const float *x0, const float *alpha, int T_train, i
     const char *who = "fd_phi_draw";
     if (!h) return FD_ERR_INVALID;
     if (!x0 || !alpha || !x_t || !z || !steps || !beta_nxt || !delta || !delta2) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
-    FD_TRY(check_batch(h, B, who));
     if (tau < 0 || T_train < 1 || (int64_t)T_train <= 2 * (int64_t)tau) FD_FAIL(h, FD_ERR_INVALID, "%s: T_train=%d must exceed 2 tau=%d", who, T_train, 2 * tau);
-    if (L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 4)", who, (long long)L);
+    FD_TRY(check_len4(h, B, L, who));
     if (!aligned(x0, 16) || !aligned(x_t, 16) || !aligned(z, 16) || !aligned(state, 8))
         FD_FAIL(h, FD_ERR_INVALID, "%s: x0, x_t and z must be 16-byte aligned, state 8-byte aligned", who);
     return run(h, stream, who, [&](const fdk::Launch &La) {
@@ -803,12 +766,10 @@ int fd_phi_residual_forward(fd_handle h, const float *eps, const float *z, const
     const char *who = "fd_phi_residual_forward";
     if (!h) return FD_ERR_INVALID;
     if (!eps || !z || !delta || !beta_hat || !m || !s) FD_FAIL(h, FD_ERR_INVALID, "%s: null pointer", who);
-    FD_TRY(check_batch(h, B, who));
-    if (L < 4 || L % 4 != 0 || (int64_t)B * L >= ((int64_t)1 << 36)) FD_FAIL(h, FD_ERR_INVALID, "%s: L=%lld (a multiple of 4)", who, (long long)L);
+    FD_TRY(check_len4(h, B, L, who));
     if (!aligned(eps, 16) || !aligned(z, 16)) FD_FAIL(h, FD_ERR_INVALID, "%s: eps and z must be 16-byte aligned", who);
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        const hipError_t e = grow(h->step_scratch, 2 * (size_t)B * (size_t)fdk::phi_residual_blocks(L));
-        return e != hipSuccess ? e : fdk::phi_residual_forward(La, eps, z, delta, beta_hat, B, L, m, s, h->step_scratch.p);
+    return run_scratch(h, stream, who, h->step_scratch, 2 * (size_t)B * (size_t)fdk::phi_residual_blocks(L), [&](const fdk::Launch &La, float *scratch) {
+        return fdk::phi_residual_forward(La, eps, z, delta, beta_hat, B, L, m, s, scratch);
     });
 }
 

@@ -43,8 +43,34 @@ int fd_mark_tail(fd_handle h, hipStream_t s);
 }
 void fd_prof_drain(fd_context *c);
 
+static bool capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return false;
+    (void)hipGetLastError();
+    return true;
+}
+
+// A scratch buffer of the handle holds at least `need` bytes: grown at the first call that needs more (hipFree waits for the calls that
+// still use the old one), never inside a capture, whose graph would keep the old pointers.  Calls on one handle share these buffers:
+// they must be ordered on one stream, as torch.autograd orders a forward and its backward.
+static int reserve(fd_handle h, const char *who, Scratch &s, size_t need, hipStream_t stream)
+{
+    if (s.bytes >= need) return FD_OK;
+    if (capturing(stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: the scratch buffer has to grow to %zu bytes, which cannot happen inside a stream capture: call it once before", who, need);
+    FD_HIP(h, hipSetDevice(h->device));
+    if (s.p) FD_HIP(h, hipFree(s.p));
+    s = Scratch{};
+    void *p = nullptr;
+    FD_HIP(h, hipMalloc(&p, need));
+    s.p = static_cast<float *>(p);
+    s.bytes = need;
+    return FD_OK;
+}
+
 // What an entry point ends with once its arguments are checked: the handle's device, one Launch on `stream`, and a failure of
-// `launch` (a scratch allocation inside it included) reported as "<who>: <HIP error>".
+// `launch` reported as "<who>: <HIP error>".
 template <class F>
 static int run(fd_handle h, void *stream, const char *who, F &&launch)
 {
@@ -52,4 +78,12 @@ static int run(fd_handle h, void *stream, const char *who, F &&launch)
     const hipError_t e = launch(fdk::Launch{h, (hipStream_t)stream, false});
     if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return FD_OK;
+}
+
+// ... with `floats` floats of scratch `s` reserved first: launch(L, s.p)
+template <class F>
+static int run_scratch(fd_handle h, void *stream, const char *who, Scratch &s, size_t floats, F &&launch)
+{
+    const int rc = reserve(h, who, s, sizeof(float) * floats, (hipStream_t)stream);
+    return rc != FD_OK ? rc : run(h, stream, who, [&](const fdk::Launch &L) { return launch(L, s.p); });
 }

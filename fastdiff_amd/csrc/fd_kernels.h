@@ -142,14 +142,13 @@ int64_t mse_blocks(int64_t n);
 int64_t adamw_blocks(const fd_adamw_item *items, int n);
 hipError_t train_draw(const Launch &L, const float *x0, const float *alpha, int T_train, int B, int64_t len, uint64_t seed,
                       const fd_train_state *state, uint64_t iter_host, float *x_t, float *z, float *steps);
-// one launch, no scratch: slot b's utterance and window chosen on the device, waveform copied, mel block transposed to [80, F]
-hipError_t train_collate(const Launch &L, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
-                         int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
-                         float *mels, int64_t *picked);
-// an evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate, fd_item_distance, fd_eval_accumulate).  item_distance's scratch:
+// one launch, no scratch: slot b's utterance and window chosen on the device, waveform copied, mel block transposed to [80, F].  eval:
+// the batch of an evaluation pass (fd_eval_collate: items in order, rank / world not read), else a training batch (fd_train_collate)
+hipError_t collate(const Launch &L, bool eval, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
+                   int hop, int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
+                   float *mels, int64_t *picked);
+// the rest of an evaluation pass (include/fastdiff_hip_train.h: fd_item_distance, fd_eval_accumulate).  item_distance's scratch:
 // step_scratch_floats(B * item_distance_blocks(n)) floats of the handle's step scratch
-hipError_t eval_collate(const Launch &L, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
-                        int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked);
 int64_t item_distance_blocks(int64_t n);
 hipError_t item_distance(const Launch &L, const float *a, const float *b, int B, int64_t n, int kind, float *out, float *scratch);
 hipError_t eval_accumulate(const Launch &L, const float *values, const float *steps, const int64_t *picked, int B, int T_train, int bins,

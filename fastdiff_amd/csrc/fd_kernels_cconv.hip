@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "fd_kernels.h"
+#include "fd_kernels_sums.h"
 
 namespace fdk_cconv {
 
@@ -429,15 +430,8 @@ __global__ void __launch_bounds__(256) k_c7_final_fwd(const float *__restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // weight-norm (FastDiff_model.py:115-122: torch.nn.utils.weight_norm on every Conv1d = torch._weight_norm(v, g, 0)):
 //   w[r, :] = v[r, :] * g[r] / ||v[r, :]||,   and from dw:   dg[r] = <dw[r], v[r]> / ||v[r]||,   dv[r] = (g / ||v||) (dw[r] - v[r] <dw[r], v[r]> / ||v||^2)
-// one wave per row (row = output channel, cols = in * k: 7 .. 400), sums by a butterfly: the same order every run
+// one wave per row (row = output channel, cols = in * k: 7 .. 400), sums by a butterfly (fd_kernels_sums.h: wave_sum): the same order every run
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The block's up-sampler on the training path: `self.upsample(F.leaky_relu(x, 0.2))` with upsample = ConvTranspose1d(32, 32, 2r, stride r,
 // padding r / 2) (modules.py:163-166,205-206), r = 8, 8, 4:
@@ -603,7 +597,7 @@ using namespace fdk_cconv;
 //      few microseconds each per training step otherwise; a single tensor is one item).  The records travel as KERNEL ARGUMENTS (<= WN_CHUNK per launch: 2.1 KB of the
 //      4 KB a launch may carry), not through a table in device memory: nothing to upload, nothing whose lifetime a captured graph
 //      would depend on.  first_block: the first workgroup of each tensor (4 rows per workgroup); a workgroup finds its tensor by
-//      bisection.
+//      bisection (fd_kernels_sums.h: find_item).
 constexpr int WN_CHUNK = 28;
 struct WnChunk {
     fd_wn_item it[WN_CHUNK];
@@ -611,19 +605,9 @@ struct WnChunk {
     int n;
 };
 
-__device__ __forceinline__ int wn_find_item(const WnChunk &c, int blk)
-{
-    int lo = 0, hi = c.n;      // first_block[lo] <= blk < first_block[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c.first_block[mid] <= blk) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) k_wn_multi_fwd(const WnChunk c)
 {
-    const int it = wn_find_item(c, blockIdx.x);
+    const int it = find_item(c, blockIdx.x);
     const fd_wn_item &I = c.it[it];
     const int64_t r = (int64_t)(blockIdx.x - c.first_block[it]) * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, cols = I.cols;
@@ -638,7 +622,7 @@ __global__ void __launch_bounds__(256) k_wn_multi_fwd(const WnChunk c)
 
 __global__ void __launch_bounds__(256) k_wn_multi_bwd(const WnChunk c)
 {
-    const int it = wn_find_item(c, blockIdx.x);
+    const int it = find_item(c, blockIdx.x);
     const fd_wn_item &I = c.it[it];
     const int64_t r = (int64_t)(blockIdx.x - c.first_block[it]) * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, cols = I.cols;

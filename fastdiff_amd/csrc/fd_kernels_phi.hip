@@ -2,52 +2,17 @@
 // a `noise_pred` it never defines), the pieces of one training step of it around the frozen denoiser (phi_loss, util.py:328-362) and the
 // greedy schedule search (noise_scheduling, util.py:254-288) with its state in device memory.  include/fastdiff_hip_train.h, last section.
 //
-// Sums follow fd_kernels_step.hip: a thread adds a run of FD_STEP_RUN terms serially, a fixed tree joins the threads, per-workgroup
-// results go to the handle's step scratch, one final workgroup adds those in a fixed order.  No workgroup touches two items, no
-// floating-point atomics: two runs agree bit for bit.
+// Sums run in the fixed order of fd_kernels_sums.h; partial sums live in the handle's step scratch.
 #include <algorithm>
 
-#include "fd_kernels.h"
-#include "fd_device.h"
+#include "fd_kernels_sums.h"
 
-// x_t, the residual, the search's update and its scalars are defined operation by operation (torch evaluates them as separate passes):
-// no multiply-add contraction in this file.  (fmaf() calls stay what they say.)
+// The scalars of the draws, the residual, the search's update and its scalars are defined operation by operation (torch evaluates them as
+// separate passes): no multiply-add contraction in this file.  (fmaf() calls stay what they say.)
 #pragma clang fp contract(off)
 
 namespace fdk {
 namespace {
-
-constexpr int RUN = FD_STEP_RUN;
-constexpr int WG = 256;
-
-// the sum of v over the workgroup's 256 threads, in every thread: butterfly inside a wave, then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ float block_sum(float v)
-{
-    __shared__ float ws[WG / 64];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-    __syncthreads();
-    return r;
-}
-
-// the final workgroup's sum of P per-workgroup results: groups of 256 through block_sum, then those (P <= 65536)
-__device__ __forceinline__ float final_sum(const float *partial, int64_t P)
-{
-    __shared__ float level[WG];
-    constexpr int64_t SPAN = (int64_t)WG * WG;
-    if (P <= WG) return block_sum(threadIdx.x < P ? partial[threadIdx.x] : 0.0f);
-    for (int c = 0; c < WG; ++c) {
-        float acc = 0.0f;
-        for (int64_t i = (int64_t)c * WG + threadIdx.x; i < P; i += SPAN) acc += partial[i];
-        acc = (int64_t)c * WG < P ? block_sum(acc) : 0.0f;
-        if (threadIdx.x == 0) level[c] = acc;
-    }
-    __syncthreads();
-    return block_sum(level[threadIdx.x]);
-}
 
 // ---- band energies -------------------------------------------------------------------------------------------------------------------
 // y[b,c,f] = bias[c] + sum_k W[c,k] x[b, 32 f + k] over F = L / 32 - 1 frames of 64 samples at stride 32; feat[b,c] = log(1e-6 + mean_f y^2).
@@ -224,13 +189,6 @@ __global__ void __launch_bounds__(WG) k_bandpool_backward_final(const float *par
 // order; the sum over the hidden units is the wave's butterfly.
 constexpr int HD_IN = 34, HD_H = 64, HD_F = 32;
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 struct HeadItem {
@@ -323,14 +281,9 @@ __global__ void __launch_bounds__(WG) k_phi_draw(const float4 *x0, const float *
 {
     const int64_t i4 = (int64_t)blockIdx.x * WG + threadIdx.x;
     if (i4 >= n4) return;
-    const unsigned long long it = state ? state->iter : iter_host;
+    const unsigned long long it = step_iter(state, iter_host);
     const int64_t b = i4 / l4;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)(b >> 2), (uint32_t)((uint64_t)(b >> 2) >> 32) ^ (uint32_t)it, 0xFFFFFFFAu, 0x5EEDu ^ (uint32_t)(it >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    const int c = (int)(b & 3);
-    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
-    const uint32_t ts = tau + (uint32_t)(((uint64_t)w * (uint64_t)(T_train - 2u * tau)) >> 32);      // in [tau, T_train - tau)
+    const uint32_t ts = tau + (uint32_t)(((uint64_t)item_word(seed, 0xFFFFFFFAu, b, it) * (uint64_t)(T_train - 2u * tau)) >> 32);      // in [tau, T_train - tau)
     const float a = alpha[ts], an = alpha[ts + tau];
     const float q = an / a;
     const float d = sqrtf(1.0f - a * a);
@@ -343,7 +296,7 @@ __global__ void __launch_bounds__(WG) k_phi_draw(const float4 *x0, const float *
     const float4 n = philox_normal4(seed, 0xFFFFFFF9u, (uint64_t)i4, it);
     const float4 x = x0[i4];
     z[i4] = n;
-    x_t[i4] = make_float4(a * x.x + d * n.x, a * x.y + d * n.y, a * x.z + d * n.z, a * x.w + d * n.w);
+    x_t[i4] = noised4(a, d, x, n);
 }
 
 // ---- the residual of phi_loss ------------------------------------------------------------------------------------------------------------

@@ -3,52 +3,21 @@
 // clip_grad_norm_ + non-finite guard + AdamW over all parameter tensors, and an optional moving average of them behind it.  Everything a step decides -- the step index of the draws, the clip coefficient, the bias corrections, whether the
 // update is skipped -- is read from and written to device memory, so a captured step replays with fresh draws and no host round trip.
 //
-// Sums (loss, squared gradient norm): a thread adds RUN = FD_STEP_RUN elements serially, the 256 threads of a workgroup are added by a
-// butterfly inside each wave and a fixed tree over the four waves, the per-workgroup results go to the handle's step scratch, and one
-// final workgroup adds those by the same tree, 256 at a time and then the up to 256 results of that (65536 partial sums, 2^28
-// elements).  An element therefore passes through RUN + ceil(log2(n / RUN)) additions at most up to that size: the bound of
-// tests/test_train_step.py.  No atomics: the order, and with it the result, is the same every run.
+// Sums (loss, squared gradient norm, distances) run in the fixed order of fd_kernels_sums.h; partial sums live in the handle's step scratch.
 //
 // All memory-bound and small next to the step (15.3 M parameters: 7 streams of 61 MB; the loss: 3 of 2 MB).  Tensors of the optimizer
 // are addressed element-wise, 256 consecutive floats per wave-group instruction: parameter and gradient tensors are views of arbitrary
 // offset and length (a weight-norm g of 1 element next to a 24576 x 64 x 3 weight), so no 16-byte alignment can be assumed there.
 #include <algorithm>
 
-#include "fd_kernels.h"
-#include "fd_device.h"
+#include "fd_kernels_sums.h"
 
-// x_t and the optimizer's update are defined operation by operation (torch evaluates them as separate element-wise passes): no
-// multiply-add contraction in this file.  (fmaf() calls stay what they say.)
+// sqrt(1 - a a) of the draws and the optimizer's update are defined operation by operation (torch evaluates them as separate
+// element-wise passes): no multiply-add contraction in this file.  (fmaf() calls stay what they say.)
 #pragma clang fp contract(off)
 
 namespace fdk {
 namespace {
-
-constexpr int RUN = FD_STEP_RUN;
-constexpr int WG = 256;
-constexpr int TILE = RUN * WG;             // elements per workgroup
-
-// inf or NaN, on the bits.  The build (-fno-honor-nans) lets the compiler assume that no float it computes with is a NaN -- it turns a
-// plain exponent test on a value that also feeds an fma into "is infinite" -- so the bits pass through an empty asm first.
-__device__ __forceinline__ bool not_finite(float v)
-{
-    unsigned u = __float_as_uint(v);
-    asm volatile("" : "+v"(u));
-    return (u & 0x7F800000u) == 0x7F800000u;
-}
-
-// the sum of v over the workgroup's 256 threads, in every thread: butterfly inside a wave, then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ float block_sum(float v)
-{
-    __shared__ float ws[WG / 64];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-    __syncthreads();      // (ws is free again: the final workgroup calls this in a loop)
-    return r;
-}
 
 // ---- the draws ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(WG) k_train_draw(const float4 *x0, const float *alpha, uint32_t T_train, int64_t l4, int64_t n4,
@@ -57,32 +26,22 @@ __global__ void __launch_bounds__(WG) k_train_draw(const float4 *x0, const float
 {
     const int64_t i4 = (int64_t)blockIdx.x * WG + threadIdx.x;
     if (i4 >= n4) return;
-    const unsigned long long it = state ? state->iter : iter_host;
+    const unsigned long long it = step_iter(state, iter_host);
     const int64_t b = i4 / l4;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)(b >> 2), (uint32_t)((uint64_t)(b >> 2) >> 32) ^ (uint32_t)it, 0xFFFFFFFDu, 0x5EEDu ^ (uint32_t)(it >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    const int c = (int)(b & 3);
-    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
-    const uint32_t ts = (uint32_t)(((uint64_t)w * (uint64_t)T_train) >> 32);      // < T_train
+    const uint32_t ts = (uint32_t)(((uint64_t)item_word(seed, 0xFFFFFFFDu, b, it) * (uint64_t)T_train) >> 32);      // < T_train
     if (i4 == b * l4) steps[b] = (float)ts;
     const float a = alpha[ts];
     const float d = sqrtf(1.0f - a * a);
     const float4 q = philox_normal4(seed, 0xFFFFFFFEu, (uint64_t)i4, it);
     const float4 x = x0[i4];
     z[i4] = q;
-    x_t[i4] = make_float4(a * x.x + d * q.x, a * x.y + d * q.y, a * x.z + d * q.z, a * x.w + d * q.w);
+    x_t[i4] = noised4(a, d, x, q);
 }
 
 // ---- the batch ---------------------------------------------------------------------------------------------------------------------
 // A training batch cut from a device-resident corpus (include/fastdiff_hip_train.h: fd_train_collate; fastdiff_amd/corpus.py holds the
 // arenas and the host twin of the choice).  Which utterance and which window slot b of step `it` takes is a pure function of
 // (seed, it, b, rank, world, n, T_item - F), recomputed by every thread (a few dozen Philox calls, uniform over the workgroup).
-__device__ __forceinline__ void philox_keyed(unsigned long long seed, uint32_t stream, uint64_t pos, unsigned long long uid, uint32_t r[4])
-{
-    philox4x32_10((uint32_t)pos, (uint32_t)(pos >> 32) ^ (uint32_t)uid, stream, 0x5EEDu ^ (uint32_t)(uid >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-}
 
 // pi_e(j): a 4-round balanced Feistel network on 2k bits (4^k >= n > 4^(k-1)), walked along its cycle until it lands below n -- a
 // bijection of [0, n) for every epoch e, evaluated per element.  Round function: word 0 of the generator keyed (seed, stream
@@ -144,63 +103,60 @@ __device__ __forceinline__ void collate_copy(float *tile, const float *wav_arena
     }
 }
 
-// grid (mel tiles + waveform chunks, B).  Source of the mel: the contiguous [F, 80] block of the arena, read element-wise in order
-// (coalesced), written into LDS row by row; destination [80, F]: a wave reads one column of the tile and writes 64 consecutive floats.
-__global__ void __launch_bounds__(WG) k_train_collate(const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
-                                                      int hop, int F, int B, unsigned long long seed, const fd_train_state *state,
-                                                      unsigned long long iter_host, int rank, int world, int mel_tiles, float *wavs,
-                                                      float *mels, int64_t *picked)
+// what the two collaters receive alike
+struct CollateArgs {
+    const float *wav_arena, *mel_arena;
+    const int64_t *frame_off;
+    int64_t n_items;
+    int hop, F, B;
+    unsigned long long seed;
+    const fd_train_state *state;
+    unsigned long long iter_host;
+    int mel_tiles;
+    float *wavs, *mels;
+    int64_t *picked;
+};
+
+// Slot b = blockIdx.y of step `it` once its item is known: the window start (stream 0xFFFFFFFC, id = it), the record in `picked`
+// ((-1, -1) for a slot that is not active), the copy.  grid (mel tiles + waveform chunks, B).  Source of the mel: the contiguous [F, 80]
+// block of the arena, read element-wise in order (coalesced), written into LDS row by row; destination [80, F]: a wave reads one
+// column of the tile and writes 64 consecutive floats.
+__device__ __forceinline__ void collate_slot(const CollateArgs &a, unsigned long long it, int64_t item, bool active)
 {
     __shared__ float tile[CL_TF * CL_LD];
     const int b = blockIdx.y;
-    const unsigned long long it = state ? state->iter : iter_host;
-    const uint64_t g = (it * (uint64_t)B + (uint64_t)b) * (uint64_t)world + (uint64_t)rank;
-    const uint64_t epoch = g / (uint64_t)n_items;
-    const int64_t item = (int64_t)collate_perm(g % (uint64_t)n_items, (uint64_t)n_items, seed, epoch);
-    const int64_t first = frame_off[item];
-    const int64_t range = frame_off[item + 1] - first - F;      // the window starts in [0, range)
-    uint32_t r[4];
-    philox_keyed(seed, 0xFFFFFFFCu, (uint64_t)(b >> 2), it, r);
-    const int c = b & 3;
-    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
-    const bool ok = range >= 1 && range < ((int64_t)1 << 32);   // (a table that breaks the corpus' filter: nothing is read)
+    const int64_t first = a.frame_off[item];
+    const int64_t range = a.frame_off[item + 1] - first - a.F;      // the window starts in [0, range)
+    const uint32_t w = item_word(a.seed, 0xFFFFFFFCu, b, it);
+    const bool ok = range >= 1 && range < ((int64_t)1 << 32);       // (a table that breaks the corpus' filter: nothing is read)
     const int64_t start = ok ? (int64_t)(((uint64_t)w * (uint64_t)range) >> 32) : -1;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        picked[2 * b] = item;
-        picked[2 * b + 1] = start;
+        a.picked[2 * b] = active ? item : -1;
+        a.picked[2 * b + 1] = active ? start : -1;
     }
     if (!ok) return;
-    collate_copy(tile, wav_arena, mel_arena, first + start, hop, F, b, mel_tiles, wavs, mels);
+    collate_copy(tile, a.wav_arena, a.mel_arena, first + start, a.hop, a.F, b, a.mel_tiles, a.wavs, a.mels);
+}
+
+// training: slot b of step `it` on rank r of w takes place g = (it B + b) w + r of the stream of epochs, item pi_epoch(g mod n)
+__global__ void __launch_bounds__(WG) k_train_collate(const CollateArgs a, int rank, int world)
+{
+    const unsigned long long it = step_iter(a.state, a.iter_host);
+    const uint64_t g = (it * (uint64_t)a.B + (uint64_t)blockIdx.y) * (uint64_t)world + (uint64_t)rank;
+    const uint64_t epoch = g / (uint64_t)a.n_items;
+    collate_slot(a, it, (int64_t)collate_perm(g % (uint64_t)a.n_items, (uint64_t)a.n_items, a.seed, epoch), true);
 }
 
 // The batch of an evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate; TrainCorpus.eval_plan is the host twin): slot b of
 // batch `it` is item g = it B + b itself, in order and without wrapping; the window start is the training collater's draw (same
 // stream, position and word, the id = the batch index).  A slot behind the last item is cut from item n - 1 -- the forward then reads
 // finite data -- and reported as (-1, -1): fd_eval_accumulate leaves it out.
-__global__ void __launch_bounds__(WG) k_eval_collate(const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
-                                                     int hop, int F, int B, unsigned long long seed, const fd_train_state *state,
-                                                     unsigned long long iter_host, int mel_tiles, float *wavs, float *mels, int64_t *picked)
+__global__ void __launch_bounds__(WG) k_eval_collate(const CollateArgs a)
 {
-    __shared__ float tile[CL_TF * CL_LD];
-    const int b = blockIdx.y;
-    const unsigned long long it = state ? state->iter : iter_host;
-    const uint64_t g = it * (uint64_t)B + (uint64_t)b;
-    const bool active = g < (uint64_t)n_items;
-    const int64_t item = active ? (int64_t)g : n_items - 1;
-    const int64_t first = frame_off[item];
-    const int64_t range = frame_off[item + 1] - first - F;
-    uint32_t r[4];
-    philox_keyed(seed, 0xFFFFFFFCu, (uint64_t)(b >> 2), it, r);
-    const int c = b & 3;
-    const uint32_t w = c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : r[3]));
-    const bool ok = range >= 1 && range < ((int64_t)1 << 32);
-    const int64_t start = ok ? (int64_t)(((uint64_t)w * (uint64_t)range) >> 32) : -1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        picked[2 * b] = active ? item : -1;
-        picked[2 * b + 1] = active ? start : -1;
-    }
-    if (!ok) return;
-    collate_copy(tile, wav_arena, mel_arena, first + start, hop, F, b, mel_tiles, wavs, mels);
+    const unsigned long long it = step_iter(a.state, a.iter_host);
+    const uint64_t g = it * (uint64_t)a.B + (uint64_t)blockIdx.y;
+    const bool active = g < (uint64_t)a.n_items;
+    collate_slot(a, it, active ? (int64_t)g : a.n_items - 1, active);
 }
 
 // ---- the loss ----------------------------------------------------------------------------------------------------------------------
@@ -218,23 +174,6 @@ __global__ void __launch_bounds__(WG) k_mse_partial(const float *eps, const floa
     }
     acc = block_sum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-// the final workgroup's sum of P per-workgroup results, a tree as well: groups of 256 through block_sum into LDS, then those (P <= 65536,
-// i.e. 2^28 elements; beyond that a thread first adds every 65536th serially).  Adding the zeros of an incomplete group is exact.
-__device__ __forceinline__ float final_sum(const float *partial, int64_t P)
-{
-    __shared__ float level[WG];
-    constexpr int64_t SPAN = (int64_t)WG * WG;
-    if (P <= WG) return block_sum(threadIdx.x < P ? partial[threadIdx.x] : 0.0f);
-    for (int c = 0; c < WG; ++c) {
-        float acc = 0.0f;
-        for (int64_t i = (int64_t)c * WG + threadIdx.x; i < P; i += SPAN) acc += partial[i];
-        acc = (int64_t)c * WG < P ? block_sum(acc) : 0.0f;      // (uniform over the workgroup)
-        if (threadIdx.x == 0) level[c] = acc;
-    }
-    __syncthreads();
-    return block_sum(level[threadIdx.x]);
 }
 
 __global__ void __launch_bounds__(WG) k_mse_final(const float *partial, int64_t P, int64_t n, float *loss, fd_train_state *state)
@@ -374,19 +313,9 @@ struct AdamDecision {
 constexpr int DEC_FLOATS = 16;
 static_assert(sizeof(AdamDecision) <= DEC_FLOATS * sizeof(float), "the decision record's slot");
 
-__device__ __forceinline__ int ad_find_item(const AdamChunk &c, int blk)
-{
-    int lo = 0, hi = c.n;      // first_block[lo] <= blk < first_block[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c.first_block[mid] <= blk) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(WG) k_adamw_norm(const AdamChunk c, float *partial, unsigned *flags)
 {
-    const int it = ad_find_item(c, blockIdx.x);
+    const int it = find_item(c, blockIdx.x);
     const float *g = c.it[it].g;
     const int64_t numel = c.it[it].numel;
     const int64_t base = (int64_t)(blockIdx.x - c.first_block[it]) * TILE + threadIdx.x;
@@ -454,7 +383,7 @@ __global__ void __launch_bounds__(WG) k_adamw_update(const AdamChunk c, const Ad
         if (d.skip) state->skipped += 1ull; else state->applied += 1ull;
     }
     if (d.skip || (int)blockIdx.x >= c.first_block[c.n]) return;
-    const int it = ad_find_item(c, blockIdx.x);
+    const int it = find_item(c, blockIdx.x);
     const float *g = c.it[it].g;
     float *p = c.it[it].p, *m = c.it[it].m, *v = c.it[it].v;
     const int64_t numel = c.it[it].numel;
@@ -514,11 +443,7 @@ __global__ void __launch_bounds__(WG) k_ema_update(const EmaChunk c, const fd_em
 {
     if (!ema->apply) return;
     const float w = ema->w;
-    int lo = 0, hi = c.n;      // first_block[lo] <= blockIdx.x < first_block[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c.first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
+    const int lo = find_item(c, blockIdx.x);
     const float *p = c.it[lo].p;
     float *e = c.it[lo].e;
     const int64_t numel = c.it[lo].numel;
@@ -554,8 +479,6 @@ __global__ void __launch_bounds__(WG) k_ema_update(const EmaChunk c, const fd_em
     }
 }
 
-inline int64_t tiles(int64_t n) { return (n + TILE - 1) / TILE; }
-
 }  // namespace
 
 size_t step_scratch_floats(int64_t blocks) { return (size_t)DEC_FLOATS + 2 * (size_t)blocks; }
@@ -578,27 +501,18 @@ hipError_t train_draw(const Launch &L_, const float *x0, const float *alpha, int
     return hipSuccess;
 }
 
-hipError_t train_collate(const Launch &L_, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
-                         int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
-                         float *mels, int64_t *picked)
+hipError_t collate(const Launch &L_, bool eval, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items,
+                   int hop, int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, int rank, int world, float *wavs,
+                   float *mels, int64_t *picked)
 {
     const int mel_tiles = (F + CL_TF - 1) / CL_TF;
     const int64_t l4 = (int64_t)F * (hop / 4);
     const int wav_chunks = (int)((l4 + CL_WAV4 - 1) / CL_WAV4);
-    FD_LAUNCH(L_, "train_collate", k_train_collate, dim3((unsigned)(mel_tiles + wav_chunks), (unsigned)B), dim3(WG), 0, wav_arena, mel_arena,
-              frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host, rank, world, mel_tiles, wavs, mels,
-              picked);
-    return hipSuccess;
-}
-
-hipError_t eval_collate(const Launch &L_, const float *wav_arena, const float *mel_arena, const int64_t *frame_off, int64_t n_items, int hop,
-                        int F, int B, uint64_t seed, const fd_train_state *state, uint64_t iter_host, float *wavs, float *mels, int64_t *picked)
-{
-    const int mel_tiles = (F + CL_TF - 1) / CL_TF;
-    const int64_t l4 = (int64_t)F * (hop / 4);
-    const int wav_chunks = (int)((l4 + CL_WAV4 - 1) / CL_WAV4);
-    FD_LAUNCH(L_, "eval_collate", k_eval_collate, dim3((unsigned)(mel_tiles + wav_chunks), (unsigned)B), dim3(WG), 0, wav_arena, mel_arena,
-              frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host, mel_tiles, wavs, mels, picked);
+    const dim3 grid((unsigned)(mel_tiles + wav_chunks), (unsigned)B);
+    const CollateArgs a = {wav_arena, mel_arena, frame_off, n_items, hop, F, B, (unsigned long long)seed, state, (unsigned long long)iter_host,
+                           mel_tiles, wavs, mels, picked};
+    if (eval) FD_LAUNCH(L_, "eval_collate", k_eval_collate, grid, dim3(WG), 0, a);
+    else FD_LAUNCH(L_, "train_collate", k_train_collate, grid, dim3(WG), 0, a, rank, world);
     return hipSuccess;
 }
 

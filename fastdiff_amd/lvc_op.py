@@ -26,7 +26,7 @@ def _handle(device):
     """One library handle per device: it supplies the device, the error text and the scratch buffers the backward kernels sum their
     partial results in (grown with hipFree + hipMalloc on first use of a larger shape).  Consequence, as for any handle of the library:
     the operators of this module must be ordered on ONE stream per device -- what torch.autograd does for a forward and its backward --
-    and their first call at a new shape must not sit inside a graph capture (warm up before capturing).  Two models
+    and their first call at a larger shape is refused inside a graph capture (warm up before capturing).  Two models
     training concurrently on one device from different threads or streams need a process each."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _handles:
@@ -962,13 +962,10 @@ def train_draw(x0, alpha, T_train, seed=0, iteration=0, state=None, out=None):
     return x_t, z, steps
 
 
-def train_collate(corpus, batch_size, seed=0, iteration=0, state=None, rank=0, world_size=1, out=None):
-    """The batch of a step cut on the device from a corpus.TrainCorpus that lies there (fd_train_collate) -> (mels [B, 80, F], wavs
-    [B, 1, F * hop], picked [B, 2] int64 = (item, start frame) per slot; corpus.plan(...) gives the same picks on the host).  The step
-    index is state's `iter` (read on the device: a captured call cuts a new batch on every replay) or, without a state, `iteration`;
-    rank / world_size: slot b stands at position (it B + b) world_size + rank of the endless item order.  out: (mels, wavs, picked)."""
+def _collate(fn, corpus, batch_size, seed, iteration, state, out, *tail):
+    """train_collate and eval_collate: entry point `fn`, whose arguments between the step index and the outputs are `tail`."""
     if not corpus.wav.is_cuda:
-        raise RuntimeError("fastdiff_amd.lvc_op.train_collate runs only on a HIP device (no CPU fallback): corpus.to(device) uploads the corpus")
+        raise RuntimeError(f"fastdiff_amd.lvc_op.{fn[3:]} runs only on a HIP device (no CPU fallback): corpus.to(device) uploads the corpus")
     dev, B, F, hop = corpus.wav.device, int(batch_size), corpus.frames, corpus.hop_size
     if out is None:
         out = (torch.empty((B, 80, F), device=dev, dtype=torch.float32), torch.empty((B, 1, F * hop), device=dev, dtype=torch.float32),
@@ -977,9 +974,17 @@ def train_collate(corpus, batch_size, seed=0, iteration=0, state=None, rank=0, w
     for t, shape, dtype in ((mels, (B, 80, F), torch.float32), (wavs, (B, 1, F * hop), torch.float32), (picked, (B, 2), torch.int64)):
         assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev, "out: (mels [B, 80, F], wavs [B, 1, F hop], picked [B, 2] int64)"
     assert state is None or state.device == dev
-    _call(dev, "fd_train_collate", "fd_train_collate", corpus.wav, corpus.mel, corpus.frame_off, corpus.n_items, hop, F, B,
-          int(seed) & 0xFFFFFFFFFFFFFFFF, state, int(iteration) & 0xFFFFFFFFFFFFFFFF, int(rank), int(world_size), wavs, mels, picked)
+    _call(dev, fn, fn, corpus.wav, corpus.mel, corpus.frame_off, corpus.n_items, hop, F, B, int(seed) & 0xFFFFFFFFFFFFFFFF, state,
+          int(iteration) & 0xFFFFFFFFFFFFFFFF, *tail, wavs, mels, picked)
     return mels, wavs, picked
+
+
+def train_collate(corpus, batch_size, seed=0, iteration=0, state=None, rank=0, world_size=1, out=None):
+    """The batch of a step cut on the device from a corpus.TrainCorpus that lies there (fd_train_collate) -> (mels [B, 80, F], wavs
+    [B, 1, F * hop], picked [B, 2] int64 = (item, start frame) per slot; corpus.plan(...) gives the same picks on the host).  The step
+    index is state's `iter` (read on the device: a captured call cuts a new batch on every replay) or, without a state, `iteration`;
+    rank / world_size: slot b stands at position (it B + b) world_size + rank of the endless item order.  out: (mels, wavs, picked)."""
+    return _collate("fd_train_collate", corpus, batch_size, seed, iteration, state, out, int(rank), int(world_size))
 
 
 class _MSE(torch.autograd.Function):
@@ -1081,19 +1086,7 @@ def eval_collate(corpus, batch_size, seed=0, iteration=0, state=None, out=None):
     slot b of batch `it` is item it B + b itself; a slot behind the last item is filled from the last item and reported as (-1, -1).
     corpus.eval_plan(it, B, seed) gives the same picks on the host.  The batch index is state's `iter` (read on the device) or, without
     a state, `iteration`.  out: (mels, wavs, picked) to write into."""
-    if not corpus.wav.is_cuda:
-        raise RuntimeError("fastdiff_amd.lvc_op.eval_collate runs only on a HIP device (no CPU fallback): corpus.to(device) uploads the corpus")
-    dev, B, F, hop = corpus.wav.device, int(batch_size), corpus.frames, corpus.hop_size
-    if out is None:
-        out = (torch.empty((B, 80, F), device=dev, dtype=torch.float32), torch.empty((B, 1, F * hop), device=dev, dtype=torch.float32),
-               torch.empty((B, 2), device=dev, dtype=torch.int64))
-    mels, wavs, picked = out
-    for t, shape, dtype in ((mels, (B, 80, F), torch.float32), (wavs, (B, 1, F * hop), torch.float32), (picked, (B, 2), torch.int64)):
-        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev, "out: (mels [B, 80, F], wavs [B, 1, F hop], picked [B, 2] int64)"
-    assert state is None or state.device == dev
-    _call(dev, "fd_eval_collate", "fd_eval_collate", corpus.wav, corpus.mel, corpus.frame_off, corpus.n_items, hop, F, B,
-          int(seed) & 0xFFFFFFFFFFFFFFFF, state, int(iteration) & 0xFFFFFFFFFFFFFFFF, wavs, mels, picked)
-    return mels, wavs, picked
+    return _collate("fd_eval_collate", corpus, batch_size, seed, iteration, state, out)
 
 
 def item_distance(a, b, kind=0, out=None):

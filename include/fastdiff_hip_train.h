@@ -188,8 +188,8 @@ FD_API int fd_conv32_backward(fd_handle h, const float *xs, const float *y, cons
  * non-finite guard and AdamW -- with every per-step quantity in DEVICE memory, so that a whole step is one graph replay that draws anew,
  * and the host never waits for it.  Sums run in a fixed order (per-thread runs of FD_STEP_RUN elements, a tree inside the workgroup,
  * per-workgroup partial sums in a scratch buffer of the handle, one final workgroup): no floating-point atomics, two runs agree bit for
- * bit.  Calls on one handle must be ordered on one stream, and the first call at a new size must not sit inside a graph capture (the
- * scratch buffer grows then).  Growing frees the old buffer: a graph captured earlier on this handle has its address baked in and must
+ * bit.  Calls on one handle must be ordered on one stream, and the first call at a larger size must not sit inside a graph capture (the
+ * scratch buffer grows then: refused with FD_ERR_STATE, here and in the operators above).  Growing frees the old buffer: a graph captured earlier on this handle has its address baked in and must
  * not be replayed after a LARGER fd_mse_forward / fd_adamw_multi call on the same handle (capture again) -- as with the scratch buffers
  * of the backward operators above.  At most 2^36 elements per call.
  *

@@ -253,6 +253,48 @@ def test_loss_and_its_gradient_against_float64(gc, n):
     assert torch.equal(e2.grad, out[0][1])
 
 
+@pytest.mark.gpu
+def test_a_growing_step_scratch_is_refused_inside_a_capture(gc):
+    """A handle of its own has no step scratch yet: fd_mse_forward's first call inside a capture would have to allocate it and is refused
+    with FD_ERR_STATE before any HIP call.  After one call outside a capture the same call captures, and replays the eager loss bit for bit."""
+    import ctypes as ct
+    lib = _capi.load()
+    cfg = _capi.FdConfig()
+    lib.fd_default_config(ct.byref(cfg))
+    h = ct.c_void_p()
+    _capi.check(lib, None, lib.fd_create(ct.byref(cfg), 0, ct.byref(h)), "fd_create")
+    n = 8192                                               # two workgroups of 16 * 256 elements
+    eps, z = gc.hash_normal_torch(13, 1, n), gc.hash_normal_torch(13, 2, n)
+    loss = torch.zeros((), device="cuda")
+
+    def call():
+        return lib.fd_mse_forward(h, eps.data_ptr(), z.data_ptr(), n, loss.data_ptr(), None, torch.cuda.current_stream().cuda_stream)
+
+    try:
+        torch.cuda.synchronize()
+        refused = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(refused):
+            eps.mul_(1.0)                                  # (so that the abandoned capture is not empty)
+            rc = call()
+        assert rc == _capi.FD_ERR_STATE and b"stream capture" in lib.fd_last_error(h), (rc, lib.fd_last_error(h))
+        assert call() == _capi.FD_OK, lib.fd_last_error(h)
+        torch.cuda.synchronize()
+        want = loss.clone()
+        d64 = eps.double() - z.double()
+        assert abs(float(want) - float((d64 ** 2).mean())) <= sum_bound(n) * float((d64 ** 2).mean())
+        loss.zero_()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rc = call()
+        assert rc == _capi.FD_OK, lib.fd_last_error(h)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(loss, want)
+    finally:
+        torch.cuda.synchronize()
+        lib.fd_destroy(h)
+
+
 def _reference_adamw(dtype, p0, grads, hp, frozen=None):
     """clip_grad_norm_ + torch.optim.AdamW (foreach=False) on the CPU in `dtype`; returns (params, exp_avg, exp_avg_sq, norms)."""
     P = [torch.nn.Parameter(p.detach().cpu().to(dtype).clone()) for p in p0]
