@@ -1,6 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
 // sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
-// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  Then taps, layout
+// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  The baseline vocoder next to it: Griffin-Lim and the mel inversion (fd_griffin_lim, fd_mel_to_linear).  Then taps, layout
 // introspection, counters and per-kernel profiling.  
 #include <math.h>
 #include <stddef.h>
@@ -512,6 +512,69 @@ int fd_spectral_measure(fd_handle h, const float *clean, const float *degraded, 
     if ((rc = upload_counts(h, valid, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) {
         return fdk::spectral(La, clean, degraded, L, B, L, valid ? lens_dev : nullptr, c, tabs, rec_dev, s.p);
+    });
+}
+
+// Griffin-Lim and the mel inversion in front of it (fastdiff_hip_ext.h; lengths, refusals, scratch and counter layout: fd_gl.h, the
+// kernels: fd_kernels_gl.hip) ----------------------------------------------------------------------------------------------------------
+int64_t fd_gl_samples(int64_t frames) { return fdgl::samples(frames); }
+
+int fd_gl_default_iters(void) { return fdgl::DEFAULT_ITERS; }
+
+int fd_mel_to_linear(fd_handle h, const float *mel, int B, int T, const float *pinv_513x80, int variant, float *amp_out, void *stream)
+{
+    // (the arguments first, as fd_spectral_measure checks them: their refusals need no handle)
+    const char *who = "fd_mel_to_linear";
+    if (!mel || !pinv_513x80 || !amp_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !mel ? "mel" : (!pinv_513x80 ? "pinv_513x80" : "amp_out"));
+    if (B < 1 || B > fdgl::MAX_B || T < 1 || T > fdgl::MAX_T)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d items (1 .. %d) of T = %d frames (1 .. %d)", who, B, fdgl::MAX_B, T, fdgl::MAX_T);
+    if (variant != FD_GL_PWG && variant != FD_GL_TACOTRON) FD_FAIL(h, FD_ERR_INVALID, "%s: unknown variant %d (FD_GL_PWG / FD_GL_TACOTRON)", who, variant);
+    const size_t np = (size_t)fdgl::BINS * fdgl::MELS;
+    for (size_t i = 0; i < np; ++i) {                      // (on the bit pattern: this file is built with -fno-honor-nans)
+        uint32_t bits;
+        memcpy(&bits, pinv_513x80 + i, sizeof(bits));
+        if ((bits & 0x7F800000u) == 0x7F800000u) FD_FAIL(h, FD_ERR_INVALID, "%s: element %zu of pinv_513x80 is not finite", who, i);
+    }
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    int rc = enter(h);
+    if (rc != FD_OK) return rc;
+    std::vector<float> &host = h->gl_pinv_host[variant];
+    if (!h->gl_pinv[variant] || memcmp(host.data(), pinv_513x80, sizeof(float) * np) != 0) {
+        if (capturing((hipStream_t)stream))
+            FD_FAIL(h, FD_ERR_STATE, "%s: the pseudo-inverse is uploaded at the first call that uses it, which cannot happen inside a stream capture: call it once before", who);
+        const void *dev = nullptr;
+        if ((rc = upload_table(h, who, pinv_513x80, sizeof(float) * np, &dev)) != FD_OK) return rc;
+        h->gl_pinv[variant] = static_cast<const float *>(dev);
+        host.assign(pinv_513x80, pinv_513x80 + np);
+    }
+    const float *P = h->gl_pinv[variant];
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::mel_to_linear(La, mel, B, T, P, variant, amp_out); });
+}
+
+int fd_griffin_lim(fd_handle h, const float *amp, const float *angles, int B, int T, const int64_t *lens, int n_iters, uint64_t seed,
+                   const uint64_t *stream_ids, float *wav_out, int64_t wav_pitch, fd_gl *rec_dev, void *stream)
+{
+    const char *who = "fd_griffin_lim";
+    if (!amp || !wav_out || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !amp ? "amp" : (!wav_out ? "wav_out" : "rec_dev"));
+    char why[fdgl::MSG];
+    if (fdgl::refusal(B, T, n_iters, wav_pitch, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    int rc = check_counts(h, who, "lens", lens, B, 0, T);
+    if (rc != FD_OK) return rc;
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    if ((rc = enter(h)) != FD_OK) return rc;
+    if (!h->mel[MEL_VARIANTS - 1].tab && capturing((hipStream_t)stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table is uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
+    if ((rc = ensure_mel_tables(h)) != FD_OK) return rc;
+    const float *tab = h->mel[0].tab;
+    Scratch &s = h->gl_scratch;
+    if ((rc = reserve(h, who, s, fdk::gl_scratch_bytes(B, T), (hipStream_t)stream)) != FD_OK) return rc;
+    const fdk::GlSlots sl = fdk::gl_slots(s.p, B, T);
+    if ((rc = upload_counts(h, lens, B, sl.lens, (hipStream_t)stream)) != FD_OK) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(int64_t), "the ids travel as the counts do");
+    if ((rc = upload_counts(h, reinterpret_cast<const int64_t *>(stream_ids), B, reinterpret_cast<long long *>(sl.ids), (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::griffin_lim(La, amp, angles, B, T, lens ? sl.lens : nullptr, stream_ids ? sl.ids : nullptr, n_iters, (unsigned long long)seed, tab, wav_out,
+                                wav_pitch, rec_dev, s.p);
     });
 }
 

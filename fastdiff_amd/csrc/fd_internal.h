@@ -15,6 +15,7 @@
 #include "fd_stoi.h"
 #include "fd_pitch.h"
 #include "fd_spectral.h"
+#include "fd_gl.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -378,6 +379,9 @@ struct fd_context {
     Scratch pitch_scratch;                   // fd_pitch_track / _compare: the device copies of valid [B] and frames [B]
     Scratch spectral_scratch;                // fd_spectral_measure: lengths, then the frame partials of every resolution
     std::map<std::pair<int, int>, const float *> spectral_tabs;      // its window and twiddles by (nfft, win) (csrc/fd_spectral.h: tables), each uploaded at the first call that uses it (in `tables`)
+    Scratch gl_scratch;                      // fd_griffin_lim: lengths, stream ids, transposed amplitudes, two frame buffers, frame sums (csrc/fd_gl.h: layout)
+    const float *gl_pinv[MEL_VARIANTS] = {nullptr, nullptr};      // fd_mel_to_linear: the pseudo-inverse [513][80] last used with each variant (in `tables`) ...
+    std::vector<float> gl_pinv_host[MEL_VARIANTS];                // ... and its values, to tell a new one
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -507,6 +511,15 @@ size_t spectral_scratch_bytes(int B, int64_t L, const fd_spectral_config &c);
 long long *spectral_lens_slot(void *scratch);
 hipError_t spectral(const Launch &L_, const float *x, const float *y, long long pitch, int B, int64_t L, const long long *lens_dev,
                     const fd_spectral_config &c, const float *const *tabs, fd_spectral *rec, void *scratch);
+// fd_griffin_lim / fd_mel_to_linear (fd_kernels_gl.hip).  lens_dev / ids_dev: null (every item T frames / id = b) or the slots of the
+// scratch buffer, filled by the caller; tab: the mel front-end's table (cos, sin, window); scratch: gl_scratch_bytes(B, T) bytes.
+struct GlSlots { long long *lens; unsigned long long *ids; };
+size_t gl_scratch_bytes(int B, int T);
+GlSlots gl_slots(void *scratch, int B, int T);
+hipError_t griffin_lim(const Launch &L_, const float *amp, const float *angles, int B, int T, const long long *lens_dev,
+                       const unsigned long long *ids_dev, int n_iters, unsigned long long seed, const float *tab, float *wav, long long pitch,
+                       fd_gl *rec, void *scratch);
+hipError_t mel_to_linear(const Launch &L_, const float *mel, int B, int T, const float *pinv_dev, int variant, float *amp);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

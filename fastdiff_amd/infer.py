@@ -14,10 +14,11 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
     `lens`, so every item is computed exactly as if it ran alone (and the padding costs nothing), then cropped to its length.
 
 Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
-synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), test_step
+synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), synthesize_griffin_lim (--vocoder griffin_lim:
+the baseline vocoder on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch] [--spectral]`).
+[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60]]`).
 """
 import argparse
 import glob
@@ -220,6 +221,52 @@ def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
     return batch, lens, names
 
 
+def _level_epilogue(model, R, sample_rate, loudness):
+    """(n_of, epilogue) of synthesize and synthesize_griffin_lim: n_of(t) = the PCM samples of t hops (at R Hz when R is not None);
+    epilogue(wav, lens) = the float waveforms of a micro-batch (item b: lens[b] hops) -> int16 PCM [B, n]: resampled to R first, then
+    peak-normalised, or with loudness = LUFS loudness-normalised, each item over its own samples."""
+    from . import resample as _resample
+    hop = model.hop_length
+    n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
+
+    def to_pcm(wav, valid, rate):
+        if loudness is None:
+            return model.peak_normalize_int16(wav, valid=valid)
+        return model.loudness_normalize(wav.reshape(wav.shape[0], -1), float(loudness), valid=valid, sample_rate=rate, out="int16")
+
+    def epilogue(wav, lens):
+        if R is None:
+            return to_pcm(wav, [t * hop for t in lens], sample_rate)
+        y = model.resample(wav.reshape(wav.shape[0], -1), sample_rate, R, valid=[t * hop for t in lens])
+        return to_pcm(y, [n_of(t) for t in lens], R)
+
+    return n_of, epilogue
+
+
+def _scorer(model, items, scored, report, sample_rate, who):
+    """score(wav, names, lens) of synthesize and synthesize_griffin_lim: every enabled score of the micro-batch's float waveforms against
+    the items' recordings, cut to the vocoded length (lens hops), into report[name]."""
+    hop = model.hop_length
+
+    def score(wav, names, lens):
+        # the recordings of the micro-batch next to its float waveform: one padded batch, one call and one record read per score
+        wav_of = {it["item_name"]: it["wav"] for it in items}
+        B, n = wav.shape[0], wav.shape[-1]
+        clean = torch.zeros((B, n), device=wav.device, dtype=torch.float32)
+        for b, (name, t) in enumerate(zip(names, lens)):
+            if wav_of[name].numel() < t * hop:
+                raise ValueError(f"{who}: the recording of {name} has {wav_of[name].numel()} samples, fewer than the {t * hop} vocoded")
+            clean[b, : t * hop] = wav_of[name][: t * hop]
+        valid = [t * hop for t in lens]
+        for sc in scored:
+            rec = getattr(model, sc.name)(clean, wav.reshape(B, n), valid=valid, **sc.kwargs(sample_rate, hop))
+            for b, name in enumerate(names):
+                report.setdefault(name, {}).update({key: float(rec[col][b]) for col, key, _, _ in sc.columns})
+                report[name][sc.status_key] = sc.module.STATUS[int(rec["status"][b])]
+
+    return score
+
+
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
                sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
@@ -248,7 +295,6 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     spectral=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"mr_sc", "mr_logmag", "lsd_db",
     "spectral_status"} (FastDiff.spectral at the default resolutions: the means over them of the spectral convergence, the log-magnitude
     distance in nepers and the log-spectral distance in dB; status by name), measured on the same waveforms, next to the other sets."""
-    from . import resample as _resample
     scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
     if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
         raise ValueError(f"synthesize: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
@@ -262,18 +308,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     if not items:
         return (out, report) if scored else out
     hop = model.hop_length
-    n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
-
-    def to_pcm(wav, valid, rate):
-        if loudness is None:
-            return model.peak_normalize_int16(wav, valid=valid)
-        return model.loudness_normalize(wav.reshape(wav.shape[0], -1), float(loudness), valid=valid, sample_rate=rate, out="int16")
-
-    def epilogue(wav, lens):
-        if R is None:
-            return to_pcm(wav, [t * hop for t in lens], sample_rate)
-        y = model.resample(wav.reshape(wav.shape[0], -1), sample_rate, R, valid=[t * hop for t in lens])
-        return to_pcm(y, [n_of(t) for t in lens], R)
+    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
 
     on_device = isinstance(items[0]["mel"], torch.Tensor) and items[0]["mel"].is_cuda
     t_max, b_max = max(lengths), min(max_batch, len(items))
@@ -290,21 +325,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     host_check = getattr(model, "_options", {}).get("fallback") == "host"
     prev_dev = None                # return_device: (ticket, wav, names, lens) of the micro-batch nobody has settled yet
 
-    def score(wav, names, lens):
-        # the recordings of the micro-batch next to its float waveform: one padded batch, one call and one record read per score
-        wav_of = {it["item_name"]: it["wav"] for it in items}
-        B, n = wav.shape[0], wav.shape[-1]
-        clean = torch.zeros((B, n), device=wav.device, dtype=torch.float32)
-        for b, (name, t) in enumerate(zip(names, lens)):
-            if wav_of[name].numel() < t * hop:
-                raise ValueError(f"synthesize: the recording of {name} has {wav_of[name].numel()} samples, fewer than the {t * hop} vocoded")
-            clean[b, : t * hop] = wav_of[name][: t * hop]
-        valid = [t * hop for t in lens]
-        for sc in scored:
-            rec = getattr(model, sc.name)(clean, wav.reshape(B, n), valid=valid, **sc.kwargs(sample_rate, hop))
-            for b, name in enumerate(names):
-                report.setdefault(name, {}).update({key: float(rec[col][b]) for col, key, _, _ in sc.columns})
-                report[name][sc.status_key] = sc.module.STATUS[int(rec["status"][b])]
+    score = _scorer(model, items, scored, report, sample_rate, "synthesize")
 
     def settle_on_device(p):
         # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
@@ -372,6 +393,46 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
         collect(pending)
     if host_check and prev_dev is not None:
         settle_on_device(prev_dev)
+    return (out, report) if scored else out
+
+
+def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_batch: int = 8, seed: int = 0, variant: str = "pwg",
+                           sort: bool = True, out_sample_rate: int = None, sample_rate: int = 22050, loudness: float = None,
+                           stoi: bool = False, pitch: bool = False, spectral: bool = False) -> Dict[str, np.ndarray]:
+    """The baseline next to synthesize(): item_name -> int16 PCM from Griffin-Lim on the device (FastDiff.griffin_lim_mel: the mel
+    inverted with the pseudo-inverse of the front-end's filter bank, then n_iters projections; the reference's GLMel, vocoders/gl_mel.py,
+    with pinv in place of its NNLS), through the same length-sorted padded micro-batches.  ALL frames of an item's mel are used: its
+    `len` frames give 256 (len - 1) samples, exactly what synthesize() produces from the same item after dropping the last frame, so
+    the two waveforms and their scores line up.  An item of fewer than 2 frames is left out, as synthesize() leaves out what it cannot
+    collate.  The starting phase of item `it` is drawn from Philox stream (seed, it["uid"], frame, bin); "uid" defaults to the item's
+    position in `items`, so a waveform does not depend on its micro-batch.  variant: the front-end the mels come from ("pwg": log10,
+    "tacotron": ln).  out_sample_rate, loudness, stoi, pitch, spectral: as in synthesize() -- the same level epilogue, the same scores
+    into the same report keys, measured on the float waveform before the epilogue."""
+    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
+    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+        raise ValueError(f"synthesize_griffin_lim: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    report: Dict[str, dict] = {}
+    out: Dict[str, np.ndarray] = {}
+    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
+    uid_of = {it["item_name"]: int(it.get("uid", i)) for i, it in enumerate(items)}
+    kept = [it for it in items if it["mel"].shape[0] >= 2]
+    if not kept:
+        return (out, report) if scored else out
+    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
+    score = _scorer(model, items, scored, report, sample_rate, "synthesize_griffin_lim")
+    on_device = isinstance(kept[0]["mel"], torch.Tensor) and kept[0]["mel"].is_cuda
+    for batch_idx in shard.micro_batches(range(len(kept)), [it["mel"].shape[0] for it in kept], max_batch, sort=sort):
+        batch_items = [kept[i] for i in batch_idx]
+        mels, frames, names = (_collate_on_device if on_device else collate_test_batch)(batch_items, False)
+        with torch.no_grad():
+            wav = model.griffin_lim_mel(mels.cuda(), lens=frames, variant=variant, n_iters=n_iters, seed=seed, stream_ids=[uid_of[n] for n in names])
+        lens = [f - 1 for f in frames]                 # in hops: 256 (frames - 1) samples
+        pcm = epilogue(wav, lens)
+        if scored:
+            score(wav, names, lens)
+        host = pcm.cpu().numpy()
+        for b, (name, t) in enumerate(zip(names, lens)):
+            out[name] = host[b, : n_of(t)].copy()
     return (out, report) if scored else out
 
 
@@ -570,6 +631,11 @@ def main(argv=None):
                     help="with --from_wav (copy synthesis): measure the multi-resolution STFT distances of every vocoded waveform against its "
                          "recording on the device (spectral convergence, log-magnitude distance, log-spectral distance in dB; the means over "
                          "512 / 1024 / 2048-point transforms), print the table and write <out_dir>/spectral.tsv")
+    ap.add_argument("--vocoder", default="fastdiff", choices=("fastdiff", "griffin_lim"),
+                    help="griffin_lim: the baseline instead of the model -- every mel inverted with the pseudo-inverse of the filter bank and "
+                         "run through --gl_iters Griffin-Lim iterations on the device; the same <name>_pred.wav files and, with --stoi / "
+                         "--pitch / --spectral, the same TSVs, so a baseline row is one command next to the model's")
+    ap.add_argument("--gl_iters", type=int, default=60, help="with --vocoder griffin_lim: iterations (griffin_lim_iters of base.yaml: 60)")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
@@ -579,6 +645,11 @@ def main(argv=None):
             ap.error(f"--{sc.name} scores the vocoded waveform against its recording: it needs --from_wav")
         if args.long_form:
             ap.error(f"--{sc.name} is not available with --long_form")
+    if args.vocoder == "griffin_lim":
+        if args.long_form:
+            ap.error("--vocoder griffin_lim is not available with --long_form")
+        if not 0 <= args.gl_iters <= 10000:
+            ap.error(f"--gl_iters {args.gl_iters} outside 0 .. 10000")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -593,7 +664,10 @@ def main(argv=None):
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
     items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored)) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
-    if args.long_form:
+    if args.vocoder == "griffin_lim":
+        pcm = synthesize_griffin_lim(model, mine, args.gl_iters, args.max_batch, args.seed, variant=args.mel_variant, out_sample_rate=args.out_sample_rate,
+                                     loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral)
+    elif args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)

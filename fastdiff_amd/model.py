@@ -390,6 +390,33 @@ class FastDiff(nn.Module):
         from . import spectral as _spectral
         return _spectral._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
 
+    def mel_to_linear(self, mel, variant="pwg"):
+        """Mel inversion on the device (fastdiff_amd/griffin_lim.py; utils/audio.py:91-95 _mel_to_linear): mel [B, 80, T] as front-end
+        `variant` produces it (log10 for "pwg", ln for "tacotron") -> amplitudes [B, 513, T] = max(1e-10, pinv(bank) @ g(mel)), with
+        the bank this module's front-end uses (mel_filterbank) and its pseudo-inverse from numpy.linalg.pinv in float64, cached per
+        variant.  This is the pseudo-inverse, not the non-negative least squares (librosa.util.nnls) of GLMel's
+        librosa.feature.inverse.mel_to_stft.  Does not synchronise."""
+        from . import griffin_lim as _gl
+        _gl.variant_id(variant)
+        lib, h, stream = self._wave_call(mel)
+        P = _gl.pinv(self.mel_filterbank(variant, device=mel.device)[0], variant)
+        return _gl._mel_to_linear(lib, h, stream, mel, P, variant)
+
+    def griffin_lim(self, amp, lens=None, n_iters=60, angles=None, seed=0, stream_ids=None, return_record=False):
+        """Griffin-Lim on the device (fastdiff_amd/griffin_lim.py; the reference's GLLinear, vocoders/gl_linear.py over utils/audio.py:
+        35-63): amplitudes [B, 513, T] of a 1024-point STFT at hop 256 -> wav [B, 256 (T - 1)] after n_iters projections.  lens: [B] frame
+        counts of a padded batch (item b: 256 (lens[b] - 1) samples, zeros behind them).  angles [B, 513, T]: the starting phase
+        (n_iters = 0: the inverse STFT alone); None: Philox angles keyed on (seed, stream_ids[b] or b, frame, bin), so with ids an item's
+        waveform does not depend on its batch.  return_record: (wav, record) with sc = || |stft(wav)| - amp || / || amp ||, norm, frames,
+        samples, iters, status (griffin_lim.OK / SHORT / SILENT / NONFINITE) per item; without it nothing synchronises."""
+        from . import griffin_lim as _gl
+        return _gl._run(*self._wave_call(amp), amp, lens, n_iters, angles, seed, stream_ids, return_record)
+
+    def griffin_lim_mel(self, mel, lens=None, variant="pwg", **kw):
+        """mel_to_linear, then griffin_lim: mel [B, 80, T] -> wav [B, 256 (T - 1)] (the reference's GLMel with the pseudo-inverse in place
+        of its NNLS).  kw: n_iters, seed, stream_ids, return_record."""
+        return self.griffin_lim(self.mel_to_linear(mel, variant), lens=lens, **kw)
+
     def pitch_track(self, wav, valid=None, **cfg):
         """(f0, aper) of `wav` on the device, float32 [B, n // hop] (fastdiff_amd/pitch.py: track); does not synchronise."""
         from . import pitch as _pitch

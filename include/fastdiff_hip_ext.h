@@ -378,6 +378,89 @@ FD_API int64_t fd_spectral_frames(int64_t n, int hop);
 FD_API int fd_spectral_measure(fd_handle h, const float *clean, const float *degraded, int B, int64_t L, const int64_t *valid,
                                const fd_spectral_config *cfg, fd_spectral *rec_dev, void *stream);
 
+/* Griffin-Lim: the baseline vocoder (the reference's GLLinear / GLMel, vocoders/gl_linear.py, vocoders/gl_mel.py over
+ * utils/audio.py:35-63 griffin_lim and :123-158 griffin_lim_torch) -- a waveform from magnitudes alone, by alternating projections
+ * (Griffin and Lim 1984).  With it come the two primitives it is made of: an inverse STFT and the magnitude-only reconstruction loop.
+ * THIS TEXT defines the computation; tests/gl_ref.py restates it in float64 numpy, and torch.stft / torch.istft on the CPU confirm that
+ * restatement.
+ *
+ * Constants: N = FD_GL_NFFT = 1024, hop = FD_GL_HOP = 256, bins k = 0 .. 512, w = the periodic Hann window of 1024 points, the mel
+ * front-end's.  Inputs: amplitudes A[b][k][t] >= 0, float32 [B][513][T]; frame counts lens[b] (NULL: T).  Item b yields
+ * L_b = fd_gl_samples(lens[b]) = 256 (lens[b] - 1) samples: the front-end's T = 1 + len / 256 read backwards, so the T + 1 frames of a
+ * recording's mel give the T 256 samples that fd_sample produces from its first T frames.
+ *
+ * stft(y):   X[k][t] = sum_n w[n] ypad[256 t + n] e^(-2 pi i k n / N), k <= 512, ypad = y with 512 zeros on each side
+ *            (librosa.stft(center=True, pad_mode="constant"), what fd_mel_spectrogram transforms; not torch.stft's reflect padding).
+ * istft(C):  f_t[n] = w[n] (1 / N) sum_{k < N} C^[k][t] e^(+2 pi i k n / N), C^ the Hermitian extension of C, the imaginary parts of
+ *            bins 0 and 512 ignored as a C2R transform ignores them;
+ *            y~[m] = sum_t f_t[m - 256 t] / sum_t w^2[m - 256 t] over the frames t < lens[b] that cover m;  y[j] = y~[j + 512], j < L_b.
+ *            The envelope sum_t w^2 is at least 1.25 on that range (1.5 where four frames overlap): no guard, no epsilon.
+ *            (librosa.istft, torch.istft(center=True).)
+ * The loop:  C_0 = A e^(i theta0), y_0 = istft(C_0); for i = 1 .. n_iters: X = stft(y_{i-1}), C = A X / |X| (X = 0: C = A, as
+ *            np.angle(0) = 0), y_i = istft(C).  No angle is formed inside the loop.
+ * theta0:    the caller's angles[b][k][t] (GLLinear.spec2wav's phase=; with a recording's own phase an upper bound), or, angles NULL,
+ *            theta = 6.2831855f u with u the float32 uniform ((float)(r >> 8) + 0.5f) 2^-24 of one Philox4x32-10 word r:
+ *            key = (seed lo, seed hi), counter = (pos lo, pos hi ^ id lo, FD_GL_PHILOX_STREAM, 0x5EED ^ id hi), pos = 129 t + k / 4,
+ *            r = output word k % 4 -- the generator of fd_sample's noise on a stream word of its own (0xFFFFFFFF is x_T, small values the
+ *            step indices, 0xFFFFFFF9 .. 0xFFFFFFFE the training draws).  id = stream_ids[b] (NULL: b), so with ids an item's start
+ *            does not depend on the batch it sits in.
+ * Results:   wav_out[b][0 .. L_b), zeros behind it up to fd_gl_samples(T); one record per item: the status and the final inconsistency
+ *            sc = || |stft(y_n)| - A ||_F / || A ||_F from one more forward pass over the returned waveform, its sums in float64 in
+ *            a fixed order as fd_spectral_measure's.  FD_GL_SHORT: lens[b] < 2; FD_GL_NONFINITE: an amplitude is negative, infinite
+ *            or NaN; FD_GL_SILENT: every amplitude is 0.  In all three the row is zeros and sc NaN; the other items are not affected.
+ *
+ * On the device.  The transform is the mel front-end's split 32 x 32 transform in float32 (fd_spectral_measure's text above) and its
+ * mirror image: with k = k1 + 32 k2, n = 32 n1 + n2,
+ *     D[k1][n2] = sum_k2 C^[k1 + 32 k2] e^(+2 pi i k2 n2 / 32);   E = D e^(+2 pi i k1 n2 / N), k1 = 0 .. 16;
+ *     x[32 n1 + n2] = (Re E[0][n2] + (-1)^n1 Re E[16][n2] + 2 sum_{k1 = 1 .. 15} Re(E[k1][n2] e^(+2 pi i k1 n1 / 32))) / N
+ * (the rows k1 > 16 are the conjugates of the rows 32 - k1), every sum one fmaf chain in ascending order over the same table of cos and
+ * sin of 2 pi m / N.  |X| = sqrt(fma(im, im, re re)) and C = (re s, im s) with s = A / |X|, each operation rounded once as written.
+ * One launch per iteration and no grid-wide barrier: a workgroup takes FD_GL_FRAME_TILE consecutive frames of one item; it forms ypad
+ * under them from the previous iteration's synthesis frames -- per sample the at most four covering frames added in ascending t, divided
+ * by the envelope, which is summed from w^2 in the same order -- then per frame: window, forward transform, re-phase, inverse
+ * transform, window, and writes the synthesis frame f_t to the other of two frame buffers [B][T][1024].  No spectrum reaches memory, no
+ * sum depends on which workgroup forms it, there are no atomics: an item's waveform and record are bit-identical alone, anywhere in a
+ * ragged batch and from call to call.  The waveform is written once, by a last gather launch.  The frame buffers, the amplitudes
+ * transposed to [B][T][513] and the per-frame sums live in a buffer of the handle that grows at the first call that needs more; that
+ * and the upload of the front-end's tables cannot happen inside a stream capture, where such a call is refused with FD_ERR_STATE: call
+ * it once before.  Otherwise a call is capturable. */
+#define FD_GL_NFFT 1024
+#define FD_GL_HOP 256
+#define FD_GL_BINS 513
+#define FD_GL_FRAME_TILE 4          /* consecutive frames of one item per workgroup */
+#define FD_GL_SUM_CHUNK 256         /* interleaved runs of frames the record's finaliser adds before it adds the runs */
+#define FD_GL_MAX_ITERS 10000
+#define FD_GL_MAX_FRAMES 1048576    /* T */
+#define FD_GL_PHILOX_STREAM 0xFFFFFFF8u
+enum { FD_GL_OK = 0, FD_GL_SHORT = 1, FD_GL_SILENT = 2, FD_GL_NONFINITE = 3 };
+enum { FD_GL_PWG = 0, FD_GL_TACOTRON = 1 };      /* fd_mel_to_linear's variant: the mel is log10 / ln of the filter bank's output */
+typedef struct fd_gl {
+    double sc;                             /* the inconsistency of the returned waveform; NaN unless FD_GL_OK */
+    double norm;                           /* || A ||_F over the item's own frames; NaN if SHORT or NONFINITE */
+    int32_t frames, samples;               /* lens[b]; L_b (0 if SHORT) */
+    int32_t iters;                         /* n_iters */
+    int32_t status;                        /* FD_GL_* */
+} fd_gl;                                   /* 32 bytes */
+
+/* 256 (frames - 1), or -1 below 2 frames (pure host code). */
+FD_API int64_t fd_gl_samples(int64_t frames);
+/* 60: griffin_lim_iters of egs_bases/tts/base.yaml (pure host code). */
+FD_API int fd_gl_default_iters(void);
+/* Mel inversion (utils/audio.py:91-95 _mel_to_linear): amp_out[b][k][t] = max(1e-10, sum_j P[k][j] g(mel[b][j][t])), g = 10^x for
+ * FD_GL_PWG, e^x for FD_GL_TACOTRON; one thread per (k, t), the 80 terms one fmaf chain in ascending j.  mel [B][80][T] and amp_out
+ * [B][513][T] device float; pinv_513x80: HOST, P = pinv(filter bank) [513][80] float32, uploaded at the first call and whenever its
+ * values differ from the last call's with that variant (not inside a stream capture: FD_ERR_STATE).  This is the pseudo-inverse, not
+ * GLMel's librosa.util.nnls.  Asynchronous on `stream`.  The arguments are checked before the handle is looked at.  FD_ERR_INVALID: a
+ * null pointer or handle, B outside 1 .. 4096, T outside 1 .. FD_GL_MAX_FRAMES, an unknown variant, an element of P that is not finite. */
+FD_API int fd_mel_to_linear(fd_handle h, const float *mel, int B, int T, const float *pinv_513x80, int variant, float *amp_out, void *stream);
+/* amp [B][513][T], angles [B][513][T] or NULL (Philox), wav_out [B] rows wav_pitch floats apart, rec_dev [B]: device; lens (frames,
+ * 0 .. T; below 2: FD_GL_SHORT) and stream_ids: HOST [B] or NULL.  Asynchronous on `stream`.  The arguments are checked before the
+ * handle is looked at, so a refusal's text is left with fd_last_error(NULL) when the handle is NULL.  FD_ERR_INVALID: a null handle or
+ * pointer, B outside 1 .. 4096, T outside 2 .. FD_GL_MAX_FRAMES, n_iters outside 0 .. FD_GL_MAX_ITERS, wav_pitch < fd_gl_samples(T),
+ * lens[b] out of range; FD_ERR_STATE: the tables or the scratch buffer would have to be made inside a stream capture. */
+FD_API int fd_griffin_lim(fd_handle h, const float *amp, const float *angles, int B, int T, const int64_t *lens, int n_iters, uint64_t seed,
+                          const uint64_t *stream_ids, float *wav_out, int64_t wav_pitch, fd_gl *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
