@@ -29,7 +29,8 @@ fastdiff_amd.spectral / FastDiff.spectral measure the multi-resolution STFT dist
 log-spectral distance) of the vocoded spectrum against the recording's, Validator(spectral=True) and infer.synthesize(spectral=True) /
 --spectral likewise (fastdiff_amd/spectral.py);
 fastdiff_amd.griffin_lim / FastDiff.griffin_lim / mel_to_linear / griffin_lim_mel are the baseline vocoder (the reference's GLLinear /
-GLMel) with its inverse STFT on the device, and infer.synthesize_griffin_lim / --vocoder griffin_lim put its rows next to the model's
+GLMel) with its inverse STFT on the device and both mel inversions (the pseudo-inverse, which is the default, and GLMel's non-negative
+least squares: mel_to_linear(inversion="nnls"), griffin_lim.mel_to_linear_nnls), and infer.synthesize_griffin_lim / --vocoder griffin_lim put its rows next to the model's
 (fastdiff_amd/griffin_lim.py).
 """
 from .model import FastDiff  # noqa: F401

@@ -1,6 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
 // sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
-// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  The baseline vocoder next to it: Griffin-Lim and the mel inversion (fd_griffin_lim, fd_mel_to_linear).  Then taps, layout
+// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  The baseline vocoder next to it: Griffin-Lim and the mel inversions (fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls).  Then taps, layout
 // introspection, counters and per-kernel profiling.  
 #include <math.h>
 #include <stddef.h>
@@ -575,6 +575,68 @@ int fd_griffin_lim(fd_handle h, const float *amp, const float *angles, int B, in
     return run(h, stream, who, [&](const fdk::Launch &La) {
         return fdk::griffin_lim(La, amp, angles, B, T, lens ? sl.lens : nullptr, stream_ids ? sl.ids : nullptr, n_iters, (unsigned long long)seed, tab, wav_out,
                                 wav_pitch, rec_dev, s.p);
+    });
+}
+
+// The non-negative mel inversion (fastdiff_hip_ext.h; refusals, L, the momentum table, the bank's images and the scratch layout:
+// fd_nnls.h, the kernels: fd_kernels_nnls.hip)
+int fd_nnls_default_iters(void) { return fdn::DEFAULT_ITERS; }
+
+int fd_nnls_step_bound(const float *bank_80x513, double *L_out)
+{
+    const fd_handle h = nullptr;
+    const char *who = "fd_nnls_step_bound";
+    if (!bank_80x513 || !L_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !bank_80x513 ? "bank_80x513" : "L_out");
+    const long bad = fdn::first_nonfinite(bank_80x513, (size_t)fdn::MELS * fdn::BINS);
+    if (bad >= 0) FD_FAIL(h, FD_ERR_INVALID, "%s: element %ld of bank_80x513 is not finite", who, bad);
+    *L_out = fdn::step_bound(bank_80x513);
+    return FD_OK;
+}
+
+int fd_mel_to_linear_nnls(fd_handle h, const float *mel, int B, int T, const int64_t *lens, const float *bank_80x513, const float *pinv_513x80,
+                          int variant, int n_iters, float *amp_out, fd_nnls *rec_dev, void *stream)
+{
+    const char *who = "fd_mel_to_linear_nnls";
+    if (!mel || !bank_80x513 || !pinv_513x80 || !amp_out)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !mel ? "mel" : (!bank_80x513 ? "bank_80x513" : (!pinv_513x80 ? "pinv_513x80" : "amp_out")));
+    char why[fdn::MSG];
+    if (fdn::refusal(B, T, n_iters, variant, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    const size_t np = (size_t)fdn::BINS * fdn::MELS;
+    long bad = fdn::first_nonfinite(bank_80x513, np);
+    if (bad >= 0) FD_FAIL(h, FD_ERR_INVALID, "%s: element %ld of bank_80x513 is not finite", who, bad);
+    if ((bad = fdn::first_nonfinite(pinv_513x80, np)) >= 0) FD_FAIL(h, FD_ERR_INVALID, "%s: element %ld of pinv_513x80 is not finite", who, bad);
+    int rc = check_counts(h, who, "lens", lens, B, 0, T);
+    if (rc != FD_OK) return rc;
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    if ((rc = enter(h)) != FD_OK) return rc;
+    fd_context::NnlsBank &nb = h->nnls_bank[variant];
+    const bool new_bank = !nb.tab || memcmp(nb.bank.data(), bank_80x513, sizeof(float) * np) != 0;
+    const bool new_pinv = !nb.pinv_dev || memcmp(nb.pinv.data(), pinv_513x80, sizeof(float) * np) != 0;
+    if ((new_bank || new_pinv) && capturing((hipStream_t)stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: the bank's tables and the pseudo-inverse are uploaded at the first call that uses them, which cannot happen inside a stream capture: call it once before", who);
+    if (new_bank) {
+        std::vector<float> tab(fdn::table().total);
+        fdn::fill_table(bank_80x513, tab.data());
+        const void *dev = nullptr;
+        if ((rc = upload_table(h, who, tab.data(), sizeof(float) * tab.size(), &dev)) != FD_OK) return rc;
+        nb.tab = static_cast<const float *>(dev);
+        nb.bank.assign(bank_80x513, bank_80x513 + np);
+        nb.L = fdn::step_bound(bank_80x513);
+    }
+    if (new_pinv) {
+        const void *dev = nullptr;
+        if ((rc = upload_table(h, who, pinv_513x80, sizeof(float) * np, &dev)) != FD_OK) return rc;
+        nb.pinv_dev = static_cast<const float *>(dev);
+        nb.pinv.assign(pinv_513x80, pinv_513x80 + np);
+    }
+    Scratch &s = h->nnls_scratch;
+    if ((rc = reserve(h, who, s, fdk::nnls_scratch_bytes(B, T), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *lens_dev = fdk::nnls_lens_slot(s.p);
+    if ((rc = upload_counts(h, lens, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    const float step = fdn::step(nb.L);
+    const float *tab = nb.tab, *P = nb.pinv_dev;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::mel_to_linear_nnls(La, mel, B, T, lens ? lens_dev : nullptr, P, tab, step, variant, n_iters, amp_out, rec_dev, s.p);
     });
 }
 

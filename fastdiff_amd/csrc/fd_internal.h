@@ -16,6 +16,7 @@
 #include "fd_pitch.h"
 #include "fd_spectral.h"
 #include "fd_gl.h"
+#include "fd_nnls.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -382,6 +383,12 @@ struct fd_context {
     Scratch gl_scratch;                      // fd_griffin_lim: lengths, stream ids, transposed amplitudes, two frame buffers, frame sums (csrc/fd_gl.h: layout)
     const float *gl_pinv[MEL_VARIANTS] = {nullptr, nullptr};      // fd_mel_to_linear: the pseudo-inverse [513][80] last used with each variant (in `tables`) ...
     std::vector<float> gl_pinv_host[MEL_VARIANTS];                // ... and its values, to tell a new one
+    Scratch nnls_scratch;                    // fd_mel_to_linear_nnls: lengths and frame sums (csrc/fd_nnls.h: layout)
+    struct NnlsBank {                        // ... per variant: the bank and P last used, the device table of the bank (fdn::table) and copy of P (in `tables`), L
+        std::vector<float> bank, pinv;
+        const float *tab = nullptr, *pinv_dev = nullptr;
+        double L = 0.0;
+    } nnls_bank[MEL_VARIANTS];
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -520,6 +527,12 @@ hipError_t griffin_lim(const Launch &L_, const float *amp, const float *angles, 
                        const unsigned long long *ids_dev, int n_iters, unsigned long long seed, const float *tab, float *wav, long long pitch,
                        fd_gl *rec, void *scratch);
 hipError_t mel_to_linear(const Launch &L_, const float *mel, int B, int T, const float *pinv_dev, int variant, float *amp);
+// fd_mel_to_linear_nnls (fd_kernels_nnls.hip).  lens_dev: null or the lens slot of the scratch buffer (nnls_scratch_bytes(B, T) bytes);
+// tab_dev: device copy of fdn::fill_table(bank); step: fdn::step(L); rec: device [B] or null.
+size_t nnls_scratch_bytes(int B, int T);
+long long *nnls_lens_slot(void *scratch);
+hipError_t mel_to_linear_nnls(const Launch &L_, const float *mel, int B, int T, const long long *lens_dev, const float *pinv_dev,
+                              const float *tab_dev, float step, int variant, int n_iters, float *amp, fd_nnls *rec, void *scratch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

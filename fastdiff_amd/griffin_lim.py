@@ -12,12 +12,19 @@ angles is the inverse STFT alone.
     pinv(filterbank, variant)    the pseudo-inverse [513, 80] of a filter bank [80, 513], float64 numpy.linalg.pinv rounded to float32,
                                  cached per variant until the bank changes
     mel_to_linear(mel, pinv, variant="pwg")                       -> amplitudes [B, 513, T]
+    mel_to_linear_nnls(mel, bank, pinv, variant="pwg", lens=None, n_iters=128, return_record=False)      -> amplitudes [B, 513, T]
+    nnls_default_iters()         128
+    nnls_step_bound(bank)        L >= lambda_max(bank bank^T): the step of the non-negative inversion is 1 / L
     griffin_lim(amp, lens=None, n_iters=60, angles=None, seed=0, stream_ids=None, return_record=False)   -> wav [B, 256 (T - 1)]
-    STATUS                       names of the record's status values
+    STATUS, NNLS_STATUS          names of the records' status values
 
 mel_to_linear is utils/audio.py:91-95 _mel_to_linear: max(1e-10, pinv(basis) @ g(mel)), g = 10^x for "pwg" mels and e^x for
-"tacotron" ones.  It is the pseudo-inverse, NOT the non-negative least squares (librosa.util.nnls, an L-BFGS solve per block) that
-GLMel's librosa.feature.inverse.mel_to_stft runs: librosa is not a dependency of this package.
+"tacotron" ones: the pseudo-inverse, and the default inversion everywhere.  mel_to_linear_nnls is the non-negative least squares that
+GLMel's librosa.feature.inverse.mel_to_stft runs (librosa.util.nnls, an L-BFGS-B solve per block): per frame min || bank x - g(mel) ||,
+x >= 0, started at the clipped pseudo-inverse and solved by n_iters accelerated projected-gradient steps of fixed size in one fused
+kernel (fd_mel_to_linear_nnls, which defines it), then floored at 1e-10 like the other.  n_iters = 0 is mel_to_linear bit for bit.
+Its record: resid (float64: || bank amp - g || / || g || over the item's own frames, NaN unless OK), norm (|| g ||), frames, iters,
+status (int32).  EMPTY: no frames; NONFINITE: a mel value is NaN or infinite or g overflows, the item's amplitudes are then all 1e-10.
 
 A record is a dict of numpy arrays over the batch: sc (float64: || |stft(y)| - A || / || A || of the returned waveform, NaN unless OK),
 norm (|| A ||), frames, samples, iters, status (int32).  SHORT: fewer than 2 frames; SILENT: every amplitude is 0; NONFINITE: an
@@ -36,6 +43,11 @@ OK, SHORT, SILENT, NONFINITE = _capi.FD_GL_OK, _capi.FD_GL_SHORT, _capi.FD_GL_SI
 STATUS = {OK: "OK", SHORT: "SHORT", SILENT: "SILENT", NONFINITE: "NONFINITE"}
 RECORD = np.dtype([("sc", "<f8"), ("norm", "<f8"), ("frames", "<i4"), ("samples", "<i4"), ("iters", "<i4"), ("status", "<i4")])
 VARIANTS = {"pwg": _capi.FD_GL_PWG, "tacotron": _capi.FD_GL_TACOTRON}
+
+NNLS_MAX_ITERS, NNLS_FRAME_TILE = _capi.FD_NNLS_MAX_ITERS, _capi.FD_NNLS_FRAME_TILE
+NNLS_OK, NNLS_EMPTY, NNLS_NONFINITE = _capi.FD_NNLS_OK, _capi.FD_NNLS_EMPTY, _capi.FD_NNLS_NONFINITE
+NNLS_STATUS = {NNLS_OK: "OK", NNLS_EMPTY: "EMPTY", NNLS_NONFINITE: "NONFINITE"}
+NNLS_RECORD = np.dtype([("resid", "<f8"), ("norm", "<f8"), ("frames", "<i4"), ("iters", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
 
 _pinv_cache = {}      # variant -> (the bank's bytes, its pseudo-inverse)
 
@@ -92,6 +104,44 @@ def _mel_to_linear(lib, handle, stream, mel, P, variant):
     return amp
 
 
+def nnls_default_iters():
+    return int(_capi.load().fd_nnls_default_iters())
+
+
+def nnls_step_bound(filterbank):
+    """L of fd_nnls_step_bound for a filter bank [80, 513]: 1.01 times the Rayleigh quotient of bank bank^T after 200 power iterations."""
+    fb = np.ascontiguousarray(filterbank, dtype=np.float32)
+    if fb.shape != (MELS, BINS):
+        raise ValueError(f"griffin_lim: expected a filter bank [80, 513], got {list(fb.shape)}")
+    lib, L = _capi.load(), ct.c_double()
+    _capi.check(lib, None, lib.fd_nnls_step_bound(fb.ctypes.data, ct.byref(L)), "fd_nnls_step_bound")
+    return float(L.value)
+
+
+def _mel_to_linear_nnls(lib, handle, stream, mel, bank, P, variant, lens, n_iters, return_record):
+    v = variant_id(variant)
+    if not isinstance(mel, torch.Tensor) or not mel.is_cuda:
+        raise ValueError("mel_to_linear_nnls: a tensor on the HIP device is expected (there is no CPU path)")
+    mel = mel.contiguous().float()
+    if mel.dim() == 2:
+        mel = mel.unsqueeze(0)
+    if mel.dim() != 3 or mel.shape[1] != MELS or mel.shape[2] < 1:
+        raise ValueError(f"mel_to_linear_nnls: expected a mel [B, 80, T], got {list(mel.shape)}")
+    bank = np.ascontiguousarray(bank, dtype=np.float32)
+    if bank.shape != (MELS, BINS):
+        raise ValueError(f"mel_to_linear_nnls: expected a filter bank [80, 513], got {list(bank.shape)}")
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    if P.shape != (BINS, MELS):
+        raise ValueError(f"mel_to_linear_nnls: expected a pseudo-inverse [513, 80], got {list(P.shape)}")
+    B, _, T = mel.shape
+    amp = torch.empty((B, BINS, T), device=mel.device, dtype=torch.float32)
+    rec = torch.empty((B, NNLS_RECORD.itemsize), device=mel.device, dtype=torch.uint8) if return_record else None
+    rc = lib.fd_mel_to_linear_nnls(handle, mel.data_ptr(), B, T, _wave.counts(lens, B, "mel_to_linear_nnls"), bank.ctypes.data, P.ctypes.data, v,
+                                   int(n_iters), amp.data_ptr(), None if rec is None else rec.data_ptr(), stream)
+    _capi.check(lib, handle, rc, "fd_mel_to_linear_nnls")
+    return (amp, _wave.records(rec, NNLS_RECORD, NNLS_RECORD.names[:5])) if return_record else amp
+
+
 def _amp(amp, angles):
     if not isinstance(amp, torch.Tensor) or not amp.is_cuda:
         raise ValueError("griffin_lim: a tensor on the HIP device is expected (there is no CPU path)")
@@ -146,6 +196,14 @@ def mel_to_linear(mel, pinv_513x80, variant="pwg"):
     """mel [B, 80, T] on the device, the pseudo-inverse [513, 80] (pinv()) -> amplitudes [B, 513, T]: max(1e-10, P @ g(mel)).  Runs on
     the current stream, on the per-device handle of the operators (lvc_op); FastDiff.mel_to_linear uses the module's own and its bank."""
     return _mel_to_linear(*_wave.default_handle(mel), mel, pinv_513x80, variant)
+
+
+def mel_to_linear_nnls(mel, bank, pinv_513x80, variant="pwg", lens=None, n_iters=128, return_record=False):
+    """mel [B, 80, T] on the device, the filter bank [80, 513] and its pseudo-inverse [513, 80] (pinv()) -> amplitudes [B, 513, T]: the
+    non-negative least-squares inversion (the module's text above), n_iters steps from max(0, P @ g(mel)).  lens: [B] frame counts of a
+    padded batch; frames behind them are not read and come back as 1e-10.  return_record: (amp, record): one synchronisation; without
+    it nothing synchronises.  Runs on the current stream, on the per-device handle of the operators."""
+    return _mel_to_linear_nnls(*_wave.default_handle(mel), mel, bank, pinv_513x80, variant, lens, n_iters, return_record)
 
 
 def griffin_lim(amp, lens=None, n_iters=60, angles=None, seed=0, stream_ids=None, return_record=False):

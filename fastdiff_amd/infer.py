@@ -18,7 +18,7 @@ synthesize_long (--long_form: windowed, any length, the utterances sharing windo
 the baseline vocoder on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60]]`).
+[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]`).
 """
 import argparse
 import glob
@@ -398,16 +398,21 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
 
 def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_batch: int = 8, seed: int = 0, variant: str = "pwg",
                            sort: bool = True, out_sample_rate: int = None, sample_rate: int = 22050, loudness: float = None,
-                           stoi: bool = False, pitch: bool = False, spectral: bool = False) -> Dict[str, np.ndarray]:
+                           stoi: bool = False, pitch: bool = False, spectral: bool = False, inversion: str = "pinv",
+                           nnls_iters: int = 128) -> Dict[str, np.ndarray]:
     """The baseline next to synthesize(): item_name -> int16 PCM from Griffin-Lim on the device (FastDiff.griffin_lim_mel: the mel
-    inverted with the pseudo-inverse of the front-end's filter bank, then n_iters projections; the reference's GLMel, vocoders/gl_mel.py,
-    with pinv in place of its NNLS), through the same length-sorted padded micro-batches.  ALL frames of an item's mel are used: its
+    inverted with the front-end's filter bank -- inversion="pinv", the default: its pseudo-inverse; inversion="nnls": the non-negative
+    least squares of the reference's GLMel, vocoders/gl_mel.py, in nnls_iters steps -- then n_iters projections), through the same
+    length-sorted padded micro-batches.  ALL frames of an item's mel are used: its
     `len` frames give 256 (len - 1) samples, exactly what synthesize() produces from the same item after dropping the last frame, so
     the two waveforms and their scores line up.  An item of fewer than 2 frames is left out, as synthesize() leaves out what it cannot
     collate.  The starting phase of item `it` is drawn from Philox stream (seed, it["uid"], frame, bin); "uid" defaults to the item's
     position in `items`, so a waveform does not depend on its micro-batch.  variant: the front-end the mels come from ("pwg": log10,
     "tacotron": ln).  out_sample_rate, loudness, stoi, pitch, spectral: as in synthesize() -- the same level epilogue, the same scores
     into the same report keys, measured on the float waveform before the epilogue."""
+    if inversion not in ("pinv", "nnls"):
+        raise ValueError(f"synthesize_griffin_lim: inversion must be 'pinv' or 'nnls', got {inversion!r}")
+    how = {} if inversion == "pinv" else dict(inversion=inversion, nnls_iters=int(nnls_iters))      # (the default passes no new keyword)
     scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
     if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
         raise ValueError(f"synthesize_griffin_lim: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
@@ -425,7 +430,7 @@ def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_
         batch_items = [kept[i] for i in batch_idx]
         mels, frames, names = (_collate_on_device if on_device else collate_test_batch)(batch_items, False)
         with torch.no_grad():
-            wav = model.griffin_lim_mel(mels.cuda(), lens=frames, variant=variant, n_iters=n_iters, seed=seed, stream_ids=[uid_of[n] for n in names])
+            wav = model.griffin_lim_mel(mels.cuda(), lens=frames, variant=variant, n_iters=n_iters, seed=seed, stream_ids=[uid_of[n] for n in names], **how)
         lens = [f - 1 for f in frames]                 # in hops: 256 (frames - 1) samples
         pcm = epilogue(wav, lens)
         if scored:
@@ -632,10 +637,14 @@ def main(argv=None):
                          "recording on the device (spectral convergence, log-magnitude distance, log-spectral distance in dB; the means over "
                          "512 / 1024 / 2048-point transforms), print the table and write <out_dir>/spectral.tsv")
     ap.add_argument("--vocoder", default="fastdiff", choices=("fastdiff", "griffin_lim"),
-                    help="griffin_lim: the baseline instead of the model -- every mel inverted with the pseudo-inverse of the filter bank and "
+                    help="griffin_lim: the baseline instead of the model -- every mel inverted with the filter bank (--gl_inversion) and "
                          "run through --gl_iters Griffin-Lim iterations on the device; the same <name>_pred.wav files and, with --stoi / "
                          "--pitch / --spectral, the same TSVs, so a baseline row is one command next to the model's")
     ap.add_argument("--gl_iters", type=int, default=60, help="with --vocoder griffin_lim: iterations (griffin_lim_iters of base.yaml: 60)")
+    ap.add_argument("--gl_inversion", default="pinv", choices=("pinv", "nnls"),
+                    help="with --vocoder griffin_lim: how the mel is inverted -- pinv: the pseudo-inverse of the filter bank, floored (the "
+                         "default); nnls: the non-negative least squares of the reference's GLMel, solved on the device in --nnls_iters steps")
+    ap.add_argument("--nnls_iters", type=int, default=128, help="with --gl_inversion nnls: accelerated projected-gradient steps per frame")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
     args = ap.parse_args(argv)
@@ -650,6 +659,8 @@ def main(argv=None):
             ap.error("--vocoder griffin_lim is not available with --long_form")
         if not 0 <= args.gl_iters <= 10000:
             ap.error(f"--gl_iters {args.gl_iters} outside 0 .. 10000")
+        if not 0 <= args.nnls_iters <= 4096:
+            ap.error(f"--nnls_iters {args.nnls_iters} outside 0 .. 4096")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -665,8 +676,9 @@ def main(argv=None):
     items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored)) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     if args.vocoder == "griffin_lim":
+        how = {} if (args.gl_inversion, args.nnls_iters) == ("pinv", 128) else dict(inversion=args.gl_inversion, nnls_iters=args.nnls_iters)
         pcm = synthesize_griffin_lim(model, mine, args.gl_iters, args.max_batch, args.seed, variant=args.mel_variant, out_sample_rate=args.out_sample_rate,
-                                     loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral)
+                                     loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, **how)
     elif args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")

@@ -390,16 +390,25 @@ class FastDiff(nn.Module):
         from . import spectral as _spectral
         return _spectral._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
 
-    def mel_to_linear(self, mel, variant="pwg"):
+    def mel_to_linear(self, mel, variant="pwg", inversion="pinv", nnls_iters=128, lens=None, return_record=False):
         """Mel inversion on the device (fastdiff_amd/griffin_lim.py; utils/audio.py:91-95 _mel_to_linear): mel [B, 80, T] as front-end
-        `variant` produces it (log10 for "pwg", ln for "tacotron") -> amplitudes [B, 513, T] = max(1e-10, pinv(bank) @ g(mel)), with
-        the bank this module's front-end uses (mel_filterbank) and its pseudo-inverse from numpy.linalg.pinv in float64, cached per
-        variant.  This is the pseudo-inverse, not the non-negative least squares (librosa.util.nnls) of GLMel's
-        librosa.feature.inverse.mel_to_stft.  Does not synchronise."""
+        `variant` produces it (log10 for "pwg", ln for "tacotron") -> amplitudes [B, 513, T], with the bank this module's front-end
+        uses (mel_filterbank) and its pseudo-inverse from numpy.linalg.pinv in float64, cached per variant.  inversion="pinv" (the
+        default): max(1e-10, pinv(bank) @ g(mel)).  inversion="nnls": the non-negative least squares of GLMel's
+        librosa.feature.inverse.mel_to_stft (librosa.util.nnls) -- nnls_iters accelerated projected-gradient steps from the clipped
+        pseudo-inverse in one fused kernel; lens: [B] frame counts of a padded batch; return_record: (amp, record with resid, norm,
+        frames, iters, status per item), which synchronises once.  Otherwise nothing synchronises."""
         from . import griffin_lim as _gl
         _gl.variant_id(variant)
+        if inversion not in ("pinv", "nnls"):
+            raise ValueError(f"mel_to_linear: inversion must be 'pinv' or 'nnls', got {inversion!r}")
         lib, h, stream = self._wave_call(mel)
-        P = _gl.pinv(self.mel_filterbank(variant, device=mel.device)[0], variant)
+        bank = self.mel_filterbank(variant, device=mel.device)[0]
+        P = _gl.pinv(bank, variant)
+        if inversion == "nnls":
+            return _gl._mel_to_linear_nnls(lib, h, stream, mel, bank, P, variant, lens, nnls_iters, return_record)
+        if return_record:
+            raise ValueError("mel_to_linear: only inversion='nnls' has a record")
         return _gl._mel_to_linear(lib, h, stream, mel, P, variant)
 
     def griffin_lim(self, amp, lens=None, n_iters=60, angles=None, seed=0, stream_ids=None, return_record=False):
@@ -412,10 +421,13 @@ class FastDiff(nn.Module):
         from . import griffin_lim as _gl
         return _gl._run(*self._wave_call(amp), amp, lens, n_iters, angles, seed, stream_ids, return_record)
 
-    def griffin_lim_mel(self, mel, lens=None, variant="pwg", **kw):
-        """mel_to_linear, then griffin_lim: mel [B, 80, T] -> wav [B, 256 (T - 1)] (the reference's GLMel with the pseudo-inverse in place
-        of its NNLS).  kw: n_iters, seed, stream_ids, return_record."""
-        return self.griffin_lim(self.mel_to_linear(mel, variant), lens=lens, **kw)
+    def griffin_lim_mel(self, mel, lens=None, variant="pwg", inversion="pinv", nnls_iters=128, **kw):
+        """mel_to_linear, then griffin_lim: mel [B, 80, T] -> wav [B, 256 (T - 1)] (the reference's GLMel).  inversion="pinv" (the
+        default) inverts the mel with the pseudo-inverse, inversion="nnls" with GLMel's own non-negative least squares (nnls_iters
+        steps).  kw: n_iters, seed, stream_ids, return_record (Griffin-Lim's record)."""
+        if inversion == "pinv":
+            return self.griffin_lim(self.mel_to_linear(mel, variant), lens=lens, **kw)
+        return self.griffin_lim(self.mel_to_linear(mel, variant, inversion=inversion, nnls_iters=nnls_iters, lens=lens), lens=lens, **kw)
 
     def pitch_track(self, wav, valid=None, **cfg):
         """(f0, aper) of `wav` on the device, float32 [B, n // hop] (fastdiff_amd/pitch.py: track); does not synchronise."""

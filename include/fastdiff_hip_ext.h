@@ -449,8 +449,8 @@ FD_API int fd_gl_default_iters(void);
 /* Mel inversion (utils/audio.py:91-95 _mel_to_linear): amp_out[b][k][t] = max(1e-10, sum_j P[k][j] g(mel[b][j][t])), g = 10^x for
  * FD_GL_PWG, e^x for FD_GL_TACOTRON; one thread per (k, t), the 80 terms one fmaf chain in ascending j.  mel [B][80][T] and amp_out
  * [B][513][T] device float; pinv_513x80: HOST, P = pinv(filter bank) [513][80] float32, uploaded at the first call and whenever its
- * values differ from the last call's with that variant (not inside a stream capture: FD_ERR_STATE).  This is the pseudo-inverse, not
- * GLMel's librosa.util.nnls.  Asynchronous on `stream`.  The arguments are checked before the handle is looked at.  FD_ERR_INVALID: a
+ * values differ from the last call's with that variant (not inside a stream capture: FD_ERR_STATE).  This is the pseudo-inverse, the
+ * default inversion; GLMel's non-negative least squares is fd_mel_to_linear_nnls below.  Asynchronous on `stream`.  The arguments are checked before the handle is looked at.  FD_ERR_INVALID: a
  * null pointer or handle, B outside 1 .. 4096, T outside 1 .. FD_GL_MAX_FRAMES, an unknown variant, an element of P that is not finite. */
 FD_API int fd_mel_to_linear(fd_handle h, const float *mel, int B, int T, const float *pinv_513x80, int variant, float *amp_out, void *stream);
 /* amp [B][513][T], angles [B][513][T] or NULL (Philox), wav_out [B] rows wav_pitch floats apart, rec_dev [B]: device; lens (frames,
@@ -460,6 +460,60 @@ FD_API int fd_mel_to_linear(fd_handle h, const float *mel, int B, int T, const f
  * lens[b] out of range; FD_ERR_STATE: the tables or the scratch buffer would have to be made inside a stream capture. */
 FD_API int fd_griffin_lim(fd_handle h, const float *amp, const float *angles, int B, int T, const int64_t *lens, int n_iters, uint64_t seed,
                           const uint64_t *stream_ids, float *wav_out, int64_t wav_pitch, fd_gl *rec_dev, void *stream);
+
+/* Non-negative mel inversion (the reference's GLMel, vocoders/gl_mel.py:15-19: librosa.util.nnls(mel_basis, spec), the pseudo-inverse
+ * clipped at 0 and refined under x >= 0).  Per frame the convex problem min_x || A x - g ||^2, x >= 0, with A = the bank [80][513]
+ * float32, P = its pseudo-inverse [513][80] float32 (what fd_mel_to_linear takes) and g = g(mel) as fd_mel_to_linear forms it, solved
+ * by an accelerated projected gradient (FISTA) with a fixed step and a fixed iteration count:
+ *     x_0 = max(0, P g)      (fd_mel_to_linear's 80-term fmaf chain in ascending j);   y_0 = x_0
+ *     k = 0 .. n_iters - 1:  r = A y_k - g  [80];   x_{k+1} = max(0, fma(-s, A^T r, y_k))  [513];   y_{k+1} = fma(beta_k, x_{k+1} - x_k, x_{k+1})
+ *     amp_out = max(1e-10, x_n)      (the pseudo-inverse path's floor; n_iters = 0 is fd_mel_to_linear bit for bit)
+ * s = float32(1 / L), L an upper bound of the largest eigenvalue of A A^T: fd_nnls_step_bound, on the host in float64 when a bank is
+ * first seen -- 200 power iterations on the 80 x 80 Gram matrix from the start vector v_j = 1 + j / 80, then 1.01 times the Rayleigh
+ * quotient -- cached with the bank and P per variant.  beta_k = (t_k - 1) / t_{k+1}, t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2: a
+ * host table in double, rounded to float32 once.  No adaptive restart and no data-dependent stopping: a frame's result is a function
+ * of that frame alone.  A is dense and of any sign to the kernel.
+ *
+ * On the device.  One launch does the whole solve: a workgroup of 256 threads takes FD_NNLS_FRAME_TILE = 32 consecutive frames of one
+ * item -- the column count of one v_mfma_f32_32x32x2_f32, the exact-fp32 matrix instruction both products run on (bit for bit an fmaf
+ * chain; no fp16 split: r cancels to 1e-7 of its operands).  y [513][32] lives in LDS as the B operand of A y, x_k in the registers
+ * of the lane that owns the element in the instruction's result layout; A streams from L2 twice per iteration, once as the zero-padded
+ * transpose [520][96] (A y: the 260 bin pairs split over the four waves in fixed ranges, the four partial sums added in wave order)
+ * and once as [80][544] (A^T r: 17 bin tiles of 32 dealt to the waves).  A tile of 32 frames needs 127 KB of the 160 KB of LDS, so
+ * one workgroup per CU; 16 frames with half of A resident would halve the columns every streamed element of A feeds.  Only
+ * amp_out and four doubles per frame reach memory.  A second pass in the same kernel forms, from the amplitudes written, in float64
+ * sum_j (A amp - g)_j^2 (each an fma chain in ascending bin, the 80 squares added in ascending j), sum_j g_j^2 and the count of g that
+ * are not finite; k_nnls_finish adds the frames as k_gl_finish does.  Frames at or behind lens[b] are never read and their amp_out is
+ * 1e-10.  Every sum has a fixed order that does not depend on the batch; no atomics: an item is bit-identical alone, anywhere in a
+ * ragged batch and from call to call.
+ *
+ * The record: resid = || A amp - g ||_F / || g ||_F over the item's own frames (0 if || g || = 0), NaN unless OK; norm = || g ||_F (NaN
+ * unless OK).  FD_NNLS_EMPTY: lens[b] == 0.  FD_NNLS_NONFINITE: a mel value is NaN or infinite, or g overflows; that item's amplitudes
+ * are all 1e-10, the other items are not affected. */
+#define FD_NNLS_MAX_ITERS 4096
+#define FD_NNLS_FRAME_TILE 32       /* consecutive frames of one item per workgroup */
+enum { FD_NNLS_OK = 0, FD_NNLS_EMPTY = 1, FD_NNLS_NONFINITE = 2 };
+typedef struct fd_nnls {
+    double resid;                          /* || A amp - g || / || g || over the item's own frames; NaN unless FD_NNLS_OK */
+    double norm;                           /* || g ||_F; NaN unless FD_NNLS_OK */
+    int32_t frames;                        /* lens[b] */
+    int32_t iters;                         /* n_iters */
+    int32_t status;                        /* FD_NNLS_* */
+    int32_t reserved;
+} fd_nnls;                                 /* 32 bytes */
+
+/* 128 (pure host code). */
+FD_API int fd_nnls_default_iters(void);
+/* L as defined above for a bank [80][513] (pure host code, no handle).  FD_ERR_INVALID: a null pointer, an element that is not finite. */
+FD_API int fd_nnls_step_bound(const float *bank_80x513, double *L_out);
+/* mel [B][80][T], amp_out [B][513][T], rec_dev [B] or NULL: device; lens (frames, 0 .. T), bank_80x513 and pinv_513x80: HOST (lens may be
+ * NULL).  The bank, P, L and the beta table are uploaded at the first call and whenever the bank's or P's values differ from the last
+ * call's with that variant; that and a growth of the scratch buffer (lens, the frame sums) cannot happen inside a stream capture:
+ * FD_ERR_STATE, call it once before.  Asynchronous on `stream`.  The arguments are checked before the handle is looked at.
+ * FD_ERR_INVALID: a null pointer or handle, B outside 1 .. 4096, T outside 1 .. FD_GL_MAX_FRAMES, n_iters outside 0 ..
+ * FD_NNLS_MAX_ITERS, an unknown variant, an element of the bank or of P that is not finite, lens[b] outside 0 .. T. */
+FD_API int fd_mel_to_linear_nnls(fd_handle h, const float *mel, int B, int T, const int64_t *lens, const float *bank_80x513,
+                                 const float *pinv_513x80, int variant, int n_iters, float *amp_out, fd_nnls *rec_dev, void *stream);
 
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
