@@ -244,6 +244,12 @@ class TrainCorpus:
             picks[~active] = -1
         return picks
 
+    def fit_bins(self, **kw):
+        """The k-means bins of NDB / JSD (fastdiff_amd.diversity.fit) over every mel frame of the corpus, on the arena where it lies:
+        nothing is copied.  Keywords as diversity.fit takes them (K, iters, n_init, seed, standardize, check_every)."""
+        from . import diversity
+        return diversity.fit(self.mel, **kw)
+
     def cut(self, items, starts):
         """(mels [B, 80, F], wavs [B, 1, F hop]) by torch slicing of the arenas, on their device: the reference's collater on given
         picks.  For inspection and tests; the training path is lvc_op.train_collate."""

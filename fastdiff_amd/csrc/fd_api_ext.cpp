@@ -640,6 +640,29 @@ int fd_mel_to_linear_nnls(fd_handle h, const float *mel, int B, int T, const int
     });
 }
 
+// The k-means bin pass (fastdiff_hip_ext.h; refusals, LDS and scratch layout: fd_bins.h, the kernels: fd_kernels_bins.hip)
+int fd_bins_chunk(void) { return fdb::CHUNK; }
+
+int fd_bins_record_bytes(void) { return (int)sizeof(fd_bins); }
+
+int fd_bins_pass(fd_handle h, const float *x, int64_t N, int D, int64_t ld, const float *shift, const float *scale, const float *centroids, int K,
+                 int32_t *assign_io, float *centroids_out, fd_bins *rec_dev, void *stream)
+{
+    const char *who = "fd_bins_pass";
+    if (!x || !centroids) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !x ? "x" : "centroids");
+    if (!assign_io && !centroids_out && !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: assign_io, centroids_out and rec_dev are all null: nothing to write", who);
+    char why[fdb::MSG];
+    if (fdb::refusal(x, N, D, ld, shift != nullptr, scale != nullptr, K, centroids, centroids_out, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    int rc;
+    if ((rc = enter(h)) != FD_OK) return rc;
+    Scratch &s = h->bins_scratch;
+    if ((rc = reserve(h, who, s, fdk::bins_scratch_bytes(N, K, D, centroids_out != nullptr), (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::bins_pass(La, x, N, D, ld, shift, scale, centroids, K, assign_io, centroids_out, rec_dev, s.p);
+    });
+}
+
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)
 {
     if (!h || !name) return FD_ERR_INVALID;

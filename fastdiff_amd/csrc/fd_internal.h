@@ -17,6 +17,7 @@
 #include "fd_spectral.h"
 #include "fd_gl.h"
 #include "fd_nnls.h"
+#include "fd_bins.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -389,6 +390,7 @@ struct fd_context {
         const float *tab = nullptr, *pinv_dev = nullptr;
         double L = 0.0;
     } nnls_bank[MEL_VARIANTS];
+    Scratch bins_scratch;                    // fd_bins_pass: per chunk the counts, inertia, moved, nonfinite and sums (csrc/fd_bins.h: layout)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -533,6 +535,10 @@ size_t nnls_scratch_bytes(int B, int T);
 long long *nnls_lens_slot(void *scratch);
 hipError_t mel_to_linear_nnls(const Launch &L_, const float *mel, int B, int T, const long long *lens_dev, const float *pinv_dev,
                               const float *tab_dev, float step, int variant, int n_iters, float *amp, fd_nnls *rec, void *scratch);
+// fd_bins_pass (fd_kernels_bins.hip).  Every pointer on the device; scratch: bins_scratch_bytes(N, K, D, cent_out != null) bytes.
+size_t bins_scratch_bytes(long long N, int K, int D, bool update);
+hipError_t bins_pass(const Launch &L_, const float *x, long long N, int D, long long ld, const float *shift, const float *scale, const float *cent,
+                     int K, int *assign_io, float *cent_out, fd_bins *rec, void *scratch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

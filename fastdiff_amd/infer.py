@@ -18,7 +18,8 @@ synthesize_long (--long_form: windowed, any length, the utterances sharing windo
 the baseline vocoder on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]`).
+[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]
+[--ndb_bins bins.npz]`).
 """
 import argparse
 import glob
@@ -647,7 +648,13 @@ def main(argv=None):
     ap.add_argument("--nnls_iters", type=int, default=128, help="with --gl_inversion nnls: accelerated projected-gradient steps per frame")
     ap.add_argument("--long_form", action="store_true",
                     help="vocode window by window, the utterances sharing window batches (FastDiff.sample_long_batch): any length, the same PCM")
+    ap.add_argument("--ndb_bins", default=None, metavar="bins.npz",
+                    help="the k-means bins of `python -m fastdiff_amd.diversity fit`: the run's output waveforms go through the mel front-end on "
+                         "the device, their frames are counted in the bins, and the run's NDB and JSD against the corpus (Richardson & Weiss "
+                         "2018) are printed and written to <out_dir>/diversity.tsv -- one row for the run, not one per utterance")
     args = ap.parse_args(argv)
+    if args.ndb_bins and args.out_sample_rate not in (None, 22050):
+        ap.error("--ndb_bins takes the mel of the output waveforms at 22050 Hz: it is not available with --out_sample_rate")
     scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch, spectral=args.spectral)
     for sc in scored:
         if not args.from_wav:
@@ -696,6 +703,15 @@ def main(argv=None):
             print("\n".join(lines))
             with open(os.path.join(args.out_dir, f"{sc.name}.tsv" if world == 1 else f"{sc.name}.rank{rank}.tsv"), "w") as f:
                 f.write("\n".join(lines) + "\n")
+    if args.ndb_bins:      # a score of the whole run against the corpus the bins were fitted on (not a row of _scores.SCORES, which are per utterance)
+        from . import diversity
+        d = diversity.score_waveforms(model, diversity.Bins.load(args.ndb_bins), [pcm[it["item_name"]] for it in mine if it["item_name"] in pcm],
+                                      variant=args.mel_variant)
+        lines = ["\t".join(["n", "ndb", "ndb_over_k", "jsd"]), "\t".join([str(d["n"]), str(d["ndb"]), format(d["ndb_over_k"], ".4f"), format(d["jsd"], ".6f")])]
+        print("\n".join(lines))
+        os.makedirs(args.out_dir, exist_ok=True)
+        with open(os.path.join(args.out_dir, "diversity.tsv" if world == 1 else f"diversity.rank{rank}.tsv"), "w") as f:
+            f.write("\n".join(lines) + "\n")
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 

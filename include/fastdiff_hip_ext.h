@@ -515,6 +515,63 @@ FD_API int fd_nnls_step_bound(const float *bank_80x513, double *L_out);
 FD_API int fd_mel_to_linear_nnls(fd_handle h, const float *mel, int B, int T, const int64_t *lens, const float *bank_80x513,
                                  const float *pinv_513x80, int variant, int n_iters, float *amp_out, fd_nnls *rec_dev, void *stream);
 
+/* K-means bins over feature rows (no counterpart in the reference): one pass of Lloyd's algorithm, the device half of the NDB / JSD
+ * diversity scores of Richardson & Weiss 2018 (fastdiff_amd/diversity.py fits the bins on the training corpus' mel frames and counts a
+ * sampler's frames in them).  Sample i is the D floats at x + i * ld (ld = D: a packed matrix; ld > D: the leading D of wider rows, whose
+ * rest is never read); x may have any 4-byte alignment and the result does not depend on it.
+ *
+ * Standardisation, as the row is loaded (x is never written):  z_d = fl(fl(x_d - shift_d) * scale_d), two float32 roundings, no fused
+ * multiply-add; shift = scale = NULL: z = x.
+ * Assignment, all in float32:
+ *     h_k   = fl(0.5 * a_D),  a_0 = 0,  a_{d+1} = fma(c_kd, c_kd, a_d)                 (once per pass)
+ *     dot_k = b_D,            b_0 = 0,  b_{d+1} = fma(c_kd, z_d, b_d)                  (ascending d; on v_mfma_f32_32x32x2_f32, exact fp32)
+ *     s_k   = fl(h_k - dot_k);   assign = the lowest k with s_k = min_j s_j             (|| z ||^2 is common to every k)
+ * so an assigned bin is the nearest in Euclidean distance up to the rounding of s: with d64 the float64 squared distance over the
+ * float32 z, d64(assigned) - min_k d64(k) <= 2 g (E_assigned + E_best), E_k = || c_k ||^2 / 2 + sum_d |z_d| |c_kd|, g = n u / (1 - n u),
+ * n = D + 2, u = 2^-24.  A row with a z_d that is not finite (a NaN or infinite x_d, or an overflow of the two operations) is assigned
+ * -1, counted in `nonfinite` and enters no sum or count; the other rows' results are those of a call without it.
+ * The record:  counts[k] = rows assigned to k (0 for k >= K);  inertia = sum over the assigned rows of sum_d (z_d - c_kd)^2 in float64 for
+ * the row's bin -- per row the two halves of d as fma chains in ascending d, rows added per position in the 128-row block over the
+ * blocks of a chunk, the 256 positions in order, then the chunks in ascending order;  moved = rows whose assignment differs from
+ * assign_io on entry (-1 when assign_io is NULL; the first pass of a fit starts from an array of -1);  nonfinite;  empty = bins k < K
+ * with counts[k] = 0;  status.
+ * Update (centroids_out not NULL):  centroids_out[k][d] = (float)(S_kd / counts[k]), S_kd = the sums over chunks of FD_BINS_CHUNK
+ * consecutive rows added in ascending chunk order in float64; inside a chunk the sum is float32, s <- fl(s + z_d) over the bin's rows in
+ * ascending row order (the product one-hot(assign)^T Z on the same matrix instruction).  A bin with counts[k] = 0 keeps centroids[k]
+ * bit for bit.  centroids_out may not overlap centroids.
+ *
+ * On the device.  One workgroup of 256 threads per chunk keeps the centroids ([K][D], at most 64 KB) in LDS and reads its rows once, 128
+ * at a time into LDS; each wave multiplies its 32 rows with every centroid, and the K x D tiles of the update are dealt to the four waves
+ * and stay in registers for the whole chunk.  Only assign_io, and per chunk the sums [K][D], counts, inertia and two integers reach
+ * memory (the handle's scratch grower; a growth cannot happen inside a stream capture: FD_ERR_STATE, call it once before).  k_bins_update
+ * (one workgroup per bin) and k_bins_record add the chunks.  Every sum has a fixed order that does not depend on the grid; the only
+ * atomics are integer adds in LDS: two calls give the same bits.  Nothing at or behind x + (N - 1) ld + D is read.  Asynchronous on
+ * `stream`; does not settle a pending lazily checked fd_sample.
+ *
+ * x, shift [D], scale [D], centroids [K][D], assign_io [N] int32, centroids_out [K][D], rec_dev: DEVICE.  shift and scale: both or
+ * neither; assign_io, centroids_out, rec_dev: each may be NULL, not all three.  The arguments are checked before the handle is looked at.
+ * FD_ERR_INVALID: a null x, centroids or handle, N outside 1 .. 2^40, D not a multiple of 4 in 4 .. 128, K outside 1 .. 128, ld < D or
+ * ld > 2^21, x not 4-byte aligned, one of shift / scale alone, no output, centroids_out overlapping centroids. */
+#define FD_BINS_CHUNK 4096          /* consecutive rows whose sums are formed in float32; one workgroup */
+#define FD_BINS_MAX_K 128
+#define FD_BINS_MAX_D 128
+enum { FD_BINS_OK = 0, FD_BINS_NONFINITE = 1, FD_BINS_EMPTY = 2 };      /* rows were left out as not finite; no row was assigned */
+typedef struct fd_bins {
+    int64_t counts[FD_BINS_MAX_K];
+    double inertia;
+    int64_t moved;
+    int64_t nonfinite;
+    int32_t empty;
+    int32_t status;                        /* FD_BINS_* */
+} fd_bins;                                 /* 1056 bytes */
+
+/* FD_BINS_CHUNK (pure host code). */
+FD_API int fd_bins_chunk(void);
+/* sizeof(fd_bins) = 1056 (pure host code). */
+FD_API int fd_bins_record_bytes(void);
+FD_API int fd_bins_pass(fd_handle h, const float *x, int64_t N, int D, int64_t ld, const float *shift, const float *scale,
+                        const float *centroids, int K, int32_t *assign_io, float *centroids_out, fd_bins *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
