@@ -28,6 +28,9 @@ cents, gross pitch error, voicing decision error), Validator(pitch=True) and inf
 fastdiff_amd.spectral / FastDiff.spectral measure the multi-resolution STFT distances (spectral convergence, log-magnitude distance,
 log-spectral distance) of the vocoded spectrum against the recording's, Validator(spectral=True) and infer.synthesize(spectral=True) /
 --spectral likewise (fastdiff_amd/spectral.py);
+fastdiff_amd.mcd / FastDiff.mcd measure the mel-cepstral distortion of a vocoded waveform against its recording, along a time-warped path
+(dynamic time warping on the device: mcd.dtw) and frame by frame, Validator(mcd=True) and infer.synthesize(mcd=True) / --mcd likewise
+(fastdiff_amd/mcd.py);
 fastdiff_amd.griffin_lim / FastDiff.griffin_lim / mel_to_linear / griffin_lim_mel are the baseline vocoder (the reference's GLLinear /
 GLMel) with its inverse STFT on the device and both mel inversions (the pseudo-inverse, which is the default, and GLMel's non-negative
 least squares: mel_to_linear(inversion="nnls"), griffin_lim.mel_to_linear_nnls), and infer.synthesize_griffin_lim / --vocoder griffin_lim put its rows next to the model's
@@ -36,7 +39,7 @@ fastdiff_amd.diversity fits k-means bins over the corpus' mel frames on the devi
 them with NDB and JSD, the paper's two diversity columns; infer --ndb_bins writes the row (fastdiff_amd/diversity.py).
 """
 from .model import FastDiff  # noqa: F401
-from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, griffin_lim, diversity  # noqa: F401
+from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, mcd, griffin_lim, diversity  # noqa: F401
 from . import sampler as util  # noqa: F401  (the reference module is called util)
 from .lvc_op import location_variable_convolution, gated_residual, kernel_conv1d, conv32  # noqa: F401
 from .trainstep import TrainStep  # noqa: F401
@@ -49,5 +52,5 @@ from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "griffin_lim", "diversity", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "mcd", "griffin_lim", "diversity", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

@@ -1,7 +1,7 @@
 """The scores of a vocoded waveform against its recording, as infer.py and validate.py offer them: one entry per keyword argument."""
 from collections import namedtuple
 
-from . import pitch, spectral, stoi
+from . import mcd, pitch, spectral, stoi
 
 # name: the keyword argument, the FastDiff method, the command-line flag and the TSV file; module: its OK / STATUS / RECORD / _enqueue /
 # _record; columns: (record key, report and result key, the statuses with which the value counts as measured, TSV format);
@@ -25,11 +25,13 @@ SCORES = (
     Score("spectral", spectral, (("mr_sc", "mr_sc", (spectral.OK,), ".6f"), ("mr_logmag", "mr_logmag", (spectral.OK,), ".6f"),
                                  ("lsd_db", "lsd_db", (spectral.OK,), ".4f")), "spectral_status",
           lambda rate, hop: {}, lambda rate, hop: spectral._config(None)),      # the resolutions are in samples, whatever the rate
+    Score("mcd", mcd, (("mcd_dtw", "mcd_dtw", (mcd.OK,), ".4f"), ("mcd_linear", "mcd_linear", (mcd.OK,), ".4f")), "mcd_status",
+          lambda rate, hop: {}, lambda rate, hop: mcd._config(None)),           # 13 coefficients of the pwg front-end's frames
 )
 
 
 def enabled(**flags):
-    """The entries whose keyword argument is true, in the table's order: enabled(stoi=stoi, pitch=pitch, spectral=spectral)."""
+    """The entries whose keyword argument is true, in the table's order: enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)."""
     return [s for s in SCORES if flags.get(s.name)]
 
 

@@ -1,6 +1,6 @@
 // fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
 // sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
-// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*) and the multi-resolution STFT distances (fd_spectral_*).  The baseline vocoder next to it: Griffin-Lim and the mel inversions (fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls).  Then taps, layout
+// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*), the multi-resolution STFT distances (fd_spectral_*) and the mel-cepstral distortion with its alignment (fd_cepstra, fd_dtw, fd_mcd_measure).  The baseline vocoder next to it: Griffin-Lim and the mel inversions (fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls).  Then taps, layout
 // introspection, counters and per-kernel profiling.  
 #include <math.h>
 #include <stddef.h>
@@ -660,6 +660,125 @@ int fd_bins_pass(fd_handle h, const float *x, int64_t N, int D, int64_t ld, cons
     if ((rc = reserve(h, who, s, fdk::bins_scratch_bytes(N, K, D, centroids_out != nullptr), (hipStream_t)stream)) != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) {
         return fdk::bins_pass(La, x, N, D, ld, shift, scale, centroids, K, assign_io, centroids_out, rec_dev, s.p);
+    });
+}
+
+// Mel-cepstral distortion with time alignment (fastdiff_hip_ext.h; constants, refusals, the DCT table and the sweep's index ranges:
+// fd_mcd.h, the kernels: fd_kernels_mcd.hip) -----------------------------------------------------------------------------------------
+int fd_mcd_default_config(fd_mcd_config *cfg)
+{
+    if (!cfg) return FD_ERR_INVALID;
+    fdm::defaults(cfg);
+    return FD_OK;
+}
+
+int64_t fd_mcd_frames(int64_t n)
+{
+    if (n < 0) return FD_ERR_INVALID;
+    return fdm::frames(n);
+}
+
+// the front-end's tables and the DCT table, made at the first call (never inside a capture)
+static int mcd_tables(fd_handle h, const char *who, hipStream_t stream)
+{
+    if ((!h->mel[MEL_VARIANTS - 1].tab || !h->mcd_dct) && capturing(stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: the front-end's tables and the DCT table are uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
+    int rc = ensure_mel_tables(h);
+    if (rc != FD_OK) return rc;
+    if (!h->mcd_dct) {
+        std::vector<float> tab((size_t)fdm::MAX_COEF * fdm::MELS);
+        fdm::dct_table(tab.data());
+        if ((rc = upload_table(h, who, tab.data(), sizeof(float) * tab.size(), reinterpret_cast<const void **>(&h->mcd_dct))) != FD_OK) return rc;
+    }
+    return FD_OK;
+}
+
+int fd_cepstra(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int n_coef, float *cep_out, int64_t T_pitch, void *stream)
+{
+    const char *who = "fd_cepstra";
+    if (!wav || !cep_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !wav ? "wav" : "cep_out");
+    char why[fdm::MSG];
+    if (fdm::coef_refusal(n_coef, why) || fdm::wave_refusal(B, L, "L", why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    if (T_pitch < fdm::frames(L) || T_pitch > fdm::MAX_FRAMES)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: T_pitch = %lld outside the %lld frames of L = %lld .. %lld", who, (long long)T_pitch, (long long)fdm::frames(L), (long long)L,
+                (long long)fdm::MAX_FRAMES);
+    int rc = check_counts(h, who, "valid", valid, B, 1, L);
+    if (rc != FD_OK) return rc;
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    if ((rc = enter(h)) != FD_OK || (rc = mcd_tables(h, who, (hipStream_t)stream)) != FD_OK) return rc;
+    Scratch &s = h->mcd_scratch;
+    if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(1, 0, 0, 0, 0), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *lens_dev = fdk::mcd_count_slot(s.p, 0);
+    if ((rc = upload_counts(h, valid, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::cepstra(La, wav, B, L, valid ? lens_dev : nullptr, n_coef, h->mcd_dct, cep_out, T_pitch); });
+}
+
+int fd_dtw(fd_handle h, const float *a, const float *b, int B, int D, int64_t ld, int64_t pitch_a, int64_t pitch_b, const int64_t *frames_a,
+           const int64_t *frames_b, fd_dtw_rec *rec_dev, int32_t *align_out, int64_t align_pitch, void *stream)
+{
+    const char *who = "fd_dtw";
+    if (!a || !b || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !a ? "a" : (!b ? "b" : "rec_dev"));
+    char why[fdm::MSG];
+    if (fdm::dtw_refusal(B, D, ld, pitch_a, pitch_b, align_out != nullptr, align_pitch, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) FD_FAIL(h, FD_ERR_INVALID, "%s: a and b must be 4-byte aligned", who);
+    int rc = check_counts(h, who, "frames_a", frames_a, B, 1, pitch_a);
+    if (rc != FD_OK || (rc = check_counts(h, who, "frames_b", frames_b, B, 1, pitch_b)) != FD_OK) return rc;
+    int64_t code_stride = 0;
+    if (align_out)
+        for (int i = 0; i < B; ++i) {
+            const int64_t Ta = frames_a ? frames_a[i] : pitch_a, Tb = frames_b ? frames_b[i] : pitch_b;
+            if (fdm::align_refusal(i, Ta, Tb, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+            code_stride = std::max(code_stride, fdm::code_bytes(Ta, Tb));
+        }
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    FD_HIP(h, hipSetDevice(h->device));      // no settle: the features are the caller's, and the alignment touches no sampler state
+    Scratch &s = h->mcd_scratch;
+    if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(B, pitch_b, code_stride, 0, 0), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *fa_dev = fdk::mcd_count_slot(s.p, 2), *fb_dev = fdk::mcd_count_slot(s.p, 3);
+    if ((rc = upload_counts(h, frames_a, B, fa_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = upload_counts(h, frames_b, B, fb_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::dtw(La, a, b, B, D, ld, pitch_a, pitch_b, frames_a ? fa_dev : nullptr, frames_b ? fb_dev : nullptr, rec_dev, align_out, align_pitch,
+                        code_stride, s.p);
+    });
+}
+
+int fd_mcd_measure(fd_handle h, const float *clean, int64_t Lc, const float *degraded, int64_t Ld, int B, const int64_t *valid_clean,
+                   const int64_t *valid_degraded, const fd_mcd_config *cfg, fd_mcd *rec_dev, void *stream)
+{
+    const char *who = "fd_mcd_measure";
+    if (!clean || !degraded || !rec_dev) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !clean ? "clean" : (!degraded ? "degraded" : "rec_dev"));
+    fd_mcd_config c;
+    if (cfg) c = *cfg; else fdm::defaults(&c);
+    char why[fdm::MSG];
+    if (fdm::refusal(c, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: configuration refused: %s", who, why);
+    if (fdm::wave_refusal(B, Lc, "Lc", why) || fdm::wave_refusal(B, Ld, "Ld", why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    int rc = check_counts(h, who, "valid_clean", valid_clean, B, 1, Lc);
+    if (rc != FD_OK || (rc = check_counts(h, who, "valid_degraded", valid_degraded, B, 1, Ld)) != FD_OK) return rc;
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    if ((rc = enter(h)) != FD_OK || (rc = mcd_tables(h, who, (hipStream_t)stream)) != FD_OK) return rc;
+    const int D = c.n_coef;
+    const int64_t Tc = fdm::frames(Lc), Td = fdm::frames(Ld), fl_a = (int64_t)B * Tc * D, fl_b = (int64_t)B * Td * D;
+    Scratch &s = h->mcd_scratch;
+    if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(B, Td, 0, fl_a, fl_b), (hipStream_t)stream)) != FD_OK) return rc;
+    long long *slot[4];
+    for (int q = 0; q < 4; ++q) slot[q] = fdk::mcd_count_slot(s.p, q);
+    std::vector<int64_t> fa, fb;      // each pair's own frames
+    if (valid_clean) { fa.resize(B); for (int b = 0; b < B; ++b) fa[b] = fdm::frames(valid_clean[b]); }
+    if (valid_degraded) { fb.resize(B); for (int b = 0; b < B; ++b) fb[b] = fdm::frames(valid_degraded[b]); }
+    if ((rc = upload_counts(h, valid_clean, B, slot[0], (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = upload_counts(h, valid_degraded, B, slot[1], (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = upload_counts(h, valid_clean ? fa.data() : nullptr, B, slot[2], (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = upload_counts(h, valid_degraded ? fb.data() : nullptr, B, slot[3], (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *na = valid_clean ? slot[0] : nullptr, *nb = valid_degraded ? slot[1] : nullptr;
+    const long long *fa_dev = valid_clean ? slot[2] : nullptr, *fb_dev = valid_degraded ? slot[3] : nullptr;
+    float *ca = fdk::mcd_cep_slot(s.p, B, Td, 0, fl_a, fl_b, 0), *cb = fdk::mcd_cep_slot(s.p, B, Td, 0, fl_a, fl_b, 1);
+    fd_dtw_rec *wrec = fdk::mcd_rec_slot(s.p, B, Td, 0);
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        hipError_t e = fdk::cepstra(La, clean, B, Lc, na, D, h->mcd_dct, ca, Tc);
+        if (e != hipSuccess || (e = fdk::cepstra(La, degraded, B, Ld, nb, D, h->mcd_dct, cb, Td)) != hipSuccess) return e;
+        if ((e = fdk::dtw(La, ca, cb, B, D, D, Tc, Td, fa_dev, fb_dev, wrec, nullptr, 0, 0, s.p)) != hipSuccess) return e;
+        return fdk::mcd_finish(La, ca, cb, B, D, Tc, Td, fa_dev, fb_dev, na, Lc, nb, Ld, wrec, rec_dev);
     });
 }
 

@@ -18,6 +18,7 @@
 #include "fd_gl.h"
 #include "fd_nnls.h"
 #include "fd_bins.h"
+#include "fd_mcd.h"
 
 // ---------------------------------------------------------------------------------------------
 // Fixed architecture of this build (modules/FastDiff/config/base.yaml:21-33).  fd_create rejects
@@ -391,6 +392,8 @@ struct fd_context {
         double L = 0.0;
     } nnls_bank[MEL_VARIANTS];
     Scratch bins_scratch;                    // fd_bins_pass: per chunk the counts, inertia, moved, nonfinite and sums (csrc/fd_bins.h: layout)
+    Scratch mcd_scratch;                     // fd_cepstra / fd_dtw / fd_mcd_measure: counts, bottom rows, direction codes, records, cepstra (fd_kernels_mcd.hip: layout)
+    const float *mcd_dct = nullptr;          // their DCT table [40][80] (csrc/fd_mcd.h: dct_table), uploaded at the first call (in `tables`)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -539,6 +542,20 @@ hipError_t mel_to_linear_nnls(const Launch &L_, const float *mel, int B, int T, 
 size_t bins_scratch_bytes(long long N, int K, int D, bool update);
 hipError_t bins_pass(const Launch &L_, const float *x, long long N, int D, long long ld, const float *shift, const float *scale, const float *cent,
                      int K, int *assign_io, float *cent_out, fd_bins *rec, void *scratch);
+// fd_cepstra / fd_dtw / fd_mcd_measure (fd_kernels_mcd.hip).  The handle's one buffer for the three: mcd_scratch_bytes(B, bot_pitch = the
+// pitch of b's rows, code_stride = bytes of direction codes per pair or 0, the floats of the two cepstra or 0); the count slots 0 .. 3 lie
+// in front whatever the rest.  Counts: null (every row whole) or a slot filled by the caller; dct: device copy of fdm::dct_table.
+size_t mcd_scratch_bytes(int B, long long bot_pitch, long long code_stride, long long cep_floats_a, long long cep_floats_b);
+long long *mcd_count_slot(void *scratch, int which);
+float *mcd_cep_slot(void *scratch, int B, long long bot_pitch, long long code_stride, long long cep_floats_a, long long cep_floats_b, int which);
+fd_dtw_rec *mcd_rec_slot(void *scratch, int B, long long bot_pitch, long long code_stride);
+hipError_t cepstra(const Launch &L_, const float *wav, int B, long long L, const long long *lens_dev, int n_coef, const float *dct, float *cep,
+                   long long T_pitch);
+hipError_t dtw(const Launch &L_, const float *a, const float *b, int B, int D, long long ld, long long pitch_a, long long pitch_b,
+               const long long *fa_dev, const long long *fb_dev, fd_dtw_rec *rec, int *align, long long align_pitch, long long code_stride, void *scratch);
+hipError_t mcd_finish(const Launch &L_, const float *ca, const float *cb, int B, int D, long long pitch_a, long long pitch_b, const long long *fa_dev,
+                      const long long *fb_dev, const long long *na_dev, long long Lc, const long long *nb_dev, long long Ld, const fd_dtw_rec *dtw_rec,
+                      fd_mcd *rec);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

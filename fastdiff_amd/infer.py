@@ -18,7 +18,7 @@ synthesize_long (--long_form: windowed, any length, the utterances sharing windo
 the baseline vocoder on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]
+[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--mcd] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]
 [--ndb_bins bins.npz]`).
 """
 import argparse
@@ -271,7 +271,7 @@ def _scorer(model, items, scored, report, sample_rate, who):
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
                noise_schedule=None, diffusion_hyperparams=None, return_device: bool = False, sort: bool = True, out_sample_rate: int = None,
                sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
-               spectral: bool = False) -> Dict[str, np.ndarray]:
+               spectral: bool = False, mcd: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM of its own length (hop 256 x frames), through length-sorted padded micro-batches.
     Noise: utterance `it` draws x_T and z from Philox stream (seed, it["uid"]) over its own samples (fd_set_noise_streams); "uid"
     defaults to the item's position in `items`, callers that shard a job put the utterance's index in the WHOLE job there, so a
@@ -295,8 +295,11 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     With stoi=True as well, report[name] holds both sets of keys.
     spectral=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"mr_sc", "mr_logmag", "lsd_db",
     "spectral_status"} (FastDiff.spectral at the default resolutions: the means over them of the spectral convergence, the log-magnitude
-    distance in nepers and the log-spectral distance in dB; status by name), measured on the same waveforms, next to the other sets."""
-    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
+    distance in nepers and the log-spectral distance in dB; status by name), measured on the same waveforms, next to the other sets.
+    mcd=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"mcd_dtw", "mcd_linear", "mcd_status"}
+    (FastDiff.mcd with 13 coefficients of the pwg front-end: the mel-cepstral distortion in dB along the time-warped path and frame by
+    frame; status by name), measured on the same waveforms, next to the other sets."""
+    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
     if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
         raise ValueError(f"synthesize: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
     report: Dict[str, dict] = {}
@@ -400,6 +403,7 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
 def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_batch: int = 8, seed: int = 0, variant: str = "pwg",
                            sort: bool = True, out_sample_rate: int = None, sample_rate: int = 22050, loudness: float = None,
                            stoi: bool = False, pitch: bool = False, spectral: bool = False, inversion: str = "pinv",
+                           mcd: bool = False,
                            nnls_iters: int = 128) -> Dict[str, np.ndarray]:
     """The baseline next to synthesize(): item_name -> int16 PCM from Griffin-Lim on the device (FastDiff.griffin_lim_mel: the mel
     inverted with the front-end's filter bank -- inversion="pinv", the default: its pseudo-inverse; inversion="nnls": the non-negative
@@ -409,12 +413,12 @@ def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_
     the two waveforms and their scores line up.  An item of fewer than 2 frames is left out, as synthesize() leaves out what it cannot
     collate.  The starting phase of item `it` is drawn from Philox stream (seed, it["uid"], frame, bin); "uid" defaults to the item's
     position in `items`, so a waveform does not depend on its micro-batch.  variant: the front-end the mels come from ("pwg": log10,
-    "tacotron": ln).  out_sample_rate, loudness, stoi, pitch, spectral: as in synthesize() -- the same level epilogue, the same scores
+    "tacotron": ln).  out_sample_rate, loudness, stoi, pitch, spectral, mcd: as in synthesize() -- the same level epilogue, the same scores
     into the same report keys, measured on the float waveform before the epilogue."""
     if inversion not in ("pinv", "nnls"):
         raise ValueError(f"synthesize_griffin_lim: inversion must be 'pinv' or 'nnls', got {inversion!r}")
     how = {} if inversion == "pinv" else dict(inversion=inversion, nnls_iters=int(nnls_iters))      # (the default passes no new keyword)
-    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral)
+    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
     if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
         raise ValueError(f"synthesize_griffin_lim: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
     report: Dict[str, dict] = {}
@@ -445,7 +449,7 @@ def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
                        sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
-                       spectral: bool = False) -> Dict[str, np.ndarray]:
+                       spectral: bool = False, mcd: bool = False) -> Dict[str, np.ndarray]:
     """BASELINE config 4 as north_star words it: rank `src` holds all utterances (items; None elsewhere) -> length-balanced
     partition (shard.partition_utterances) -> scatter of the mels -> every rank vocodes its share in padded micro-batches on its
     own GPU -> gather of the int16 PCM on `src`, which returns item_name -> PCM (the other ranks return {}).  The process group
@@ -463,9 +467,9 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     balance = "time" (default): the partition weighs an utterance as frames + a per-utterance constant (shard.utterance_cost);
     "frames": by frames alone (rounds 1-5).
     out_sample_rate, loudness: as in synthesize() -- every rank resamples and normalises its own share, the gathered PCM is at that rate.
-    stoi=True, pitch=True and spectral=True are refused: the recordings are not scattered (score with synthesize(stoi=True, pitch=True,
-    spectral=True))."""
-    _scores.refuse("synthesize_sharded", " (the recordings are not scattered): use synthesize({name}=True)", stoi=stoi, pitch=pitch, spectral=spectral)
+    stoi=True, pitch=True, spectral=True and mcd=True are refused: the recordings are not scattered (score with synthesize(stoi=True,
+    pitch=True, spectral=True, mcd=True))."""
+    _scores.refuse("synthesize_sharded", " (the recordings are not scattered): use synthesize({name}=True)", stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
     if gather not in ("src", "none"):
         raise ValueError(f"synthesize_sharded: gather must be 'src' or 'none', got {gather!r}")
     if balance not in ("time", "frames"):
@@ -556,15 +560,16 @@ LONG_FORM_GROUP_FRAMES = 1 << 16      # mel frames per sample_long_batch call: 6
 
 def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 0, drop_last_frame: bool = True, noise_schedule=None,
                     diffusion_hyperparams=None, window_frames=None, group_frames: int = LONG_FORM_GROUP_FRAMES, loudness: float = None,
-                    sample_rate: int = 22050, stoi: bool = False, pitch: bool = False, spectral: bool = False) -> Dict[str, np.ndarray]:
+                    sample_rate: int = 22050, stoi: bool = False, pitch: bool = False, spectral: bool = False,
+                    mcd: bool = False) -> Dict[str, np.ndarray]:
     """item_name -> int16 PCM through FastDiff.sample_long_batch (windowed: any length, device memory of one window batch): the
     utterances are taken in order in groups of up to group_frames mel frames, so their outputs fit, and the windows of a group share the
     sampler's batches.  Utterance `it` draws its noise from Philox stream (seed, it["uid"]) as in synthesize(), so the PCM is the same,
     byte for byte; peak normalisation runs on each whole utterance afterwards (FastDiff.py:110) -- or, with loudness = LUFS, the
     loudness epilogue as in synthesize(): the filter runs over the whole utterance in tiles, however long it is.
-    stoi=True, pitch=True and spectral=True are refused (score the result with FastDiff.stoi, FastDiff.pitch and FastDiff.spectral, which
+    stoi=True, pitch=True, spectral=True and mcd=True are refused (score the result with FastDiff.stoi, FastDiff.pitch, FastDiff.spectral and FastDiff.mcd, which
     take any length)."""
-    _scores.refuse("synthesize_long", ": score the waveforms with FastDiff.{name}", stoi=stoi, pitch=pitch, spectral=spectral)
+    _scores.refuse("synthesize_long", ": score the waveforms with FastDiff.{name}", stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
     hop = model.hop_length
     out: Dict[str, np.ndarray] = {}
@@ -637,10 +642,14 @@ def main(argv=None):
                     help="with --from_wav (copy synthesis): measure the multi-resolution STFT distances of every vocoded waveform against its "
                          "recording on the device (spectral convergence, log-magnitude distance, log-spectral distance in dB; the means over "
                          "512 / 1024 / 2048-point transforms), print the table and write <out_dir>/spectral.tsv")
+    ap.add_argument("--mcd", action="store_true",
+                    help="with --from_wav (copy synthesis): measure the mel-cepstral distortion of every vocoded waveform against its recording "
+                         "on the device (13 mel-filter-bank cepstral coefficients; in dB along the time-warped path and frame by frame), print "
+                         "the table and write <out_dir>/mcd.tsv")
     ap.add_argument("--vocoder", default="fastdiff", choices=("fastdiff", "griffin_lim"),
                     help="griffin_lim: the baseline instead of the model -- every mel inverted with the filter bank (--gl_inversion) and "
                          "run through --gl_iters Griffin-Lim iterations on the device; the same <name>_pred.wav files and, with --stoi / "
-                         "--pitch / --spectral, the same TSVs, so a baseline row is one command next to the model's")
+                         "--pitch / --spectral / --mcd, the same TSVs, so a baseline row is one command next to the model's")
     ap.add_argument("--gl_iters", type=int, default=60, help="with --vocoder griffin_lim: iterations (griffin_lim_iters of base.yaml: 60)")
     ap.add_argument("--gl_inversion", default="pinv", choices=("pinv", "nnls"),
                     help="with --vocoder griffin_lim: how the mel is inverted -- pinv: the pseudo-inverse of the filter bank, floored (the "
@@ -655,7 +664,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.ndb_bins and args.out_sample_rate not in (None, 22050):
         ap.error("--ndb_bins takes the mel of the output waveforms at 22050 Hz: it is not available with --out_sample_rate")
-    scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch, spectral=args.spectral)
+    scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, mcd=args.mcd)
     for sc in scored:
         if not args.from_wav:
             ap.error(f"--{sc.name} scores the vocoded waveform against its recording: it needs --from_wav")
@@ -682,17 +691,18 @@ def main(argv=None):
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
     items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored)) if args.from_wav else load_mel_inputs(args.test_input_dir)
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
+    more = dict(mcd=True) if args.mcd else {}              # (the default passes no new keyword)
     if args.vocoder == "griffin_lim":
         how = {} if (args.gl_inversion, args.nnls_iters) == ("pinv", 128) else dict(inversion=args.gl_inversion, nnls_iters=args.nnls_iters)
         pcm = synthesize_griffin_lim(model, mine, args.gl_iters, args.max_batch, args.seed, variant=args.mel_variant, out_sample_rate=args.out_sample_rate,
-                                     loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, **how)
+                                     loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, **how, **more)
     elif args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")
         pcm = synthesize_long(model, mine, args.N, args.seed, loudness=args.loudness)
     else:
         pcm = synthesize(model, mine, args.N, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate, loudness=args.loudness, stoi=args.stoi, pitch=args.pitch,
-                         spectral=args.spectral)
+                         spectral=args.spectral, **more)
     if scored:
         pcm, report = pcm
         os.makedirs(args.out_dir, exist_ok=True)

@@ -390,6 +390,15 @@ class FastDiff(nn.Module):
         from . import spectral as _spectral
         return _spectral._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg)
 
+    def mcd(self, clean, degraded, valid=None, valid_degraded=None, **cfg):
+        """The mel-cepstral distortion of `degraded` against `clean` on the device, with and without time alignment (fastdiff_amd/mcd.py):
+        two tensors [n] / [B, n] / [B, 1, n] whose lengths may differ -> a dict of numpy arrays over the batch: mcd_dtw, mcd_linear (dB,
+        NaN unless OK), cost, path_len, n_diag, frames_clean, frames_degraded, status (mcd.OK / SHORT / NONFINITE).  valid,
+        valid_degraded: [B] sample counts of the padded batches (valid_degraded=None: valid counts for both); cfg: n_coef, variant.
+        Synchronises once, for the records."""
+        from . import mcd as _mcd
+        return _mcd._measure(*self._wave_call(clean, degraded), clean, degraded, valid, cfg, valid_degraded=valid_degraded)
+
     def mel_to_linear(self, mel, variant="pwg", inversion="pinv", nnls_iters=128, lens=None, return_record=False):
         """Mel inversion on the device (fastdiff_amd/griffin_lim.py; utils/audio.py:91-95 _mel_to_linear): mel [B, 80, T] as front-end
         `variant` produces it (log10 for "pwg", ln for "tacotron") -> amplitudes [B, 513, T], with the bank this module's front-end

@@ -27,6 +27,8 @@ With pitch=True on top of it, both are tracked with YIN on the mel frame grid an
 (FastDiff.pitch's kernels, fastdiff_amd/pitch.py: F0 RMSE in cents, gross pitch error, voicing decision error), likewise.
 With spectral=True on top of it, the vocoded window's spectrum is scored against the ground truth's with the multi-resolution STFT
 distances at the default resolutions (FastDiff.spectral's kernels, fastdiff_amd/spectral.py), likewise.
+With mcd=True on top of it, the vocoded window is scored against the ground truth's with the mel-cepstral distortion, along the
+time-warped path and frame by frame (FastDiff.mcd's kernels, fastdiff_amd/mcd.py), likewise.
 
 The default seed differs from TrainStep's (0), so that batch j of a pass does not repeat the noise of training step j.  The operators
 share the per-device step scratch with TrainStep (lvc_op._handle): a pass asks for far less of it than an optimizer step over the
@@ -43,7 +45,7 @@ DEFAULT_SEED = 0x56414C      # "VAL"
 
 class Validator:
     def __init__(self, model, diffusion_hyperparams, *, corpus, batch_size, seed=DEFAULT_SEED, bins=10, sample_schedule=None, weights=None, stoi=False, sample_rate=22050,
-                 pitch=False, spectral=False):
+                 pitch=False, spectral=False, mcd=False):
         if int(batch_size) < 1:
             raise ValueError(f"Validator: batch_size={batch_size} (at least 1)")
         if not 1 <= int(bins) <= lvc_op.EVAL_MAX_BINS:
@@ -85,7 +87,7 @@ class Validator:
         self.item_mel_l1 = torch.zeros(corpus.n_items, device=dev, dtype=torch.float32) if self.table is not None else None
         self.sample_rate = int(sample_rate)                    # the rate of the corpus' waveforms
         self._scored = []                                      # (score, its configuration, its records: slot b of batch j is row j B + b)
-        for sc in _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral):
+        for sc in _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd):
             if self.table is None:
                 raise ValueError(f"Validator: {sc.name}=True scores the vocoded windows, which needs sample_schedule")
             cfg = sc.config(self.sample_rate, corpus.hop_size)      # refused now, not inside a pass
@@ -148,7 +150,8 @@ class Validator:
         with status OK), "vde" (over the items OK or UNVOICED), "item_f0_rmse_cents", "item_gpe", "item_vde" [n] (NaN where not measured) and
         "pitch_skipped" (the items not OK) with pitch=True, plus "mr_sc", "mr_logmag", "lsd_db" (the means over the items with status OK),
         "item_mr_sc", "item_mr_logmag", "item_lsd_db" [n] (NaN where not OK) and "spectral_skipped" (the items not OK: windows of at most
-        1024 samples) with spectral=True.  loss = the mean over the items (the reference's validation_end averages batch means:
+        1024 samples) with spectral=True, plus "mcd_dtw", "mcd_linear" (the means over the items with status OK), "item_mcd_dtw",
+        "item_mcd_linear" [n] (NaN where not OK) and "mcd_skipped" (the items not OK) with mcd=True.  loss = the mean over the items (the reference's validation_end averages batch means:
         the two differ only through a short last batch); loss_by_t[k] = the mean over the items whose step fell into
         [k T / bins, (k + 1) T / bins), NaN where none did.  Synchronises once."""
         acc = lvc_op.read_eval_state(self._acc, self.bins)

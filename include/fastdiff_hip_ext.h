@@ -572,6 +572,91 @@ FD_API int fd_bins_record_bytes(void);
 FD_API int fd_bins_pass(fd_handle h, const float *x, int64_t N, int D, int64_t ld, const float *shift, const float *scale,
                         const float *centroids, int K, int32_t *assign_io, float *centroids_out, fd_bins *rec_dev, void *stream);
 
+/* Mel-cepstral distortion with time alignment: the MCD column of the vocoder tables, and the one score here that does not compare frame i
+ * with frame i.  Three layers, each an entry point of its own.  The reference has no MCD; its alignment (utils/pitch_distance.py:
+ * time_warp, align_from_distances) is a numba-compiled double loop on the CPU.  THIS TEXT defines the computation; tests/mcd_ref.py
+ * restates it in float64 numpy.
+ *
+ * 1. fd_cepstra: waveform -> mel-cepstral rows.  A row of n samples has T = 1 + n / 256 frames (fd_mcd_frames), those of
+ *    fd_mel_spectrogram: frame t is the log-mel of the front-end that option "mel" selects -- pwg: zero padding, log10(max(1e-6, .));
+ *    tacotron: reflection, ln(max(1e-5, .)), which needs n > 512 -- through the SAME device code as fd_mel_spectrogram, with the handle's
+ *    filter bank (fd_set_mel_filterbank).  Nothing at or behind the row's own n is read.  The 80 values become natural logarithms in
+ *    float32 (pwg: m_j = fl(log10 value * fl(ln 10)); tacotron: as they are) and then, by the orthonormal DCT-II over the 80 bands,
+ *        c_d = sqrt(2 / 80) sum_j m_j cos(pi d (j + 1/2) / 80),   d = 1 .. n_coef
+ *    one fmaf chain per d over ascending j from a table rounded once from double (csrc/fd_mcd.h: dct_table), kept in LDS.  c_0, the
+ *    gain, is dropped.  n_coef 1 .. FD_MCD_MAX_COEF [13].  No mel reaches memory.  cep_out [B][T_pitch][n_coef]: the rows t < T of item b
+ *    hold the cepstra, the rows T <= t < T_pitch zeros.  A tacotron row with n <= 512 holds NaN in its T rows, and so does a frame
+ *    under whose window a sample is NaN or infinite (the front-end's floor alone would take it for silence).
+ *    This is the cepstrum of the mel filter bank, NOT the SPTK / WORLD mcep of a spectral envelope: the values are comparable among runs
+ *    of this tool (and with other mel-filter-bank MCDs of the same front-end), not with tables computed from mcep.
+ *
+ * 2. fd_dtw: dynamic time warping of two sequences of feature rows.  a: item b has frames_a[b] rows of D floats, row i at
+ *    a + (b pitch_a + i) ld; b likewise with pitch_b and frames_b (NULL: pitch_a / pitch_b rows); D 1 .. FD_MCD_MAX_COEF, ld >= D, any
+ *    4-byte alignment.  Nothing behind an item's own rows, and nothing of a row behind its D floats, is read.
+ *        cost(i, j) = sqrtf(s_D),  s_0 = 0,  s_{d+1} = fmaf(a_id - b_jd, a_id - b_jd, s_d)      (float32, from the differences)
+ *        D(0, 0) = cost(0, 0);   D(i, j) = cost(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1))   (float64; outside the matrix: absent)
+ *    A tie goes to the first of (diagonal, i - 1, j - 1): a later candidate replaces an earlier one only when strictly smaller.  Each cell
+ *    carries (D, cells on its path, diagonal steps on its path) forward from the predecessor it chose; with the fixed tie rule these are
+ *    the values of the path a trace-back from (Ta - 1, Tb - 1) finds, so the record needs no trace-back and no matrix in memory:
+ *        cost = D(Ta - 1, Tb - 1);  path_len = cells of the path (a copy: T);  n_diag = its diagonal steps (a copy: T - 1).
+ *    FD_MCD_NONFINITE: a feature of the pair is NaN or infinite (read from its bits): cost is NaN, path_len = n_diag = 0 and align_out is
+ *    -1.  align_out (may be NULL) [B][align_pitch] int32: for each i < frames_a[b] the smallest j with (i, j) on the path (the reference's
+ *    align_from_distances), -1 for i >= frames_a[b].  Only then are the directions kept: two bits per cell, four cells of a row to a byte,
+ *    frames_a ceil(frames_b / 4) bytes of the handle's scratch per pair, walked back by the pair's workgroup when the sweep is done.  A
+ *    pair of more than FD_DTW_MAX_ALIGN_CELLS cells is then refused.  No float [Ta][Tb] matrix exists at any time.
+ *    On the device: ONE WORKGROUP PER PAIR; workgroups never wait for each other (no flags, no grid barrier).  It takes FD_DTW_ROWS
+ *    consecutive rows of a at a time; thread r keeps row i0 + r in registers and is at column s - r in step s.  b is staged in LDS in
+ *    tiles of FD_DTW_COLS columns (a ring of FD_DTW_ROWS + FD_DTW_COLS).  The value above comes from thread r - 1: by a cross-lane move
+ *    inside a wavefront, through LDS between wavefronts; the diagonal one is the value above of the step before; one workgroup barrier
+ *    per step.  The bottom row of a row block goes through the scratch to the next block.  The order of every operation depends on the
+ *    pair alone: a record is bit-identical alone, anywhere in a ragged batch, at any ld and alignment, and from call to call.
+ *
+ * 3. fd_mcd_measure: cepstra of both waveforms, then the alignment -- the same kernels, so the record is bit-identical to two fd_cepstra
+ *    and one fd_dtw.  clean [B][Lc] and degraded [B][Ld] may differ in length.  With K = 10 sqrt(2) / ln 10:
+ *        mcd_dtw    = K cost / path_len
+ *        mcd_linear = K mean_{i < min(Tc, Td)} cost(i, i): no alignment; thread t adds the frames t, t + 256, ... in float64 in ascending
+ *                     order, thread 0 the 256 sums in thread order.
+ *    A copy scores exactly 0 with path_len = n_diag + 1 = T.  FD_MCD_SHORT: tacotron front-end and one of the two has n <= 512;
+ *    FD_MCD_NONFINITE: a cepstral value is not finite; the values are then NaN and path_len = n_diag = 0.
+ *
+ * All three: asynchronous on `stream`; like fd_spectral_measure they do not settle a pending lazily checked fd_sample, and the arguments
+ * are checked before the handle is looked at.  The tables (front-end, DCT) are uploaded at the first call and the scratch grows at the first
+ * call that needs more; neither can happen inside a stream capture (FD_ERR_STATE: call it once before).  B 1 .. 4096; a row has at most
+ * FD_MCD_MAX_FRAMES frames.  FD_ERR_INVALID: a null handle or pointer, a count or configuration value out of range (the message names
+ * the value). */
+#define FD_MCD_MAX_COEF 40
+#define FD_MCD_MAX_FRAMES 4194304   /* 2^22 frames of one row */
+#define FD_DTW_ROWS 256             /* rows of a one workgroup sweeps together; its threads */
+#define FD_DTW_COLS 64              /* columns of b staged together */
+#define FD_DTW_MAX_ALIGN_CELLS 67108864      /* 2^26: the largest Ta Tb with align_out */
+enum { FD_MCD_OK = 0, FD_MCD_SHORT = 1, FD_MCD_NONFINITE = 2 };
+typedef struct fd_mcd_config { int32_t n_coef, reserved; } fd_mcd_config;      /* 8 bytes; reserved: 0 */
+typedef struct fd_dtw_rec {
+    double cost;
+    int32_t path_len, n_diag, frames_a, frames_b;
+    int32_t status, reserved;              /* FD_MCD_OK / FD_MCD_NONFINITE */
+} fd_dtw_rec;                              /* 32 bytes */
+typedef struct fd_mcd {
+    double mcd_dtw, mcd_linear, cost;      /* dB, dB, the accumulated distance */
+    int32_t path_len, n_diag, frames_clean, frames_degraded;
+    int32_t status, reserved;              /* FD_MCD_* */
+} fd_mcd;                                  /* 48 bytes */
+
+/* n_coef = 13 (pure host code).  FD_ERR_INVALID: a null pointer. */
+FD_API int fd_mcd_default_config(fd_mcd_config *cfg);
+/* T for n samples (pure host code): 1 + n / 256.  FD_ERR_INVALID (< 0): n < 0. */
+FD_API int64_t fd_mcd_frames(int64_t n);
+/* wav [B][L] device, valid HOST [B] or NULL (1 .. L) -> cep_out [B][T_pitch][n_coef] device, T_pitch >= fd_mcd_frames(L). */
+FD_API int fd_cepstra(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int n_coef, float *cep_out, int64_t T_pitch,
+                      void *stream);
+/* a, b device; frames_a, frames_b HOST [B] or NULL (1 .. pitch_a / pitch_b) -> rec_dev [B] device, align_out NULL or [B][align_pitch]
+ * device int32 with align_pitch >= pitch_a. */
+FD_API int fd_dtw(fd_handle h, const float *a, const float *b, int B, int D, int64_t ld, int64_t pitch_a, int64_t pitch_b,
+                  const int64_t *frames_a, const int64_t *frames_b, fd_dtw_rec *rec_dev, int32_t *align_out, int64_t align_pitch, void *stream);
+/* clean [B][Lc], degraded [B][Ld] device; valid_clean, valid_degraded HOST [B] or NULL -> rec_dev [B] device.  cfg: NULL = the default. */
+FD_API int fd_mcd_measure(fd_handle h, const float *clean, int64_t Lc, const float *degraded, int64_t Ld, int B, const int64_t *valid_clean,
+                          const int64_t *valid_degraded, const fd_mcd_config *cfg, fd_mcd *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
