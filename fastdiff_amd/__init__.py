@@ -31,6 +31,9 @@ log-spectral distance) of the vocoded spectrum against the recording's, Validato
 fastdiff_amd.mcd / FastDiff.mcd measure the mel-cepstral distortion of a vocoded waveform against its recording, along a time-warped path
 (dynamic time warping on the device: mcd.dtw) and frame by frame, Validator(mcd=True) and infer.synthesize(mcd=True) / --mcd likewise
 (fastdiff_amd/mcd.py);
+fastdiff_amd.trim / FastDiff.trim_silences cut the long silences of a recording on the device -- the reference's trim_long_sil, with an energy
+detector in place of WebRTC's -- and infer.load_wav_inputs(trim_long_sil=True) / --trim_long_sil and TrainCorpus.from_wav_dir(trim_long_sil=True)
+put it in front of the mel (fastdiff_amd/trim.py);
 fastdiff_amd.griffin_lim / FastDiff.griffin_lim / mel_to_linear / griffin_lim_mel are the baseline vocoder (the reference's GLLinear /
 GLMel) with its inverse STFT on the device and both mel inversions (the pseudo-inverse, which is the default, and GLMel's non-negative
 least squares: mel_to_linear(inversion="nnls"), griffin_lim.mel_to_linear_nnls), and infer.synthesize_griffin_lim / --vocoder griffin_lim put its rows next to the model's
@@ -39,7 +42,7 @@ fastdiff_amd.diversity fits k-means bins over the corpus' mel frames on the devi
 them with NDB and JSD, the paper's two diversity columns; infer --ndb_bins writes the row (fastdiff_amd/diversity.py).
 """
 from .model import FastDiff  # noqa: F401
-from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, mcd, griffin_lim, diversity  # noqa: F401
+from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, mcd, trim, griffin_lim, diversity  # noqa: F401
 from . import sampler as util  # noqa: F401  (the reference module is called util)
 from .lvc_op import location_variable_convolution, gated_residual, kernel_conv1d, conv32  # noqa: F401
 from .trainstep import TrainStep  # noqa: F401
@@ -52,5 +55,5 @@ from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "mcd", "griffin_lim", "diversity", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "mcd", "trim", "griffin_lim", "diversity", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

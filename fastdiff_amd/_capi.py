@@ -25,6 +25,9 @@ FD_BINS_CHUNK, FD_BINS_MAX_K, FD_BINS_MAX_D, FD_BINS_RECORD_BYTES = 4096, 128, 1
 FD_BINS_OK, FD_BINS_NONFINITE, FD_BINS_EMPTY = 0, 1, 2
 FD_MCD_MAX_COEF, FD_MCD_MAX_FRAMES, FD_DTW_ROWS, FD_DTW_COLS, FD_DTW_MAX_ALIGN_CELLS = 40, 1 << 22, 256, 64, 1 << 26      # fastdiff_hip_ext.h: cepstral coefficients and frames of a row; rows one workgroup of fd_dtw sweeps together, columns it stages together; cells with align_out
 FD_MCD_OK, FD_MCD_SHORT, FD_MCD_NONFINITE = 0, 1, 2
+FD_TRIM_CHUNK = 256                                       # fastdiff_hip_ext.h: windows of one utterance per pass of fd_trim_silences' mask kernel
+FD_TRIM_OK, FD_TRIM_SILENT, FD_TRIM_EMPTY = 0, 1, 2
+FD_TRIM_LONG, FD_TRIM_EDGES = 0, 1
 
 
 class FdConfig(ct.Structure):
@@ -76,6 +79,11 @@ class FdRingChunk(ct.Structure):
                 ("src_pitch", ct.c_int64), ("frames", ct.c_int64)]
 
 
+class FdTrimParams(ct.Structure):
+    _fields_ = [("sample_rate", ct.c_int32), ("window_ms", ct.c_int32), ("average_width", ct.c_int32), ("max_silence", ct.c_int32),
+                ("mode", ct.c_int32), ("reserved", ct.c_int32), ("top_db", ct.c_double), ("floor_db", ct.c_double)]
+
+
 def step_table(rows):
     """[{t, c_eps, c_div, sigma, c1, c2, c3, add_noise}] (executed first -> last) -> the fd_step array fd_sample takes."""
     steps = (FdStep * len(rows))()
@@ -86,7 +94,7 @@ def step_table(rows):
 
 
 EXPORTS = ["fd_default_config", "fd_create", "fd_destroy", "fd_last_error", "fd_set_weight", "fd_commit_weights",
-           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_resample_out_len", "fd_resample_taps", "fd_resample", "fd_loudness_design", "fd_loudness_blocks", "fd_loudness_measure", "fd_loudness_normalize", "fd_stoi_bands", "fd_stoi_frames", "fd_stoi_measure", "fd_pitch_default_config", "fd_pitch_lags", "fd_pitch_frames", "fd_pitch_track", "fd_pitch_compare", "fd_spectral_default_config", "fd_spectral_frames", "fd_spectral_measure", "fd_gl_samples", "fd_gl_default_iters", "fd_mel_to_linear", "fd_griffin_lim", "fd_nnls_default_iters", "fd_nnls_step_bound", "fd_mel_to_linear_nnls", "fd_bins_chunk", "fd_bins_record_bytes", "fd_bins_pass", "fd_mcd_default_config", "fd_mcd_frames", "fd_cepstra", "fd_dtw", "fd_mcd_measure", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_bandpool_forward", "fd_bandpool_backward", "fd_npred_head_forward", "fd_npred_head_backward", "fd_phi_draw", "fd_phi_residual_forward", "fd_sched_init", "fd_sched_begin", "fd_sched_update", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
+           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_resample_out_len", "fd_resample_taps", "fd_resample", "fd_loudness_design", "fd_loudness_blocks", "fd_loudness_measure", "fd_loudness_normalize", "fd_stoi_bands", "fd_stoi_frames", "fd_stoi_measure", "fd_pitch_default_config", "fd_pitch_lags", "fd_pitch_frames", "fd_pitch_track", "fd_pitch_compare", "fd_spectral_default_config", "fd_spectral_frames", "fd_spectral_measure", "fd_gl_samples", "fd_gl_default_iters", "fd_mel_to_linear", "fd_griffin_lim", "fd_nnls_default_iters", "fd_nnls_step_bound", "fd_mel_to_linear_nnls", "fd_bins_chunk", "fd_bins_record_bytes", "fd_bins_pass", "fd_mcd_default_config", "fd_mcd_frames", "fd_cepstra", "fd_dtw", "fd_mcd_measure", "fd_trim_default_params", "fd_trim_windows", "fd_trim_mask", "fd_trim_levels", "fd_trim_silences", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_bandpool_forward", "fd_bandpool_backward", "fd_npred_head_forward", "fd_npred_head_backward", "fd_phi_draw", "fd_phi_residual_forward", "fd_sched_init", "fd_sched_begin", "fd_sched_update", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
            "fd_get_profile", "fd_reset_profile", "fd_get_counter", "fd_version", "fd_abi_revision"]
 
 _lib = None
@@ -177,6 +185,11 @@ def load():
     lib.fd_cepstra.argtypes = [vp, vp, ci, ct.c_int64, vp, ci, vp, ct.c_int64, vp]
     lib.fd_dtw.argtypes = [vp, vp, vp, ci, ci, ct.c_int64, ct.c_int64, ct.c_int64, vp, vp, vp, vp, ct.c_int64, vp]
     lib.fd_mcd_measure.argtypes = [vp, vp, ct.c_int64, vp, ct.c_int64, ci, vp, vp, vp, vp, vp]
+    lib.fd_trim_default_params.argtypes = [ci, ct.POINTER(FdTrimParams)]
+    lib.fd_trim_windows.argtypes = [ct.c_int64, ci, ci, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]
+    lib.fd_trim_mask.argtypes = [vp, ct.c_int64, ci, ci, ci, vp]
+    lib.fd_trim_levels.argtypes = [vp, vp, ci, ct.c_int64, vp, ci, ci, vp, vp]
+    lib.fd_trim_silences.argtypes = [vp, vp, ci, ct.c_int64, vp, ct.POINTER(FdTrimParams), vp, vp, vp, vp, vp]
     lib.fd_lvc_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     lib.fd_lvc_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.fd_lvc_forward_strided.argtypes = [vp, vp, vp, ct.c_int64, vp, ci, ci, ci, ci, ci, ci, vp, vp]

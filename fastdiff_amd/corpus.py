@@ -170,7 +170,7 @@ class TrainCorpus:
 
     @classmethod
     def from_wav_dir(cls, model, wav_dir, sample_rate=22050, mel_variant="pwg", hop_size=256, max_samples=25600, aux_context_window=0,
-                     device=None, loud_norm=False):
+                     device=None, loud_norm=False, trim_long_sil=False):
         """A corpus straight from recordings, without the reference's binarizer (which needs librosa): every *.wav below `wav_dir`, in
         sorted order, goes through what process_utterance does per item (data_gen/tts/data_gen_utils.py:93-147), on the device of
         `model` (a FastDiff on the GPU): any rate, sample type and channel count -> float mono at `sample_rate` (infer.wav_to_device:
@@ -178,7 +178,9 @@ class TrainCorpus:
         samples and cut there (:138-140).  One recording at a time -- peak memory is one recording plus the arenas -- and nothing comes
         back to the host.  Items the length rule drops are counted in n_skipped, `kept` lists the positions of the kept ones among the
         sorted files.  loud_norm: the reference's `loud_norm: true` -- every recording is brought to -22 LUFS (infer.loud_norm_wav) before its
-        mel is taken and before the corpus keeps it; one shorter than a 400 ms block raises ValueError naming the file."""
+        mel is taken and before the corpus keeps it; one shorter than a 400 ms block raises ValueError naming the file.  trim_long_sil: the
+        reference's `trim_long_sil: true` -- the long silences of every recording are cut first (infer.trim_long_sil_wav, in front of
+        loud_norm as in process_utterance, :108-120); a recording of which no window is kept is skipped and counted in n_skipped."""
         import glob
         from scipy.io import wavfile
         from . import infer
@@ -190,6 +192,10 @@ class TrainCorpus:
         for i, path in enumerate(paths):
             sr, pcm = wavfile.read(path)
             wav = infer.wav_to_device(model, pcm, sr, sample_rate, path)
+            if trim_long_sil:
+                wav = infer.trim_long_sil_wav(model, wav, sample_rate, path)
+                if wav.shape[0] == 0:                      # SILENT: no window kept
+                    continue
             if loud_norm:
                 wav = infer.loud_norm_wav(model, wav, sample_rate, path)
             T = 1 + wav.shape[0] // hop

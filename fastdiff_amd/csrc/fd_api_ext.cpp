@@ -1,5 +1,5 @@
-// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end and
-// sample-rate conversion (fd_resample).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
+// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end,
+// sample-rate conversion (fd_resample) and the cutting of long silences (fd_trim_*).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
 // waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*), the multi-resolution STFT distances (fd_spectral_*) and the mel-cepstral distortion with its alignment (fd_cepstra, fd_dtw, fd_mcd_measure).  The baseline vocoder next to it: Griffin-Lim and the mel inversions (fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls).  Then taps, layout
 // introspection, counters and per-kernel profiling.  
 #include <math.h>
@@ -779,6 +779,87 @@ int fd_mcd_measure(fd_handle h, const float *clean, int64_t Lc, const float *deg
         if (e != hipSuccess || (e = fdk::cepstra(La, degraded, B, Ld, nb, D, h->mcd_dct, cb, Td)) != hipSuccess) return e;
         if ((e = fdk::dtw(La, ca, cb, B, D, D, Tc, Td, fa_dev, fb_dev, wrec, nullptr, 0, 0, s.p)) != hipSuccess) return e;
         return fdk::mcd_finish(La, ca, cb, B, D, Tc, Td, fa_dev, fb_dev, na, Lc, nb, Ld, wrec, rec_dev);
+    });
+}
+
+// Cutting long silences (fastdiff_hip_ext.h; limits, refusals, the window grid and the host statement of the mask: fd_trim.h, the
+// kernels: fd_kernels_trim.hip) ----------------------------------------------------------------------------------------------------------
+int fd_trim_default_params(int sample_rate, fd_trim_params *p)
+{
+    if (!p) return FD_ERR_INVALID;
+    p->sample_rate = sample_rate; p->window_ms = 30; p->average_width = 8; p->max_silence = 12; p->mode = FD_TRIM_LONG; p->reserved = 0;
+    p->top_db = 40.0; p->floor_db = -70.0;
+    return FD_OK;
+}
+
+int fd_trim_windows(int64_t n, int sample_rate, int window_ms, int64_t *W, int64_t *M)
+{
+    return fdtr::windows(n, sample_rate, window_ms, W, M) ? FD_OK : FD_ERR_INVALID;
+}
+
+int fd_trim_mask(const uint8_t *speech, int64_t M, int average_width, int max_silence, int mode, uint8_t *flags_out)
+{
+    char why[fdtr::MSG];
+    if (!speech || !flags_out || M < 1 || fdtr::refusal(fdl::RATE_MIN, 30, 1.0, 0.0, average_width, max_silence, mode, 0, why)) return FD_ERR_INVALID;
+    fdtr::mask(speech, M, average_width, max_silence, mode, flags_out);
+    return FD_OK;
+}
+
+// what the two device entry points check and prepare alike: the batch, the window grid, the counts on the device
+static int trim_enter(fd_handle h, const char *who, const float *wav, int B, int64_t L, const int64_t *valid, int rate, int window_ms, void *stream,
+                      int64_t *W, int64_t *Mp, int64_t *M_grid, long long **valid_dev)
+{
+    if (!h) return FD_ERR_INVALID;
+    if (!wav) FD_FAIL(h, FD_ERR_INVALID, "%s: null wav", who);
+    if (reinterpret_cast<uintptr_t>(wav) & 3) FD_FAIL(h, FD_ERR_INVALID, "%s: wav must be 4-byte aligned", who);
+    if (B < 1 || B > 4096 || L < 1 || L > fdtr::MAX_SAMPLES)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d utterances (1 .. 4096) of L = %lld samples (1 .. 2^31 - 1)", who, B, (long long)L);
+    if (!fdtr::windows(L, rate, window_ms, W, Mp))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: sample rate %d outside %d .. %d, or window_ms = %d not 10, 20 or 30", who, rate, fdl::RATE_MIN, fdl::RATE_MAX, window_ms);
+    int rc = check_counts(h, who, "valid", valid, B, 0, L);
+    if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
+    int64_t longest = valid ? 0 : L;
+    for (int b = 0; valid && b < B; ++b) longest = std::max(longest, valid[b]);
+    fdtr::windows(longest, rate, window_ms, nullptr, M_grid);
+    Scratch &s = h->trim_scratch;
+    if ((rc = reserve(h, who, s, fdk::trim_scratch_bytes(B, *Mp), (hipStream_t)stream)) != FD_OK) return rc;
+    *valid_dev = valid ? fdk::trim_valid_slot(s.p) : nullptr;
+    return upload_counts(h, valid, B, fdk::trim_valid_slot(s.p), (hipStream_t)stream);
+}
+
+int fd_trim_levels(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int sample_rate, int window_ms, double *levels_out,
+                   void *stream)
+{
+    const char *who = "fd_trim_levels";
+    if (h && !levels_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null levels_out", who);
+    int64_t W = 0, Mp = 0, M_grid = 0;
+    long long *valid_dev = nullptr;
+    const int rc = trim_enter(h, who, wav, B, L, valid, sample_rate, window_ms, stream, &W, &Mp, &M_grid, &valid_dev);
+    if (rc != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::trim_levels(La, wav, B, L, valid_dev, W, Mp, levels_out, Mp, true); });
+}
+
+int fd_trim_silences(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_trim_params *params, float *out,
+                     int32_t *out_valid, uint8_t *flags, fd_trim *rec_dev, void *stream)
+{
+    const char *who = "fd_trim_silences";
+    if (!h) return FD_ERR_INVALID;
+    if (!params || !out || !out_valid) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !params ? "params" : (!out ? "out" : "out_valid"));
+    const fd_trim_params p = *params;
+    char why[fdtr::MSG];
+    if (fdtr::refusal(p.sample_rate, p.window_ms, p.top_db, p.floor_db, p.average_width, p.max_silence, p.mode, p.reserved, why))
+        FD_FAIL(h, FD_ERR_INVALID, "%s: parameters refused: %s", who, why);
+    if (reinterpret_cast<uintptr_t>(out) & 3) FD_FAIL(h, FD_ERR_INVALID, "%s: out must be 4-byte aligned", who);
+    if (wav && B >= 1 && L >= 1) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(wav), b0 = reinterpret_cast<uintptr_t>(out), bytes = sizeof(float) * (uintptr_t)B * (uintptr_t)L;
+        if (a0 < b0 + bytes && b0 < a0 + bytes) FD_FAIL(h, FD_ERR_INVALID, "%s: out overlaps wav (the compaction is not done in place)", who);
+    }
+    int64_t W = 0, Mp = 0, M_grid = 0;
+    long long *valid_dev = nullptr;
+    const int rc = trim_enter(h, who, wav, B, L, valid, p.sample_rate, p.window_ms, stream, &W, &Mp, &M_grid, &valid_dev);
+    if (rc != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::trim(La, wav, B, L, valid_dev, p, W, Mp, M_grid, out, out_valid, flags, rec_dev, h->trim_scratch.p);
     });
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/fastdiff_hip_ext.h"
 #include "../../include/fastdiff_hip_train.h"
 #include "fd_loudness.h"
+#include "fd_trim.h"
 #include "fd_stoi.h"
 #include "fd_pitch.h"
 #include "fd_spectral.h"
@@ -394,6 +395,7 @@ struct fd_context {
     Scratch bins_scratch;                    // fd_bins_pass: per chunk the counts, inertia, moved, nonfinite and sums (csrc/fd_bins.h: layout)
     Scratch mcd_scratch;                     // fd_cepstra / fd_dtw / fd_mcd_measure: counts, bottom rows, direction codes, records, cepstra (fd_kernels_mcd.hip: layout)
     const float *mcd_dct = nullptr;          // their DCT table [40][80] (csrc/fd_mcd.h: dct_table), uploaded at the first call (in `tables`)
+    Scratch trim_scratch;                    // fd_trim_silences / fd_trim_levels: lengths, window levels, prefix tables (fd_kernels_trim.hip: layout)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
     std::vector<hipEvent_t> event_pool;
@@ -556,6 +558,15 @@ hipError_t dtw(const Launch &L_, const float *a, const float *b, int B, int D, l
 hipError_t mcd_finish(const Launch &L_, const float *ca, const float *cb, int B, int D, long long pitch_a, long long pitch_b, const long long *fa_dev,
                       const long long *fb_dev, const long long *na_dev, long long Lc, const long long *nb_dev, long long Ld, const fd_dtw_rec *dtw_rec,
                       fd_mcd *rec);
+// fd_trim_silences / fd_trim_levels (fd_kernels_trim.hip).  W, Mp: the window and the windows of L samples (fdtr::windows); M_grid: the
+// windows of the longest row, which the levels' grid covers; valid_dev: null or the valid slot of the scratch buffer (trim_scratch_bytes(B, Mp)
+// bytes), filled by the caller; p: parameters the caller has validated (fdtr::refusal).
+size_t trim_scratch_bytes(int B, int64_t Mp);
+long long *trim_valid_slot(void *scratch);
+hipError_t trim_levels(const Launch &L_, const float *wav, int B, int64_t L, const long long *valid_dev, int64_t W, int64_t M_grid, double *levels,
+                       int64_t pitch, bool fill_tail);
+hipError_t trim(const Launch &L_, const float *wav, int B, int64_t L, const long long *valid_dev, const fd_trim_params &p, int64_t W, int64_t Mp,
+                int64_t M_grid, float *out, int *out_valid, unsigned char *flags, fd_trim *rec, void *scratch);
 }  // namespace fdk
 
 // profiling-aware launch helper.  Option profile = 1: the launch goes through hipExtLaunchKernelGGL with a start and a stop event, which

@@ -35,6 +35,14 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+// ... and of a float64 (fd_kernels_trim.hip), by the same butterfly
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
 // the sum of v over the workgroup's 256 threads, in every thread: wave_sum, then (w0 + w1) + (w2 + w3)
 __device__ __forceinline__ float block_sum(float v)
 {

@@ -13,11 +13,12 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
     The reference CLI runs B = 1 (config `max_sentences`); batching is this path's extension: the batch goes down with its
     `lens`, so every item is computed exactly as if it ran alone (and the padding costs nothing), then cropped to its length.
 
-Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), collate_test_batch, distributed_sampler_indices, synthesize,
+Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), trim_long_sil_wav (the reference's trim_long_sil on the
+device), collate_test_batch, distributed_sampler_indices, synthesize,
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), synthesize_griffin_lim (--vocoder griffin_lim:
 the baseline vocoder on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
-(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--out_sample_rate R]
+(`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--trim_long_sil [--trim_top_db 40] [--trim_mode long|edges]] [--out_sample_rate R]
 [--loudness LUFS] [--stoi] [--pitch] [--spectral] [--mcd] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]
 [--ndb_bins bins.npz]`).
 """
@@ -97,8 +98,45 @@ def loud_norm_wav(model, wav: torch.Tensor, sample_rate: int = 22050, what: str 
     return y
 
 
+TRIM_NORM_LUFS = -20.0      # trim_long_silences(norm=True): pyln.normalize.loudness(wav_raw, loudness, -20.0) (data_gen_utils.py:45)
+
+
+def trim_long_sil_wav(model, wav: torch.Tensor, sample_rate: int = 22050, what: str = "wav", norm: bool = True, top_db: float = 40.0,
+                      mode: str = "long", return_record: bool = False):
+    """The trim_long_sil branch of process_utterance (data_gen/tts/data_gen_utils.py:108-109 -> trim_long_silences, :27-90) on a device
+    waveform [n]: with norm, first brought to -20 LUFS (or divided by its new peak where that would exceed 1, :42-47; shorter than one
+    400 ms block: ValueError naming `what`, as loud_norm_wav raises), then the long silences cut (FastDiff.trim_silences: an energy
+    detector in place of WebRTC's, the reference's smoothing and dilation).  Returns the device waveform cut to its n_out samples -- empty
+    for a recording without a kept window, as the reference's wav_raw[audio_mask] is; with return_record also the record (a dict of
+    scalars)."""
+    from . import loudness as _loudness
+    wav = wav.reshape(-1)
+    if norm:
+        wav, rec = model.loudness_normalize(wav, TRIM_NORM_LUFS, sample_rate=sample_rate, out="float", return_record=True)
+        if int(rec["status"][0]) == _loudness.SHORT:
+            raise ValueError(f"{what}: {wav.shape[-1]} samples at {sample_rate} Hz are shorter than one 400 ms block: loudness cannot be measured")
+    out, _, rec = model.trim_silences(wav, sample_rate=sample_rate, top_db=top_db, mode=mode, return_record=True)
+    rec = {k: v[0].item() for k, v in rec.items()}
+    cut = out[0, :rec["n_out"]].contiguous()
+    return (cut, rec) if return_record else cut
+
+
+def write_trim_report(report, path: str) -> str:
+    """The (item_name, samples in, record) rows of load_wav_inputs(trim_report=...) as <out_dir>/trim.tsv; returns the text."""
+    from . import trim as _trim
+    lines = ["\t".join(["name", "samples_in", "samples_out", "windows", "kept_windows", "peak_db", "status"])]
+    for name, n_in, r in report:
+        lines.append("\t".join([name, str(n_in), str(r["n_out"]), str(r["windows"]), str(r["kept_windows"]), format(r["peak_db"], ".2f"),
+                                _trim.STATUS[r["status"]]]))
+    text = "\n".join(lines)
+    with open(path, "w") as f:
+        f.write(text + "\n")
+    return text
+
+
 def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_variant: str = "pwg", loud_norm: bool = False,
-                    keep_wav: bool = False) -> List[dict]:
+                    keep_wav: bool = False, trim_long_sil: bool = False, trim_top_db: float = 40.0, trim_mode: str = "long",
+                    trim_report: list = None) -> List[dict]:
     """Copy-synthesis inputs (`test_input_dir` with recordings, tasks/vocoder/dataset_utils.py:162-184): every *.wav below the
     directory, in sorted order, through the device mel front-end (`FastDiff.mel_spectrogram` = process_utterance of
     data_gen/tts/data_gen_utils.py:93-147, or with mel_variant="tacotron" the TacotronSTFT of vocoder_binarizer_tacotron.py:110-116
@@ -108,6 +146,10 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     data_gen_utils.py:111); a mono recording at the model's rate takes the direct path, bit for bit as before.
     loud_norm: the reference's `loud_norm: true` configurations -- every recording is brought to -22 LUFS before its mel is taken
     (loud_norm_wav: FastDiff.loudness_normalize).
+    trim_long_sil: the reference's `trim_long_sil: true` -- the long silences of every recording are cut before anything else sees it
+    (trim_long_sil_wav, in front of loud_norm as in process_utterance): the mel, the vocoder and every score's reference get the trimmed
+    recording.  A recording without a kept window is left out with a warning (the reference would hand an empty array on).  trim_report: a list that receives one
+    (item_name, samples in, record) per recording.
     keep_wav: every item also carries "wav", its device waveform [n] at the model's rate as the mel was taken from it (what
     synthesize(stoi=True), synthesize(pitch=True) and synthesize(spectral=True) score the vocoded waveform against)."""
     from scipy.io import wavfile
@@ -115,10 +157,20 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     for path in sorted(glob.glob(f"{test_input_dir}/*.wav")):
         sr, pcm = wavfile.read(path)
         wav = wav_to_device(model, pcm, sr, sample_rate, path)
+        name = path[len(test_input_dir) + 1:].replace("/", "_")
+        if trim_long_sil:
+            n_in = wav.numel()
+            wav, rec = trim_long_sil_wav(model, wav, sample_rate, path, top_db=trim_top_db, mode=trim_mode, return_record=True)
+            if trim_report is not None:
+                trim_report.append((name, n_in, rec))
+            if rec["n_out"] == 0:
+                import warnings
+                warnings.warn(f"{path}: no window of the recording is kept (silence?): left out", stacklevel=2)
+                continue
         if loud_norm:
             wav = loud_norm_wav(model, wav, sample_rate, path)
         mel = model.mel_spectrogram(wav, variant=mel_variant)[0].transpose(0, 1).contiguous().cpu()      # [T, 80] as on disk
-        items.append({"item_name": path[len(test_input_dir) + 1:].replace("/", "_"), "mel": mel, "len": mel.shape[0]})
+        items.append({"item_name": name, "mel": mel, "len": mel.shape[0]})
         if keep_wav:
             items[-1]["wav"] = wav.reshape(-1)
     return items
@@ -661,7 +713,17 @@ def main(argv=None):
                     help="the k-means bins of `python -m fastdiff_amd.diversity fit`: the run's output waveforms go through the mel front-end on "
                          "the device, their frames are counted in the bins, and the run's NDB and JSD against the corpus (Richardson & Weiss "
                          "2018) are printed and written to <out_dir>/diversity.tsv -- one row for the run, not one per utterance")
+    ap.add_argument("--trim_long_sil", action="store_true",
+                    help="with --from_wav: cut the long silences of every recording on the device before its mel is taken (the reference's "
+                         "trim_long_sil: true, with an energy detector in place of WebRTC's); the mel, the vocoder and every score's reference "
+                         "get the trimmed recording, and <out_dir>/trim.tsv lists what was cut")
+    ap.add_argument("--trim_top_db", type=float, default=40.0, help="with --trim_long_sil: a window is speech within this many dB of the loudest")
+    ap.add_argument("--trim_mode", default="long", choices=("long", "edges"),
+                    help="with --trim_long_sil: long = the reference's mask (pauses of more than 12 windows shortened); edges = only leading and "
+                         "trailing silence")
     args = ap.parse_args(argv)
+    if args.trim_long_sil and not args.from_wav:
+        ap.error("--trim_long_sil cuts recordings: it needs --from_wav")
     if args.ndb_bins and args.out_sample_rate not in (None, 22050):
         ap.error("--ndb_bins takes the mel of the output waveforms at 22050 Hz: it is not available with --out_sample_rate")
     scored = _scores.enabled(stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, mcd=args.mcd)
@@ -689,7 +751,12 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"]["model"], strict=True)
     if args.mel_basis:
         model.set_mel_filterbank(np.load(args.mel_basis), variant=args.mel_variant)
-    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored)) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    trimmed = [] if args.trim_long_sil else None
+    more_in = dict(trim_long_sil=True, trim_top_db=args.trim_top_db, trim_mode=args.trim_mode, trim_report=trimmed) if args.trim_long_sil else {}      # (the default passes no new keyword)
+    items = load_wav_inputs(model, args.test_input_dir, mel_variant=args.mel_variant, loud_norm=args.loud_norm, keep_wav=bool(scored), **more_in) if args.from_wav else load_mel_inputs(args.test_input_dir)
+    if trimmed is not None and rank == 0:                  # (every rank trims every recording; one of them writes the table)
+        os.makedirs(args.out_dir, exist_ok=True)
+        print(write_trim_report(trimmed, os.path.join(args.out_dir, "trim.tsv")))
     mine = [dict(items[i], uid=i) for i in sorted(set(distributed_sampler_indices(len(items), rank, world)))]
     more = dict(mcd=True) if args.mcd else {}              # (the default passes no new keyword)
     if args.vocoder == "griffin_lim":

@@ -364,6 +364,21 @@ class FastDiff(nn.Module):
         from . import loudness as _loudness
         return _loudness._normalize(*self._wave_call(wav), wav, target, valid, sample_rate, out, return_record)
 
+    def trim_silences(self, wav, valid=None, sample_rate=22050, window_ms=30, top_db=40., floor_db=-70., average_width=8, max_silence=12,
+                      mode="long", return_flags=False, return_record=False):
+        """Long silences cut on the device (fastdiff_amd/trim.py; the reference's trim_long_silences, data_gen/tts/data_gen_utils.py:27-90,
+        with an energy detector in place of WebRTC's): wav [n] / [B, n] / [B, 1, n] -> (out [B, n] float32: each utterance's kept samples in
+        order, 0 behind them; out_valid device int32 [B]), then the window flags and the record on request.  Nothing synchronises without
+        return_record."""
+        from . import trim as _trim
+        return _trim._trim(*self._wave_call(wav), wav, valid, sample_rate, window_ms, top_db, floor_db, average_width, max_silence, mode,
+                           return_flags, return_record)
+
+    def trim_levels(self, wav, valid=None, sample_rate=22050, window_ms=30):
+        """The level of every window of trim_silences, dB re full scale: device float64 [B, Mmax] (fastdiff_amd/trim.py: levels)."""
+        from . import trim as _trim
+        return _trim._levels(*self._wave_call(wav), wav, valid, sample_rate, window_ms)
+
     def stoi(self, clean, degraded, valid=None, sample_rate=22050):
         """STOI and ESTOI of `degraded` against `clean` on the device (fastdiff_amd/stoi.py; what people run pystoi for over the reference's
         *_gt.wav / *_pred.wav pairs, FastDiff.py:113-117): two tensors [n] / [B, n] / [B, 1, n] of one shape at `sample_rate` -> a dict of

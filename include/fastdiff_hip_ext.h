@@ -657,6 +657,78 @@ FD_API int fd_dtw(fd_handle h, const float *a, const float *b, int B, int D, int
 FD_API int fd_mcd_measure(fd_handle h, const float *clean, int64_t Lc, const float *degraded, int64_t Ld, int B, const int64_t *valid_clean,
                           const int64_t *valid_degraded, const fd_mcd_config *cfg, fd_mcd *rec_dev, void *stream);
 
+/* Cutting long silences: the `trim_long_sil` switch of the reference's process_utterance (data_gen/tts/data_gen_utils.py:93-147 ->
+ * trim_long_silences, :27-90): flag short windows as speech or not, smooth the flags with a moving average, dilate them so that a short
+ * pause survives, and drop every sample that is not under the mask.  THIS TEXT defines the method; tests/trim_ref.py restates it in
+ * float64 numpy.  Two things differ from the reference on purpose.  (1) The detector is an ENERGY detector, not WebRTC's sub-band GMM
+ * (webrtcvad is not in the build image and nobody can run it here): the flags of step 3 are not WebRTC's, and nothing claims closeness
+ * to them; steps 4-5 are the reference's exactly.  (2) The reference resamples to 16 kHz to get windows of 480 samples and maps the mask
+ * back; here the windows lie on the NATIVE rate's grid (661 samples at 22050 Hz), so no sample is filtered and the output is a bit copy
+ * of input samples.  The reference's loudness normalisation in front (to -20 LUFS, :42-47) is fd_loudness_normalize: the caller's step.
+ *
+ * Parameters (fd_trim_params): sample_rate; window_ms 10, 20 or 30 [30]; top_db [40, the dynamic range fd_stoi_measure uses for the same
+ * question] finite and > 0; floor_db [-70] finite; average_width A [8] 1 .. 64; max_silence G [12] even, 0 .. 254; mode
+ * FD_TRIM_LONG / FD_TRIM_EDGES; reserved 0.  One utterance of n valid samples:
+ *  1. Windows.  W = window_ms sample_rate / 1000, M = max(1, n / W) (integer divisions; fd_trim_windows).  Window w < M - 1 covers
+ *     [w W, (w + 1) W), the last one [(M - 1) W, n): it takes the tail, up to 2 W - 1 samples, or fewer than W when n < W.
+ *  2. Level.  m_w = the window's mean, e_w = the mean of (x - m_w)^2, level_w = 10 log10(max(e_w, 1e-20)) dB re full scale; float64
+ *     from the float32 samples.  A window that holds a sample that is not finite (on the bits) has no level: it is not speech, takes no
+ *     part in the peak and is counted in `nonfinite`.
+ *  3. Decision.  peak = max_w level_w (-inf if no window has a level); threshold = max(peak - top_db, floor_db);
+ *     speech_w = level_w > threshold.
+ *  4. Smoothing (:75-82).  c_w = the speech flags among windows w - (A - 1) / 2 .. w + A / 2 (integer divisions; outside 0 .. M - 1:
+ *     0);  smooth_w = 2 c_w > A  (np.round takes halves to even: 4 of 8 is 0).
+ *  5. Dilation (:85).  keep_w = any smooth_v with |v - w| <= G / 2: binary_dilation(smooth, ones(G + 1)).  FD_TRIM_EDGES instead keeps
+ *     every window from the first kept one to the last: the edge-only trim of vocoder recipes.
+ *  6. Compaction.  out = the samples of the kept windows in order, bit copies; n_out = their count; out[n_out .. L - 1] = 0.
+ *  7. Status.  FD_TRIM_OK;  FD_TRIM_SILENT: no window kept, n_out = 0;  FD_TRIM_EMPTY: n = 0 (the record then counts 0 windows).
+ *
+ * On the device, three launches, none of which waits on another workgroup.  Levels: a wavefront per window; a lane adds every 64th
+ * group of 4 consecutive samples of the window in ascending order, the lanes are added by a butterfly (xor 32 .. 1), once for the mean
+ * and once for the squares (a window of up to 3075 samples -- every rate up to 48 kHz -- is loaded once and held in registers for
+ * both; a longer one is read again from the cache, in the same order); 16-byte loads where a group's address allows,
+ * 4-byte ones elsewhere -- the order of the sum does not depend on the address.  Mask: one workgroup per utterance, FD_TRIM_CHUNK windows
+ * at a time with the running counts carried from chunk to chunk: the peak, then prefix counts of the speech flags, from them the
+ * smoothed flags and their prefix counts, from those the kept flags and the exclusive prefix of kept samples per window; it writes
+ * out_valid, the flags and the record.  Gather: a workgroup per tile of output samples finds the window of its first sample by
+ * bisection in that prefix table and copies run by run; tiles behind n_out write zeros.  A window's level depends on its samples alone, and
+ * nothing at or behind valid[b] is read: an utterance's outputs are bit-identical alone, anywhere in a ragged batch with anything behind
+ * it, at any 4-byte alignment and from call to call.  Scratch (levels, prefix tables) lives in a buffer of the handle that grows at the
+ * first call that needs more -- never inside a stream capture (FD_ERR_STATE). */
+#define FD_TRIM_CHUNK 256           /* windows of one utterance per pass of the mask kernel's workgroup */
+enum { FD_TRIM_OK = 0, FD_TRIM_SILENT = 1, FD_TRIM_EMPTY = 2 };
+enum { FD_TRIM_LONG = 0, FD_TRIM_EDGES = 1 };
+typedef struct fd_trim_params {
+    int32_t sample_rate, window_ms, average_width, max_silence, mode, reserved;      /* reserved: 0 */
+    double top_db, floor_db;
+} fd_trim_params;                   /* 40 bytes */
+typedef struct fd_trim {
+    int32_t n_out, windows, speech, kept_windows, nonfinite, status;      /* status: FD_TRIM_* */
+    double peak_db, threshold_db;
+} fd_trim;                          /* 40 bytes */
+
+/* 30 ms windows, top_db 40, floor_db -70, A = 8, G = 12, FD_TRIM_LONG at `sample_rate` (pure host code).  FD_ERR_INVALID: null. */
+FD_API int fd_trim_default_params(int sample_rate, fd_trim_params *p);
+/* W and M of n samples (pure host code; either pointer may be NULL).  FD_ERR_INVALID: n < 0, a rate outside 8000 .. 192000, a window_ms
+ * other than 10, 20, 30. */
+FD_API int fd_trim_windows(int64_t n, int sample_rate, int window_ms, int64_t *W, int64_t *M);
+/* Steps 4-5 on the host (csrc/fd_trim.h), for tests and for callers with flags of their own: speech [M] (0 / 1) -> flags_out [M], bit 0
+ * speech, bit 1 smooth, bit 2 keep.  FD_ERR_INVALID: a null pointer, M < 1, A, G or mode out of range. */
+FD_API int fd_trim_mask(const uint8_t *speech, int64_t M, int average_width, int max_silence, int mode, uint8_t *flags_out);
+/* Step 2 alone: wav [B][L] device -> levels_out [B][Mmax] device float64, Mmax = M of L; a window without a level holds a quiet NaN
+ * (0x7FF8000000000000), columns behind an item's M hold 0.  Arguments as in fd_trim_silences. */
+FD_API int fd_trim_levels(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int sample_rate, int window_ms,
+                          double *levels_out, void *stream);
+/* wav [B][L] device float -> out [B][L] device float (steps 1-6; must not overlap wav) and out_valid [B] device int32 = n_out.
+ * valid: HOST [B] or NULL = samples of each row that count (0 .. L).  flags: NULL or device uint8 [B][Mmax], Mmax = M of L: bit 0
+ * speech, bit 1 smooth, bit 2 keep, 0 behind an item's M.  rec_dev: NULL or device [B].  Asynchronous on `stream` and capturable: the
+ * output has the input's capacity, so no host read decides a launch.  B 1 .. 4096, L 1 .. 2^31 - 1.  Like fd_loudness_measure it does
+ * not settle a pending lazily checked fd_sample.
+ * FD_ERR_INVALID: a null pointer, wav or out not 4-byte aligned, out overlapping wav, B, L or valid[b] out of range, parameters refused
+ * (the message says which); FD_ERR_STATE: the scratch buffer would have to grow inside a stream capture. */
+FD_API int fd_trim_silences(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_trim_params *params, float *out,
+                            int32_t *out_valid, uint8_t *flags, fd_trim *rec_dev, void *stream);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
