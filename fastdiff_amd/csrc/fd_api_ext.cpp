@@ -1,7 +1,8 @@
-// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end,
-// sample-rate conversion (fd_resample) and the cutting of long silences (fd_trim_*).  Behind it: the int16 waveform epilogue and BS.1770 loudness (fd_loudness_*).  Scores of a vocoded
-// waveform against its recording: STOI / ESTOI (fd_stoi_*), F0 tracking with the pitch scores (fd_pitch_*), the multi-resolution STFT distances (fd_spectral_*) and the mel-cepstral distortion with its alignment (fd_cepstra, fd_dtw, fd_mcd_measure).  The baseline vocoder next to it: Griffin-Lim and the mel inversions (fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls).  Then taps, layout
-// introspection, counters and per-kernel profiling.  
+// fd_api_ext.cpp -- host side of the entry points of include/fastdiff_hip_ext.h.  In front of the vocoder: the mel front-end, sample-rate
+// conversion (fd_resample), the cutting of long silences (fd_trim_*).  Behind it: the int16 epilogue, BS.1770 loudness (fd_loudness_*).
+// Scores against a recording: STOI / ESTOI (fd_stoi_*), F0 and the pitch scores (fd_pitch_*), the STFT distances (fd_spectral_*), MCD with
+// its alignment (fd_cepstra, fd_dtw, fd_mcd_measure); against a corpus: the k-means bin pass under NDB / JSD (fd_bins_pass).  The baseline
+// vocoder: fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls.  Then taps, layout introspection, counters, profiling.  
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -13,10 +14,9 @@
 #include "fd_host.h"
 #include "fd_resample.h"
 
-extern "C" {
-
-// The host path the waveform tools below share ("One host path under these tools"): check_counts, enter, upload_table,
-// upload_counts, and reserve and run (fd_host.h) ----------------------------------------------------------------------------------------------
+// The host path the tools below share ("One host path under these tools"): check_counts, enter, the tables (upload_table
+// under first_use and refresh), stage_counts, and reserve and run (fd_host.h), in the order arguments, counts, handle, tables, scratch,
+// launch.  Every table refuses to be made inside a stream capture but the mel tables under fd_mel_spectrogram / fd_get_mel_filterbank ----
 static_assert(sizeof(long long) == sizeof(int64_t), "the kernels read the callers' int64_t counts as long long");
 
 // the caller's counts [B] (null: every row whole) lie in [lo, hi]; checked before the call touches the device or the handle
@@ -52,11 +52,46 @@ static int upload_table(fd_handle h, const char *who, const void *src, size_t by
     return FD_OK;
 }
 
-// host counts [B] -> `dst` on the device through the pinned staging ring (null counts: nothing to do)
-static int upload_counts(fd_handle h, const int64_t *counts, int B, long long *dst, hipStream_t stream)
+// what is made at a first use is never made inside a stream capture, whose replays would not make it again; what: as the refusal names it
+static int refuse_in_capture(fd_handle h, const char *who, hipStream_t stream, const char *what)
 {
-    return counts ? fd_stage_upload(h, counts, sizeof(long long) * B, dst, stream) : FD_OK;
+    if (capturing(stream))
+        FD_FAIL(h, FD_ERR_STATE, "%s: %s is made at the first call that uses it, which cannot happen inside a stream capture: call it once before", who, what);
+    return FD_OK;
 }
+
+// A constant table of the handle made at its first use: `slot` once it is set; else, outside a capture, build() -> std::vector<float>
+// on the host and upload_table
+template <class Build>
+static int first_use(fd_handle h, const char *who, hipStream_t stream, const char *what, const float *&slot, Build &&build)
+{
+    if (slot) return FD_OK;
+    const int rc = refuse_in_capture(h, who, stream, what);
+    if (rc != FD_OK) return rc;
+    const std::vector<float> tab = build();
+    return upload_table(h, who, tab.data(), tab.size() * sizeof(float), reinterpret_cast<const void **>(&slot));
+}
+
+// ... and a table keyed on the caller's host values src[n] (fd_context::KeyedTable): kept while they compare equal to the last call's,
+// else made again as at a first use from build() (the replaced one stays in `tables`: launches in flight may still read it)
+template <class Build>
+static int refresh(fd_handle h, const char *who, hipStream_t stream, const char *what, fd_context::KeyedTable &t, const float *src, size_t n, Build &&build)
+{
+    if (t.dev && memcmp(t.host.data(), src, sizeof(float) * n) == 0) return FD_OK;
+    const float *dev = nullptr;
+    const int rc = first_use(h, who, stream, what, dev, build);
+    if (rc == FD_OK) { t.dev = dev; t.host.assign(src, src + n); }
+    return rc;
+}
+
+// host counts [B] -> `slot` on the device through the pinned staging ring; *dev: the slot, or null with null counts (every row whole)
+static int stage_counts(fd_handle h, const int64_t *counts, int B, long long *slot, hipStream_t stream, const long long **dev)
+{
+    *dev = counts ? slot : nullptr;
+    return counts ? fd_stage_upload(h, counts, sizeof(long long) * B, slot, stream) : FD_OK;
+}
+
+extern "C" {
 
 // The DEFAULT filter bank of a front-end, dense [80][513]: librosa.filters.mel(22050, 1024, 80, fmin, fmax) restated in double
 // precision (Slaney mel scale, triangular weights on the FFT bin centres, each filter scaled by 2 / (f[m+2] - f[m])) for 'pwg' (fmin
@@ -140,6 +175,14 @@ static int ensure_mel_tables(fd_handle h)
     return FD_OK;
 }
 
+// ... for the tools behind the front-end (fd_griffin_lim, fd_cepstra, fd_mcd_measure): made at their first call, never inside a capture
+static int mel_tables_first_use(fd_handle h, const char *who, hipStream_t stream)
+{
+    if (h->mel[MEL_VARIANTS - 1].tab) return FD_OK;
+    const int rc = refuse_in_capture(h, who, stream, "the set of the mel front-end's tables");
+    return rc != FD_OK ? rc : ensure_mel_tables(h);
+}
+
 int fd_set_mel_filterbank(fd_handle h, const float *fb, int n_mels, int n_bins)
 {
     if (!h) return FD_ERR_INVALID;
@@ -152,11 +195,8 @@ int fd_set_mel_filterbank(fd_handle h, const float *fb, int n_mels, int n_bins)
         h->mel_bank_user[v] = false;
         return upload_mel_bank(h, v, def.data());
     }
-    for (size_t i = 0; i < (size_t)MEL_NM * MEL_NB; ++i) {      // (on the bit pattern: this file is built with -fno-honor-nans)
-        uint32_t bits;
-        memcpy(&bits, fb + i, sizeof(bits));
-        if ((bits & 0x7F800000u) == 0x7F800000u) FD_FAIL(h, FD_ERR_INVALID, "fd_set_mel_filterbank: element %zu is not finite", i);
-    }
+    const long bad = fdn::first_nonfinite(fb, (size_t)MEL_NM * MEL_NB);
+    if (bad >= 0) FD_FAIL(h, FD_ERR_INVALID, "fd_set_mel_filterbank: element %zu is not finite", (size_t)bad);
     const int rc = upload_mel_bank(h, v, fb);
     if (rc == FD_OK) h->mel_bank_user[v] = true;
     return rc;
@@ -193,10 +233,9 @@ int fd_peak_normalize_int16_ragged(fd_handle h, const float *wav, int B, int64_t
     int rc = enter(h);      // (this entry point has always settled before it looks at the counts)
     if (rc != FD_OK) return rc;
     if ((rc = check_counts(h, "fd_peak_normalize_int16_ragged", "valid", valid, B, 1, len)) != FD_OK) return rc;
-    long long *valid_dev = reinterpret_cast<long long *>(reinterpret_cast<char *>(h->scratch) + 32768);      // behind the abs-max words
-    if ((rc = upload_counts(h, valid, B, valid_dev, (hipStream_t)stream)) != FD_OK) return rc;
-    return run(h, stream, "fd_peak_normalize_int16",
-               [&](const fdk::Launch &L) { return fdk::peak_normalize_int16(L, wav, B, len, pcm, valid ? valid_dev : nullptr); });
+    const long long *valid_dev = nullptr;      // behind the abs-max words
+    if ((rc = stage_counts(h, valid, B, reinterpret_cast<long long *>(reinterpret_cast<char *>(h->scratch) + 32768), (hipStream_t)stream, &valid_dev)) != FD_OK) return rc;
+    return run(h, stream, "fd_peak_normalize_int16", [&](const fdk::Launch &L) { return fdk::peak_normalize_int16(L, wav, B, len, pcm, valid_dev); });
 }
 
 int fd_peak_normalize_int16(fd_handle h, const float *wav, int B, int64_t len, int16_t *pcm, void *stream)
@@ -229,17 +268,14 @@ int fd_resample_taps(int sr_in, int sr_out, float *taps, int64_t capacity, int *
     return n;
 }
 
-// the device table of a ratio: built and uploaded at its first use
-static int resample_table(fd_handle h, const fdr::Ratio &r, hipStream_t stream, const float **dev)
+// the device table of a ratio (fd_resample, and fd_stoi_measure's way to 10 kHz)
+static int resample_table(fd_handle h, const char *who, const fdr::Ratio &r, hipStream_t stream, const float **dev)
 {
-    for (const auto &t : h->resample_tabs)
-        if (t.up == r.up && t.down == r.down) { *dev = t.dev; return FD_OK; }
-    if (capturing(stream))
-        FD_FAIL(h, FD_ERR_STATE, "fd_resample: the table of ratio %d/%d is built at the first use of that ratio, which cannot happen inside a stream capture: call it once before",
-                r.up, r.down);
-    const std::vector<float> tab = fdr::table(r);
-    const int rc = upload_table(h, "fd_resample", tab.data(), tab.size() * sizeof(float), reinterpret_cast<const void **>(dev));
-    if (rc == FD_OK) h->resample_tabs.push_back({r.up, r.down, *dev});
+    const float *&slot = h->resample_tabs[{r.up, r.down}];      // (a null slot counts as none)
+    char what[64] = "";
+    if (!slot) snprintf(what, sizeof(what), "the table of ratio %d/%d", r.up, r.down);
+    const int rc = first_use(h, who, stream, what, slot, [&] { return fdr::table(r); });
+    *dev = slot;
     return rc;
 }
 
@@ -264,7 +300,7 @@ int fd_resample(fd_handle h, const void *src, int format, int channels, int B, i
     int rc = check_counts(h, "fd_resample", "valid_in", valid_in, B, 1, n_in);
     if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
     const float *table = nullptr;
-    if (r.up != r.down && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
+    if (r.up != r.down && (rc = resample_table(h, "fd_resample", r, (hipStream_t)stream, &table)) != FD_OK) return rc;
     return run(h, stream, "fd_resample", [&](const fdk::Launch &La) {
         return fdk::resample(La, src, format, channels, B, n_in, src_pitch, valid_in, r.up, r.down, r.half, r.K, r.Kp, n_out, table, dst, dst_pitch);
     });
@@ -298,12 +334,12 @@ static int loudness_call(fd_handle h, const char *who, const float *wav, int B, 
     if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
     Scratch &s = h->loud_scratch;
     if ((rc = reserve(h, who, s, fdk::loudness_scratch_bytes(B, L, rate), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *valid_dev = fdk::loudness_valid_slot(s.p, B, L, rate);
-    if ((rc = upload_counts(h, valid, B, valid_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *valid_dev = nullptr;
+    if ((rc = stage_counts(h, valid, B, fdk::loudness_valid_slot(s.p, B, L, rate), (hipStream_t)stream, &valid_dev)) != FD_OK) return rc;
     fdk::LoudnessFilter F;
     fdl::make_filter(rate, F);
     return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::loudness(La, wav, B, L, valid ? valid_dev : nullptr, rate, F, normalize, target, rec_dev, out_f32, out_pcm, s.p);
+        return fdk::loudness(La, wav, B, L, valid_dev, rate, F, normalize, target, rec_dev, out_f32, out_pcm, s.p);
     });
 }
 
@@ -352,24 +388,21 @@ int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int 
     if (n10 > ((int64_t)1 << 30)) FD_FAIL(h, FD_ERR_INVALID, "%s: L = %lld is %lld samples at 10 kHz, at most 2^30 are supported", who, (long long)L, (long long)n10);
     int rc = check_counts(h, who, "valid", valid, B, 1, L);
     if (rc != FD_OK || (rc = enter(h)) != FD_OK) return rc;
-    if (!h->stoi_tab) {
-        if (capturing((hipStream_t)stream))
-            FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table is uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
-        float tab[fds::TAB_FLOATS];
-        fds::tables(tab);
-        if ((rc = upload_table(h, who, tab, sizeof(tab), reinterpret_cast<const void **>(&h->stoi_tab))) != FD_OK) return rc;
-    }
+    rc = first_use(h, who, (hipStream_t)stream, "the window and twiddle table", h->stoi_tab,
+                   [] { std::vector<float> t(fds::TAB_FLOATS); fds::tables(t.data()); return t; });
+    if (rc != FD_OK) return rc;
     Scratch &s = h->stoi_scratch;
     if ((rc = reserve(h, who, s, fdk::stoi_scratch_bytes(B, n10, resampled), (hipStream_t)stream)) != FD_OK) return rc;
     const float *table = nullptr;
-    if (resampled && (rc = resample_table(h, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
+    if (resampled && (rc = resample_table(h, who, r, (hipStream_t)stream, &table)) != FD_OK) return rc;
     const fdk::StoiSlots sl10 = fdk::stoi_slots(s.p, B, n10, resampled);
     std::vector<int64_t> lens10;      // each pair's own length at 10 kHz
     if (valid && resampled) {
         lens10.resize(B);
         for (int b = 0; b < B; ++b) lens10[b] = fdr::out_len(valid[b], r);
     }
-    if ((rc = upload_counts(h, lens10.empty() ? valid : lens10.data(), B, sl10.lens, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *lens_dev = nullptr;
+    if ((rc = stage_counts(h, lens10.empty() ? valid : lens10.data(), B, sl10.lens, (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
     fdk::StoiBands bd;
     fds::bands(bd.lo, bd.hi);
     return run(h, stream, who, [&](const fdk::Launch &La) {
@@ -383,7 +416,7 @@ int fd_stoi_measure(fd_handle h, const float *clean, const float *degraded, int 
             }
             x = sl10.x10; y = sl10.y10; pitch = sl10.pitch10;
         }
-        return fdk::stoi(La, x, y, pitch, B, n10, valid ? sl10.lens : nullptr, h->stoi_tab, bd, rec_dev, s.p, resampled);
+        return fdk::stoi(La, x, y, pitch, B, n10, lens_dev, h->stoi_tab, bd, rec_dev, s.p, resampled);
     });
 }
 
@@ -416,12 +449,10 @@ static int pitch_counts(fd_handle h, const char *who, const int64_t *counts, int
 {
     *dev = nullptr;
     if (!counts) return FD_OK;
-    const size_t slot = (sizeof(long long) * 4096 + 255) & ~(size_t)255;      // B <= 4096
+    const size_t slot = fdk::align256(sizeof(long long) * 4096);      // B <= 4096
     const int rc = reserve(h, who, h->pitch_scratch, 2 * slot, stream);
     if (rc != FD_OK) return rc;
-    long long *dst = reinterpret_cast<long long *>(reinterpret_cast<char *>(h->pitch_scratch.p) + which * slot);
-    *dev = dst;
-    return upload_counts(h, counts, B, dst, stream);
+    return stage_counts(h, counts, B, reinterpret_cast<long long *>(reinterpret_cast<char *>(h->pitch_scratch.p) + which * slot), stream, dev);
 }
 
 int fd_pitch_track(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_pitch_config *cfg, float *f0_dev,
@@ -494,25 +525,19 @@ int fd_spectral_measure(fd_handle h, const float *clean, const float *degraded, 
     if ((rc = enter(h)) != FD_OK) return rc;
     const float *tabs[fdx::MAX_RES] = {nullptr, nullptr, nullptr, nullptr};
     for (int r = 0; r < c.n_res; ++r) {
-        const float *&slot = h->spectral_tabs[{c.nfft[r], c.win[r]}];
-        if (!slot) {
-            if (capturing((hipStream_t)stream))
-                FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table of nfft = %d, win = %d is uploaded at the first call that uses it, which cannot happen inside a stream capture: call it once before", who, c.nfft[r], c.win[r]);
-            std::vector<float> tab(fdx::table_floats(c.nfft[r]));
-            fdx::tables(c.nfft[r], c.win[r], tab.data());
-            const void *dev = nullptr;
-            if ((rc = upload_table(h, who, tab.data(), tab.size() * sizeof(float), &dev)) != FD_OK) return rc;      // (a null slot counts as none)
-            slot = static_cast<const float *>(dev);
-        }
+        const float *&slot = h->spectral_tabs[{c.nfft[r], c.win[r]}];      // (a null slot counts as none)
+        char what[96] = "";
+        if (!slot) snprintf(what, sizeof(what), "the window and twiddle table of nfft = %d, win = %d", c.nfft[r], c.win[r]);
+        rc = first_use(h, who, (hipStream_t)stream, what, slot,
+                       [&] { std::vector<float> t(fdx::table_floats(c.nfft[r])); fdx::tables(c.nfft[r], c.win[r], t.data()); return t; });
+        if (rc != FD_OK) return rc;
         tabs[r] = slot;
     }
     Scratch &s = h->spectral_scratch;
     if ((rc = reserve(h, who, s, fdk::spectral_scratch_bytes(B, L, c), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *lens_dev = fdk::spectral_lens_slot(s.p);
-    if ((rc = upload_counts(h, valid, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
-    return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::spectral(La, clean, degraded, L, B, L, valid ? lens_dev : nullptr, c, tabs, rec_dev, s.p);
-    });
+    const long long *lens_dev = nullptr;
+    if ((rc = stage_counts(h, valid, B, fdk::spectral_lens_slot(s.p), (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::spectral(La, clean, degraded, L, B, L, lens_dev, c, tabs, rec_dev, s.p); });
 }
 
 // Griffin-Lim and the mel inversion in front of it (fastdiff_hip_ext.h; lengths, refusals, scratch and counter layout: fd_gl.h, the
@@ -530,24 +555,15 @@ int fd_mel_to_linear(fd_handle h, const float *mel, int B, int T, const float *p
         FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d items (1 .. %d) of T = %d frames (1 .. %d)", who, B, fdgl::MAX_B, T, fdgl::MAX_T);
     if (variant != FD_GL_PWG && variant != FD_GL_TACOTRON) FD_FAIL(h, FD_ERR_INVALID, "%s: unknown variant %d (FD_GL_PWG / FD_GL_TACOTRON)", who, variant);
     const size_t np = (size_t)fdgl::BINS * fdgl::MELS;
-    for (size_t i = 0; i < np; ++i) {                      // (on the bit pattern: this file is built with -fno-honor-nans)
-        uint32_t bits;
-        memcpy(&bits, pinv_513x80 + i, sizeof(bits));
-        if ((bits & 0x7F800000u) == 0x7F800000u) FD_FAIL(h, FD_ERR_INVALID, "%s: element %zu of pinv_513x80 is not finite", who, i);
-    }
+    const long bad = fdn::first_nonfinite(pinv_513x80, np);
+    if (bad >= 0) FD_FAIL(h, FD_ERR_INVALID, "%s: element %zu of pinv_513x80 is not finite", who, (size_t)bad);
     if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
     int rc = enter(h);
     if (rc != FD_OK) return rc;
-    std::vector<float> &host = h->gl_pinv_host[variant];
-    if (!h->gl_pinv[variant] || memcmp(host.data(), pinv_513x80, sizeof(float) * np) != 0) {
-        if (capturing((hipStream_t)stream))
-            FD_FAIL(h, FD_ERR_STATE, "%s: the pseudo-inverse is uploaded at the first call that uses it, which cannot happen inside a stream capture: call it once before", who);
-        const void *dev = nullptr;
-        if ((rc = upload_table(h, who, pinv_513x80, sizeof(float) * np, &dev)) != FD_OK) return rc;
-        h->gl_pinv[variant] = static_cast<const float *>(dev);
-        host.assign(pinv_513x80, pinv_513x80 + np);
-    }
-    const float *P = h->gl_pinv[variant];
+    rc = refresh(h, who, (hipStream_t)stream, "the device copy of this pseudo-inverse", h->gl_pinv[variant], pinv_513x80, np,
+                 [&] { return std::vector<float>(pinv_513x80, pinv_513x80 + np); });
+    if (rc != FD_OK) return rc;
+    const float *P = h->gl_pinv[variant].dev;
     return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::mel_to_linear(La, mel, B, T, P, variant, amp_out); });
 }
 
@@ -561,20 +577,18 @@ int fd_griffin_lim(fd_handle h, const float *amp, const float *angles, int B, in
     int rc = check_counts(h, who, "lens", lens, B, 0, T);
     if (rc != FD_OK) return rc;
     if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
-    if ((rc = enter(h)) != FD_OK) return rc;
-    if (!h->mel[MEL_VARIANTS - 1].tab && capturing((hipStream_t)stream))
-        FD_FAIL(h, FD_ERR_STATE, "%s: the window and twiddle table is uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
-    if ((rc = ensure_mel_tables(h)) != FD_OK) return rc;
+    if ((rc = enter(h)) != FD_OK || (rc = mel_tables_first_use(h, who, (hipStream_t)stream)) != FD_OK) return rc;
     const float *tab = h->mel[0].tab;
     Scratch &s = h->gl_scratch;
     if ((rc = reserve(h, who, s, fdk::gl_scratch_bytes(B, T), (hipStream_t)stream)) != FD_OK) return rc;
     const fdk::GlSlots sl = fdk::gl_slots(s.p, B, T);
-    if ((rc = upload_counts(h, lens, B, sl.lens, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *lens_dev = nullptr, *ids_dev = nullptr;
+    if ((rc = stage_counts(h, lens, B, sl.lens, (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
     static_assert(sizeof(uint64_t) == sizeof(int64_t), "the ids travel as the counts do");
-    if ((rc = upload_counts(h, reinterpret_cast<const int64_t *>(stream_ids), B, reinterpret_cast<long long *>(sl.ids), (hipStream_t)stream)) != FD_OK) return rc;
+    if ((rc = stage_counts(h, reinterpret_cast<const int64_t *>(stream_ids), B, reinterpret_cast<long long *>(sl.ids), (hipStream_t)stream, &ids_dev)) != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::griffin_lim(La, amp, angles, B, T, lens ? sl.lens : nullptr, stream_ids ? sl.ids : nullptr, n_iters, (unsigned long long)seed, tab, wav_out,
-                                wav_pitch, rec_dev, s.p);
+        return fdk::griffin_lim(La, amp, angles, B, T, lens_dev, reinterpret_cast<const unsigned long long *>(ids_dev), n_iters, (unsigned long long)seed, tab,
+                                wav_out, wav_pitch, rec_dev, s.p);
     });
 }
 
@@ -610,33 +624,22 @@ int fd_mel_to_linear_nnls(fd_handle h, const float *mel, int B, int T, const int
     if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
     if ((rc = enter(h)) != FD_OK) return rc;
     fd_context::NnlsBank &nb = h->nnls_bank[variant];
-    const bool new_bank = !nb.tab || memcmp(nb.bank.data(), bank_80x513, sizeof(float) * np) != 0;
-    const bool new_pinv = !nb.pinv_dev || memcmp(nb.pinv.data(), pinv_513x80, sizeof(float) * np) != 0;
-    if ((new_bank || new_pinv) && capturing((hipStream_t)stream))
-        FD_FAIL(h, FD_ERR_STATE, "%s: the bank's tables and the pseudo-inverse are uploaded at the first call that uses them, which cannot happen inside a stream capture: call it once before", who);
-    if (new_bank) {
-        std::vector<float> tab(fdn::table().total);
-        fdn::fill_table(bank_80x513, tab.data());
-        const void *dev = nullptr;
-        if ((rc = upload_table(h, who, tab.data(), sizeof(float) * tab.size(), &dev)) != FD_OK) return rc;
-        nb.tab = static_cast<const float *>(dev);
-        nb.bank.assign(bank_80x513, bank_80x513 + np);
-        nb.L = fdn::step_bound(bank_80x513);
-    }
-    if (new_pinv) {
-        const void *dev = nullptr;
-        if ((rc = upload_table(h, who, pinv_513x80, sizeof(float) * np, &dev)) != FD_OK) return rc;
-        nb.pinv_dev = static_cast<const float *>(dev);
-        nb.pinv.assign(pinv_513x80, pinv_513x80 + np);
-    }
+    const float *const tab_before = nb.bank.dev;      // (inside a capture the first table that is new refuses: neither is uploaded there)
+    rc = refresh(h, who, (hipStream_t)stream, "the device table of this bank", nb.bank, bank_80x513, np,
+                 [&] { std::vector<float> t(fdn::table().total); fdn::fill_table(bank_80x513, t.data()); return t; });
+    if (rc != FD_OK) return rc;
+    if (nb.bank.dev != tab_before) nb.L = fdn::step_bound(bank_80x513);
+    rc = refresh(h, who, (hipStream_t)stream, "the device copy of this pseudo-inverse", nb.pinv, pinv_513x80, np,
+                 [&] { return std::vector<float>(pinv_513x80, pinv_513x80 + np); });
+    if (rc != FD_OK) return rc;
     Scratch &s = h->nnls_scratch;
     if ((rc = reserve(h, who, s, fdk::nnls_scratch_bytes(B, T), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *lens_dev = fdk::nnls_lens_slot(s.p);
-    if ((rc = upload_counts(h, lens, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *lens_dev = nullptr;
+    if ((rc = stage_counts(h, lens, B, fdk::nnls_lens_slot(s.p), (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
     const float step = fdn::step(nb.L);
-    const float *tab = nb.tab, *P = nb.pinv_dev;
+    const float *tab = nb.bank.dev, *P = nb.pinv.dev;
     return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::mel_to_linear_nnls(La, mel, B, T, lens ? lens_dev : nullptr, P, tab, step, variant, n_iters, amp_out, rec_dev, s.p);
+        return fdk::mel_to_linear_nnls(La, mel, B, T, lens_dev, P, tab, step, variant, n_iters, amp_out, rec_dev, s.p);
     });
 }
 
@@ -678,19 +681,12 @@ int64_t fd_mcd_frames(int64_t n)
     return fdm::frames(n);
 }
 
-// the front-end's tables and the DCT table, made at the first call (never inside a capture)
+// the front-end's tables and the DCT table
 static int mcd_tables(fd_handle h, const char *who, hipStream_t stream)
 {
-    if ((!h->mel[MEL_VARIANTS - 1].tab || !h->mcd_dct) && capturing(stream))
-        FD_FAIL(h, FD_ERR_STATE, "%s: the front-end's tables and the DCT table are uploaded at the first call, which cannot happen inside a stream capture: call it once before", who);
-    int rc = ensure_mel_tables(h);
-    if (rc != FD_OK) return rc;
-    if (!h->mcd_dct) {
-        std::vector<float> tab((size_t)fdm::MAX_COEF * fdm::MELS);
-        fdm::dct_table(tab.data());
-        if ((rc = upload_table(h, who, tab.data(), sizeof(float) * tab.size(), reinterpret_cast<const void **>(&h->mcd_dct))) != FD_OK) return rc;
-    }
-    return FD_OK;
+    const int rc = mel_tables_first_use(h, who, stream);
+    return rc != FD_OK ? rc : first_use(h, who, stream, "the DCT table", h->mcd_dct,
+                                        [] { std::vector<float> t((size_t)fdm::MAX_COEF * fdm::MELS); fdm::dct_table(t.data()); return t; });
 }
 
 int fd_cepstra(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int n_coef, float *cep_out, int64_t T_pitch, void *stream)
@@ -708,9 +704,9 @@ int fd_cepstra(fd_handle h, const float *wav, int B, int64_t L, const int64_t *v
     if ((rc = enter(h)) != FD_OK || (rc = mcd_tables(h, who, (hipStream_t)stream)) != FD_OK) return rc;
     Scratch &s = h->mcd_scratch;
     if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(1, 0, 0, 0, 0), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *lens_dev = fdk::mcd_count_slot(s.p, 0);
-    if ((rc = upload_counts(h, valid, B, lens_dev, (hipStream_t)stream)) != FD_OK) return rc;
-    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::cepstra(La, wav, B, L, valid ? lens_dev : nullptr, n_coef, h->mcd_dct, cep_out, T_pitch); });
+    const long long *lens_dev = nullptr;
+    if ((rc = stage_counts(h, valid, B, fdk::mcd_count_slot(s.p, 0), (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::cepstra(La, wav, B, L, lens_dev, n_coef, h->mcd_dct, cep_out, T_pitch); });
 }
 
 int fd_dtw(fd_handle h, const float *a, const float *b, int B, int D, int64_t ld, int64_t pitch_a, int64_t pitch_b, const int64_t *frames_a,
@@ -734,12 +730,11 @@ int fd_dtw(fd_handle h, const float *a, const float *b, int B, int D, int64_t ld
     FD_HIP(h, hipSetDevice(h->device));      // no settle: the features are the caller's, and the alignment touches no sampler state
     Scratch &s = h->mcd_scratch;
     if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(B, pitch_b, code_stride, 0, 0), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *fa_dev = fdk::mcd_count_slot(s.p, 2), *fb_dev = fdk::mcd_count_slot(s.p, 3);
-    if ((rc = upload_counts(h, frames_a, B, fa_dev, (hipStream_t)stream)) != FD_OK) return rc;
-    if ((rc = upload_counts(h, frames_b, B, fb_dev, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *fa_dev = nullptr, *fb_dev = nullptr;
+    if ((rc = stage_counts(h, frames_a, B, fdk::mcd_count_slot(s.p, 2), (hipStream_t)stream, &fa_dev)) != FD_OK) return rc;
+    if ((rc = stage_counts(h, frames_b, B, fdk::mcd_count_slot(s.p, 3), (hipStream_t)stream, &fb_dev)) != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) {
-        return fdk::dtw(La, a, b, B, D, ld, pitch_a, pitch_b, frames_a ? fa_dev : nullptr, frames_b ? fb_dev : nullptr, rec_dev, align_out, align_pitch,
-                        code_stride, s.p);
+        return fdk::dtw(La, a, b, B, D, ld, pitch_a, pitch_b, fa_dev, fb_dev, rec_dev, align_out, align_pitch, code_stride, s.p);
     });
 }
 
@@ -761,17 +756,14 @@ int fd_mcd_measure(fd_handle h, const float *clean, int64_t Lc, const float *deg
     const int64_t Tc = fdm::frames(Lc), Td = fdm::frames(Ld), fl_a = (int64_t)B * Tc * D, fl_b = (int64_t)B * Td * D;
     Scratch &s = h->mcd_scratch;
     if ((rc = reserve(h, who, s, fdk::mcd_scratch_bytes(B, Td, 0, fl_a, fl_b), (hipStream_t)stream)) != FD_OK) return rc;
-    long long *slot[4];
-    for (int q = 0; q < 4; ++q) slot[q] = fdk::mcd_count_slot(s.p, q);
     std::vector<int64_t> fa, fb;      // each pair's own frames
     if (valid_clean) { fa.resize(B); for (int b = 0; b < B; ++b) fa[b] = fdm::frames(valid_clean[b]); }
     if (valid_degraded) { fb.resize(B); for (int b = 0; b < B; ++b) fb[b] = fdm::frames(valid_degraded[b]); }
-    if ((rc = upload_counts(h, valid_clean, B, slot[0], (hipStream_t)stream)) != FD_OK) return rc;
-    if ((rc = upload_counts(h, valid_degraded, B, slot[1], (hipStream_t)stream)) != FD_OK) return rc;
-    if ((rc = upload_counts(h, valid_clean ? fa.data() : nullptr, B, slot[2], (hipStream_t)stream)) != FD_OK) return rc;
-    if ((rc = upload_counts(h, valid_degraded ? fb.data() : nullptr, B, slot[3], (hipStream_t)stream)) != FD_OK) return rc;
-    const long long *na = valid_clean ? slot[0] : nullptr, *nb = valid_degraded ? slot[1] : nullptr;
-    const long long *fa_dev = valid_clean ? slot[2] : nullptr, *fb_dev = valid_degraded ? slot[3] : nullptr;
+    const int64_t *const counts[4] = {valid_clean, valid_degraded, valid_clean ? fa.data() : nullptr, valid_degraded ? fb.data() : nullptr};
+    const long long *dev[4];
+    for (int q = 0; q < 4; ++q)
+        if ((rc = stage_counts(h, counts[q], B, fdk::mcd_count_slot(s.p, q), (hipStream_t)stream, &dev[q])) != FD_OK) return rc;
+    const long long *na = dev[0], *nb = dev[1], *fa_dev = dev[2], *fb_dev = dev[3];
     float *ca = fdk::mcd_cep_slot(s.p, B, Td, 0, fl_a, fl_b, 0), *cb = fdk::mcd_cep_slot(s.p, B, Td, 0, fl_a, fl_b, 1);
     fd_dtw_rec *wrec = fdk::mcd_rec_slot(s.p, B, Td, 0);
     return run(h, stream, who, [&](const fdk::Launch &La) {
@@ -807,7 +799,7 @@ int fd_trim_mask(const uint8_t *speech, int64_t M, int average_width, int max_si
 
 // what the two device entry points check and prepare alike: the batch, the window grid, the counts on the device
 static int trim_enter(fd_handle h, const char *who, const float *wav, int B, int64_t L, const int64_t *valid, int rate, int window_ms, void *stream,
-                      int64_t *W, int64_t *Mp, int64_t *M_grid, long long **valid_dev)
+                      int64_t *W, int64_t *Mp, int64_t *M_grid, const long long **valid_dev)
 {
     if (!h) return FD_ERR_INVALID;
     if (!wav) FD_FAIL(h, FD_ERR_INVALID, "%s: null wav", who);
@@ -823,8 +815,7 @@ static int trim_enter(fd_handle h, const char *who, const float *wav, int B, int
     fdtr::windows(longest, rate, window_ms, nullptr, M_grid);
     Scratch &s = h->trim_scratch;
     if ((rc = reserve(h, who, s, fdk::trim_scratch_bytes(B, *Mp), (hipStream_t)stream)) != FD_OK) return rc;
-    *valid_dev = valid ? fdk::trim_valid_slot(s.p) : nullptr;
-    return upload_counts(h, valid, B, fdk::trim_valid_slot(s.p), (hipStream_t)stream);
+    return stage_counts(h, valid, B, fdk::trim_valid_slot(s.p), (hipStream_t)stream, valid_dev);
 }
 
 int fd_trim_levels(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, int sample_rate, int window_ms, double *levels_out,
@@ -833,7 +824,7 @@ int fd_trim_levels(fd_handle h, const float *wav, int B, int64_t L, const int64_
     const char *who = "fd_trim_levels";
     if (h && !levels_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null levels_out", who);
     int64_t W = 0, Mp = 0, M_grid = 0;
-    long long *valid_dev = nullptr;
+    const long long *valid_dev = nullptr;
     const int rc = trim_enter(h, who, wav, B, L, valid, sample_rate, window_ms, stream, &W, &Mp, &M_grid, &valid_dev);
     if (rc != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) { return fdk::trim_levels(La, wav, B, L, valid_dev, W, Mp, levels_out, Mp, true); });
@@ -855,7 +846,7 @@ int fd_trim_silences(fd_handle h, const float *wav, int B, int64_t L, const int6
         if (a0 < b0 + bytes && b0 < a0 + bytes) FD_FAIL(h, FD_ERR_INVALID, "%s: out overlaps wav (the compaction is not done in place)", who);
     }
     int64_t W = 0, Mp = 0, M_grid = 0;
-    long long *valid_dev = nullptr;
+    const long long *valid_dev = nullptr;
     const int rc = trim_enter(h, who, wav, B, L, valid, p.sample_rate, p.window_ms, stream, &W, &Mp, &M_grid, &valid_dev);
     if (rc != FD_OK) return rc;
     return run(h, stream, who, [&](const fdk::Launch &La) {

@@ -212,7 +212,7 @@ struct Workspace {
 struct ProfEntry { std::string name; hipEvent_t e0, e1; };
 struct Scratch { float *p = nullptr; size_t bytes = 0; };      // a device buffer of the handle that grows on demand
 
-// Constant tables of the mel front-end (fd_kernels_mel.hip), built in double precision at fd_create.
+// Constant tables of the mel front-end (fd_kernels_mel.hip; fd_griffin_lim and the MCD read them too), built in double precision at the first call that needs them.
 struct MelTables {
     const float *tab = nullptr;      // cos[1024], sin[1024] of 2*pi*i/1024, periodic Hann window [1024]
     const int *fb_lo = nullptr, *fb_n = nullptr, *fb_off = nullptr;      // per mel filter: first FFT bin, #bins, offset into fb_w
@@ -289,9 +289,13 @@ struct fd_context {
     int mel_variant = MEL_PWG;               // option "mel"
     std::vector<float> mel_bank[MEL_VARIANTS];   // the dense [80][513] bank each front-end uses (host copy: fd_get_mel_filterbank)
     bool mel_bank_user[MEL_VARIANTS] = {false, false};   // supplied through fd_set_mel_filterbank (else the restated default)
-    std::vector<void *> tables;               // every constant table uploaded so far (mel, resampler, STOI, spectral): owned here, freed at fd_destroy
-    struct ResampleTable { int up, down; const float *dev; };
-    std::vector<ResampleTable> resample_tabs; // fd_resample's polyphase tables, one per reduced ratio used so far (`dev` is in `tables`)
+    // Every constant table uploaded so far, owned here and freed at fd_destroy (fd_api_ext.cpp: upload_table): mel, resampler ratios,
+    // STOI, spectral, the pseudo-inverses of both mel inversions, NNLS banks, the MCD's DCT.  The members that point into it are made at
+    // the first call that needs them, never inside a stream capture (first_use / refresh; but see ensure_mel_tables).
+    std::vector<void *> tables;
+    // a table keyed on the caller's host values: the values last uploaded and their device image (refresh: made again when they differ)
+    struct KeyedTable { std::vector<float> host; const float *dev = nullptr; };
+    std::map<std::pair<int, int>, const float *> resample_tabs;      // fd_resample's polyphase tables by reduced ratio (up, down); fd_stoi_measure's too
     int last_B = 0, last_T = 0;
     hipStream_t cap_stream = nullptr;
     // Calls on one handle share the workspace, the embedding rows and the pending range check: they are ordered by the stream they run
@@ -379,22 +383,19 @@ struct fd_context {
     long long n_span_batches = 0, n_span_windows = 0;   // fd_get_counter: fd_sample calls / windows made by the span entry points
     Scratch loud_scratch;                    // fd_loudness_measure / _normalize: peak words, lengths, tile states, partial sums, block powers
     Scratch stoi_scratch;                    // fd_stoi_measure: lengths, the 10 kHz signals, frame energies, src, band amplitudes, segment partials
-    const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables), uploaded at the first call (in `tables`)
+    const float *stoi_tab = nullptr;         // its window and twiddles (csrc/fd_stoi.h: tables)
     Scratch pitch_scratch;                   // fd_pitch_track / _compare: the device copies of valid [B] and frames [B]
     Scratch spectral_scratch;                // fd_spectral_measure: lengths, then the frame partials of every resolution
-    std::map<std::pair<int, int>, const float *> spectral_tabs;      // its window and twiddles by (nfft, win) (csrc/fd_spectral.h: tables), each uploaded at the first call that uses it (in `tables`)
+    std::map<std::pair<int, int>, const float *> spectral_tabs;      // its window and twiddles by (nfft, win) (csrc/fd_spectral.h: tables)
     Scratch gl_scratch;                      // fd_griffin_lim: lengths, stream ids, transposed amplitudes, two frame buffers, frame sums (csrc/fd_gl.h: layout)
-    const float *gl_pinv[MEL_VARIANTS] = {nullptr, nullptr};      // fd_mel_to_linear: the pseudo-inverse [513][80] last used with each variant (in `tables`) ...
-    std::vector<float> gl_pinv_host[MEL_VARIANTS];                // ... and its values, to tell a new one
+    KeyedTable gl_pinv[MEL_VARIANTS];        // fd_mel_to_linear: the pseudo-inverse [513][80] last used with each variant
     Scratch nnls_scratch;                    // fd_mel_to_linear_nnls: lengths and frame sums (csrc/fd_nnls.h: layout)
-    struct NnlsBank {                        // ... per variant: the bank and P last used, the device table of the bank (fdn::table) and copy of P (in `tables`), L
-        std::vector<float> bank, pinv;
-        const float *tab = nullptr, *pinv_dev = nullptr;
-        double L = 0.0;
-    } nnls_bank[MEL_VARIANTS];
+    // ... per variant: the bank last used with its device table (fdn::table) and L, and the pseudo-inverse last used.  Its own slots, apart
+    // from gl_pinv: callers of the two inversions that alternate with different matrices would otherwise upload at every call.
+    struct NnlsBank { KeyedTable bank, pinv; double L = 0.0; } nnls_bank[MEL_VARIANTS];
     Scratch bins_scratch;                    // fd_bins_pass: per chunk the counts, inertia, moved, nonfinite and sums (csrc/fd_bins.h: layout)
     Scratch mcd_scratch;                     // fd_cepstra / fd_dtw / fd_mcd_measure: counts, bottom rows, direction codes, records, cepstra (fd_kernels_mcd.hip: layout)
-    const float *mcd_dct = nullptr;          // their DCT table [40][80] (csrc/fd_mcd.h: dct_table), uploaded at the first call (in `tables`)
+    const float *mcd_dct = nullptr;          // their DCT table [40][80] (csrc/fd_mcd.h: dct_table); their front-end's tables: `mel`
     Scratch trim_scratch;                    // fd_trim_silences / fd_trim_levels: lengths, window levels, prefix tables (fd_kernels_trim.hip: layout)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;

@@ -345,6 +345,51 @@ def test_two_runs_and_every_layout_give_the_same_bits(N, D, K, ld, off):
 
 
 @gpu
+def test_a_first_call_inside_a_capture_is_refused_and_a_later_one_replays(N=5, D=4, K=2):
+    """fastdiff_hip_ext.h: the scratch buffer grows at the first call that needs more, never inside a stream capture.  Assignment and
+    record only."""
+    import gpu_common
+    m = gpu_common.make_model()                            # a handle of its own: no scratch yet
+    lib, h = m._ready(torch.device("cuda"))
+    rng = np.random.default_rng(31)
+    xa, xb = (torch.from_numpy(rng.standard_normal((N, D)).astype(np.float32)).cuda() for _ in range(2))
+    cent = torch.from_numpy(rng.standard_normal((K, D)).astype(np.float32)).cuda()
+    x = xa.clone()
+
+    def outputs():
+        return torch.full((N,), -1, device="cuda", dtype=torch.int32), torch.zeros((dv.RECORD.itemsize,), device="cuda", dtype=torch.uint8)
+
+    def call(rows, assign, rec):
+        return lib.fd_bins_pass(h, rows.data_ptr(), N, D, D, None, None, cent.data_ptr(), K, assign.data_ptr(), None, rec.data_ptr(), m._stream(rows.device))
+
+    assign, rec = outputs()
+    torch.cuda.synchronize()
+    first = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(first):
+        x.mul_(1.0)                                        # (so that the capture is not empty)
+        rc = call(x, assign, rec)
+        msg = lib.fd_last_error(h)
+    assert rc == _capi.FD_ERR_STATE and b"stream capture" in msg, (rc, msg)
+    torch.cuda.synchronize()
+    want = []
+    for rows in (xa, xb):                                  # outside: the scratch buffer
+        a, r = outputs()
+        _capi.check(lib, h, call(rows, a, r), "fd_bins_pass")
+        want.append((a, r))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _capi.check(lib, h, call(x, assign, rec), "fd_bins_pass")
+    for src, (a, r) in zip((xa, xb), want):
+        x.copy_(src)
+        assign.fill_(-1)                                   # (the previous assignments are an input: `moved` counts against them)
+        rec.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(assign, a) and torch.equal(rec, r) and int(dv._record(rec, K)["counts"].sum()) == N
+    assert not torch.equal(want[0][0], want[1][0]) or not torch.equal(want[0][1], want[1][1])
+
+
+@gpu
 def test_rows_that_are_not_finite_are_left_out_and_touch_nothing_else():
     N, D, K = 257, 80, 33
     x, shift, scale, cent, prev, z = inputs(N, D, K)

@@ -238,3 +238,20 @@ def test_pointer_arrays_structures_and_host_tables_are_looked_into():
     rep = guarded.run_case(case, "cpu", lib)
     assert rep.unguarded == [("fd_fake_multi", 3), ("fd_fake_items", 1), ("fd_adamw_multi", 1)], rep.unguarded
     assert rep.calls == {"fd_fake_multi": 2, "fd_fake_items": 2, "fd_adamw_multi": 2}
+
+
+def test_the_case_registry_is_whole_after_one_import_and_no_case_module_is_left_out():
+    """tests/guarded_suite.py: importing it alone registers every case -- at least the 115 names of tests/golden/guarded_cases.txt, each
+    once -- and every tests/guarded_cases_*.py on disk is in its import list, so a case module nobody imports fails here, without a GPU."""
+    import glob
+    import os
+
+    from conftest import GOLD
+    import guarded_suite as gs
+    names = open(os.path.join(GOLD, "guarded_cases.txt")).read().split()
+    assert len(names) == len(set(names)) >= 115
+    assert not [n for n in names if n not in gs.CASES], "cases that are gone"
+    with pytest.raises(AssertionError):                    # a name registers once
+        gs.case(names[0])(lambda g: {})
+    on_disk = {os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "guarded_cases_*.py"))}
+    assert on_disk == set(gs.CASE_MODULES) == {fn.__module__ for fn, _, _ in gs.CASES.values()}

@@ -277,6 +277,40 @@ def test_refusals_leave_a_message():
     torch.cuda.synchronize()
 
 
+@pytest.mark.gpu
+def test_a_first_call_inside_a_capture_is_refused_and_a_later_one_replays():
+    """fastdiff_hip_ext.h: a ratio's table is made at its first use, never inside a stream capture."""
+    import gpu_common
+    m = gpu_common.make_model()                            # a handle of its own: no table of any ratio yet
+    lib, h = m._ready(torch.device("cuda"))
+    pair, n = (48000, 22050), 64
+    n_out = rs.out_len(n, *pair)
+    rng = np.random.default_rng(21)
+    xa, xb = (torch.from_numpy(rng.standard_normal((1, n)).astype(np.float32)).cuda() for _ in range(2))
+    x, y = xa.clone(), torch.zeros((1, n_out), device="cuda")
+
+    def call():
+        return lib.fd_resample(h, x.data_ptr(), _capi.FD_PCM_F32, 1, 1, n, n, None, *pair, y.data_ptr(), n_out, m._stream(x.device))
+
+    torch.cuda.synchronize()
+    first = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(first):
+        x.mul_(1.0)                                        # (so that the capture is not empty)
+        rc = call()
+        msg = lib.fd_last_error(h)
+    assert rc == _capi.FD_ERR_STATE and b"stream capture" in msg, (rc, msg)
+    torch.cuda.synchronize()
+    want_a, want_b = m.resample(xa, *pair), m.resample(xb, *pair)      # outside: the table
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _capi.check(lib, h, call(), "fd_resample")
+    for src, want in ((xa, want_a), (xb, want_b)):
+        x.copy_(src)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert want.shape == y.shape and torch.equal(y, want)
+
+
 @pytest.fixture(scope="module")
 def model():
     import gpu_common

@@ -332,6 +332,40 @@ def test_the_call_captures_and_replays_to_the_same_bits(model, rate=22050):
 
 
 @pytest.mark.gpu
+def test_a_first_levels_call_inside_a_capture_is_refused_and_a_later_one_replays(rate=8000, window_ms=10):
+    """fastdiff_hip_ext.h: the scratch buffer grows at the first call that needs more, never inside a stream capture."""
+    import gpu_common
+    m = gpu_common.make_model()                            # a handle of its own: no scratch yet
+    lib, h = m._ready(torch.device("cuda"))
+    n = 2 * 80 + 3                                         # two windows and three samples
+    xa, xb = (torch.from_numpy(signal_of(s, rate, n).copy()).cuda().reshape(1, n) for s in (1, 9))
+    x = xa.clone()
+    lv = torch.zeros((1, tr.windows(n, rate, window_ms)[1]), device="cuda", dtype=torch.float64)
+
+    def call():
+        return lib.fd_trim_levels(h, x.data_ptr(), 1, n, None, rate, window_ms, lv.data_ptr(), m._stream(x.device))
+
+    torch.cuda.synchronize()
+    first = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(first):
+        x.mul_(1.0)                                        # (so that the capture is not empty)
+        rc = call()
+        msg = lib.fd_last_error(h)
+    assert rc == _capi.FD_ERR_STATE and b"stream capture" in msg, (rc, msg)
+    torch.cuda.synchronize()
+    want_a, want_b = (m.trim_levels(t, sample_rate=rate, window_ms=window_ms) for t in (xa, xb))      # outside: the scratch buffer
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _capi.check(lib, h, call(), "fd_trim_levels")
+    for src, want in ((xa, want_a), (xb, want_b)):
+        x.copy_(src)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert want.shape == lv.shape and torch.equal(lv.view(torch.uint8), want.view(torch.uint8))
+    assert not torch.equal(want_a, want_b)
+
+
+@pytest.mark.gpu
 def test_refusals_leave_a_message(model):
     lib, h = model._ready(torch.device("cuda"))
     x = torch.zeros(2, 9000, device="cuda")
