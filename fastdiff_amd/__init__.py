@@ -42,7 +42,7 @@ fastdiff_amd.diversity fits k-means bins over the corpus' mel frames on the devi
 them with NDB and JSD, the paper's two diversity columns; infer --ndb_bins writes the row (fastdiff_amd/diversity.py).
 """
 from .model import FastDiff  # noqa: F401
-from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, mcd, trim, griffin_lim, diversity  # noqa: F401
+from . import sampler, schedules, resample, loudness, stoi, pitch, spectral, mcd, trim, griffin_lim, diversity, pwg  # noqa: F401
 from . import sampler as util  # noqa: F401  (the reference module is called util)
 from .lvc_op import location_variable_convolution, gated_residual, kernel_conv1d, conv32  # noqa: F401
 from .trainstep import TrainStep  # noqa: F401
@@ -55,5 +55,5 @@ from .longform import StreamPool, SampleStream  # noqa: F401
 from .sampler import (compute_hyperparams_given_schedule, sampling_given_noise_schedule, noise_scheduling,  # noqa: F401
                    map_noise_scale_to_time_step, calc_diffusion_step_embedding, std_normal, theta_timestep_loss, phi_loss, calc_diffusion_hyperparams)
 
-__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "mcd", "trim", "griffin_lim", "diversity", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
+__all__ = ["FastDiff", "TrainStep", "TrainCorpus", "Validator", "ParamEMA", "NoisePredictor", "PhiStep", "StreamPool", "SampleStream", "location_variable_convolution", "gated_residual", "kernel_conv1d", "conv32", "util", "schedules", "resample", "loudness", "stoi", "pitch", "spectral", "mcd", "trim", "griffin_lim", "diversity", "pwg", "compute_hyperparams_given_schedule", "sampling_given_noise_schedule",
            "noise_scheduling", "map_noise_scale_to_time_step", "calc_diffusion_step_embedding", "std_normal", "theta_timestep_loss", "phi_loss", "calc_diffusion_hyperparams"]

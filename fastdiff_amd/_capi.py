@@ -28,6 +28,8 @@ FD_MCD_OK, FD_MCD_SHORT, FD_MCD_NONFINITE = 0, 1, 2
 FD_TRIM_CHUNK = 256                                       # fastdiff_hip_ext.h: windows of one utterance per pass of fd_trim_silences' mask kernel
 FD_TRIM_OK, FD_TRIM_SILENT, FD_TRIM_EMPTY = 0, 1, 2
 FD_TRIM_LONG, FD_TRIM_EDGES = 0, 1
+FD_PWG_TILE, FD_PWG_PHILOX_STREAM, FD_PWG_MAX_LAYERS, FD_PWG_MAX_DILATION, FD_PWG_MAX_CONTEXT, FD_PWG_MAX_SCALES, FD_PWG_MAX_SCALE, FD_PWG_MAX_HOP, FD_PWG_MAX_FRAMES = 512, 0xFFFFFFF7, 30, 512, 4, 4, 16, 512, 32768      # fastdiff_hip_ext.h: samples per workgroup of fd_pwg_generate's layer kernel, the Philox stream word of its z, the caps of a configuration and of T
+FD_PWG_CONV_IN_UPSAMPLE, FD_PWG_UPSAMPLE, FD_PWG_MELGAN = 0, 1, 2
 
 
 class FdConfig(ct.Structure):
@@ -84,6 +86,21 @@ class FdTrimParams(ct.Structure):
                 ("mode", ct.c_int32), ("reserved", ct.c_int32), ("top_db", ct.c_double), ("floor_db", ct.c_double)]
 
 
+class FdPwgConfig(ct.Structure):
+    _fields_ = [(k, ct.c_int32) for k in ("in_channels", "out_channels", "kernel_size", "layers", "stacks", "residual_channels", "gate_channels",
+                                          "skip_channels", "aux_channels", "aux_context_window", "bias", "use_causal_conv",
+                                          "upsample_conditional_features", "use_pitch_embed", "use_nsf", "upsample_net", "n_scales")] + \
+               [("upsample_scales", ct.c_int32 * 8), ("upsample_activation", ct.c_int32), ("interpolate_nearest", ct.c_int32),
+                ("freq_axis_kernel_size", ct.c_int32)]
+
+
+def float_ptr(t):
+    """A tensor's or a numpy array's address (None: NULL) as the float pointer the fd_pwg_* entry points declare."""
+    if t is None:
+        return None
+    return ct.cast(t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data, ct.POINTER(ct.c_float))
+
+
 def step_table(rows):
     """[{t, c_eps, c_div, sigma, c1, c2, c3, add_noise}] (executed first -> last) -> the fd_step array fd_sample takes."""
     steps = (FdStep * len(rows))()
@@ -94,7 +111,7 @@ def step_table(rows):
 
 
 EXPORTS = ["fd_default_config", "fd_create", "fd_destroy", "fd_last_error", "fd_set_weight", "fd_commit_weights",
-           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_resample_out_len", "fd_resample_taps", "fd_resample", "fd_loudness_design", "fd_loudness_blocks", "fd_loudness_measure", "fd_loudness_normalize", "fd_stoi_bands", "fd_stoi_frames", "fd_stoi_measure", "fd_pitch_default_config", "fd_pitch_lags", "fd_pitch_frames", "fd_pitch_track", "fd_pitch_compare", "fd_spectral_default_config", "fd_spectral_frames", "fd_spectral_measure", "fd_gl_samples", "fd_gl_default_iters", "fd_mel_to_linear", "fd_griffin_lim", "fd_nnls_default_iters", "fd_nnls_step_bound", "fd_mel_to_linear_nnls", "fd_bins_chunk", "fd_bins_record_bytes", "fd_bins_pass", "fd_mcd_default_config", "fd_mcd_frames", "fd_cepstra", "fd_dtw", "fd_mcd_measure", "fd_trim_default_params", "fd_trim_windows", "fd_trim_mask", "fd_trim_levels", "fd_trim_silences", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_bandpool_forward", "fd_bandpool_backward", "fd_npred_head_forward", "fd_npred_head_backward", "fd_phi_draw", "fd_phi_residual_forward", "fd_sched_init", "fd_sched_begin", "fd_sched_update", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
+           "fd_forward", "fd_sample", "fd_sample_check", "fd_sample_ticket", "fd_sample_settle", "fd_set_noise_streams", "fd_sample_halo_frames", "fd_sample_span", "fd_sample_spans_plan", "fd_sample_spans", "fd_mel_ring_append", "fd_peak_normalize_int16", "fd_peak_normalize_int16_ragged", "fd_mel_spectrogram", "fd_set_mel_filterbank", "fd_get_mel_filterbank", "fd_resample_out_len", "fd_resample_taps", "fd_resample", "fd_loudness_design", "fd_loudness_blocks", "fd_loudness_measure", "fd_loudness_normalize", "fd_stoi_bands", "fd_stoi_frames", "fd_stoi_measure", "fd_pitch_default_config", "fd_pitch_lags", "fd_pitch_frames", "fd_pitch_track", "fd_pitch_compare", "fd_spectral_default_config", "fd_spectral_frames", "fd_spectral_measure", "fd_gl_samples", "fd_gl_default_iters", "fd_mel_to_linear", "fd_griffin_lim", "fd_nnls_default_iters", "fd_nnls_step_bound", "fd_mel_to_linear_nnls", "fd_bins_chunk", "fd_bins_record_bytes", "fd_bins_pass", "fd_mcd_default_config", "fd_mcd_frames", "fd_cepstra", "fd_dtw", "fd_mcd_measure", "fd_trim_default_params", "fd_trim_windows", "fd_trim_mask", "fd_trim_levels", "fd_trim_silences", "fd_pwg_default_config", "fd_pwg_samples", "fd_pwg_receptive_field", "fd_pwg_create", "fd_pwg_set_weight", "fd_pwg_commit", "fd_pwg_set_scaler", "fd_pwg_generate", "fd_pwg_draw", "fd_pwg_destroy", "fd_lvc_forward", "fd_lvc_backward", "fd_lvc_forward_strided", "fd_lvc_backward_strided", "fd_gate_forward", "fd_gate_backward", "fd_kconv_forward", "fd_kconv_backward", "fd_weight_norm_multi_forward", "fd_weight_norm_multi_backward", "fd_refresh_weights_device", "fd_get_weight_image", "fd_get_weight_flags", "fd_pack_source", "fd_fan_forward", "fd_fan_backward", "fd_input_conv_forward", "fd_input_conv_backward", "fd_kconv_backward_w_multi", "fd_kconv_forward_act_multi", "fd_kconv_backward_x_multi", "fd_input_conv_forward_multi", "fd_input_conv_backward_multi", "fd_kconv_forward_act", "fd_kconv_backward_act", "fd_kconv_forward_frames", "fd_kconv_backward_frames", "fd_lvc_forward_frames", "fd_lvc_backward_frames", "fd_conv32_forward", "fd_conv32_backward", "fd_weight_norm_forward", "fd_weight_norm_backward", "fd_conv7_forward", "fd_conv7_backward", "fd_upsample_forward", "fd_upsample_backward", "fd_train_draw", "fd_train_collate", "fd_eval_collate", "fd_item_distance", "fd_eval_accumulate", "fd_mse_forward", "fd_mse_backward", "fd_adamw_multi", "fd_ema_multi", "fd_bandpool_forward", "fd_bandpool_backward", "fd_npred_head_forward", "fd_npred_head_backward", "fd_phi_draw", "fd_phi_residual_forward", "fd_sched_init", "fd_sched_begin", "fd_sched_update", "fd_set_option", "fd_read_tap", "fd_kernel_index", "fd_bias_index",
            "fd_get_profile", "fd_reset_profile", "fd_get_counter", "fd_version", "fd_abi_revision"]
 
 _lib = None
@@ -190,6 +207,21 @@ def load():
     lib.fd_trim_mask.argtypes = [vp, ct.c_int64, ci, ci, ci, vp]
     lib.fd_trim_levels.argtypes = [vp, vp, ci, ct.c_int64, vp, ci, ci, vp, vp]
     lib.fd_trim_silences.argtypes = [vp, vp, ci, ct.c_int64, vp, ct.POINTER(FdTrimParams), vp, vp, vp, vp, vp]
+    lib.fd_pwg_default_config.argtypes = [ct.POINTER(FdPwgConfig)]
+    lib.fd_pwg_default_config.restype = None
+    lib.fd_pwg_samples.argtypes = [ct.POINTER(FdPwgConfig), ct.c_int64]
+    lib.fd_pwg_samples.restype = ct.c_int64
+    lib.fd_pwg_receptive_field.argtypes = [ct.POINTER(FdPwgConfig)]
+    lib.fd_pwg_receptive_field.restype = ct.c_int64
+    lib.fd_pwg_create.argtypes = [vp, ct.POINTER(FdPwgConfig), ct.POINTER(vp)]
+    # (float pointers, host or device, are declared as such: pwg.py casts tensors' addresses)
+    fp = ct.POINTER(ct.c_float)
+    lib.fd_pwg_set_weight.argtypes = [vp, ct.c_char_p, fp, ct.c_int64]
+    lib.fd_pwg_commit.argtypes = [vp]
+    lib.fd_pwg_set_scaler.argtypes = [vp, fp, fp]
+    lib.fd_pwg_generate.argtypes = [vp, fp, ci, ci, ci, ct.POINTER(ct.c_int64), fp, ct.c_uint64, ct.POINTER(ct.c_uint64), fp, ct.c_int64, vp]
+    lib.fd_pwg_draw.argtypes = [vp, ci, ct.c_int64, ct.c_uint64, ct.POINTER(ct.c_uint64), fp, ct.c_int64, vp]
+    lib.fd_pwg_destroy.argtypes = [vp]
     lib.fd_lvc_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     lib.fd_lvc_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.fd_lvc_forward_strided.argtypes = [vp, vp, vp, ct.c_int64, vp, ci, ci, ci, ci, ci, ci, vp, vp]

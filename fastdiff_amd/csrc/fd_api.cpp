@@ -207,7 +207,7 @@ static void release_handle(fd_context *h)
     if (h->refresh_bad) hipHostFree(h->refresh_bad);
     if (h->refresh_done) hipEventDestroy(h->refresh_done);
     if (h->scratch) hipFree(h->scratch);
-    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->ring_scratch, &h->step_scratch, &h->loud_scratch, &h->stoi_scratch, &h->pitch_scratch, &h->spectral_scratch, &h->gl_scratch, &h->nnls_scratch, &h->bins_scratch, &h->mcd_scratch, &h->trim_scratch})
+    for (Scratch *s : {&h->lvc_scratch, &h->kconv_scratch, &h->cconv_scratch, &h->span_scratch, &h->ring_scratch, &h->step_scratch, &h->loud_scratch, &h->stoi_scratch, &h->pitch_scratch, &h->spectral_scratch, &h->gl_scratch, &h->nnls_scratch, &h->bins_scratch, &h->mcd_scratch, &h->trim_scratch, &h->pwg_scratch})
         if (s->p) hipFree(s->p);
     for (auto &sl : h->stage) {
         if (sl.host) hipHostFree(sl.host);

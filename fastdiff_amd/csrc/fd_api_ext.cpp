@@ -2,17 +2,21 @@
 // conversion (fd_resample), the cutting of long silences (fd_trim_*).  Behind it: the int16 epilogue, BS.1770 loudness (fd_loudness_*).
 // Scores against a recording: STOI / ESTOI (fd_stoi_*), F0 and the pitch scores (fd_pitch_*), the STFT distances (fd_spectral_*), MCD with
 // its alignment (fd_cepstra, fd_dtw, fd_mcd_measure); against a corpus: the k-means bin pass under NDB / JSD (fd_bins_pass).  The baseline
-// vocoder: fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls.  Then taps, layout introspection, counters, profiling.  
+// vocoder: fd_griffin_lim, fd_mel_to_linear, fd_mel_to_linear_nnls; the neural baseline: fd_pwg_*.  Then taps, layout introspection, counters, profiling.  
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
 
 #include "fd_kernels.h"
 #include "fd_host.h"
 #include "fd_resample.h"
+#include "fd_pwg.h"
 
 // The host path the tools below share ("One host path under these tools"): check_counts, enter, the tables (upload_table
 // under first_use and refresh), stage_counts, and reserve and run (fd_host.h), in the order arguments, counts, handle, tables, scratch,
@@ -90,6 +94,17 @@ static int stage_counts(fd_handle h, const int64_t *counts, int B, long long *sl
     *dev = counts ? slot : nullptr;
     return counts ? fd_stage_upload(h, counts, sizeof(long long) * B, slot, stream) : FD_OK;
 }
+
+// A Parallel WaveGAN generator (fd_pwg_create): the host copies of its tensors by name, and their device image once committed
+struct fd_pwg {
+    fd_handle owner = nullptr;
+    fd_pwg_config cfg{};
+    std::vector<fdpwg::Tensor> tensors;
+    std::map<std::string, std::vector<float>> w;
+    std::vector<float> scaler;          // mean [80], scale [80]
+    float *img = nullptr;
+    bool committed = false, has_scaler = false;
+};
 
 extern "C" {
 
@@ -852,6 +867,190 @@ int fd_trim_silences(fd_handle h, const float *wav, int B, int64_t L, const int6
     return run(h, stream, who, [&](const fdk::Launch &La) {
         return fdk::trim(La, wav, B, L, valid_dev, p, W, Mp, M_grid, out, out_valid, flags, rec_dev, h->trim_scratch.p);
     });
+}
+
+// Parallel WaveGAN (fastdiff_hip_ext.h; the configuration's refusals, the tensors, the images and the scratch layout: fd_pwg.h, the
+// kernels: fd_kernels_pwg.hip)
+void fd_pwg_default_config(fd_pwg_config *cfg)
+{
+    if (cfg) fdpwg::default_config(cfg);
+}
+
+int64_t fd_pwg_samples(const fd_pwg_config *cfg, int64_t frames) { return cfg ? fdpwg::samples(*cfg, frames) : -1; }
+
+int64_t fd_pwg_receptive_field(const fd_pwg_config *cfg) { return cfg ? fdpwg::receptive_field(*cfg) : -1; }
+
+int fd_pwg_create(fd_handle h, const fd_pwg_config *cfg, fd_pwg_handle *out)
+{
+    const char *who = "fd_pwg_create";
+    if (!cfg || !out) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !cfg ? "cfg" : "out");
+    char why[fdpwg::MSG];
+    if (fdpwg::refusal(*cfg, why)) FD_FAIL(h, FD_ERR_UNSUPPORTED, "%s: %s", who, why);
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    fd_pwg *p = new fd_pwg();
+    p->owner = h;
+    p->cfg = *cfg;
+    p->tensors = fdpwg::tensors(*cfg);
+    p->scaler.assign(2 * fdpwg::AUX, 0.0f);
+    std::fill(p->scaler.begin() + fdpwg::AUX, p->scaler.end(), 1.0f);
+    *out = p;
+    return FD_OK;
+}
+
+int fd_pwg_set_weight(fd_pwg_handle p, const char *name, const float *data, int64_t n)
+{
+    const char *who = "fd_pwg_set_weight";
+    const fd_handle h = p ? p->owner : nullptr;
+    if (!p || !name || !data) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !p ? "generator" : (!name ? "name" : "data"));
+    for (const fdpwg::Tensor &t : p->tensors) {
+        if (t.name != name) continue;
+        if (n != (int64_t)t.n) FD_FAIL(h, FD_ERR_INVALID, "%s: %s has %zu elements, got %lld", who, name, t.n, (long long)n);
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(data[i])) FD_FAIL(h, FD_ERR_INVALID, "%s: element %lld of %s is not finite", who, (long long)i, name);
+        p->w[t.name].assign(data, data + n);
+        p->committed = false;
+        return FD_OK;
+    }
+    FD_FAIL(h, FD_ERR_MISSING, "%s: no tensor %s in this configuration", who, name);
+}
+
+int fd_pwg_commit(fd_pwg_handle p)
+{
+    const char *who = "fd_pwg_commit";
+    const fd_handle h = p ? p->owner : nullptr;
+    if (!p) FD_FAIL(h, FD_ERR_INVALID, "%s: null generator", who);
+    for (const fdpwg::Tensor &t : p->tensors)
+        if (!p->w.count(t.name)) FD_FAIL(h, FD_ERR_MISSING, "%s: %s was never set", who, t.name.c_str());
+    const fd_pwg_config &c = p->cfg;
+    const fdpwg::Image im = fdpwg::image(c);
+    std::vector<float> img(im.total, 0.0f);
+    auto W = [&](const std::string &n) -> const float * { return p->w[n].data(); };
+    const int K = 2 * c.aux_context_window + 1, A = fdpwg::AUX, G = fdpwg::GATE, R = fdpwg::RES;
+    const float *cin = W("upsample_net.conv_in.weight");            // [80 j][80 m][K]
+    for (int l = 0; l < c.layers; ++l) {
+        const std::string pre = "conv_layers." + std::to_string(l) + ".";
+        const float *aux = W(pre + "conv1x1_aux.weight");           // [128][80]
+        float *front = img.data() + im.front + (size_t)l * G * A * K;
+        for (int g = 0; g < G; ++g)
+            for (int mk = 0; mk < A * K; ++mk) {
+                double sum = 0.0;
+                for (int j = 0; j < A; ++j) sum += (double)aux[g * A + j] * (double)cin[(size_t)j * A * K + mk];
+                front[(size_t)g * A * K + mk] = (float)sum;
+            }
+        float *Ll = img.data() + im.layer + fdpwg::LAYER_FLOATS * l;
+        fdpwg::pack_a(Ll + fdpwg::L_CONV, W(pre + "conv.weight"), G, 3 * R, 3 * R, [&](int k) { return (k % R) * 3 + k / R; });      // k = tap 64 + channel
+        std::copy_n(W(pre + "conv.bias"), G, Ll + fdpwg::L_BIAS);
+        std::vector<float> mix((size_t)G * fdpwg::HALF);
+        std::copy_n(W(pre + "conv1x1_out.weight"), (size_t)R * fdpwg::HALF, mix.begin());
+        std::copy_n(W(pre + "conv1x1_skip.weight"), (size_t)fdpwg::SKIP * fdpwg::HALF, mix.begin() + (size_t)R * fdpwg::HALF);
+        fdpwg::pack_a(Ll + fdpwg::L_MIX, mix.data(), G, fdpwg::HALF, fdpwg::HALF, [](int k) { return k; });
+        std::copy_n(W(pre + "conv1x1_out.bias"), R, Ll + fdpwg::L_MIXB);
+        std::copy_n(W(pre + "conv1x1_skip.bias"), fdpwg::SKIP, Ll + fdpwg::L_MIXB + R);
+    }
+    std::copy_n(W("first_conv.weight"), R, img.data() + im.first_w);
+    std::copy_n(W("first_conv.bias"), R, img.data() + im.first_b);
+    fdpwg::pack_a(img.data() + im.tail_w1, W("last_conv_layers.1.weight"), fdpwg::SKIP, fdpwg::SKIP, fdpwg::SKIP, [](int k) { return k; });
+    std::copy_n(W("last_conv_layers.1.bias"), fdpwg::SKIP, img.data() + im.tail_b1);
+    std::copy_n(W("last_conv_layers.3.weight"), fdpwg::SKIP, img.data() + im.tail_w2);
+    img[im.tail_b2] = W("last_conv_layers.3.bias")[0];
+    for (int i = 0; i < c.n_scales; ++i)
+        fdpwg::phase_sums(W("upsample_net.upsample.up_layers." + std::to_string(2 * i + 1) + ".weight"), c.upsample_scales[i],
+                          img.data() + im.phase + (size_t)i * fdpwg::MAX_SCALE * 3);
+    std::copy(p->scaler.begin(), p->scaler.end(), img.begin() + im.scaler);
+    FD_HIP(h, hipSetDevice(h->device));
+    if (!p->img) {
+        void *d = nullptr;
+        FD_HIP(h, hipMalloc(&d, sizeof(float) * im.total));
+        p->img = static_cast<float *>(d);
+    } else {
+        FD_HIP(h, hipDeviceSynchronize());      // launches in flight may still read the old values
+    }
+    FD_HIP(h, hipMemcpy(p->img, img.data(), sizeof(float) * im.total, hipMemcpyHostToDevice));
+    p->committed = true;
+    return FD_OK;
+}
+
+int fd_pwg_set_scaler(fd_pwg_handle p, const float *mean, const float *scale)
+{
+    const char *who = "fd_pwg_set_scaler";
+    const fd_handle h = p ? p->owner : nullptr;
+    if (!p) FD_FAIL(h, FD_ERR_INVALID, "%s: null generator", who);
+    if (!mean != !scale) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s (both or neither)", who, !mean ? "mean" : "scale");
+    for (int m = 0; mean && m < fdpwg::AUX; ++m)
+        if (!std::isfinite(mean[m]) || !std::isfinite(scale[m]) || scale[m] == 0.0f)
+            FD_FAIL(h, FD_ERR_INVALID, "%s: channel %d: mean %g, scale %g", who, m, (double)mean[m], (double)scale[m]);
+    for (int m = 0; m < fdpwg::AUX; ++m) {
+        p->scaler[m] = mean ? mean[m] : 0.0f;
+        p->scaler[fdpwg::AUX + m] = mean ? scale[m] : 1.0f;
+    }
+    p->has_scaler = mean != nullptr;
+    if (p->img) {
+        FD_HIP(h, hipSetDevice(h->device));
+        FD_HIP(h, hipDeviceSynchronize());
+        FD_HIP(h, hipMemcpy(p->img + fdpwg::image(p->cfg).scaler, p->scaler.data(), sizeof(float) * p->scaler.size(), hipMemcpyHostToDevice));
+    }
+    return FD_OK;
+}
+
+int fd_pwg_generate(fd_pwg_handle p, const float *mel_or_c, int padded, int B, int T, const int64_t *lens, const float *z, uint64_t seed,
+                    const uint64_t *stream_ids, float *wav_out, int64_t wav_pitch, void *stream)
+{
+    const char *who = "fd_pwg_generate";
+    const fd_handle h = p ? p->owner : nullptr;
+    if (!mel_or_c || !wav_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null %s", who, !mel_or_c ? "mel_or_c" : "wav_out");
+    if (padded != 0 && padded != 1) FD_FAIL(h, FD_ERR_INVALID, "%s: padded = %d is neither 0 nor 1", who, padded);
+    char why[fdpwg::MSG];
+    if (fdpwg::call_refusal(p ? fdpwg::hop(p->cfg) : 1, B, T, p ? wav_pitch : INT64_MAX, why)) FD_FAIL(h, FD_ERR_INVALID, "%s: %s", who, why);
+    int rc = check_counts(h, who, "lens", lens, B, 0, T);
+    if (rc != FD_OK) return rc;
+    if (!p) FD_FAIL(h, FD_ERR_INVALID, "%s: null generator", who);
+    if (!p->committed) FD_FAIL(h, FD_ERR_STATE, "%s: fd_pwg_commit has not run since the last fd_pwg_set_weight", who);
+    if ((rc = enter(h)) != FD_OK) return rc;
+    const fdpwg::Layout o = fdpwg::layout(p->cfg.layers, fdpwg::hop(p->cfg), B, T);
+    Scratch &s = h->pwg_scratch;
+    if ((rc = reserve(h, who, s, o.total, (hipStream_t)stream)) != FD_OK) return rc;
+    char *base = reinterpret_cast<char *>(s.p);
+    const long long *lens_dev = nullptr, *ids_dev = nullptr;
+    if ((rc = stage_counts(h, lens, B, reinterpret_cast<long long *>(base + o.lens), (hipStream_t)stream, &lens_dev)) != FD_OK) return rc;
+    if ((rc = stage_counts(h, reinterpret_cast<const int64_t *>(stream_ids), B, reinterpret_cast<long long *>(base + o.ids), (hipStream_t)stream, &ids_dev)) != FD_OK)
+        return rc;
+    const fdk::PwgNet net{p->img, p->cfg, p->has_scaler};
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::pwg_generate(La, net, mel_or_c, padded, B, T, lens_dev, reinterpret_cast<const unsigned long long *>(ids_dev), z, (unsigned long long)seed,
+                                 wav_out, wav_pitch, s.p);
+    });
+}
+
+int fd_pwg_draw(fd_handle h, int B, int64_t L, uint64_t seed, const uint64_t *stream_ids, float *z_out, int64_t z_pitch, void *stream)
+{
+    const char *who = "fd_pwg_draw";
+    if (!z_out) FD_FAIL(h, FD_ERR_INVALID, "%s: null z_out", who);
+    if (B < 1 || B > fdpwg::MAX_B || L < 1 || L > INT32_MAX || z_pitch < L)
+        FD_FAIL(h, FD_ERR_INVALID, "%s: B = %d items (1 .. %d) of L = %lld samples (1 .. 2^31 - 1) at a pitch of %lld", who, B, fdpwg::MAX_B, (long long)L, (long long)z_pitch);
+    if (!h) FD_FAIL(h, FD_ERR_INVALID, "%s: null handle", who);
+    int rc = enter(h);
+    if (rc != FD_OK) return rc;
+    const fdpwg::Layout o = fdpwg::layout(1, 1, B, 1);      // (the slots of the counts depend on B alone)
+    Scratch &s = h->pwg_scratch;
+    if ((rc = reserve(h, who, s, o.G, (hipStream_t)stream)) != FD_OK) return rc;
+    const long long *ids_dev = nullptr;
+    if ((rc = stage_counts(h, reinterpret_cast<const int64_t *>(stream_ids), B, reinterpret_cast<long long *>(reinterpret_cast<char *>(s.p) + o.ids), (hipStream_t)stream, &ids_dev)) != FD_OK)
+        return rc;
+    return run(h, stream, who, [&](const fdk::Launch &La) {
+        return fdk::pwg_draw(La, B, L, (unsigned long long)seed, reinterpret_cast<const unsigned long long *>(ids_dev), z_out, z_pitch);
+    });
+}
+
+int fd_pwg_destroy(fd_pwg_handle p)
+{
+    if (!p) return FD_OK;
+    if (p->img) {
+        (void)hipSetDevice(p->owner->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p->img);
+    }
+    delete p;
+    return FD_OK;
 }
 
 int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capacity)

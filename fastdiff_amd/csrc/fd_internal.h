@@ -396,6 +396,7 @@ struct fd_context {
     Scratch bins_scratch;                    // fd_bins_pass: per chunk the counts, inertia, moved, nonfinite and sums (csrc/fd_bins.h: layout)
     Scratch mcd_scratch;                     // fd_cepstra / fd_dtw / fd_mcd_measure: counts, bottom rows, direction codes, records, cepstra (fd_kernels_mcd.hip: layout)
     const float *mcd_dct = nullptr;          // their DCT table [40][80] (csrc/fd_mcd.h: dct_table); their front-end's tables: `mel`
+    Scratch pwg_scratch;                     // fd_pwg_generate: lengths, stream ids, G, the up-sampling coefficients, two x buffers, skip (csrc/fd_pwg.h: layout)
     Scratch trim_scratch;                    // fd_trim_silences / fd_trim_levels: lengths, window levels, prefix tables (fd_kernels_trim.hip: layout)
     Scratch step_scratch;                    // fd_mse_forward / fd_adamw_multi: per-workgroup partial sums and the optimizer's per-step scalars
     std::vector<ProfEntry> prof_pending;
@@ -535,6 +536,12 @@ hipError_t griffin_lim(const Launch &L_, const float *amp, const float *angles, 
                        const unsigned long long *ids_dev, int n_iters, unsigned long long seed, const float *tab, float *wav, long long pitch,
                        fd_gl *rec, void *scratch);
 hipError_t mel_to_linear(const Launch &L_, const float *mel, int B, int T, const float *pinv_dev, int variant, float *amp);
+// fd_pwg_generate / fd_pwg_draw (fd_kernels_pwg.hip).  net: a committed generator (img: its device image, csrc/fd_pwg.h: image);
+// lens_dev / ids_dev as above; src: the mel or the padded c; z: device [B][hop T] or null; scratch: fdpwg::layout(...).total bytes.
+struct PwgNet { const float *img; fd_pwg_config cfg; bool has_scaler; };
+hipError_t pwg_generate(const Launch &L_, const PwgNet &net, const float *src, int padded, int B, int T, const long long *lens_dev,
+                        const unsigned long long *ids_dev, const float *z, unsigned long long seed, float *wav, long long pitch, void *scratch);
+hipError_t pwg_draw(const Launch &L_, int B, long long L, unsigned long long seed, const unsigned long long *ids_dev, float *z_out, long long pitch);
 // fd_mel_to_linear_nnls (fd_kernels_nnls.hip).  lens_dev: null or the lens slot of the scratch buffer (nnls_scratch_bytes(B, T) bytes);
 // tab_dev: device copy of fdn::fill_table(bank); step: fdn::step(L); rec: device [B] or null.
 size_t nnls_scratch_bytes(int B, int T);

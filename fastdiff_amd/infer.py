@@ -16,10 +16,10 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
 Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), trim_long_sil_wav (the reference's trim_long_sil on the
 device), collate_test_batch, distributed_sampler_indices, synthesize,
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), synthesize_griffin_lim (--vocoder griffin_lim:
-the baseline vocoder on the same items), test_step
+the baseline vocoder on the same items), synthesize_pwg (--vocoder pwg --pwg_dir DIR: the neural baseline on the same items), test_step
 (the mirror of FastDiffTask.test_step itself), save_wavs and a small CLI
 (`python -m fastdiff_amd.infer --test_input_dir D --out_dir O [--N 4] [--ckpt model.ckpt] [--from_wav] [--loud_norm] [--trim_long_sil [--trim_top_db 40] [--trim_mode long|edges]] [--out_sample_rate R]
-[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--mcd] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]]
+[--loudness LUFS] [--stoi] [--pitch] [--spectral] [--mcd] [--vocoder griffin_lim [--gl_iters 60] [--gl_inversion pinv|nnls [--nnls_iters 128]]] [--vocoder pwg --pwg_dir DIR]
 [--ndb_bins bins.npz]`).
 """
 import argparse
@@ -498,6 +498,45 @@ def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_
     return (out, report) if scored else out
 
 
+def synthesize_pwg(model, pwg, items: Sequence[dict], max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, sort: bool = True,
+                   out_sample_rate: int = None, sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
+                   spectral: bool = False, mcd: bool = False) -> Dict[str, np.ndarray]:
+    """The neural baseline next to synthesize(): item_name -> int16 PCM from Parallel WaveGAN on the device (`pwg`: a loaded
+    fastdiff_amd.pwg.ParallelWaveGAN; its spec2wav applies the scaler and the edge padding, as the reference's vocoders/pwg.py), through
+    the same length-sorted padded micro-batches.  As in synthesize() the last frame of a mel is dropped, so the two waveforms and their
+    scores line up.  The network is convolutional and takes any length up to FD_PWG_MAX_FRAMES: there is no windowed variant.  z of
+    item `it` is drawn from Philox stream (seed, it["uid"], sample); "uid" defaults to the item's position in `items`, so a waveform does
+    not depend on its micro-batch.  `model` (a FastDiff) supplies the level epilogue and the scores: out_sample_rate, loudness, stoi,
+    pitch, spectral, mcd as in synthesize() -- the same report keys, measured on the float waveform before the epilogue."""
+    if pwg.hop_size != model.hop_length:
+        raise ValueError(f"synthesize_pwg: the generator's hop {pwg.hop_size} is not the {model.hop_length} samples of the mels' frames")
+    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
+    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+        raise ValueError(f"synthesize_pwg: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    report: Dict[str, dict] = {}
+    out: Dict[str, np.ndarray] = {}
+    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
+    uid_of = {it["item_name"]: int(it.get("uid", i)) for i, it in enumerate(items)}
+    kept = [it for it in items if it["mel"].shape[0] >= (2 if drop_last_frame else 1)]
+    if not kept:
+        return (out, report) if scored else out
+    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
+    score = _scorer(model, items, scored, report, sample_rate, "synthesize_pwg")
+    on_device = isinstance(kept[0]["mel"], torch.Tensor) and kept[0]["mel"].is_cuda
+    for batch_idx in shard.micro_batches(range(len(kept)), [it["mel"].shape[0] for it in kept], max_batch, sort=sort):
+        batch_items = [kept[i] for i in batch_idx]
+        mels, lens, names = (_collate_on_device if on_device else collate_test_batch)(batch_items, drop_last_frame)
+        with torch.no_grad():
+            wav = pwg.spec2wav(mels.cuda(), lens=lens, seed=seed, stream_ids=[uid_of[n] for n in names])
+        pcm = epilogue(wav, lens)
+        if scored:
+            score(wav, names, lens)
+        host = pcm.cpu().numpy()
+        for b, (name, t) in enumerate(zip(names, lens)):
+            out[name] = host[b, : n_of(t)].copy()
+    return (out, report) if scored else out
+
+
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
                        device=None, force_collectives: int = 0, gather: str = "src", balance: str = "time", out_sample_rate: int = None,
                        sample_rate: int = 22050, loudness: float = None, stoi: bool = False, pitch: bool = False,
@@ -698,10 +737,13 @@ def main(argv=None):
                     help="with --from_wav (copy synthesis): measure the mel-cepstral distortion of every vocoded waveform against its recording "
                          "on the device (13 mel-filter-bank cepstral coefficients; in dB along the time-warped path and frame by frame), print "
                          "the table and write <out_dir>/mcd.tsv")
-    ap.add_argument("--vocoder", default="fastdiff", choices=("fastdiff", "griffin_lim"),
-                    help="griffin_lim: the baseline instead of the model -- every mel inverted with the filter bank (--gl_inversion) and "
+    ap.add_argument("--vocoder", default="fastdiff", choices=("fastdiff", "griffin_lim", "pwg"),
+                    help="pwg: the neural baseline instead of the model -- Parallel WaveGAN on the device from --pwg_dir; griffin_lim: the baseline instead of the model -- every mel inverted with the filter bank (--gl_inversion) and "
                          "run through --gl_iters Griffin-Lim iterations on the device; the same <name>_pred.wav files and, with --stoi / "
                          "--pitch / --spectral / --mcd, the same TSVs, so a baseline row is one command next to the model's")
+    ap.add_argument("--pwg_dir", default=None, metavar="DIR",
+                    help="with --vocoder pwg: the directory of the generator (config.yaml, the newest model_ckpt_steps_*.ckpt or "
+                         "checkpoint-*steps.pkl, and for the latter the scaler's stats.npy / stats.h5), as the reference's vocoder_ckpt")
     ap.add_argument("--gl_iters", type=int, default=60, help="with --vocoder griffin_lim: iterations (griffin_lim_iters of base.yaml: 60)")
     ap.add_argument("--gl_inversion", default="pinv", choices=("pinv", "nnls"),
                     help="with --vocoder griffin_lim: how the mel is inverted -- pinv: the pseudo-inverse of the filter bank, floored (the "
@@ -739,6 +781,11 @@ def main(argv=None):
             ap.error(f"--gl_iters {args.gl_iters} outside 0 .. 10000")
         if not 0 <= args.nnls_iters <= 4096:
             ap.error(f"--nnls_iters {args.nnls_iters} outside 0 .. 4096")
+    if args.vocoder == "pwg":
+        if args.long_form:
+            ap.error("--vocoder pwg is not available with --long_form (the network takes any length in one call)")
+        if not args.pwg_dir:
+            ap.error("--vocoder pwg needs --pwg_dir")
     from . import FastDiff
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -763,6 +810,10 @@ def main(argv=None):
         how = {} if (args.gl_inversion, args.nnls_iters) == ("pinv", 128) else dict(inversion=args.gl_inversion, nnls_iters=args.nnls_iters)
         pcm = synthesize_griffin_lim(model, mine, args.gl_iters, args.max_batch, args.seed, variant=args.mel_variant, out_sample_rate=args.out_sample_rate,
                                      loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, **how, **more)
+    elif args.vocoder == "pwg":
+        from .pwg import ParallelWaveGAN
+        pcm = synthesize_pwg(model, ParallelWaveGAN.from_dir(args.pwg_dir), mine, args.max_batch, args.seed, out_sample_rate=args.out_sample_rate,
+                             loudness=args.loudness, stoi=args.stoi, pitch=args.pitch, spectral=args.spectral, **more)
     elif args.long_form:
         if args.out_sample_rate is not None:
             ap.error("--out_sample_rate is not available with --long_form (resample its output whole with FastDiff.resample)")

@@ -729,6 +729,105 @@ FD_API int fd_trim_levels(fd_handle h, const float *wav, int B, int64_t L, const
 FD_API int fd_trim_silences(fd_handle h, const float *wav, int B, int64_t L, const int64_t *valid, const fd_trim_params *params, float *out,
                             int32_t *out_valid, uint8_t *flags, fd_trim *rec_dev, void *stream);
 
+/* Parallel WaveGAN: the reference's neural baseline vocoder (vocoders/pwg.py over modules/parallel_wavegan: ParallelWaveGANGenerator,
+ * Yamamoto et al. 2020), behind the interface of the other two vocoders.  THIS TEXT defines the computation; tests/pwg_ref.py restates
+ * it in float64, and the executed reference confirms that restatement (tools/gen_pwg_reference.py).
+ *
+ * The network, weight norm removed.  w = aux_context_window, scales s_1 .. s_n, hop = their product, T frames -> L = hop T samples.
+ *   c      [80][T + 2 w]: the conditioning, already padded.  fd_pwg_generate forms it from a mel [80][T] when padded = 0, as
+ *          PWG.spec2wav does: the optional (mel - mean) / scale per channel, then w frames of edge replication on each side.
+ *   u_0    = conv_in(c): 80 -> 80, 2 w + 1 taps, no bias, no padding: [80][T].
+ *   u_i    [80][T s_1 .. s_i], i = 1 .. n: u_{i-1} stretched by s_i (each sample repeated s_i times), then 2 s_i + 1 taps per channel
+ *          with zero padding s_i, no bias: u_i[m] = sum_k taps_i[k] stretched[m + k - s_i], zero outside the stretched signal.
+ *   x_0    = first_conv(z): 1 -> 64, x_0[j][t] = w[j] z[t] + b[j].
+ *   layer l = 0 .. layers - 1, dilation d = 2^(l mod (layers / stacks)):
+ *          g = conv(x_l): 64 -> 128, taps at t - d, t, t + d, zero outside [0, L), with bias;  g += W_aux_l u_n  (128 x 80, no bias);
+ *          h = tanh(g[0 .. 63]) * sigmoid(g[64 .. 127]);   skip += W_skip h + b_skip;   x_{l+1} = (W_out h + b_out + x_l) * sqrt(1/2).
+ *   y      = W_2 relu(W_1 relu(skip * sqrt(1 / layers)) + b_1) + b_2: 64 -> 64 -> 1.
+ * z is the caller's [B][L], or, z NULL, sample t of item b is component t & 3 of the float4 t >> 2 of fd_sample's generator
+ * (Philox4x32-10 + Box-Muller) on the stream word FD_PWG_PHILOX_STREAM with id = stream_ids[b] (NULL: b): with ids an item's noise does
+ * not depend on the batch it sits in.  fd_pwg_draw writes exactly those values.
+ *
+ * What is fixed: residual 64, gate 128, skip 64, aux 80 channels, kernel size 3, non-causal, bias, one input and one output channel,
+ * ConvInUpsampleNetwork with nearest interpolation, no activation and frequency kernel 1.  Free: layers 1 .. 30, stacks dividing
+ * layers with the largest dilation <= 512, w 0 .. 4, 1 .. 4 scales of 2 .. 16 with hop <= 512.  fd_pwg_create refuses everything else
+ * with the field and its value in the message.
+ *
+ * On the device.  The up-sampling network is linear, has no activation and acts per channel along time, so it commutes with every
+ * layer's 128 x 80 projection, the zero padding of every stage included.  fd_pwg_commit composes W_aux_l conv_in on the host in float64
+ * into one convolution of 2 w + 1 taps with 128 layers outputs; the front kernel runs it at the frame rate: G[b][l][128][T], float32,
+ * each output one fmaf chain over (channel, tap) ascending.  The [80][L] conditioning never exists.  The n stages composed act on G as
+ * at most five neighbouring frames with coefficients that depend on the sample alone (its phase in every stage, and which of its
+ * neighbours lie outside the item at that stage's rate: those contribute zero): one small kernel per call writes them, K[b][5][L], summed
+ * in float64 over the stage paths in a fixed order.  Then one kernel per residual block: a workgroup of 256 threads owns FD_PWG_TILE = 512
+ * samples of one item, each wave 64 of them at a time.  Both contractions (128 x 192 and 128 x 64, out and skip stacked) run on the exact-fp32
+ * matrix instruction v_mfma_f32_32x32x2_f32 (bit for bit an fmaf chain): the x operand is read straight from x_l [B][64][L] -- 32
+ * consecutive samples per half wave, zero outside [0, L_b) whatever lies there in memory -- the weights from an image packed at commit
+ * in the instruction's operand order.  The conditioning and the biases are further steps of the same contractions (k = a frame of G under the wave times the
+ * sample's coefficient on it; k = the bias times one), after the taps; the 128 rows go in two passes of 32 + 32; h crosses from the result
+ * layout to the operand layout through LDS.  x_{l+1} goes to the other of two buffers, skip is float32 and read, added to and written
+ * by its one owner (layer 0 writes it; the last layer writes no x).  Layer 0 forms x_0 from z itself, halo included.  The tail is a
+ * kernel of its own on the same instruction; it writes zeros from L_b to hop T.  Every sum has a fixed order that does not depend on
+ * the batch, there are no atomics and no workgroup waits for another: an item is bit-identical alone, anywhere in a ragged batch and
+ * from call to call.  Tiles behind an item's L_b return at once.  G, K, the two x buffers and skip live in a buffer of the handle that
+ * grows at the first call that needs more (not inside a stream capture: FD_ERR_STATE; call it once before); otherwise a call is
+ * asynchronous on `stream` and capturable. */
+#define FD_PWG_TILE 512                 /* samples of one item per workgroup of the layer kernel */
+#define FD_PWG_PHILOX_STREAM 0xFFFFFFF7u
+#define FD_PWG_MAX_LAYERS 30
+#define FD_PWG_MAX_DILATION 512
+#define FD_PWG_MAX_CONTEXT 4
+#define FD_PWG_MAX_SCALES 4
+#define FD_PWG_MAX_SCALE 16
+#define FD_PWG_MAX_HOP 512
+#define FD_PWG_MAX_FRAMES 32768         /* T: 64 channels of hop T float32 samples stay below 2^32 bytes */
+enum { FD_PWG_CONV_IN_UPSAMPLE = 0, FD_PWG_UPSAMPLE = 1, FD_PWG_MELGAN = 2 };      /* fd_pwg_config::upsample_net */
+typedef struct fd_pwg_config {          /* the reference constructor's arguments; fd_pwg_default_config sets its defaults */
+    int32_t in_channels, out_channels, kernel_size, layers, stacks;
+    int32_t residual_channels, gate_channels, skip_channels, aux_channels, aux_context_window;
+    int32_t bias, use_causal_conv, upsample_conditional_features, use_pitch_embed, use_nsf;
+    int32_t upsample_net;               /* FD_PWG_CONV_IN_UPSAMPLE */
+    int32_t n_scales, upsample_scales[8];
+    int32_t upsample_activation;        /* 0: none (nonlinear_activation = None) */
+    int32_t interpolate_nearest;        /* 1: interpolate_mode = "nearest" */
+    int32_t freq_axis_kernel_size;      /* 1 */
+} fd_pwg_config;                        /* 112 bytes */
+typedef struct fd_pwg *fd_pwg_handle;
+
+FD_API void fd_pwg_default_config(fd_pwg_config *cfg);
+/* hop * frames, or -1 for a configuration fd_pwg_create refuses or frames < 0 (pure host code). */
+FD_API int64_t fd_pwg_samples(const fd_pwg_config *cfg, int64_t frames);
+/* 2 * (the sum of the layers' dilations) + 1: 6139 for the default; -1 for a configuration fd_pwg_create refuses (pure host code). */
+FD_API int64_t fd_pwg_receptive_field(const fd_pwg_config *cfg);
+/* A generator on the device of `h`, whose error text and scratch buffer it uses (fd_last_error(h); of a refusal made before any handle
+ * exists: fd_last_error(NULL)).  Destroy it before `h`.  The configuration is checked before the handle is looked at.
+ * FD_ERR_INVALID: a null pointer; FD_ERR_UNSUPPORTED: a field outside the specialised path, named with its value. */
+FD_API int fd_pwg_create(fd_handle h, const fd_pwg_config *cfg, fd_pwg_handle *out);
+/* One tensor by the reference's state-dict name after weight-norm removal (first_conv.weight, upsample_net.conv_in.weight,
+ * upsample_net.upsample.up_layers.{1,3,..}.weight, conv_layers.L.{conv,conv1x1_aux,conv1x1_out,conv1x1_skip}.{weight,bias},
+ * last_conv_layers.{1,3}.{weight,bias}): HOST float32, n elements in the reference's layout.  FD_ERR_MISSING: no such tensor in this
+ * configuration; FD_ERR_INVALID: n is not its size, or an element is not finite. */
+FD_API int fd_pwg_set_weight(fd_pwg_handle p, const char *name, const float *data, int64_t n);
+/* Packs the images and uploads them (synchronous; not inside a stream capture).  FD_ERR_MISSING: a tensor was never set (named). */
+FD_API int fd_pwg_commit(fd_pwg_handle p);
+/* mean, scale: HOST [80] (a StandardScaler's mean_ and scale_), or both NULL: no scaler.  Applies to calls with padded = 0.  Synchronous
+ * upload: not inside a stream capture.  FD_ERR_INVALID: one NULL, a value not finite, a scale of 0. */
+FD_API int fd_pwg_set_scaler(fd_pwg_handle p, const float *mean, const float *scale);
+/* mel_or_c: device, [B][80][T] (padded = 0: a mel; the scaler and the edge replication happen inside, by index clamp against lens[b])
+ * or [B][80][T + 2 w] (padded = 1: c as ParallelWaveGANGenerator.forward takes it; item b's frames are its first lens[b] + 2 w columns).
+ * lens: HOST [B] frames, 0 .. T, or NULL (T); item b yields L_b = hop lens[b] samples.  z: device [B][hop T] or NULL (Philox: seed,
+ * stream_ids HOST [B] or NULL).  wav_out: device, [B] rows wav_pitch >= hop T floats apart: y on [0, L_b), zeros from L_b to hop T.
+ * Asynchronous on `stream`.  The arguments are checked before the handles are looked at.  FD_ERR_INVALID: a null pointer or handle, B
+ * outside 1 .. 4096, T outside 1 .. FD_PWG_MAX_FRAMES, wav_pitch < hop T, lens[b] out of range; FD_ERR_STATE: not committed, or the
+ * scratch buffer would have to grow inside a stream capture. */
+FD_API int fd_pwg_generate(fd_pwg_handle p, const float *mel_or_c, int padded, int B, int T, const int64_t *lens, const float *z, uint64_t seed,
+                           const uint64_t *stream_ids, float *wav_out, int64_t wav_pitch, void *stream);
+/* z_out[b][t], t < L, rows z_pitch >= L floats apart: the z that fd_pwg_generate draws for item b with z NULL (device; stream_ids HOST
+ * [B] or NULL).  Asynchronous on `stream`.  FD_ERR_INVALID: a null pointer or handle, B outside 1 .. 4096, L outside 1 .. 2^31 - 1. */
+FD_API int fd_pwg_draw(fd_handle h, int B, int64_t L, uint64_t seed, const uint64_t *stream_ids, float *z_out, int64_t z_pitch, void *stream);
+/* Frees the device images (waits for the device).  NULL is accepted. */
+FD_API int fd_pwg_destroy(fd_pwg_handle p);
+
 /* Long-form and streaming synthesis (no counterpart in the reference, which vocodes an utterance in one piece).  The denoiser's
  * receptive field is finite: one reverse step moves an output sample only through inputs within h = 16 frames of it, N steps within
  * H = N*h.  fd_sample_span therefore computes an utterance window by window -- each window a batch item of fd_sample
