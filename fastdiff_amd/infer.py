@@ -13,6 +13,12 @@ Reference behaviour restated (none of this is on the GPU path, so plain torch/nu
     The reference CLI runs B = 1 (config `max_sentences`); batching is this path's extension: the batch goes down with its
     `lens`, so every item is computed exactly as if it ran alone (and the padding costs nothing), then cropped to its length.
 
+One job, three vocoders: synthesize, synthesize_griffin_lim and synthesize_pwg check their own arguments and hand _run_job a callable
+(mels, frame counts, stream ids -> float waveform, hops per item); the job owns the score flags, the output rate, the selection
+(_select: the one copy of "frames kept per item", also under collate_test_batch, synthesize_sharded and synthesize_long), the stream ids,
+the micro-batches, the two legs across PCIe (pinned double buffers for synthesize, plain copies for the baselines), the level
+epilogue, the scores and the delivery -- so the baselines' rows line up with the model's by construction.
+
 Entry points: load_mel_inputs, load_wav_inputs (device resampler + mel front-end), trim_long_sil_wav (the reference's trim_long_sil on the
 device), collate_test_batch, distributed_sampler_indices, synthesize,
 synthesize_long (--long_form: windowed, any length, the utterances sharing window batches), synthesize_griffin_lim (--vocoder griffin_lim:
@@ -176,30 +182,40 @@ def load_wav_inputs(model, test_input_dir: str, sample_rate: int = 22050, mel_va
     return items
 
 
-def collate_test_batch(items: Sequence[dict], drop_last_frame: bool = True, out: "np.ndarray" = None):
-    """mels [B, 80, T'] zero-padded, lens [B] (frames kept per item), item_names -- the test-time collater.
+def _select(items: Sequence[dict], drop_last_frame: bool):
+    """The test-time collater's selection, the one copy of the rule: (mels, frames kept per item, item_names, positions in `items`) of
+    the items that yield a hop.  With drop_last_frame every mel loses its last frame (dataset_utils.py:116-125), and a one-frame item
+    is left out: the reference cannot collate it (dataset_utils.py:110 squeezes it away)."""
+    mels, lens, names, where = [], [], [], []
+    for i, it in enumerate(items):
+        t = it["mel"].shape[0] - (1 if drop_last_frame else 0)
+        if t >= 1:
+            mels.append(it["mel"])
+            lens.append(t)
+            names.append(it["item_name"])
+            where.append(i)
+    return mels, lens, names, where
+
+
+def _pad_on_host(mels, lens, out: "np.ndarray" = None) -> "np.ndarray":
+    """[T, 80] mels, the first lens[b] frames of each -> the zero-padded [B, 80, max lens] batch, in `out` (flat float32) if given.
     The padding and the [T, 80] -> [80, T] transposition are plain numpy slice copies (torch's CPU kernels wake a whole OpenMP team
-    for these few hundred KB, which on a 256-core host now and then costs tens of milliseconds).  `out`: optional flat float32
-    buffer (e.g. pinned memory) that receives the batch; the returned tensor is then a view of it."""
-    kept, lens, names = [], [], []
-    for it in items:
-        c = it["mel"]
-        t = c.shape[0] - 1 if drop_last_frame else c.shape[0]
-        if drop_last_frame and c.shape[0] < 2:
-            continue                          # the reference cannot collate a one-frame item (dataset_utils.py:110 squeezes it away)
-        kept.append(c)
-        lens.append(t)
-        names.append(it["item_name"])
-    if not kept:
-        return None, [], []
-    B, C, T = len(kept), kept[0].shape[1], max(lens)
+    for these few hundred KB, which on a 256-core host now and then costs tens of milliseconds)."""
+    B, C, T = len(mels), mels[0].shape[1], max(lens)
     buf = np.empty(B * C * T, np.float32) if out is None else out[: B * C * T]
     batch = buf.reshape(B, C, T)
-    for b, (c, t) in enumerate(zip(kept, lens)):
+    for b, (c, t) in enumerate(zip(mels, lens)):
         a = c.numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
         batch[b, :, :t] = a[:t].T
         batch[b, :, t:] = 0.0
-    return torch.from_numpy(batch), lens, names
+    return batch
+
+
+def collate_test_batch(items: Sequence[dict], drop_last_frame: bool = True, out: "np.ndarray" = None):
+    """mels [B, 80, T'] zero-padded, lens [B] (frames kept per item), item_names -- the test-time collater (_select, _pad_on_host).
+    `out`: optional flat float32 buffer (e.g. pinned memory) that receives the batch; the returned tensor is then a view of it."""
+    mels, lens, names, _ = _select(items, drop_last_frame)
+    return (torch.from_numpy(_pad_on_host(mels, lens, out)), lens, names) if mels else (None, [], [])
 
 
 def distributed_sampler_indices(n_items: int, rank: int, world_size: int) -> List[int]:
@@ -254,32 +270,22 @@ def _pinned_staging(model, n_mel: int, n_pcm: int):
     return pin
 
 
-def _collate_on_device(items: Sequence[dict], drop_last_frame: bool):
-    """collate_test_batch for mels that already live on the GPU (the RCCL scatter of synthesize_sharded delivers them there):
-    the same padded [B, 80, T'] batch, built with device copies -- no round trip over PCIe."""
-    kept, lens, names = [], [], []
-    for it in items:
-        c = it["mel"]
-        t = c.shape[0] - 1 if drop_last_frame else c.shape[0]
-        if drop_last_frame and c.shape[0] < 2:
-            continue
-        kept.append(c)
-        lens.append(t)
-        names.append(it["item_name"])
-    if not kept:
-        return None, [], []
-    batch = torch.zeros(len(kept), kept[0].shape[1], max(lens), dtype=torch.float32, device=kept[0].device)
-    for b, (c, t) in enumerate(zip(kept, lens)):
+def _pad_on_device(mels, lens) -> torch.Tensor:
+    """_pad_on_host for mels that already live on the GPU (the RCCL scatter of synthesize_sharded delivers them there): the same
+    padded [B, 80, max lens] batch, built with device copies -- no round trip over PCIe."""
+    batch = torch.zeros(len(mels), mels[0].shape[1], max(lens), dtype=torch.float32, device=mels[0].device)
+    for b, (c, t) in enumerate(zip(mels, lens)):
         batch[b, :, :t] = c[:t].transpose(0, 1)
-    return batch, lens, names
+    return batch
 
 
-def _level_epilogue(model, R, sample_rate, loudness):
-    """(n_of, epilogue) of synthesize and synthesize_griffin_lim: n_of(t) = the PCM samples of t hops (at R Hz when R is not None);
-    epilogue(wav, lens) = the float waveforms of a micro-batch (item b: lens[b] hops) -> int16 PCM [B, n]: resampled to R first, then
-    peak-normalised, or with loudness = LUFS loudness-normalised, each item over its own samples."""
+def _level_epilogue(model, out_sample_rate, sample_rate, loudness):
+    """(n_of, epilogue) of a synthesis job: n_of(t) = the PCM samples of t hops (at R = out_sample_rate where that is another rate than
+    `sample_rate`); epilogue(wav, lens) = the float waveforms of a micro-batch (item b: lens[b] hops) -> int16 PCM [B, n]: resampled to
+    R first, then peak-normalised, or with loudness = LUFS loudness-normalised, each item over its own samples."""
     from . import resample as _resample
     hop = model.hop_length
+    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     n_of = (lambda t: t * hop) if R is None else (lambda t: _resample.out_len(t * hop, sample_rate, R))      # PCM samples of t frames
 
     def to_pcm(wav, valid, rate):
@@ -297,7 +303,7 @@ def _level_epilogue(model, R, sample_rate, loudness):
 
 
 def _scorer(model, items, scored, report, sample_rate, who):
-    """score(wav, names, lens) of synthesize and synthesize_griffin_lim: every enabled score of the micro-batch's float waveforms against
+    """score(wav, names, lens) of a synthesis job: every enabled score of the micro-batch's float waveforms against
     the items' recordings, cut to the vocoded length (lens hops), into report[name]."""
     hop = model.hop_length
 
@@ -318,6 +324,108 @@ def _scorer(model, items, scored, report, sample_rate, who):
                 report[name][sc.status_key] = sc.module.STATUS[int(rec["status"][b])]
 
     return score
+
+
+def _run_job(who, model, items, vocode, max_batch, sort, drop_last_frame, out_sample_rate, sample_rate, loudness, scores,
+             all_frames_in=False, pinned=False, return_device=False):
+    """The synthesis job of synthesize, synthesize_griffin_lim and synthesize_pwg (`who`: the one named in a refusal): item_name -> int16
+    PCM, with scores=dict(stoi=, pitch=, spectral=, mcd=) enabled (pcm, report).  The items that yield a hop (_select) go longest first
+    (sort) into padded micro-batches; each is collated where its mels live, vocoded, taken through the level epilogue and the scores,
+    and unpacked to n_of(hops) samples per item.  An item's noise-stream id is its "uid", by default its position in `items`.
+    vocode(mels [B, 80, T'] on the device, frames [B], stream_ids [B]) is the only per-vocoder part: it returns (float waveform, hops
+    per item) -- all_frames_in: it is given every frame of a mel and returns one hop less, as the selection counts them -- and may add
+    settle(), which is True when the call has been run again since (FastDiff's option fallback = "host"): the epilogue and the scores
+    of that micro-batch are then redone, when the batch is collected on the host or, with return_device, one batch late.
+    pinned: the two legs across PCIe go through pinned double buffers (_pinned_staging) -- the collater writes into one, one
+    asynchronous copy per micro-batch each way, and the previous batch is unpacked on the host while this one runs; otherwise
+    mels.cuda() and pcm.cpu().  return_device: the values are int16 device tensors, nothing comes back."""
+    scored = _scores.enabled(**scores)
+    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
+        raise ValueError(f"{who}: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
+    report: Dict[str, dict] = {}
+    out: Dict[str, np.ndarray] = {}
+    job_mels, frames, job_names, picked = _select(items, drop_last_frame)
+    if not picked:
+        return (out, report) if scored else out
+    n_of, epilogue = _level_epilogue(model, out_sample_rate, sample_rate, loudness)
+    score = _scorer(model, items, scored, report, sample_rate, who)
+    uids = [int(items[i].get("uid", i)) for i in picked]
+    if all_frames_in:
+        frames = [t + 1 for t in frames]           # selected by its hops, collated with every frame
+    on_device = isinstance(job_mels[0], torch.Tensor) and job_mels[0].is_cuda
+    # pinned staging, two mel and two PCM buffers used alternately -- buffer k & 1 is free again once micro-batch k - 2 has been
+    # collected, which happens in iteration k - 1.  Only the legs that cross PCIe need it.
+    if pinned and not (on_device and return_device):
+        t_max, b_max = max(frames), min(max_batch, len(picked))
+        mel_pin, pcm_pin = _pinned_staging(model, 0 if on_device else b_max * job_mels[0].shape[1] * t_max, 0 if return_device else b_max * n_of(t_max))
+        mel_np = [m.numpy() for m in mel_pin]      # the collater writes the batch straight into the pinned buffer
+    mel_up = [None, None]          # event behind the upload that last read mel_pin[i]: the collater waits for it before writing there again
+    pending = None                 # pinned: the micro-batch still on its way to the host, as collect() takes it
+    unsettled = None               # return_device: (settle, wav, names, lens) of the micro-batch nobody has settled yet
+
+    def finish(wav, names, lens):
+        pcm = epilogue(wav, lens)
+        if scored:
+            score(wav, names, lens)
+        return pcm
+
+    def collect(done, host, names, lens, wav, settle):
+        if done is not None:
+            done.synchronize()
+        if settle is not None and settle():      # an operand left the fp16 range: the call was run again on fp32 -- so is its epilogue
+            host.copy_(finish(wav, names, lens), non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        rows = host.numpy()
+        for b, (name, t) in enumerate(zip(names, lens)):
+            out[name] = rows[b, : n_of(t)].copy()
+
+    def keep_on_device(pcm, names, lens):
+        for b, (name, t) in enumerate(zip(names, lens)):
+            out[name] = pcm[b, : n_of(t)]
+
+    def resettle(p):
+        if p is not None and p[0]():             # run again on fp32: so is its epilogue
+            keep_on_device(finish(*p[1:]), *p[2:])
+
+    # (the frames kept are the full counts or one less for every item, so longest first is the order of the full counts)
+    for k, idx in enumerate(shard.micro_batches(range(len(picked)), frames, max_batch, sort=sort)):
+        mels, lens, names = [job_mels[i] for i in idx], [frames[i] for i in idx], [job_names[i] for i in idx]
+        if on_device:
+            mels = _pad_on_device(mels, lens)
+        elif pinned:
+            if mel_up[k & 1] is not None:            # the upload of micro-batch k - 2 read this pinned buffer
+                mel_up[k & 1].synchronize()
+            batch = _pad_on_host(mels, lens, out=mel_np[k & 1])
+            mels = mel_pin[k & 1][: batch.size].view(batch.shape).cuda(non_blocking=True)
+            mel_up[k & 1] = torch.cuda.Event()
+            mel_up[k & 1].record()
+        else:
+            mels = torch.from_numpy(_pad_on_host(mels, lens)).cuda()
+        with torch.no_grad():
+            wav, lens, *settle = vocode(mels, lens, [uids[i] for i in idx])
+        settle = settle[0] if settle else None
+        # one epilogue call and one asynchronous copy per micro-batch; the previous batch is unpacked on the host while this one runs
+        pcm = finish(wav, names, lens)
+        if return_device:
+            keep_on_device(pcm, names, lens)
+            # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
+            # next call has looked at it (no wait by then) and not at the end of the job
+            resettle(unsettled)
+            unsettled = (settle, wav, names, lens) if settle is not None else None
+        elif pinned:
+            host = pcm_pin[k & 1][: pcm.numel()].view(pcm.shape)
+            host.copy_(pcm, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            if pending is not None:
+                collect(*pending)
+            pending = (done, host, names, lens, wav, settle)
+        else:
+            collect(None, pcm.cpu(), names, lens, wav, settle)
+    if pending is not None:
+        collect(*pending)
+    resettle(unsettled)
+    return (out, report) if scored else out
 
 
 def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True,
@@ -351,105 +459,20 @@ def synthesize(model, items: Sequence[dict], n_steps: int = 4, max_batch: int = 
     mcd=True (copy synthesis, items as for stoi=True): returns (pcm, report) with report[name] = {"mcd_dtw", "mcd_linear", "mcd_status"}
     (FastDiff.mcd with 13 coefficients of the pwg front-end: the mel-cepstral distortion in dB along the time-warped path and frame by
     frame; status by name), measured on the same waveforms, next to the other sets."""
-    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
-    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
-        raise ValueError(f"synthesize: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
-    report: Dict[str, dict] = {}
-    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
     # the step table depends on the schedule only: derived once per schedule and model (sampling_given_noise_schedule derives it on
     # every call, as the reference does), the same rows then drive every micro-batch
     rows = _step_rows(model, n_steps, noise_schedule, diffusion_hyperparams)
-    lengths = [it["len"] for it in items]
-    out: Dict[str, np.ndarray] = {}
-    if not items:
-        return (out, report) if scored else out
-    hop = model.hop_length
-    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
-
-    on_device = isinstance(items[0]["mel"], torch.Tensor) and items[0]["mel"].is_cuda
-    t_max, b_max = max(lengths), min(max_batch, len(items))
-    # pinned staging, two mel and two PCM buffers used alternately -- buffer k & 1 is free again once micro-batch k - 2 has been
-    # collected, which happens in iteration k - 1.  Only the legs that cross PCIe need it.
-    mel_pin = pcm_pin = mel_np = None
-    if not (on_device and return_device):
-        mel_pin, pcm_pin = _pinned_staging(model, 0 if on_device else b_max * 80 * t_max, 0 if return_device else b_max * n_of(t_max))
-        mel_np = [m.numpy() for m in mel_pin]      # the collater writes the batch straight into the pinned buffer
-    mel_up = [None, None]          # event behind the upload that last read mel_pin[i]: the collater waits for it before writing there again
-    pending = None                 # (event, pinned PCM view, names, lens, ticket, wav) of the micro-batch still on its way to the host
     # library option fallback = "host": the range check of a sample call is looked at by the NEXT call, after that one has enqueued
     # itself (FastDiff.settle); until then the waveform and everything computed from it is provisional
     host_check = getattr(model, "_options", {}).get("fallback") == "host"
-    prev_dev = None                # return_device: (ticket, wav, names, lens) of the micro-batch nobody has settled yet
 
-    score = _scorer(model, items, scored, report, sample_rate, "synthesize")
-
-    def settle_on_device(p):
-        # the library remembers a bounded number of redone tickets (fd_sample_settle), so a micro-batch is settled as soon as the
-        # next sample() has looked at it (no wait by then) and not at the end of the job
-        ticket, wav, names, lens = p
-        if model.settle(ticket):                     # run again on fp32: so is its epilogue
-            pcm = epilogue(wav, lens)
-            if scored:
-                score(wav, names, lens)
-            for b, (name, t) in enumerate(zip(names, lens)):
-                out[name] = pcm[b, : n_of(t)]
-
-    def collect(p):
-        done, host, names, lens, ticket, wav = p
-        done.synchronize()
-        if host_check and model.settle(ticket):      # an operand left the fp16 range: the call was run again on fp32 -- so is its epilogue
-            host.copy_(epilogue(wav, lens), non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            if scored:
-                score(wav, names, lens)
-        for b, (name, t) in enumerate(zip(names, lens)):
-            out[name] = host[b, : n_of(t)].numpy().copy()
-
-    k = 0
-    for batch_idx in shard.micro_batches(range(len(items)), lengths, max_batch, sort=sort):
-        batch_items = [items[i] for i in batch_idx]
-        if on_device:
-            mels, lens, names = _collate_on_device(batch_items, drop_last_frame)
-        else:
-            if mel_up[k & 1] is not None:            # the upload of micro-batch k - 2 read this pinned buffer
-                mel_up[k & 1].synchronize()
-            mels, lens, names = collate_test_batch(batch_items, drop_last_frame, out=mel_np[k & 1])
-        if mels is None:
-            continue
-        uid_of = {items[i]["item_name"]: int(items[i].get("uid", i)) for i in batch_idx}
-        B, _, T = mels.shape
-        if not on_device:
-            mels = mel_pin[k & 1][: B * 80 * T].view(B, 80, T).cuda(non_blocking=True)
-            mel_up[k & 1] = torch.cuda.Event()
-            mel_up[k & 1].record()
-        with torch.no_grad():
-            wav = model.sample(mels, rows, ddim=False, seed=seed, lens=lens, stream_ids=[uid_of[n] for n in names], defer_check=host_check)
+    def vocode(mels, lens, stream_ids):
+        wav = model.sample(mels, rows, ddim=False, seed=seed, lens=lens, stream_ids=stream_ids, defer_check=host_check)
         ticket = getattr(model, "last_ticket", 0)
-        # one epilogue call and one asynchronous copy per micro-batch; the previous batch is unpacked on the host while this one runs
-        pcm = epilogue(wav, lens)
-        if scored:
-            score(wav, names, lens)
-        if return_device:
-            for b, (name, t) in enumerate(zip(names, lens)):
-                out[name] = pcm[b, : n_of(t)]
-            if host_check and prev_dev is not None:
-                settle_on_device(prev_dev)
-            prev_dev = (ticket, wav, names, lens)
-            k += 1
-            continue
-        host = pcm_pin[k & 1][: B * n_of(T)].view(B, n_of(T))
-        host.copy_(pcm, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        if pending is not None:
-            collect(pending)
-        pending = (done, host, names, lens, ticket, wav)
-        k += 1
-    if pending is not None:
-        collect(pending)
-    if host_check and prev_dev is not None:
-        settle_on_device(prev_dev)
-    return (out, report) if scored else out
+        return (wav, lens, lambda: model.settle(ticket)) if host_check else (wav, lens)
+
+    return _run_job("synthesize", model, items, vocode, max_batch, sort, drop_last_frame, out_sample_rate, sample_rate, loudness,
+                    dict(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd), pinned=True, return_device=return_device)
 
 
 def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_batch: int = 8, seed: int = 0, variant: str = "pwg",
@@ -470,32 +493,14 @@ def synthesize_griffin_lim(model, items: Sequence[dict], n_iters: int = 60, max_
     if inversion not in ("pinv", "nnls"):
         raise ValueError(f"synthesize_griffin_lim: inversion must be 'pinv' or 'nnls', got {inversion!r}")
     how = {} if inversion == "pinv" else dict(inversion=inversion, nnls_iters=int(nnls_iters))      # (the default passes no new keyword)
-    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
-    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
-        raise ValueError(f"synthesize_griffin_lim: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
-    report: Dict[str, dict] = {}
-    out: Dict[str, np.ndarray] = {}
-    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
-    uid_of = {it["item_name"]: int(it.get("uid", i)) for i, it in enumerate(items)}
-    kept = [it for it in items if it["mel"].shape[0] >= 2]
-    if not kept:
-        return (out, report) if scored else out
-    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
-    score = _scorer(model, items, scored, report, sample_rate, "synthesize_griffin_lim")
-    on_device = isinstance(kept[0]["mel"], torch.Tensor) and kept[0]["mel"].is_cuda
-    for batch_idx in shard.micro_batches(range(len(kept)), [it["mel"].shape[0] for it in kept], max_batch, sort=sort):
-        batch_items = [kept[i] for i in batch_idx]
-        mels, frames, names = (_collate_on_device if on_device else collate_test_batch)(batch_items, False)
-        with torch.no_grad():
-            wav = model.griffin_lim_mel(mels.cuda(), lens=frames, variant=variant, n_iters=n_iters, seed=seed, stream_ids=[uid_of[n] for n in names], **how)
-        lens = [f - 1 for f in frames]                 # in hops: 256 (frames - 1) samples
-        pcm = epilogue(wav, lens)
-        if scored:
-            score(wav, names, lens)
-        host = pcm.cpu().numpy()
-        for b, (name, t) in enumerate(zip(names, lens)):
-            out[name] = host[b, : n_of(t)].copy()
-    return (out, report) if scored else out
+
+    def vocode(mels, frames, stream_ids):              # all frames in, in hops: 256 (frames - 1) samples out
+        wav = model.griffin_lim_mel(mels, lens=frames, variant=variant, n_iters=n_iters, seed=seed, stream_ids=stream_ids, **how)
+        return wav, [f - 1 for f in frames]
+
+    return _run_job("synthesize_griffin_lim", model, items, vocode, max_batch, sort, drop_last_frame=True, all_frames_in=True,
+                    out_sample_rate=out_sample_rate, sample_rate=sample_rate, loudness=loudness,
+                    scores=dict(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd))
 
 
 def synthesize_pwg(model, pwg, items: Sequence[dict], max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, sort: bool = True,
@@ -510,31 +515,8 @@ def synthesize_pwg(model, pwg, items: Sequence[dict], max_batch: int = 8, seed: 
     pitch, spectral, mcd as in synthesize() -- the same report keys, measured on the float waveform before the epilogue."""
     if pwg.hop_size != model.hop_length:
         raise ValueError(f"synthesize_pwg: the generator's hop {pwg.hop_size} is not the {model.hop_length} samples of the mels' frames")
-    scored = _scores.enabled(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd)
-    if scored and not all(isinstance(it.get("wav"), torch.Tensor) and it["wav"].is_cuda for it in items):
-        raise ValueError(f"synthesize_pwg: {scored[0].name}=True needs items that carry their device waveform as 'wav' (load_wav_inputs(keep_wav=True))")
-    report: Dict[str, dict] = {}
-    out: Dict[str, np.ndarray] = {}
-    R = None if out_sample_rate is None or int(out_sample_rate) == int(sample_rate) else int(out_sample_rate)
-    uid_of = {it["item_name"]: int(it.get("uid", i)) for i, it in enumerate(items)}
-    kept = [it for it in items if it["mel"].shape[0] >= (2 if drop_last_frame else 1)]
-    if not kept:
-        return (out, report) if scored else out
-    n_of, epilogue = _level_epilogue(model, R, sample_rate, loudness)
-    score = _scorer(model, items, scored, report, sample_rate, "synthesize_pwg")
-    on_device = isinstance(kept[0]["mel"], torch.Tensor) and kept[0]["mel"].is_cuda
-    for batch_idx in shard.micro_batches(range(len(kept)), [it["mel"].shape[0] for it in kept], max_batch, sort=sort):
-        batch_items = [kept[i] for i in batch_idx]
-        mels, lens, names = (_collate_on_device if on_device else collate_test_batch)(batch_items, drop_last_frame)
-        with torch.no_grad():
-            wav = pwg.spec2wav(mels.cuda(), lens=lens, seed=seed, stream_ids=[uid_of[n] for n in names])
-        pcm = epilogue(wav, lens)
-        if scored:
-            score(wav, names, lens)
-        host = pcm.cpu().numpy()
-        for b, (name, t) in enumerate(zip(names, lens)):
-            out[name] = host[b, : n_of(t)].copy()
-    return (out, report) if scored else out
+    return _run_job("synthesize_pwg", model, items, lambda mels, lens, stream_ids: (pwg.spec2wav(mels, lens=lens, seed=seed, stream_ids=stream_ids), lens),
+                    max_batch, sort, drop_last_frame, out_sample_rate, sample_rate, loudness, dict(stoi=stoi, pitch=pitch, spectral=spectral, mcd=mcd))
 
 
 def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed: int = 0, drop_last_frame: bool = True, src: int = 0,
@@ -572,9 +554,9 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     rank, world = dist.get_rank(), dist.get_world_size()
     meta = [None]
     if rank == src:      # the collater's view of every item: the on-disk [T', 80] rows with the last frame dropped (a view: no copy, no
-        kept = [(i, it) for i, it in enumerate(items) if not drop_last_frame or it["mel"].shape[0] >= 2]      # transposition on the host)
-        mels = [it["mel"][: it["mel"].shape[0] - (1 if drop_last_frame else 0)] for _, it in kept]
-        meta = [([it["item_name"] for _, it in kept], [int(it.get("uid", i)) for i, it in kept], [int(m.shape[0]) for m in mels])]
+        mels, lens, names, kept = _select(items, drop_last_frame)                                             # transposition on the host)
+        mels = [m[:t] for m, t in zip(mels, lens)]
+        meta = [(names, [int(items[i].get("uid", i)) for i in kept], lens)]
     dist.broadcast_object_list(meta, src=src)          # names, noise-stream ids and lengths in one message
     names, uids, lens = meta[0]
     parts = shard.partition_utterances(lens, loop or world, cost="time" if balance == "time" else None)
@@ -587,12 +569,9 @@ def synthesize_sharded(model, items, n_steps: int = 4, max_batch: int = 8, seed:
     pcm = synthesize(model, local, n_steps, max_batch, seed, drop_last_frame=False, return_device=on_gpu, out_sample_rate=out_sample_rate,
                      sample_rate=sample_rate, loudness=loudness)
     wavs = [(i, pcm[str(i)] if on_gpu else torch.from_numpy(pcm[str(i)])) for i, _ in mine]
-    if out_sample_rate is None or int(out_sample_rate) == int(sample_rate):
-        sizes_of, unit = lens, model.hop_length
-    else:      # the gather sizes its messages as lens * hop: hand it the resampled sample counts with a hop of 1
-        from . import resample as _resample
-        sizes_of, unit = [_resample.out_len(t * model.hop_length, sample_rate, out_sample_rate) for t in lens], 1
-    out = shard.gather_waveforms(wavs, sizes_of, parts, hop=unit, dst=src, device=device, dtype=torch.int16, loopback=bool(loop))
+    # the gather sizes its messages as lens * hop: hand it the sample counts the epilogue delivered, with a hop of 1
+    n_of = _level_epilogue(model, out_sample_rate, sample_rate, loudness)[0]
+    out = shard.gather_waveforms(wavs, [n_of(t) for t in lens], parts, hop=1, dst=src, device=device, dtype=torch.int16, loopback=bool(loop))
     if rank != src:
         return {}
     if not on_gpu:
@@ -677,15 +656,11 @@ def synthesize_long(model, items: Sequence[dict], n_steps: int = 4, seed: int = 
                 pcm = model.loudness_normalize(wav.reshape(1, -1), float(loudness), sample_rate=sample_rate, out="int16")
             out[name] = pcm[0, : m.shape[-1] * hop].cpu().numpy()
 
-    for i, it in enumerate(items):
-        c = torch.as_tensor(it["mel"])
-        t = c.shape[0] - 1 if drop_last_frame else c.shape[0]
-        if t < 1:
-            continue
+    for c, t, name, i in zip(*_select(items, drop_last_frame)):
         if group and frames + t > group_frames:
             run()
             group, frames = [], 0
-        group.append((it["item_name"], int(it.get("uid", i)), c[:t].to(device="cuda", dtype=torch.float32).transpose(0, 1).contiguous()))
+        group.append((name, int(items[i].get("uid", i)), torch.as_tensor(c)[:t].to(device="cuda", dtype=torch.float32).transpose(0, 1).contiguous()))
         frames += t
     if group:
         run()
@@ -701,6 +676,17 @@ def save_wavs(pcm: Dict[str, np.ndarray], out_dir: str, sample_rate: int = 22050
         wavfile.write(path, sample_rate, data)
         paths.append(path)
     return paths
+
+
+def _write_table(rows, out_dir: str, stem: str, rank: int = 0, world: int = 1) -> str:
+    """Prints a table (rows of cells, the header first) tab-separated and writes it as <out_dir>/<stem>.tsv, one process per job, or as
+    <stem>.rank<r>.tsv where several ranks each write their own; returns the text."""
+    text = "\n".join("\t".join(row) for row in rows)
+    print(text)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, f"{stem}.tsv" if world == 1 else f"{stem}.rank{rank}.tsv"), "w") as f:
+        f.write(text + "\n")
+    return text
 
 
 def main(argv=None):
@@ -823,23 +809,15 @@ def main(argv=None):
                          spectral=args.spectral, **more)
     if scored:
         pcm, report = pcm
-        os.makedirs(args.out_dir, exist_ok=True)
         rows = [(it["item_name"], report[it["item_name"]]) for it in mine if it["item_name"] in report]
         for sc in scored:
-            lines = ["\t".join(["name"] + [key for _, key, _, _ in sc.columns] + ["status"])]
-            lines += ["\t".join([name] + [format(r[key], fmt) for _, key, _, fmt in sc.columns] + [r[sc.status_key]]) for name, r in rows]
-            print("\n".join(lines))
-            with open(os.path.join(args.out_dir, f"{sc.name}.tsv" if world == 1 else f"{sc.name}.rank{rank}.tsv"), "w") as f:
-                f.write("\n".join(lines) + "\n")
+            _write_table([["name"] + [key for _, key, _, _ in sc.columns] + ["status"]]
+                  + [[name] + [format(r[key], fmt) for _, key, _, fmt in sc.columns] + [r[sc.status_key]] for name, r in rows], args.out_dir, sc.name, rank, world)
     if args.ndb_bins:      # a score of the whole run against the corpus the bins were fitted on (not a row of _scores.SCORES, which are per utterance)
         from . import diversity
         d = diversity.score_waveforms(model, diversity.Bins.load(args.ndb_bins), [pcm[it["item_name"]] for it in mine if it["item_name"] in pcm],
                                       variant=args.mel_variant)
-        lines = ["\t".join(["n", "ndb", "ndb_over_k", "jsd"]), "\t".join([str(d["n"]), str(d["ndb"]), format(d["ndb_over_k"], ".4f"), format(d["jsd"], ".6f")])]
-        print("\n".join(lines))
-        os.makedirs(args.out_dir, exist_ok=True)
-        with open(os.path.join(args.out_dir, "diversity.tsv" if world == 1 else f"diversity.rank{rank}.tsv"), "w") as f:
-            f.write("\n".join(lines) + "\n")
+        _write_table([["n", "ndb", "ndb_over_k", "jsd"], [str(d["n"]), str(d["ndb"]), format(d["ndb_over_k"], ".4f"), format(d["jsd"], ".6f")]], args.out_dir, "diversity", rank, world)
     paths = save_wavs(pcm, args.out_dir, sample_rate=args.out_sample_rate or 22050)
     print(f"rank {rank}/{world}: wrote {len(paths)} files to {args.out_dir}")
 

@@ -297,6 +297,70 @@ def test_the_baseline_driver_uses_every_frame_and_the_items_own_streams(monkeypa
         infer.synthesize_griffin_lim(m, items, stoi=True)
 
 
+class _StubGenerator:
+    """What synthesize_pwg touches of a ParallelWaveGAN, on the CPU: the calls are recorded, the waveform is a ramp per item"""
+
+    def __init__(self, hop_size=256):
+        self.hop_size, self.calls = hop_size, []
+
+    def spec2wav(self, mels, lens=None, **kw):
+        self.calls.append(dict(shape=tuple(mels.shape), lens=list(lens), **kw))
+        wav = torch.zeros(mels.shape[0], 256 * mels.shape[2])
+        for b, n in enumerate(lens):
+            wav[b, : 256 * n] = torch.linspace(-1.0, 1.0, 256 * n) * (b + 1) / 4
+        return wav
+
+
+def _five_items():
+    rng = np.random.default_rng(0)
+    items = [{"item_name": f"u{i}", "mel": torch.from_numpy(rng.standard_normal((t, 80)).astype(np.float32)), "len": t} for i, t in enumerate((9, 1, 4, 12, 6))]
+    items[3]["uid"] = 40
+    return items
+
+
+def test_the_neural_baseline_driver_drops_the_last_frame_and_uses_the_items_own_streams(monkeypatch):
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
+    items, m, g = _five_items(), _StubModel(), _StubGenerator()
+    pcm = infer.synthesize_pwg(m, g, items, max_batch=2, seed=5)
+    assert {k: v.shape for k, v in pcm.items()} == {"u0": (2048,), "u2": (768,), "u3": (2816,), "u4": (1280,)}      # 256 (len - 1); the one-frame item is left out
+    assert all(v.dtype == np.int16 and np.abs(v).max() == 32767 for v in pcm.values())
+    assert [c["lens"] for c in g.calls] == [[11, 8], [5, 3]] and [c["shape"] for c in g.calls] == [(2, 80, 11), (2, 80, 5)]
+    assert [c["stream_ids"] for c in g.calls] == [[40, 0], [4, 2]]
+    assert all(c["seed"] == 5 for c in g.calls)
+    assert infer.synthesize_pwg(m, g, []) == {} and infer.synthesize_pwg(m, g, items[1:2]) == {}
+    assert len(g.calls) == 2 and not m.calls
+
+
+def test_the_neural_baseline_driver_keeps_every_frame_on_request(monkeypatch):
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
+    items, g = _five_items(), _StubGenerator()
+    pcm = infer.synthesize_pwg(_StubModel(), g, items, max_batch=2, seed=5, drop_last_frame=False)
+    assert {k: v.shape for k, v in pcm.items()} == {f"u{i}": (256 * t,) for i, t in enumerate((9, 1, 4, 12, 6))}
+    assert all(v.dtype == np.int16 for v in pcm.values())
+    assert [c["lens"] for c in g.calls] == [[12, 9], [6, 4], [1]]
+
+
+def test_the_neural_baseline_driver_refuses_another_hop_and_scores_without_recordings(monkeypatch):
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
+    items, g = _five_items(), _StubGenerator(hop_size=300)
+    with pytest.raises(ValueError, match=r"300.*256"):
+        infer.synthesize_pwg(_StubModel(), g, items)
+    with pytest.raises(ValueError, match=r"300.*256"):
+        infer.synthesize_pwg(_StubModel(), g, [])                  # refused before the items are looked at
+    with pytest.raises(ValueError, match="wav"):
+        infer.synthesize_pwg(_StubModel(), _StubGenerator(), items, stoi=True)
+    assert not g.calls
+
+
+def test_the_two_baselines_line_up(monkeypatch):
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
+    items = _five_items()
+    gl_pcm = infer.synthesize_griffin_lim(_StubModel(), items, n_iters=7, max_batch=2, seed=5)
+    pwg_pcm = infer.synthesize_pwg(_StubModel(), _StubGenerator(), items, max_batch=2, seed=5)
+    assert list(gl_pcm) == list(pwg_pcm) == ["u3", "u0", "u4", "u2"]                              # the same names, delivered in the same order
+    assert {k: v.shape for k, v in gl_pcm.items()} == {k: v.shape for k, v in pwg_pcm.items()}    # with the same sample counts
+
+
 def test_the_command_line_routes_the_vocoder(monkeypatch, tmp_path):
     seen = {}
 
@@ -332,6 +396,23 @@ def test_the_command_line_routes_the_vocoder(monkeypatch, tmp_path):
     infer.main(base + ["--vocoder", "griffin_lim", "--gl_iters", "0"])
     assert seen.pop("griffin_lim")[0][0] == 0
     assert os.path.exists(tmp_path / "o" / "a.npy_pred.wav")
+    # the neural baseline: the generator loaded from --pwg_dir goes in behind the model, then the items, (max_batch, seed) and the keywords
+    from fastdiff_amd.pwg import ParallelWaveGAN
+
+    def fake_pwg(model, gen, items, *a, **kw):
+        seen.setdefault("pwg", []).append((gen, a, kw))
+        return {it["item_name"]: np.zeros(256, np.int16) for it in items}
+
+    monkeypatch.setattr(ParallelWaveGAN, "from_dir", classmethod(lambda cls, d: ("generator of", d)))
+    monkeypatch.setattr(infer, "synthesize_pwg", fake_pwg)
+    infer.main(base + ["--vocoder", "pwg", "--pwg_dir", "D", "--seed", "9", "--max_batch", "3"])
+    (gen, a, kw), = seen.pop("pwg")
+    assert not seen and gen == ("generator of", "D") and a == (3, 9)
+    assert kw == dict(out_sample_rate=None, loudness=None, stoi=False, pitch=False, spectral=False)
+    for bad in (["--vocoder", "pwg"], ["--vocoder", "pwg", "--pwg_dir", "D", "--long_form"]):
+        with pytest.raises(SystemExit):
+            infer.main(base + bad)
+    assert not seen
     for bad in (["--vocoder", "wavenet"], ["--vocoder", "griffin_lim", "--long_form"], ["--vocoder", "griffin_lim", "--gl_iters", "-1"],
                 ["--vocoder", "griffin_lim", "--gl_iters", "10001"], ["--vocoder", "griffin_lim", "--stoi"]):
         with pytest.raises(SystemExit):

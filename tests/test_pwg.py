@@ -275,6 +275,69 @@ def test_from_dir_reads_both_checkpoint_formats(tmp_path):
         pwg.ParallelWaveGAN.from_dir(str(tmp_path / "empty"))
 
 
+@pytest.fixture(scope="module")
+def job():
+    """infer.synthesize_pwg's two models and a small job: a generator of 6 layers in 2 stacks, a FastDiff for the epilogue, mels of
+    2, 3, 9 and 1 frames (item 2 with a stream id of its own)"""
+    import gpu_common
+    from fastdiff_amd import infer
+    cfg = ref.config(layers=6, stacks=2)
+    gen = pwg.ParallelWaveGAN(**cfg).load_state_dict(ref.make_weights(cfg, 5))
+    mels = [torch.from_numpy(np.ascontiguousarray(ref.synth_mel(50 + i, 1, t)[0].T, dtype=np.float32)) for i, t in enumerate((2, 3, 9, 1))]
+    items = [{"item_name": f"u{i}", "mel": m, "len": m.shape[0]} for i, m in enumerate(mels)]
+    items[2]["uid"] = 40
+    return infer, gpu_common.make_model(), gen, items
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("where", ("host", "device"))
+def test_synthesize_pwg_equals_direct_calls_item_by_item(job, where):
+    infer, model, gen, items = job
+    if where == "device":
+        items = [dict(it, mel=it["mel"].cuda()) for it in items]
+    pcm = infer.synthesize_pwg(model, gen, items, max_batch=2, seed=7)
+    assert sorted(pcm) == ["u0", "u1", "u2"]                              # the one-frame item is absent
+    for i, it in enumerate(items[:3]):
+        t = it["mel"].shape[0] - 1                                        # spec2wav on the item's frames but the last, alone, then its own peak
+        mel = it["mel"].T.unsqueeze(0).contiguous().cuda()
+        want = model.peak_normalize_int16(gen.spec2wav(mel[:, :, :t].contiguous(), seed=7, stream_ids=[int(it.get("uid", i))])).cpu().numpy().reshape(-1)
+        got = pcm[it["item_name"]]
+        assert got.dtype == np.int16 and got.shape == (256 * t,) and np.abs(got).max() == 32767
+        assert np.array_equal(got, want), it["item_name"]
+
+
+@pytest.mark.gpu
+def test_synthesize_pwg_at_another_rate_equals_each_item_alone(job):
+    from fastdiff_amd import resample
+    infer, model, gen, items = job
+    pcm = infer.synthesize_pwg(model, gen, items, max_batch=2, seed=7, out_sample_rate=16000)
+    assert sorted(pcm) == ["u0", "u1", "u2"]
+    for i, it in enumerate(items[:3]):
+        one = infer.synthesize_pwg(model, gen, [dict(it, uid=int(it.get("uid", i)))], max_batch=2, seed=7, out_sample_rate=16000)
+        assert list(one) == [it["item_name"]] and np.array_equal(pcm[it["item_name"]], one[it["item_name"]])
+        assert pcm[it["item_name"]].shape == (resample.out_len(256 * (it["mel"].shape[0] - 1), 22050, 16000),)
+
+
+@pytest.mark.gpu
+def test_synthesize_pwg_scores_into_the_models_report_keys(job, tmp_path):
+    import synth
+    from scipy.io import wavfile
+    infer, model, gen, _ = job
+    for i, frames in enumerate((86, 61)):                                  # two recordings, as tests/test_griffin_lim.py makes them
+        x = np.clip(0.1 * synth.synth_audio(31 + i, 1, frames).reshape(-1), -0.9, 0.9)
+        wavfile.write(tmp_path / f"r{i}.wav", 22050, np.round(x * 32767.0).astype(np.int16))
+    items = infer.load_wav_inputs(model, str(tmp_path), keep_wav=True)
+    assert [it["len"] for it in items] == [87, 62]
+    _, theirs = infer.synthesize(model, items, n_steps=4, max_batch=2, seed=3, stoi=True, spectral=True)
+    pcm, report = infer.synthesize_pwg(model, gen, items, max_batch=2, seed=3, stoi=True, spectral=True)
+    plain = infer.synthesize_pwg(model, gen, items, max_batch=2, seed=3)
+    assert set(pcm) == set(report) == set(plain) == {"r0.wav", "r1.wav"}
+    for name in pcm:
+        assert set(report[name]) == set(theirs[name])
+        assert report[name]["status"] == "OK" and report[name]["spectral_status"] == "OK"
+        assert np.array_equal(pcm[name], plain[name])
+
+
 @pytest.mark.gpu
 def test_cli_vocoder_pwg(tmp_path):
     """infer --vocoder pwg on two tiny recordings writes the wavs and a score table."""
