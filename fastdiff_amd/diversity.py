@@ -32,8 +32,7 @@ from . import _capi, _wave
 CHUNK, MAX_K, MAX_D = _capi.FD_BINS_CHUNK, _capi.FD_BINS_MAX_K, _capi.FD_BINS_MAX_D
 OK, NONFINITE, EMPTY = _capi.FD_BINS_OK, _capi.FD_BINS_NONFINITE, _capi.FD_BINS_EMPTY
 STATUS = {OK: "OK", NONFINITE: "NONFINITE", EMPTY: "EMPTY"}
-RECORD = np.dtype([("counts", "<i8", (MAX_K,)), ("inertia", "<f8"), ("moved", "<i8"), ("nonfinite", "<i8"), ("empty", "<i4"), ("status", "<i4")])
-assert RECORD.itemsize == _capi.FD_BINS_RECORD_BYTES
+RECORD = _capi.record("fd_bins")
 
 
 def ndb_jsd(ref_counts, counts, alpha=0.05):

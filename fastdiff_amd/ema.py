@@ -50,13 +50,13 @@ class ParamEMA:
             at += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
         self.shadow = torch.zeros(at, device=self.device, dtype=torch.float32)
         self.tensors = OrderedDict((k, self.shadow[o: o + p.numel()].view(p.shape)) for k, o, p in zip(keys, offsets, self.params))
-        self._hyper_dev = torch.zeros(2, dtype=torch.float64, device=self.device)      # fd_ema_hyper
+        self._hyper_dev = lvc_op.new_state("fd_ema_hyper", self.device, torch.float64)
         self._write_hyper()
         self._state = lvc_op.new_ema_state(self.device)                                 # fd_ema_state
         self.reset()
 
     def _write_hyper(self):
-        self._hyper_dev.copy_(torch.tensor([self.decay, 1.0 if self.warmup else 0.0], dtype=torch.float64))
+        self._hyper_dev.copy_(lvc_op.pack_state("fd_ema_hyper", torch.float64, decay=self.decay, warmup=1.0 if self.warmup else 0.0))
 
     def reset(self, seen_applied=0):
         """The shadow := the parameters as they are now, no update counted; seen_applied: the optimizer's `applied` count that the
@@ -64,7 +64,7 @@ class ParamEMA:
         with torch.no_grad():
             for e, p in zip(self.tensors.values(), self.params):
                 e.copy_(p)
-        self._state.copy_(torch.tensor([0, int(seen_applied), 0], dtype=torch.int64))
+        self._state.copy_(lvc_op.pack_state("fd_ema_state", seen_applied=int(seen_applied)))
 
     def update(self, train_state, ema_state=None):
         """One lvc_op.ema_multi call on the current stream, behind the optimizer that advances `train_state` (a new_train_state
@@ -75,7 +75,7 @@ class ParamEMA:
     def set_decay(self, decay):
         """The decay of the following updates: a copy of 8 bytes into device memory, between two replays."""
         self.decay = float(decay)
-        self._hyper_dev[0:1].copy_(torch.tensor([self.decay], dtype=torch.float64))
+        lvc_op.state_field(self._hyper_dev, "fd_ema_hyper", "decay").copy_(torch.tensor([self.decay], dtype=torch.float64))
 
     def state(self):
         """{"updates", "seen_applied"} of the device's fd_ema_state.  Synchronises."""
@@ -101,7 +101,7 @@ class ParamEMA:
                 t.copy_(shadow[k])
         self.decay, self.warmup = float(sd["decay"]), bool(sd["warmup"])
         self._write_hyper()
-        self._state.copy_(torch.tensor([int(sd["updates"]), int(sd["seen_applied"]), 0], dtype=torch.int64))
+        self._state.copy_(lvc_op.pack_state("fd_ema_state", updates=int(sd["updates"]), seen_applied=int(sd["seen_applied"])))
 
     def copy_to(self, module):
         """Write the shadow over the parameters of `module` (this one or another of the same architecture) with torch's copy_: for

@@ -41,13 +41,13 @@ NFFT, HOP, BINS, MELS = _capi.FD_GL_NFFT, _capi.FD_GL_HOP, _capi.FD_GL_BINS, 80
 FRAME_TILE, MAX_ITERS, PHILOX_STREAM = _capi.FD_GL_FRAME_TILE, _capi.FD_GL_MAX_ITERS, _capi.FD_GL_PHILOX_STREAM
 OK, SHORT, SILENT, NONFINITE = _capi.FD_GL_OK, _capi.FD_GL_SHORT, _capi.FD_GL_SILENT, _capi.FD_GL_NONFINITE
 STATUS = {OK: "OK", SHORT: "SHORT", SILENT: "SILENT", NONFINITE: "NONFINITE"}
-RECORD = np.dtype([("sc", "<f8"), ("norm", "<f8"), ("frames", "<i4"), ("samples", "<i4"), ("iters", "<i4"), ("status", "<i4")])
+RECORD = _capi.record("fd_gl")
 VARIANTS = {"pwg": _capi.FD_GL_PWG, "tacotron": _capi.FD_GL_TACOTRON}
 
 NNLS_MAX_ITERS, NNLS_FRAME_TILE = _capi.FD_NNLS_MAX_ITERS, _capi.FD_NNLS_FRAME_TILE
 NNLS_OK, NNLS_EMPTY, NNLS_NONFINITE = _capi.FD_NNLS_OK, _capi.FD_NNLS_EMPTY, _capi.FD_NNLS_NONFINITE
 NNLS_STATUS = {NNLS_OK: "OK", NNLS_EMPTY: "EMPTY", NNLS_NONFINITE: "NONFINITE"}
-NNLS_RECORD = np.dtype([("resid", "<f8"), ("norm", "<f8"), ("frames", "<i4"), ("iters", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+NNLS_RECORD = _capi.record("fd_nnls")
 
 _pinv_cache = {}      # variant -> (the bank's bytes, its pseudo-inverse)
 

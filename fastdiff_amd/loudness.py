@@ -25,7 +25,7 @@ from . import _capi, _wave
 TILE = _capi.FD_LOUDNESS_TILE
 OK, SHORT, SILENT, CLIPPED = _capi.FD_LOUDNESS_OK, _capi.FD_LOUDNESS_SHORT, _capi.FD_LOUDNESS_SILENT, _capi.FD_LOUDNESS_CLIPPED
 STATUS = {OK: "OK", SHORT: "SHORT", SILENT: "SILENT", CLIPPED: "CLIPPED"}
-RECORD = np.dtype([("lufs", "<f8"), ("gain", "<f4"), ("peak", "<f4"), ("blocks", "<i4"), ("gated", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+RECORD = _capi.record("fd_loudness")
 
 
 def design(rate):

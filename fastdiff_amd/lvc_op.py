@@ -628,13 +628,13 @@ class _WeightNormAll(torch.autograd.Function):
         ow, on = np.concatenate(([0], np.cumsum(numel)[:-1])), np.concatenate(([0], np.cumsum(rows)[:-1]))
         W = torch.empty(int(numel.sum()), device=dev, dtype=torch.float32)
         N = torch.empty(int(rows.sum()), device=dev, dtype=torch.float32)
-        tab = np.zeros((n, 9), dtype=np.int64)      # fd_wn_item: v, g, w, norm, dw, dv, dg, rows, cols (+ reserved)
-        tab[:, 0] = [v.data_ptr() for v in vs]
-        tab[:, 1] = [g.data_ptr() for g in gs]
-        tab[:, 2] = W.data_ptr() + 4 * ow
-        tab[:, 3] = N.data_ptr() + 4 * on
-        tab[:, 7] = rows
-        tab[:, 8] = numel // rows
+        tab = np.zeros(n, dtype=_capi.record("fd_wn_item"))
+        tab["v"] = [v.data_ptr() for v in vs]
+        tab["g"] = [g.data_ptr() for g in gs]
+        tab["w"] = W.data_ptr() + 4 * ow
+        tab["norm"] = N.data_ptr() + 4 * on
+        tab["rows"] = rows
+        tab["cols"] = numel // rows
         _call(dev, "fd_weight_norm_multi_forward", "fd_weight_norm_multi_forward", tab.ctypes.data, n)
         ctx.save_for_backward(N, *vs, *gs)
         ctx.tab, ctx.ow, ctx.on, ctx.sizes = tab, ow, on, (numel.tolist(), rows.tolist())
@@ -649,9 +649,9 @@ class _WeightNormAll(torch.autograd.Function):
         DG = torch.empty(sum(ctx.sizes[1]), device=dev, dtype=torch.float32)
         dws = [None if d is None else d.contiguous().float() for d in dws]      # (kept alive until the launch is enqueued)
         tab = ctx.tab.copy()
-        tab[:, 4] = [0 if d is None else d.data_ptr() for d in dws]
-        tab[:, 5] = DV.data_ptr() + 4 * ctx.ow
-        tab[:, 6] = DG.data_ptr() + 4 * ctx.on
+        tab["dw"] = [0 if d is None else d.data_ptr() for d in dws]
+        tab["dv"] = DV.data_ptr() + 4 * ctx.ow
+        tab["dg"] = DG.data_ptr() + 4 * ctx.on
         _call(dev, "fd_weight_norm_multi_backward", "fd_weight_norm_multi_backward", tab.ctypes.data, n)
         out = []
         for dv, dg, v, g in zip(DV.split(ctx.sizes[0]), DG.split(ctx.sizes[1]), vs, gs):
@@ -928,23 +928,49 @@ def location_variable_convolution_frames(x, kernel_frames, bias, hop_size, grad_
 TS_STREAM, Z_STREAM = 0xFFFFFFFD, 0xFFFFFFFE      # the Philox streams of a training step's ts and z
 
 
-class AdamWHyper(ct.Structure):
-    """fd_adamw_hyper."""
-    _fields_ = [(k, ct.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
+AdamWHyper = _capi.struct("fd_adamw_hyper")
+
+
+def new_state(name, device, dtype=torch.int64):
+    """A zeroed C struct `name` (include/fastdiff_hip_train.h) in device memory, as whole words of `dtype`."""
+    return torch.zeros(_capi.record(name).itemsize // dtype.itemsize, dtype=dtype, device=device)
+
+
+def pack_state(name, dtype=torch.int64, **values):
+    """The C struct `name` with `values` in the fields they name and zero elsewhere, as a host tensor of `dtype` words: what a state
+    tensor's copy_ takes."""
+    import numpy as np
+    r = np.zeros(1, _capi.record(name))
+    for k, v in values.items():
+        r[k] = v
+    return torch.from_numpy(r.view(np.uint8)).view(dtype)
+
+
+def state_field(t, name, field):
+    """The one-element view, in the field's own type, of scalar `field` of the C struct `name` that the state tensor `t` holds."""
+    ftype, offset = _capi.record(name).fields[field][:2]
+    return t.view(getattr(torch, ftype.name))[offset // ftype.itemsize:][:1]
+
+
+def _is_state(t, name, dtype=torch.int64):
+    return t.dtype == dtype and t.is_contiguous() and t.numel() * t.element_size() == _capi.record(name).itemsize
+
+
+def _read_state(t, name):
+    """The tensor's bytes on the host as the one record `name`, read by field name (synchronises)."""
+    return t.cpu().numpy().view(_capi.record(name))[0]
 
 
 def new_train_state(device):
-    """A zeroed fd_train_state: 32 bytes of device memory, as four int64 words (iter, applied, skipped, {grad_norm, loss})."""
-    return torch.zeros(4, dtype=torch.int64, device=device)
+    """A zeroed fd_train_state in device memory, as int64 words."""
+    return new_state("fd_train_state", device)
 
 
 def read_train_state(state):
     """fd_train_state -> dict (synchronises)."""
-    import numpy as np
-    raw = state.cpu().numpy()
-    f = raw[3:4].view(np.float32)
-    return {"iter": int(raw[0]) & 0xFFFFFFFFFFFFFFFF, "applied": int(raw[1]) & 0xFFFFFFFFFFFFFFFF, "skipped": int(raw[2]) & 0xFFFFFFFFFFFFFFFF,
-            "grad_norm": float(f[0]), "loss": float(f[1])}
+    r = _read_state(state, "fd_train_state")
+    return {"iter": int(r["iter"]), "applied": int(r["applied"]), "skipped": int(r["skipped"]), "grad_norm": float(r["grad_norm"]),
+            "loss": float(r["loss"])}
 
 
 def train_draw(x0, alpha, T_train, seed=0, iteration=0, state=None, out=None):
@@ -1020,26 +1046,24 @@ def adamw_multi(items, hyper, state):
     """clip_grad_norm_ + non-finite guard + AdamW.step() over all tensors (fd_adamw_multi).  items: [(p, g or None, m, v)] float32
     contiguous HIP tensors; hyper: a device tensor holding an AdamWHyper; state: a new_train_state tensor."""
     import numpy as np
-    tab = np.zeros((len(items), 5), dtype=np.int64)      # fd_adamw_item: p, g, m, v, numel
+    tab = np.zeros(len(items), dtype=_capi.record("fd_adamw_item"))
     for i, (p, g, m, v) in enumerate(items):
         assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and p.dtype == m.dtype == v.dtype == torch.float32
         assert g is None or (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == p.numel())
-        tab[i] = (p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+        row = tab[i]
+        row["p"], row["g"], row["m"], row["v"], row["numel"] = p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
     _call(state.device, "fd_adamw_multi", "fd_adamw_multi", tab.ctypes.data, len(items), hyper, state)
 
 
 def new_ema_state(device):
-    """A zeroed fd_ema_state: 24 bytes of device memory, as three int64 words (updates, seen_applied, {w, apply})."""
-    return torch.zeros(3, dtype=torch.int64, device=device)
+    """A zeroed fd_ema_state in device memory, as int64 words."""
+    return new_state("fd_ema_state", device)
 
 
 def read_ema_state(ema_state):
     """fd_ema_state -> dict (synchronises)."""
-    import numpy as np
-    raw = ema_state.cpu().numpy()
-    tail = raw[2:3]
-    return {"updates": int(raw[0]) & 0xFFFFFFFFFFFFFFFF, "seen_applied": int(raw[1]) & 0xFFFFFFFFFFFFFFFF,
-            "w": float(tail.view(np.float32)[0]), "apply": int(tail.view(np.int32)[1])}
+    r = _read_state(ema_state, "fd_ema_state")
+    return {"updates": int(r["updates"]), "seen_applied": int(r["seen_applied"]), "w": float(r["w"]), "apply": int(r["apply"])}
 
 
 def ema_multi(items, hyper, state, ema_state):
@@ -1049,36 +1073,34 @@ def ema_multi(items, hyper, state, ema_state):
     optimizer applied a step since the last update.  Does not synchronise."""
     import numpy as np
     dev = ema_state.device
-    assert hyper.dtype == torch.float64 and hyper.numel() == 2 and hyper.is_contiguous() and hyper.device == dev, "hyper: two float64 on the device"
-    assert state.dtype == torch.int64 and state.numel() == 4 and state.device == dev, "state: a new_train_state tensor on the device"
-    assert ema_state.dtype == torch.int64 and ema_state.numel() == 3 and ema_state.is_cuda, "ema_state: a new_ema_state tensor"
-    tab = np.zeros((len(items), 3), dtype=np.int64)      # fd_ema_item: p, e, numel
+    assert _is_state(hyper, "fd_ema_hyper", torch.float64) and hyper.device == dev, "hyper: an fd_ema_hyper as float64 on the device"
+    assert _is_state(state, "fd_train_state") and state.device == dev, "state: a new_train_state tensor on the device"
+    assert _is_state(ema_state, "fd_ema_state") and ema_state.is_cuda, "ema_state: a new_ema_state tensor"
+    tab = np.zeros(len(items), dtype=_capi.record("fd_ema_item"))
     for i, (p, e) in enumerate(items):
         assert p.is_contiguous() and e.is_contiguous() and p.dtype == e.dtype == torch.float32 and p.numel() == e.numel()
         assert p.device == dev and e.device == dev
-        tab[i] = (p.data_ptr(), e.data_ptr(), p.numel())
+        row = tab[i]
+        row["p"], row["e"], row["numel"] = p.data_ptr(), e.data_ptr(), p.numel()
     _call(dev, "fd_ema_multi", "fd_ema_multi", tab.ctypes.data, len(items), hyper, state, ema_state)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # An evaluation pass (include/fastdiff_hip_train.h: fd_eval_collate, fd_item_distance, fd_eval_accumulate; fastdiff_amd/validate.py)
 # ---------------------------------------------------------------------------------------------------------------------------------
-EVAL_MAX_BINS = 64
-_EVAL_WORDS = 4 + 2 * EVAL_MAX_BINS      # fd_eval_state as 8-byte words: sum, count, nonfinite, reserved, bin_sum[64], bin_count[64]
+EVAL_MAX_BINS = _capi.FD_EVAL_MAX_BINS
 
 
 def new_eval_state(device):
-    """A zeroed fd_eval_state: 1056 bytes of device memory as int64 words (the double sums are read through a float64 view)."""
-    return torch.zeros(_EVAL_WORDS, dtype=torch.int64, device=device)
+    """A zeroed fd_eval_state in device memory, as int64 words."""
+    return new_state("fd_eval_state", device)
 
 
 def read_eval_state(acc, bins=EVAL_MAX_BINS):
     """fd_eval_state -> {"sum", "count", "nonfinite", "bin_sum" [bins] float64, "bin_count" [bins] int64} (synchronises)."""
-    import numpy as np
-    raw = acc.cpu().numpy()
-    f = raw.view(np.float64)
-    return {"sum": float(f[0]), "count": int(raw[1]), "nonfinite": int(raw[2]), "bin_sum": f[4: 4 + bins].copy(),
-            "bin_count": raw[4 + EVAL_MAX_BINS: 4 + EVAL_MAX_BINS + bins].copy()}
+    r = _read_state(acc, "fd_eval_state")
+    return {"sum": float(r["sum"]), "count": int(r["count"]), "nonfinite": int(r["nonfinite"]), "bin_sum": r["bin_sum"][:bins].copy(),
+            "bin_count": r["bin_count"][:bins].astype("int64")}
 
 
 def eval_collate(corpus, batch_size, seed=0, iteration=0, state=None, out=None):
@@ -1109,10 +1131,11 @@ def eval_accumulate(values, picked, acc, steps=None, T_train=1, bins=1, item_out
     (fd_eval_accumulate); with steps [B] also to bin (ts bins) // T_train; item_out[item] = value; advance: the pass's train state,
     whose batch index goes up by one behind this call."""
     dev, B = values.device, values.numel()
-    for t, n, dtype in ((values, B, torch.float32), (steps, B, torch.float32), (picked, 2 * B, torch.int64), (acc, _EVAL_WORDS, torch.int64),
-                        (advance, 4, torch.int64), (item_out, None, torch.float32)):
+    for t, n, dtype in ((values, B, torch.float32), (steps, B, torch.float32), (picked, 2 * B, torch.int64), (item_out, None, torch.float32)):
         assert t is None or (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and n in (None, t.numel())), \
             "eval_accumulate: contiguous HIP tensors of one device: values / steps [B] float32, picked [B, 2] int64"
+    for t, name in ((acc, "fd_eval_state"), (advance, "fd_train_state")):
+        assert t is None or (t.is_cuda and t.device == dev and _is_state(t, name)), f"eval_accumulate: {name} as int64 words on the device of the values"
     _call(dev, "fd_eval_accumulate", "fd_eval_accumulate", values, steps, picked, B, int(T_train), int(bins), acc, item_out, advance)
 
 
@@ -1244,13 +1267,12 @@ def phi_residual(eps, z, delta, beta_hat):
     return _PhiResidual.apply(eps, z, delta, beta_hat)
 
 
-SCHED_MAX_STEPS = 64
-_SCHED_WORDS = 4 + SCHED_MAX_STEPS + 2 + 4 + 2      # fd_sched_state as 4-byte words
+SCHED_MAX_STEPS = _capi.FD_SCHED_MAX_STEPS
 
 
 def new_sched_state(device, betaN, alphaN):
-    """An fd_sched_state in device memory, initialised on the device (fd_sched_init)."""
-    state = torch.zeros(_SCHED_WORDS, dtype=torch.int32, device=device)
+    """An fd_sched_state in device memory (int32 words), initialised on the device (fd_sched_init)."""
+    state = new_state("fd_sched_state", device, torch.int32)
     lib, h = _handle(device)
     _capi.check(lib, h, lib.fd_sched_init(h, state.data_ptr(), float(betaN), float(alphaN), _stream(device)), "fd_sched_init")
     return state
@@ -1258,12 +1280,10 @@ def new_sched_state(device, betaN, alphaN):
 
 def read_sched_state(state):
     """fd_sched_state -> dict (synchronises: the one read of a search)."""
-    import numpy as np
-    raw = state.cpu().numpy()
-    f = raw.view(np.float32)
-    n = int(raw[3])
-    return {"alpha_cur": float(f[0]), "beta_cur": float(f[1]), "stopped": int(raw[2]), "n_found": n, "found": f[4: 4 + n].copy(),
-            "step": float(f[4 + SCHED_MAX_STEPS])}
+    r = _read_state(state, "fd_sched_state")
+    n = int(r["n_found"])
+    return {"alpha_cur": float(r["alpha_cur"]), "beta_cur": float(r["beta_cur"]), "stopped": int(r["stopped"]), "n_found": n,
+            "found": r["found"][:n].copy(), "step": float(r["step"])}
 
 
 def sched_begin(state, beta_hat, rho, alpha, ddim, steps_out):

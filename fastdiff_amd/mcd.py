@@ -36,20 +36,11 @@ MAX_COEF, MAX_FRAMES, ROWS, COLS, MAX_ALIGN_CELLS = (_capi.FD_MCD_MAX_COEF, _cap
                                                       _capi.FD_DTW_MAX_ALIGN_CELLS)
 OK, SHORT, NONFINITE = _capi.FD_MCD_OK, _capi.FD_MCD_SHORT, _capi.FD_MCD_NONFINITE
 STATUS = {OK: "OK", SHORT: "SHORT", NONFINITE: "NONFINITE"}
-RECORD = np.dtype([("mcd_dtw", "<f8"), ("mcd_linear", "<f8"), ("cost", "<f8"), ("path_len", "<i4"), ("n_diag", "<i4"), ("frames_clean", "<i4"),
-                   ("frames_degraded", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
-DTW_RECORD = np.dtype([("cost", "<f8"), ("path_len", "<i4"), ("n_diag", "<i4"), ("frames_a", "<i4"), ("frames_b", "<i4"), ("status", "<i4"),
-                       ("reserved", "<i4")])
+RECORD, DTW_RECORD = _capi.record("fd_mcd"), _capi.record("fd_dtw_rec")
 FIELDS = tuple(k for k in RECORD.names if k != "reserved")
 DTW_FIELDS = tuple(k for k in DTW_RECORD.names if k != "reserved")
 K_DB = 10.0 * np.sqrt(2.0) / np.log(10.0)
-assert RECORD.itemsize == 48 and DTW_RECORD.itemsize == 32
-
-
-class FdMcdConfig(ct.Structure):
-    _fields_ = [("n_coef", ct.c_int32), ("reserved", ct.c_int32)]
-
-
+FdMcdConfig = _capi.struct("fd_mcd_config")
 KEYS = ("n_coef", "variant")
 VARIANTS = ("pwg", "tacotron")
 

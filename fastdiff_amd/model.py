@@ -707,7 +707,7 @@ class FastDiff(nn.Module):
             else:
                 names = [k.encode() for k in sd]
                 dims = [(ct.c_int64 * t.dim())(*t.shape) for t in sd.values()]
-                items = (_capi.FdWeightRef * len(sd))(*[_capi.FdWeightRef(k, t.data_ptr(), d, t.dim(), 0)
+                items = (_capi.FdWeightRef * len(sd))(*[_capi.FdWeightRef(k, t.data_ptr(), ct.addressof(d), t.dim(), 0)
                                                         for k, t, d in zip(names, sd.values(), dims)])
                 s = self._stream(p.device) if stream is None else ct.c_void_p(getattr(stream, "cuda_stream", stream))
                 rc = lib.fd_refresh_weights_device(self._handle, items, len(sd), s)

@@ -37,7 +37,7 @@ class PhiStep(TrainStep):
             raise ValueError(f"PhiStep: T={self.T_train} must exceed 2 tau={2 * self.tau}")
         self.alpha = dh["alpha"].detach().to(self.device, torch.float32).contiguous()
         self.seed = int(seed)
-        self._state_loss = self._state.view(torch.float32)[7:8]                         # the `loss` field of the fd_train_state
+        self._state_loss = lvc_op.state_field(self._state, "fd_train_state", "loss")
         self.ema = None                                                                  # (no average: state_dict() asks)
         self._init_batch_source(corpus, batch_size, rank, world_size)
         self.mel = self.wav = self.draw = None      # the buffers of the current batch shape

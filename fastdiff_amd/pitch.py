@@ -21,7 +21,6 @@ otherwise.
 """
 import ctypes as ct
 
-import numpy as np
 import torch
 
 from . import _capi, _wave
@@ -29,16 +28,9 @@ from . import _capi, _wave
 MAX_LAGS, FRAME_TILE, LAG_CHUNK, STAGE_FLOATS = _capi.FD_PITCH_MAX_LAGS, _capi.FD_PITCH_FRAME_TILE, _capi.FD_PITCH_LAG_CHUNK, _capi.FD_PITCH_STAGE_FLOATS
 OK, SHORT, UNVOICED = _capi.FD_PITCH_OK, _capi.FD_PITCH_SHORT, _capi.FD_PITCH_UNVOICED
 STATUS = {OK: "OK", SHORT: "SHORT", UNVOICED: "UNVOICED"}
-RECORD = np.dtype([("rmse_cents", "<f8"), ("gpe", "<f8"), ("vde", "<f8"), ("frames", "<i4"), ("both_voiced", "<i4"), ("ref_voiced", "<i4"),
-                   ("deg_voiced", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+RECORD = _capi.record("fd_pitch")
 FIELDS = tuple(k for k in RECORD.names if k != "reserved")
-
-
-class FdPitchConfig(ct.Structure):
-    _fields_ = [("rate", ct.c_int32), ("hop", ct.c_int32), ("win", ct.c_int32), ("reserved", ct.c_int32),
-                ("f0_min", ct.c_double), ("f0_max", ct.c_double), ("threshold", ct.c_double)]
-
-
+FdPitchConfig = _capi.struct("fd_pitch_config")
 KEYS = ("rate", "hop", "win", "f0_min", "f0_max", "threshold")
 
 

@@ -180,7 +180,7 @@ class ParallelWaveGAN:
         state = fold_weight_norm(unwrap_checkpoint(state)[0])
         for name, v in state.items():
             v = np.ascontiguousarray(v, dtype=np.float32)
-            self._check(self._lib.fd_pwg_set_weight(self._p, name.encode(), _capi.float_ptr(v), v.size), "fd_pwg_set_weight")
+            self._check(self._lib.fd_pwg_set_weight(self._p, name.encode(), v.ctypes.data, v.size), "fd_pwg_set_weight")
         self._check(self._lib.fd_pwg_commit(self._p), "fd_pwg_commit")
         self.committed = True
         return self
@@ -193,7 +193,7 @@ class ParallelWaveGAN:
         mean, scale = np.ascontiguousarray(mean, dtype=np.float32), np.ascontiguousarray(scale, dtype=np.float32)
         if mean.shape != (MELS,) or scale.shape != (MELS,):
             raise ValueError(f"ParallelWaveGAN: expected mean and scale [80], got {list(mean.shape)} and {list(scale.shape)}")
-        self._check(self._lib.fd_pwg_set_scaler(self._p, _capi.float_ptr(mean), _capi.float_ptr(scale)), "fd_pwg_set_scaler")
+        self._check(self._lib.fd_pwg_set_scaler(self._p, mean.ctypes.data, scale.ctypes.data), "fd_pwg_set_scaler")
         self.scaler = (mean, scale)
         return self
 
@@ -249,8 +249,8 @@ class ParallelWaveGAN:
                 raise ValueError(f"ParallelWaveGAN: stream_ids has {len(stream_ids)} entries for {B} items")
             ids = (ct.c_uint64 * B)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in stream_ids])
         from . import lvc_op
-        rc = self._lib.fd_pwg_generate(self._p, _capi.float_ptr(src), int(padded), B, T, _wave.counts(lens, B, "ParallelWaveGAN"),
-                                       _capi.float_ptr(z), int(seed) & 0xFFFFFFFFFFFFFFFF, ids, _capi.float_ptr(wav), wav.stride(0),
+        rc = self._lib.fd_pwg_generate(self._p, src.data_ptr(), int(padded), B, T, _wave.counts(lens, B, "ParallelWaveGAN"),
+                                       None if z is None else z.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, ids, wav.data_ptr(), wav.stride(0),
                                        lvc_op._stream(src.device))
         self._check(rc, "fd_pwg_generate")
         return wav
@@ -271,5 +271,5 @@ class ParallelWaveGAN:
         z = torch.empty((B, L), device=self.device, dtype=torch.float32)
         ids = None if stream_ids is None else (ct.c_uint64 * B)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in stream_ids])
         from . import lvc_op
-        self._check(self._lib.fd_pwg_draw(self._h, B, L, int(seed) & 0xFFFFFFFFFFFFFFFF, ids, _capi.float_ptr(z), L, lvc_op._stream(self.device)), "fd_pwg_draw")
+        self._check(self._lib.fd_pwg_draw(self._h, B, L, int(seed) & 0xFFFFFFFFFFFFFFFF, ids, z.data_ptr(), L, lvc_op._stream(self.device)), "fd_pwg_draw")
         return z

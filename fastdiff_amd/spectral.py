@@ -21,7 +21,6 @@ copy scores exactly 0.
 """
 import ctypes as ct
 
-import numpy as np
 import torch
 
 from . import _capi, _wave
@@ -29,15 +28,8 @@ from . import _capi, _wave
 MAX_RES, FRAME_TILE, SUM_CHUNK = _capi.FD_SPECTRAL_MAX_RES, _capi.FD_SPECTRAL_FRAME_TILE, _capi.FD_SPECTRAL_SUM_CHUNK
 OK, SHORT = _capi.FD_SPECTRAL_OK, _capi.FD_SPECTRAL_SHORT
 STATUS = {OK: "OK", SHORT: "SHORT"}
-RECORD = np.dtype([("sc", "<f8", (MAX_RES,)), ("logmag", "<f8", (MAX_RES,)), ("lsd", "<f8", (MAX_RES,)), ("mr_sc", "<f8"), ("mr_logmag", "<f8"),
-                   ("lsd_db", "<f8"), ("frames", "<i4", (MAX_RES,)), ("n_res", "<i4"), ("status", "<i4")])
-
-
-class FdSpectralConfig(ct.Structure):
-    _fields_ = [("n_res", ct.c_int32), ("reserved", ct.c_int32), ("nfft", ct.c_int32 * MAX_RES), ("hop", ct.c_int32 * MAX_RES),
-                ("win", ct.c_int32 * MAX_RES), ("floor", ct.c_double)]
-
-
+RECORD = _capi.record("fd_spectral")
+FdSpectralConfig = _capi.struct("fd_spectral_config")
 KEYS = ("resolutions", "floor")
 
 

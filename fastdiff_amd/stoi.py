@@ -23,7 +23,7 @@ from . import _capi, _wave
 SCAN_TILE, SEG_TILE = _capi.FD_STOI_SCAN_TILE, _capi.FD_STOI_SEG_TILE
 OK, SHORT, SILENT = _capi.FD_STOI_OK, _capi.FD_STOI_SHORT, _capi.FD_STOI_SILENT
 STATUS = {OK: "OK", SHORT: "SHORT", SILENT: "SILENT"}
-RECORD = np.dtype([("stoi", "<f8"), ("estoi", "<f8"), ("frames", "<i4"), ("kept", "<i4"), ("segments", "<i4"), ("status", "<i4")])
+RECORD = _capi.record("fd_stoi")
 
 
 def bands():

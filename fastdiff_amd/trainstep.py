@@ -60,7 +60,7 @@ class TrainStep:
         self.device = self.params[0].device
         self.hyper = dict(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), weight_decay=float(weight_decay),
                           max_norm=float(clip_grad_norm or 0.0))
-        self._hyper_dev = torch.zeros(6, dtype=torch.float64, device=self.device)      # fd_adamw_hyper
+        self._hyper_dev = lvc_op.new_state("fd_adamw_hyper", self.device, torch.float64)
         self._write_hyper()
         self._state = lvc_op.new_train_state(self.device)                               # fd_train_state
         sizes = [p.numel() for p in self.params]
@@ -85,13 +85,12 @@ class TrainStep:
 
     # ---- hyper-parameters and state ------------------------------------------------------------------------------------------------
     def _write_hyper(self):
-        h = self.hyper
-        self._hyper_dev.copy_(torch.tensor([h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["max_norm"]], dtype=torch.float64))
+        self._hyper_dev.copy_(lvc_op.pack_state("fd_adamw_hyper", torch.float64, **self.hyper))      # (the keys are the struct's fields)
 
     def set_lr(self, lr):
         """The learning rate of the following steps: a copy of 8 bytes into device memory, between two replays."""
         self.hyper["lr"] = float(lr)
-        self._hyper_dev[0:1].copy_(torch.tensor([float(lr)], dtype=torch.float64))
+        lvc_op.state_field(self._hyper_dev, "fd_adamw_hyper", "lr").copy_(torch.tensor([float(lr)], dtype=torch.float64))
 
     def state(self):
         """{"iter", "applied", "skipped", "grad_norm", "loss"} of the device's fd_train_state.  Synchronises."""
@@ -149,7 +148,7 @@ class TrainStep:
         if "clip_grad_norm" in extra:
             self.hyper["max_norm"] = float(extra["clip_grad_norm"])
             self._write_hyper()
-        self._state.copy_(torch.tensor([int(extra.get("iter", step)), step, int(extra.get("skipped", 0)), 0], dtype=torch.int64))
+        self._state.copy_(lvc_op.pack_state("fd_train_state", iter=int(extra.get("iter", step)), applied=step, skipped=int(extra.get("skipped", 0))))
         if self.ema is not None:
             if sd.get("ema") is not None:
                 self.ema.load_state_dict(sd["ema"])

@@ -31,8 +31,7 @@ CHUNK = _capi.FD_TRIM_CHUNK
 OK, SILENT, EMPTY = _capi.FD_TRIM_OK, _capi.FD_TRIM_SILENT, _capi.FD_TRIM_EMPTY
 STATUS = {OK: "OK", SILENT: "SILENT", EMPTY: "EMPTY"}
 MODES = {"long": _capi.FD_TRIM_LONG, "edges": _capi.FD_TRIM_EDGES}
-RECORD = np.dtype([("n_out", "<i4"), ("windows", "<i4"), ("speech", "<i4"), ("kept_windows", "<i4"), ("nonfinite", "<i4"), ("status", "<i4"),
-                   ("peak_db", "<f8"), ("threshold_db", "<f8")])
+RECORD = _capi.record("fd_trim")
 SPEECH, SMOOTH, KEEP = 1, 2, 4
 
 

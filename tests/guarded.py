@@ -28,17 +28,29 @@ from collections import Counter
 
 import torch
 
+from fastdiff_amd import _capi
+
 PAD = 1024
 GRANULE = 512
 FILLS = (float("nan"), -12345.678)
 
 # host tables of structures whose columns hold device pointers: function -> (index of the table argument, index of the count argument,
-# 8-byte words per item, the pointer columns)
+# 8-byte words per item, the pointer columns): the words and columns are those of the item structure as the header declares it
+
+
+def _host_table(item, at, n_at, looked=None):
+    """looked: the pointer fields the call reads or writes (None: all of them)."""
+    rec = _capi.record(item)
+    pointers = [name for name, typ in _capi.struct(item)._fields_ if typ is ct.c_void_p]
+    assert rec.itemsize % 8 == 0 and set(looked or ()) <= set(pointers)
+    return at, n_at, rec.itemsize // 8, tuple(rec.fields[name][1] // 8 for name in pointers if looked is None or name in looked)
+
+
 HOST_TABLES = {
-    "fd_adamw_multi": (1, 2, 5, (0, 1, 2, 3)),                       # fd_adamw_item: p, g, m, v, numel
-    "fd_ema_multi": (1, 2, 3, (0, 1)),                               # fd_ema_item: p, e, numel
-    "fd_weight_norm_multi_forward": (1, 2, 9, (0, 1, 2, 3)),         # fd_wn_item: v, g, w, norm, dw, dv, dg, rows, cols
-    "fd_weight_norm_multi_backward": (1, 2, 9, (0, 1, 2, 3, 4, 5, 6)),
+    "fd_adamw_multi": _host_table("fd_adamw_item", 1, 2),
+    "fd_ema_multi": _host_table("fd_ema_item", 1, 2),
+    "fd_weight_norm_multi_forward": _host_table("fd_wn_item", 1, 2, ("v", "g", "w", "norm")),
+    "fd_weight_norm_multi_backward": _host_table("fd_wn_item", 1, 2),
 }
 
 _FLOATS = (torch.float16, torch.bfloat16, torch.float32, torch.float64)

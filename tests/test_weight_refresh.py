@@ -350,7 +350,7 @@ def _refs(sd, drop=None, reshape=None):
     tensors = [sd[k.decode()] for k in names]
     shapes = [tuple(t.shape) if k.decode() != reshape else tuple(t.shape)[::-1] for k, t in zip(names, tensors)]
     dims = [(ct.c_int64 * len(s))(*s) for s in shapes]
-    items = (_capi.FdWeightRef * len(names))(*[_capi.FdWeightRef(k, t.data_ptr(), d, len(d), 0) for k, t, d in zip(names, tensors, dims)])
+    items = (_capi.FdWeightRef * len(names))(*[_capi.FdWeightRef(k, t.data_ptr(), ct.addressof(d), len(d), 0) for k, t, d in zip(names, tensors, dims)])
     return items, len(names), (names, dims)
 
 
