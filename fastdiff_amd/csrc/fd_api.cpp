@@ -329,57 +329,51 @@ static int ensure_workspace(fd_context *h, int B, int T, int pmult = 1)
 // ------------------------------------------------------------------------------------------------
 namespace fdk {
 
-hipError_t first_conv(const Launch &L, const StepIO &io, int B, int T)
+// fast | naive (option kernels.<stage>): each stage's one dispatch
+static hipError_t first_conv(const Launch &L, const StepIO &io, int B, int T)
 {
     return L.mode->fast[ST_FIRST] ? fast_first_conv(L, io, B, T) : naive_first_conv(L, io, B, T);
 }
-hipError_t dblock(const Launch &L, const StepIO &io, int d, int B, int T)
+static hipError_t dblock(const Launch &L, const StepIO &io, int d, int B, int T)
 {
     return L.mode->fast[ST_DBLOCK] ? fast_dblock(L, d, B, T, io.x_in) : naive_dblock(L, d, B, T);
 }
-hipError_t kp_front(const Launch &L, const StepIO &io, int B, int T)
+static hipError_t convt(const Launch &L, int n, const float *x_in, float *x_out, int B, int Lin)
 {
-    return L.mode->fast[ST_KP_FRONT] ? fast_kp_front(L, io, B, T) : naive_kp_front(L, io, B, T);
+    return L.mode->fast[ST_CONVT] ? fast_convt(L, n, x_in, x_out, B, Lin) : naive_convt(L, n, x_in, x_out, B, Lin);
 }
-hipError_t kp_gemm(const Launch &L, int B, int T) { return L.mode->fast[ST_KP_GEMM] ? fast_kp_gemm(L, B, T) : naive_kp_gemm(L, B, T); }
+// cur -> cur: the fast layer writes `other` and the two change places; the naive one works in place with `other` as scratch
+static hipError_t lvc_layer(const Launch &L, const StepIO &io, int n, int i, float *&cur, float *&other, const float *skip, int B, int T)
+{
+    if (!L.mode->fast[ST_LVC]) return naive_lvc_layer(L, n, i, cur, skip, other, B, T);
+    const hipError_t e = fast_lvc_layer(L, io, n, i, cur, skip, other, B, T);
+    std::swap(cur, other);
+    return e;
+}
+// The predictor (front + GEMM) over `entries` batch entries: a step's own B utterances, or a hoisted batch of (step, utterance) entries
+static hipError_t predictor(const Launch &L, const StepIO &io, int entries, int T)
+{
+    const hipError_t e = L.mode->fast[ST_KP_FRONT] ? fast_kp_front(L, io, entries, T) : naive_kp_front(L, io, entries, T);
+    if (e != hipSuccess) return e;
+    return L.mode->fast[ST_KP_GEMM] ? fast_kp_gemm(L, entries, T) : naive_kp_gemm(L, entries, T);
+}
 
 // One TimeAware_LVCBlock (modules.py:190-218) given the packed kernels of kp_gemm.  x_in: [B,32,Lin].
 static hipError_t lvc_block_run(const Launch &L, const StepIO &io, int n, const float *x_in, int B, int T, float **x_out)
 {
-    fd_context *c = L.ctx;
-    const StepMode &m = *L.mode;
-    Workspace &ws = c->ws;
+    Workspace &ws = L.ctx->ws;
     const int Lin = T * (fd::hop(n) / fd::ratio(n));
     float *cur = (x_in == ws.xA) ? ws.xB : ws.xA;
     float *other = (cur == ws.xA) ? ws.xB : ws.xA;
     const float *skip = ws.a[2 - n];
-    // blocks 1 and 2 (hop 64, 256) on the fp16x2 pipe with the range check on the host: the up-sampler runs inside the first layer
-    // (k_lvc_h2<.., UP>), its output never goes to HBM and back; x_in is read by that layer, which writes the other buffer
-    const bool fuse_up = m.fuse_up && n >= 1 && m.fast[ST_CONVT] && m.fast[ST_LVC] &&
-                         fd_pipe(m, m.conv_f16 && c->w.convt_f16_ok, 16 + n) == PIPE_F16_ONLY &&
-                         fd_pipe(m, m.lvc_f16 && c->w.lvc_f16_ok, 1 + n * fd::LAYERS) == PIPE_F16_ONLY;
-    hipError_t e = hipSuccess;
-    if (fuse_up) {
-        if ((e = fast_lvc_layer(L, io, n, 0, x_in, skip, cur, B, T, true)) != hipSuccess) return e;
-    } else {
-        e = m.fast[ST_CONVT] ? fast_convt(L, n, x_in, cur, B, Lin) : naive_convt(L, n, x_in, cur, B, Lin);
-        if (e != hipSuccess) return e;
-    }
-    for (int i = fuse_up ? 1 : 0; i < fd::LAYERS; ++i) {
-        if (m.fast[ST_LVC]) {
-            e = fast_lvc_layer(L, io, n, i, cur, skip, other, B, T);
-            std::swap(cur, other);
-        } else {
-            e = naive_lvc_layer(L, n, i, cur, skip, other, B, T);
-        }
-        if (e != hipSuccess) return e;
-    }
-    if (m.keep_taps) {
+    // fuse_up: the up-sampler runs inside the first layer, which reads x_in and writes the other buffer
+    const bool fuse_up = L.plan->fuse_up[n];
+    hipError_t e = fuse_up ? fast_lvc_layer(L, io, n, 0, x_in, skip, cur, B, T, true) : convt(L, n, x_in, cur, B, Lin);
+    for (int i = fuse_up ? 1 : 0; i < fd::LAYERS && e == hipSuccess; ++i) e = lvc_layer(L, io, n, i, cur, other, skip, B, T);
+    if (e == hipSuccess && L.mode->keep_taps)
         e = hipMemcpyAsync(ws.xtap[n], cur, sizeof(float) * (size_t)B * fd::C * T * fd::hop(n), hipMemcpyDeviceToDevice, L.stream);
-        if (e != hipSuccess) return e;
-    }
     *x_out = cur;
-    return hipSuccess;
+    return e;
 }
 
 static hipError_t run_step(const Launch &L, const StepIO &io, int B, int T)
@@ -395,10 +389,7 @@ static hipError_t run_step(const Launch &L, const StepIO &io, int B, int T)
     if ((e = first_conv(L, io, B, T)) != hipSuccess) return e;
     for (int d = 0; d < fd::NBLK; ++d)
         if ((e = dblock(L, io, d, B, T)) != hipSuccess) return e;
-    if (!hoisted) {
-        if ((e = kp_front(L, io, B, T)) != hipSuccess) return e;
-        if ((e = kp_gemm(L, B, T)) != hipSuccess) return e;
-    }
+    if (!hoisted && (e = predictor(L, io, B, T)) != hipSuccess) return e;
     float *x = ws.a[3];
     for (int n = 0; n < fd::NBLK; ++n) {
         float *xo = nullptr;
@@ -539,7 +530,8 @@ int fd_forward(fd_handle h, const float *x, const float *mel, const float *steps
         if ((rc = set_lens(h, lens, B, T, (hipStream_t)stream, "fd_forward", reinterpret_cast<int *>(sl->host), &mode.ragged)) != FD_OK) return rc;
         if ((rc = fd_stage_commit(h, sl, (hipStream_t)stream)) != FD_OK) return rc;
     }
-    fdk::Launch L = {h, (hipStream_t)stream, false, &mode};
+    const StepPlan plan = plan_step(mode, h->w);      // (behind check_common: the weights' *_ok bits are settled)
+    fdk::Launch L = {h, (hipStream_t)stream, false, &mode, &plan};
     StepIO io = {x, mel, steps, eps_out, 0};
     hipError_t e = fdk::embed(L, io, B, 1);
     if (e == hipSuccess) e = fdk::clear_range_flags(L);
@@ -580,11 +572,7 @@ static int enqueue_steps(fd_handle h, int B, int T, int count, const StepMode &m
     auto enqueue_piece = [&](const fdk::Launch &L, int steps) -> hipError_t {
         const int np = L.mode->hoist_chunk ? L.mode->hoist_np : 1;
         hipError_t e = hipSuccess;
-        if (np > 1) {
-            StepIO iop = {ws.x, ws.mel_rep, nullptr, nullptr, np};
-            e = fdk::kp_front(L, iop, B * np, T);
-            if (e == hipSuccess) e = fdk::kp_gemm(L, B * np, T);
-        }
+        if (np > 1) e = fdk::predictor(L, {ws.x, ws.mel_rep, nullptr, nullptr, np}, B * np, T);
         for (int k = 0; k < steps && e == hipSuccess; ++k) {
             StepIO io = {ws.x, ws.mel, nullptr, nullptr, 1};
             io.hoist_step = L.mode->hoist_np > 1 ? k : 0;      // (hoisted: the piece is the whole call or one 8-step piece of it)
@@ -599,7 +587,8 @@ static int enqueue_steps(fd_handle h, int B, int T, int count, const StepMode &m
         for (int first = 0; first < count; first += piece) {
             const int steps = std::min(piece, count - first);
             const StepMode m = piece_mode(steps);
-            const hipError_t e = enqueue_piece({h, stream, false, &m}, steps);
+            const StepPlan plan = plan_step(m, h->w);
+            const hipError_t e = enqueue_piece({h, stream, false, &m, &plan}, steps);
             if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: launch of steps %d.. failed: %s", first, hipGetErrorString(e));
         }
         return FD_OK;
@@ -633,7 +622,8 @@ static int enqueue_steps(fd_handle h, int B, int T, int count, const StepMode &m
             }
             ++h->n_graph_captures;
             FD_HIP(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            const hipError_t ec = enqueue_piece({h, h->cap_stream, true, &m}, steps);
+            const StepPlan plan = plan_step(m, h->w);      // (the graph stays keyed on the mode: the plan follows from it and the weights)
+            const hipError_t ec = enqueue_piece({h, h->cap_stream, true, &m, &plan}, steps);
             hipGraph_t g = nullptr;
             const hipError_t e2 = hipStreamEndCapture(h->cap_stream, &g);
             if (ec != hipSuccess || e2 != hipSuccess) {
@@ -685,11 +675,11 @@ static int hoist_mult(const fd_context *h, int B, int T, int N)
 static int resolve_call(fd_handle h, const fd_context::PendingCall &p, unsigned *mask)
 {
     FD_HIP(h, hipEventSynchronize(p.slot ? h->flags_done2 : h->flags_done));
-    const int *fl = h->flags_host + 32 * p.slot;
+    const int *fl = h->flags_host + fd::flags::WORDS * p.slot;
     unsigned m = 0;
-    for (int i = 0; i < 32; ++i)
+    for (int i = 0; i < fd::flags::WORDS; ++i)
         if (fl[i]) m |= 1u << i;
-    if (m & (1u << 19)) m |= 1u;                 // the predictor front feeds the GEMM: both go
+    m = fd::flags::with_dependents(m);
     *mask |= m;
     if (m == 0) return 0;
     h->redone_ring[h->redone_next++ % 16] = p.ticket;
@@ -816,9 +806,9 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
             FD_FAIL(h, FD_ERR_HIP, "fd_sample: mel replication failed: %s", hipGetErrorString(e));
     }
     if (np > 1 && !mode.hoist_chunk) {      // (hoist_chunk: enqueue_steps puts one in front of every piece)
-        StepIO iop = {ws.x, ws.mel_rep, nullptr, nullptr, 0};      // "forward" addressing: batch entry n * B + b reads noise row n * B + b
-        e = fdk::kp_front(L, iop, B * N, T);
-        if (e == hipSuccess) e = fdk::kp_gemm(L, B * N, T);
+        const StepPlan plan = plan_step(mode, h->w);      // (this piece is the whole call: the same plan as its steps')
+        // "forward" addressing: batch entry n * B + b reads noise row n * B + b
+        e = fdk::predictor({h, stream, false, &mode, &plan}, {ws.x, ws.mel_rep, nullptr, nullptr, 0}, B * N, T);
         if (e != hipSuccess) FD_FAIL(h, FD_ERR_HIP, "fd_sample: predictor launch failed: %s", hipGetErrorString(e));
     }
     if (force_mask != 0) {
@@ -830,7 +820,7 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
         // fd_sample_settle; a flagged call is then run again as a whole.
         if ((rc = enqueue_steps(h, B, T, N, mode, stream)) != FD_OK) return rc;
         const int slot = (int)(ticket & 1);
-        FD_HIP(h, hipMemcpyAsync(h->flags_host + 32 * slot, ws.range_flag + 64, sizeof(int) * 32, hipMemcpyDeviceToHost, stream));
+        FD_HIP(h, hipMemcpyAsync(h->flags_host + fd::flags::WORDS * slot, ws.range_flag + fd::flags::STICKY, sizeof(int) * fd::flags::WORDS, hipMemcpyDeviceToHost, stream));
         FD_HIP(h, hipEventRecord(slot ? h->flags_done2 : h->flags_done, stream));
         if ((rc = copy_out()) != FD_OK) return rc;      // provisional until checked
         h->pending.active = true; h->pending.lazy = true; h->pending.slot = slot; h->pending.ticket = ticket;
@@ -851,7 +841,7 @@ static int sample_core(fd_handle h, const fd_context::SampleArgs &a, unsigned fo
             mode.inline_fallback = mask != 0;
             if ((rc = enqueue_steps(h, B, T, count, mode, stream)) != FD_OK) return rc;
             if (mask != 0) continue;              // already on the safe path: nothing to look at
-            FD_HIP(h, hipMemcpyAsync(h->flags_host, ws.range_flag + 64, sizeof(int) * 32, hipMemcpyDeviceToHost, stream));
+            FD_HIP(h, hipMemcpyAsync(h->flags_host, ws.range_flag + fd::flags::STICKY, sizeof(int) * fd::flags::WORDS, hipMemcpyDeviceToHost, stream));
             FD_HIP(h, hipEventRecord(h->flags_done, stream));
             h->pending.active = true; h->pending.lazy = false; h->pending.slot = 0; h->pending.ticket = ticket;
             h->pending.B = B; h->pending.T = T; h->pending.T_io = T_io; h->pending.N = N; h->pending.first = first; h->pending.count = count; h->pending.out = a.out;

@@ -1082,9 +1082,9 @@ int64_t fd_read_tap(fd_handle h, const char *name, float *host_dst, int64_t capa
         const int blk = k[1] - '0';
         src = w.xtap[blk]; n = (int64_t)B * fd::C * T * fd::hop(blk);
     } else if (k == "range_flags") {       // 32 int32 (bit patterns): fp16-range flags of the last step, see Workspace::range_flag
-        src = reinterpret_cast<const float *>(w.range_flag); n = 32;
-    } else if (k == "range_flags_call") {  // the same, OR-ed over every step since the start of the last call (words 64..95)
-        src = reinterpret_cast<const float *>(w.range_flag + 64); n = 32;
+        src = reinterpret_cast<const float *>(w.range_flag); n = fd::flags::WORDS;
+    } else if (k == "range_flags_call") {  // the same, OR-ed over every step since the start of the last call (the sticky words)
+        src = reinterpret_cast<const float *>(w.range_flag + fd::flags::STICKY); n = fd::flags::WORDS;
     } else FD_FAIL(h, FD_ERR_INVALID, "fd_read_tap: unknown tap '%s'", name);
     if (!host_dst) return n;
     if (capacity < n) FD_FAIL(h, FD_ERR_INVALID, "fd_read_tap: capacity %lld < %lld", (long long)capacity, (long long)n);

@@ -133,6 +133,7 @@ enum Stage { ST_EMBED = 0, ST_FIRST, ST_DBLOCK, ST_KP_FRONT, ST_KP_GEMM, ST_CONV
 
 // Everything that decides which kernels a denoiser step (or a captured piece of steps) enqueues and with which arguments.  A captured
 // graph is keyed on (B, T, steps, StepMode).  fd_context::mode holds the option values; a call copies it and fills in its own fields.
+// Nobody but plan_step (fd_plan.h) reads the pipe bits, the fusion switches and fp32_mask: the drivers read the StepPlan it returns.
 struct StepMode {
     // options
     bool fast[ST_COUNT] = {true, true, true, true, true, true, true, true};   // "kernels.<stage>" = fast | naive
@@ -150,12 +151,12 @@ struct StepMode {
     bool fuse_advance = true;    // option "fuse_advance": between two steps of one graph / launch sequence the end-of-step bookkeeping
                                  // (k_advance) rides in the next step's first kernel instead of a launch of its own
     bool keep_taps = false;      // option "taps"
-    // per call.  How a stage that has an fp16x2 kernel is launched (fd_pipe below):
+    // per call.  How a stage that has an fp16x2 kernel is launched (fd_plan.h: Pipe):
     //   inline_fallback  the fp32 kernel is enqueued right behind the fp16x2 one and exits at once unless that one raised its flag
     //                    (fully asynchronous, works inside a captured graph; ~2 us per stage and step)
-    //   !inline_fallback only the fp16x2 kernel; flags accumulate in range_flag[64..95] and the HOST redoes the work with
+    //   !inline_fallback only the fp16x2 kernel; flags accumulate in the sticky words of range_flag and the HOST redoes the work with
     //                    fp32_mask set (option fallback = host: fd_sample_check)
-    //   fp32_mask        bit i set: the stage whose flag word is i runs its fp32 kernel outright
+    //   fp32_mask        bit i set: the stage whose flag word is i (fd::flags) runs its fp32 kernel outright
     unsigned fp32_mask = 0;
     bool inline_fallback = true;
     bool ragged = false;         // the call's `lens` are in Workspace::lens_dev (a ragged batch)
@@ -177,6 +178,8 @@ struct StepMode {
     }
 };
 
+#include "fd_plan.h"
+
 struct Workspace {
     int B = 0;                  // capacity: utterances (per-utterance arrays),
     int64_t frames = 0;         //           B*T frames (activations, predicted kernels),
@@ -191,10 +194,7 @@ struct Workspace {
     unsigned long long *uid_dev = nullptr;   // [B] noise stream ids of the current call (fd_set_noise_streams)
     long long *off_dev = nullptr;            // [B] Philox position offsets (float4s) of the current call (StepParams::offs4)
     float *xsave = nullptr;     // [B][L] x at the start of the call / of the current graph chunk (option fallback = host: what a redo starts from)
-    int *range_flag = nullptr;  // (128 words) [0] predictor GEMM, [1 + 4*block + layer] LVC layers, [13 + d] DBlocks,
-                                // [16 + n] ConvTranspose of block n, [19] predictor front: an operand did not fit fp16; 32 words, zeroed every step;
-                                // words 32..63: the same flags of the previous sampler step (skip_after_previous_overflow);
-                                // words 64..95: OR over all steps since the last clear (what option fallback = host reads back)
+    int *range_flag = nullptr;  // (128 words) the fp16-range flags of the stages, of this step, the previous one and the call: fd::flags (fd_plan.h)
     float *xA = nullptr, *xB = nullptr;                           // [B][32][L] ping-pong
     float *xtap[fd::NBLK] = {}; // block outputs kept for fd_read_tap
     int64_t pframes = 0, prows = 0, plens = 0;   // capacity of the predictor's buffers (kp_h*, kpack, mel_rep / h_f16 / lens_dev): frames, image
@@ -404,26 +404,6 @@ struct fd_context {
     std::map<std::string, std::pair<int64_t, double>> prof_acc;
 };
 
-enum Pipe { PIPE_F16_THEN_F32, PIPE_F16_ONLY, PIPE_F32_ONLY };
-inline Pipe fd_pipe(const StepMode &m, bool f16_possible, int flag_word)
-{
-    if (!f16_possible || ((m.fp32_mask >> flag_word) & 1u)) return PIPE_F32_ONLY;
-    return m.inline_fallback ? PIPE_F16_THEN_F32 : PIPE_F16_ONLY;
-}
-// What one launch leaves for another, as a function of the mode: producer and consumer both ask, so they agree by construction.
-// The fp16-pipe predictor front writes the direct fp16x2 GEMM's piece image of h itself (k_h_split is then not launched).
-inline bool front_writes_h_image(const StepMode &m, const DevWeights &w)
-{
-    return m.fast[ST_KP_FRONT] && fd_pipe(m, m.conv_f16 && w.kpf_f16_ok, 19) != PIPE_F32_ONLY &&
-           fd_pipe(m, m.gemm_f16 && w.gemm_f16_ok, 0) != PIPE_F32_ONLY && !(m.gemm_wino && w.gemm_w_ok);
-}
-// The last LVC layer (block 2, layer 3, flag word 12) leaves the final_conv sums in eps_acc; fast_final then adds the bias and updates x.
-inline bool last_lvc_fuses_final(const StepMode &m, const DevWeights &w)
-{
-    return m.fast[ST_LVC] && m.fast[ST_FINAL] && !m.keep_taps && m.fuse_final &&
-           fd_pipe(m, m.lvc_f16 && w.lvc_f16_ok, 1 + 2 * fd::LAYERS + 3) != PIPE_F32_ONLY;
-}
-
 // Arguments of one denoiser step (all device pointers)
 struct StepIO {
     const float *x_in;     // [B][L] current x_t
@@ -441,13 +421,18 @@ struct Launch {
     fd_context *ctx;
     hipStream_t stream;
     bool capturing;
-    const StepMode *mode = nullptr;   // what the denoiser step's launchers read; left out (null) by the paths that launch no step
+    const StepMode *mode = nullptr;   // what the denoiser step's launchers read, and the plan resolved from it (fd_plan.h: plan_step);
+    const StepPlan *plan = nullptr;   // left out (null) by the paths that launch no step
+    const int *lens() const { return mode->ragged ? ctx->ws.lens_dev : nullptr; }
+    // block n's records of this step; with a hoisted predictor the batch behind kpack is hoist_np * B entries and this step's are the
+    // hoist_step-th B of them
+    const float *kpack(int n, const StepIO &io, int B, int T) const
+    {
+        return ctx->ws.kpack + ((int64_t)n * mode->hoist_np + io.hoist_step) * B * T * fd::KREC;
+    }
+    Twin twin(int word, bool f16_on = true) const { return twin_of(*plan, word, ctx->ws.range_flag, f16_on); }
 };
 hipError_t embed(const Launch &L, const StepIO &io, int B, int n_steps);
-hipError_t first_conv(const Launch &L, const StepIO &io, int B, int T);
-hipError_t dblock(const Launch &L, const StepIO &io, int d, int B, int T);
-hipError_t kp_front(const Launch &L, const StepIO &io, int B, int T);
-hipError_t kp_gemm(const Launch &L, int B, int T);
 hipError_t advance_step(const Launch &L);
 hipError_t clear_range_flags(const Launch &L, int set_step = 0);     // before the first step of a call / of a redo: step counter := set_step
 hipError_t mel_frontend(const Launch &L, const float *wav, int B, int64_t n_samples, float *mel, int T);

@@ -52,15 +52,24 @@ __device__ __forceinline__ int frames_of(const int *lens, int b, int T) { return
 __device__ __forceinline__ long long own_len(const long long *lens, int b, long long n_all) { return lens ? lens[b] : n_all; }
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 
-// Range flags (Workspace::range_flag): word i = "an operand of fp16-pipe launch i did not fit in this step", word 32 + i = the
-// same for the previous step of the sampler (copied by k_advance).  A launch whose flag was raised in the previous step does
-// not try again: it raises its flag at once and leaves the step to the fp32 kernel behind it -- a trajectory that has left the
+// Range flags (Workspace::range_flag; words: fd::flags): word i = "an operand of fp16-pipe launch i did not fit in this step", word
+// PREV + i = the same for the previous step of the sampler (roll_range_flags).  A launch whose flag was raised in the previous step
+// does not try again: it raises its flag at once and leaves the step to the fp32 kernel behind it -- a trajectory that has left the
 // fp16 range (an untrained network over 1000 steps does) then costs the fp32 kernels only, not both.
 __device__ __forceinline__ bool skip_after_previous_overflow(int *flag)
 {
-    if (flag[32] == 0) return false;
+    if (flag[fd::flags::PREV] == 0) return false;
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) atomicOr(flag, 1);
     return true;
+}
+// End of a sampler step, word i (one thread per word): this step's flag becomes "previous step" and joins the sticky set of the call
+// (what the host looks at), and is cleared for the next step.  inc == 0 (start of a call or of a redo): all three cleared.
+__device__ __forceinline__ void roll_range_flags(int *range_flags, int i, int inc)
+{
+    const int f = range_flags[i];
+    range_flags[fd::flags::PREV + i] = inc ? f : 0;
+    range_flags[fd::flags::STICKY + i] = inc ? (range_flags[fd::flags::STICKY + i] | f) : 0;
+    range_flags[i] = 0;
 }
 
 // ---- 2-piece fp16 operands: v = v1 + 2^-11 v2, v1 = fp16(v), v2 = fp16((v - v1) * 2^11) ----------------

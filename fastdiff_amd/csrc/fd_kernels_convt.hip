@@ -185,25 +185,17 @@ hipError_t fast_convt(const Launch &L, int n, const float *x_in, float *x_out, i
 {
     const DevWeights &w = L.ctx->w;
     const dim3 grid((Lin + 127) / 128, B);
-    fd_context *c = L.ctx;
-    const int *run_if = nullptr;
-    const char *n8 = "convt_r8", *n4 = "convt_r4";
-    const int *lens = L.mode->ragged ? c->ws.lens_dev : nullptr;
-    const Pipe pipe = fd_pipe(*L.mode, L.mode->conv_f16 && w.convt_f16_ok, 16 + n);
-    if (pipe != PIPE_F32_ONLY) {
-        int *flag = c->ws.range_flag + 16 + n;
-        if (fd::ratio(n) == 8)
-            FD_LAUNCH(L, n8, k_convt_h2<8>, grid, dim3(256), 0, x_in, reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, x_out, Lin, flag, lens, fd::hop(n) / fd::ratio(n));
-        else
-            FD_LAUNCH(L, n4, k_convt_h2<4>, grid, dim3(256), 0, x_in, reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, x_out, Lin, flag, lens, fd::hop(n) / fd::ratio(n));
-        run_if = flag;
-        n8 = n4 = "convt_fp32_fallback";
-        if (pipe == PIPE_F16_ONLY) return hipSuccess;
-    }
-    if (fd::ratio(n) == 8)
-        FD_LAUNCH(L, n8, k_convt<8>, grid, dim3(256), 0, x_in, w.up_pack[n], w.blk[n].up.b, x_out, Lin, run_if, lens, fd::hop(n) / fd::ratio(n));
-    else
-        FD_LAUNCH(L, n4, k_convt<4>, grid, dim3(256), 0, x_in, w.up_pack[n], w.blk[n].up.b, x_out, Lin, run_if, lens, fd::hop(n) / fd::ratio(n));
+    const int *lens = L.lens();
+    const Twin s = L.twin(fd::flags::convt(n));
+    const bool r8 = fd::ratio(n) == 8;
+    if (s.f16 && r8)
+        FD_LAUNCH(L, "convt_r8", k_convt_h2<8>, grid, dim3(256), 0, x_in, reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, x_out, Lin, s.flag, lens, fd::hop(n) / fd::ratio(n));
+    else if (s.f16)
+        FD_LAUNCH(L, "convt_r4", k_convt_h2<4>, grid, dim3(256), 0, x_in, reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, x_out, Lin, s.flag, lens, fd::hop(n) / fd::ratio(n));
+    if (s.f32 && r8)
+        FD_LAUNCH(L, s.label("convt_r8", "convt_fp32_fallback"), k_convt<8>, grid, dim3(256), 0, x_in, w.up_pack[n], w.blk[n].up.b, x_out, Lin, s.run_if, lens, fd::hop(n) / fd::ratio(n));
+    else if (s.f32)
+        FD_LAUNCH(L, s.label("convt_r4", "convt_fp32_fallback"), k_convt<4>, grid, dim3(256), 0, x_in, w.up_pack[n], w.blk[n].up.b, x_out, Lin, s.run_if, lens, fd::hop(n) / fd::ratio(n));
     return hipSuccess;
 }
 

@@ -295,37 +295,31 @@ hipError_t fast_dblock(const Launch &L, int d, int B, int T, const float *audio)
     for (int i = 0; i < d; ++i) Lin /= fd::down_factor(i);
     const int f = fd::down_factor(d), Lo = Lin / f;
     const dim3 grid((Lo + DB_STRIDE - 1) / DB_STRIDE, B);
-    const int *run_if = nullptr;
-    const char *n4 = "dblock_f4", *n8 = "dblock_f8";
-    const int *lens = L.mode->ragged ? c->ws.lens_dev : nullptr;
-    const Pipe pipe = fd_pipe(*L.mode, L.mode->conv_f16 && w.dblock_f16_ok, 13 + d);
-    if (pipe != PIPE_F32_ONLY) {
-        int *flag = c->ws.range_flag + 13 + d;
+    const int *lens = L.lens();
+    const Twin s = L.twin(fd::flags::dblock(d));
+    if (s.f16) {
         const float4 *q0 = reinterpret_cast<const float4 *>(w.down_h2[d][0]), *q1 = reinterpret_cast<const float4 *>(w.down_h2[d][1]),
                      *q2 = reinterpret_cast<const float4 *>(w.down_h2[d][2]), *q3 = reinterpret_cast<const float4 *>(w.down_h2[d][3]);
         const float *none = nullptr;
         if (f == 4 && d == 0 && audio)      // a[0] = first_audio_conv(audio): recomputed at the picked columns, not read
-            FD_LAUNCH(L, n4, (k_dblock_h2<4, true>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
-                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, flag, lens, Lo / T, audio,
+            FD_LAUNCH(L, "dblock_f4", (k_dblock_h2<4, true>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
+                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, s.flag, lens, Lo / T, audio,
                       (const float *)w.first.w, (const float *)w.first.b);
         else if (f == 4)
-            FD_LAUNCH(L, n4, (k_dblock_h2<4, false>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
-                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, flag, lens, Lo / T, none, none, none);
+            FD_LAUNCH(L, "dblock_f4", (k_dblock_h2<4, false>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
+                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, s.flag, lens, Lo / T, none, none, none);
         else
-            FD_LAUNCH(L, n8, (k_dblock_h2<8, false>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
-                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, flag, lens, Lo / T, none, none, none);
-        run_if = flag;
-        n4 = n8 = "dblock_fp32_fallback";
-        if (pipe == PIPE_F16_ONLY) return hipSuccess;
+            FD_LAUNCH(L, "dblock_f8", (k_dblock_h2<8, false>), grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], q0, q1, q2, q3, w.down[d].conv[0].b,
+                      w.down[d].conv[1].b, w.down[d].conv[2].b, w.down[d].res.b, Lin, Lo, s.flag, lens, Lo / T, none, none, none);
     }
-    if (f == 4)
-        FD_LAUNCH(L, n4, k_dblock<4>, grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], w.down_pack[d][0], w.down_pack[d][1],
-                  w.down_pack[d][2], w.down_pack[d][3], w.down[d].conv[0].b, w.down[d].conv[1].b, w.down[d].conv[2].b,
-                  w.down[d].res.b, Lin, Lo, run_if, lens, Lo / T);
-    else
-        FD_LAUNCH(L, n8, k_dblock<8>, grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], w.down_pack[d][0], w.down_pack[d][1],
-                  w.down_pack[d][2], w.down_pack[d][3], w.down[d].conv[0].b, w.down[d].conv[1].b, w.down[d].conv[2].b,
-                  w.down[d].res.b, Lin, Lo, run_if, lens, Lo / T);
+    if (s.f32 && f == 4)
+        FD_LAUNCH(L, s.label("dblock_f4", "dblock_fp32_fallback"), k_dblock<4>, grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], w.down_pack[d][0],
+                  w.down_pack[d][1], w.down_pack[d][2], w.down_pack[d][3], w.down[d].conv[0].b, w.down[d].conv[1].b, w.down[d].conv[2].b,
+                  w.down[d].res.b, Lin, Lo, s.run_if, lens, Lo / T);
+    else if (s.f32)
+        FD_LAUNCH(L, s.label("dblock_f8", "dblock_fp32_fallback"), k_dblock<8>, grid, dim3(256), 0, c->ws.a[d], c->ws.a[d + 1], w.down_pack[d][0],
+                  w.down_pack[d][1], w.down_pack[d][2], w.down_pack[d][3], w.down[d].conv[0].b, w.down[d].conv[1].b, w.down[d].conv[2].b,
+                  w.down[d].res.b, Lin, Lo, s.run_if, lens, Lo / T);
     return hipSuccess;
 }
 

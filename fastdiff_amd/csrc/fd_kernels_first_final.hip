@@ -20,12 +20,7 @@ __global__ void __launch_bounds__(256) k_first_conv(const float *__restrict__ x,
 {
     if (advance && blockIdx.x == 0 && blockIdx.y == 0) {
         if (threadIdx.x == 0) advance->step_idx += 1;
-        if (threadIdx.x < 32) {
-            const int f = range_flags[threadIdx.x];
-            range_flags[32 + threadIdx.x] = f;
-            range_flags[64 + threadIdx.x] |= f;
-            range_flags[threadIdx.x] = 0;
-        }
+        if (threadIdx.x < fd::flags::WORDS) roll_range_flags(range_flags, threadIdx.x, 1);
     }
     __shared__ float wl[fd::C * 8];      // [out][7 taps + bias]
     {
@@ -139,9 +134,8 @@ hipError_t fast_first_conv(const Launch &L, const StepIO &io, int B, int T)
     const DevWeights &w = L.ctx->w;
     const int Lf = T * fd::HOPT;
     fd_context *c = L.ctx;
-    const int *lens = L.mode->ragged ? c->ws.lens_dev : nullptr;
     const bool adv = io.sampler && io.advance;      // the previous step of this sequence left its bookkeeping to us
-    FD_LAUNCH(L, "first_conv", k_first_conv, dim3((Lf + 1023) / 1024, B), dim3(256), 0, io.x_in, w.first.w, w.first.b, c->ws.a[0], Lf, lens,
+    FD_LAUNCH(L, "first_conv", k_first_conv, dim3((Lf + 1023) / 1024, B), dim3(256), 0, io.x_in, w.first.w, w.first.b, c->ws.a[0], Lf, L.lens(),
               adv ? c->ws.params : (StepParams *)nullptr, c->ws.range_flag);
     return hipSuccess;
 }
@@ -149,22 +143,18 @@ hipError_t fast_first_conv(const Launch &L, const StepIO &io, int B, int T)
 hipError_t fast_final(const Launch &L, const StepIO &io, const float *x32, int B, int T)
 {
     fd_context *c = L.ctx;
-    const StepMode &m = *L.mode;
     const DevWeights &w = c->w;
     const int Lf = T * fd::HOPT;
-    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
-    const int *run_if = nullptr;
-    const char *name = "final_conv_update";
-    if (last_lvc_fuses_final(m, w)) {       // the last LVC layer already left the conv sums in eps_acc
-        const int *flag = c->ws.range_flag + 1 + 2 * fd::LAYERS + 3;
+    const int *lens = L.lens();
+    // fused: the last LVC layer already left the conv sums in eps_acc, and its flag says whether they count (fallback = host: a flagged
+    // last layer is redone from the host, no k_final behind it)
+    const Twin s = L.twin(fd::flags::lvc(fd::NBLK - 1, fd::LAYERS - 1), L.plan->fuse_final);
+    if (s.f16)
         FD_LAUNCH(L, "final_update", k_final_acc, dim3((Lf + 1023) / 1024, B), dim3(256), 0, c->ws.eps_acc, w.final_.b, io.eps_out, c->ws.x,
-                  (const StepParams *)c->ws.params, io.sampler, Lf, lens, flag);
-        run_if = flag;
-        name = "final_conv_fallback";
-        if (!m.inline_fallback) return hipSuccess;      // fallback = host: a flagged last layer is redone from the host
-    }
-    FD_LAUNCH(L, name, k_final, dim3((Lf + 1023) / 1024, B), dim3(256), 0, x32, w.final_.w, w.final_.b, io.eps_out,
-              c->ws.x, (const StepParams *)c->ws.params, io.sampler, Lf, lens, run_if);
+                  (const StepParams *)c->ws.params, io.sampler, Lf, lens, s.run_if);
+    if (s.f32)
+        FD_LAUNCH(L, s.label("final_conv_update", "final_conv_fallback"), k_final, dim3((Lf + 1023) / 1024, B), dim3(256), 0, x32, w.final_.w,
+                  w.final_.b, io.eps_out, c->ws.x, (const StepParams *)c->ws.params, io.sampler, Lf, lens, s.run_if);
     return hipSuccess;
 }
 

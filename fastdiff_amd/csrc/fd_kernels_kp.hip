@@ -136,8 +136,8 @@ __global__ void __launch_bounds__(256, 2) k_kp_front_h2(const float *__restrict_
     __shared__ __attribute__((aligned(16))) char hB[66 * 256];
     const int blk = blockIdx.z, b = blockIdx.y, t0 = blockIdx.x * KPF_VALID;
     const int Tb = frames_of(lens, b, T);
-    if (range_flags[32 + 19] | range_flags[32]) {      // did not fit in the previous step: fp32 front and fp32 GEMM take this one
-        if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) { atomicOr(range_flags + 19, 1); atomicOr(range_flags, 1); }
+    if (range_flags[fd::flags::PREV + fd::flags::KP_FRONT] | range_flags[fd::flags::PREV + fd::flags::GEMM]) {      // did not fit in the previous step: fp32 front and fp32 GEMM take this one
+        if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) { atomicOr(range_flags + fd::flags::KP_FRONT, 1); atomicOr(range_flags + fd::flags::GEMM, 1); }
         return;
     }
     if (t0 > Tb) return;      // the tile holding frame Tb still runs: it writes the zero row the GEMM reads behind the utterance
@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(256, 2) k_kp_front_h2(const float *__restrict_
         if (blockIdx.x == gridDim.x - 1)
             for (int e = tid; e < (R - 1 - T) * 16; e += 256) *reinterpret_cast<float4 *>(ib + (T + 1) * 256 + e * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if (!(mx < GX_LIMIT)) { atomicOr(range_flags + 19, 1); atomicOr(range_flags, 1); }      // [19] this kernel, [0] the GEMM behind it
+    if (!(mx < GX_LIMIT)) { atomicOr(range_flags + fd::flags::KP_FRONT, 1); atomicOr(range_flags + fd::flags::GEMM, 1); }      // this kernel and the GEMM behind it
 }
 
 // =================================================================================================
@@ -302,8 +302,6 @@ __global__ void __launch_bounds__(256, 2) k_kp_front_h2(const float *__restrict_
 // =================================================================================================
 constexpr int GEMM_CT = 4;                       // frame tiles (of 32) per work item
 constexpr int GEMM_LDH = GEMM_CT * 32 + 4;       // 128 frames + 1 halo each side, padded
-constexpr int GEMM_NCOLS = GEMM_CT * 32 + 2;
-constexpr int GEMM_NK = (fd::HID * GEMM_NCOLS + 255) / 256;   // staged floats per thread
 
 #ifdef FD_GEMM_TIMING
 __device__ long long fd_gdbg[64 * 4 * 4];
@@ -449,7 +447,7 @@ __global__ void __launch_bounds__(256) k_h_split(const float *__restrict__ h, un
     const int bb = blockIdx.y;                           // blk*B + b
     const int e = blockIdx.x * 256 + threadIdx.x, cp = e / R, row = e - cp * R;     // lanes along rows: coalesced h reads
     if (cp >= 32) return;
-    if (range_flag[32] != 0) {      // h did not fit in the previous step: the fp32 GEMM takes this one as well
+    if (range_flag[fd::flags::PREV] != 0) {      // h did not fit in the previous step: the fp32 GEMM takes this one as well
         if (e == 0 && bb == 0) atomicOr(range_flag, 1);
         return;
     }
@@ -763,7 +761,7 @@ __global__ void __launch_bounds__(256) k_h_wino(const float *__restrict__ h, cha
     const int bb = blockIdx.y;                           // blk*B + b
     const int e = blockIdx.x * 256 + threadIdx.x, p = e >> 3, g = e & 7;
     if (p >= P) return;
-    if (range_flag[32] != 0) {      // h did not fit in the previous step: the fp32 GEMM takes this one as well
+    if (range_flag[fd::flags::PREV] != 0) {      // h did not fit in the previous step: the fp32 GEMM takes this one as well
         if (e == 0 && bb == 0) atomicOr(range_flag, 1);
         return;
     }
@@ -1119,33 +1117,29 @@ hipError_t fast_kp_front(const Launch &L, const StepIO &io, int B, int T)
     fd_context *c = L.ctx;
     const DevWeights &w = c->w;
     const dim3 grid((T + KPF_VALID - 1) / KPF_VALID, B, fd::NBLK);
-    const StepMode &m = *L.mode;
-    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
-    const int *run_if = nullptr;
-    const char *name = "kp_front";
-    const Pipe pipe = fd_pipe(m, m.conv_f16 && w.kpf_f16_ok, 19);
-    if (pipe != PIPE_F32_ONLY) {
+    const int *lens = L.lens();
+    const Twin s = L.twin(fd::flags::KP_FRONT);
+    if (s.f16) {
         KpFrontW2 k2;
         for (int n = 0; n < fd::NBLK; ++n) {
             k2.in_pack[n] = reinterpret_cast<const float4 *>(w.kp_in_h2[n]); k2.in_b[n] = w.blk[n].kp_in.b;
             for (int l = 0; l < 6; ++l) { k2.res_pack[n][l] = reinterpret_cast<const float4 *>(w.kp_res_h2[n][l]); k2.res_b[n][l] = w.blk[n].kp_res[l].b; }
         }
         // the direct fp16x2 GEMM reads the piece image this kernel can write on its way out; the Winograd form builds its own (k_h_wino)
-        // and the fp32 GEMM reads hout
-        const bool image = front_writes_h_image(m, w);
-        FD_LAUNCH(L, name, k_kp_front_h2, grid, dim3(256), 0, io.mel, c->ws.kp_hB, image ? reinterpret_cast<char *>(c->ws.h_f16) : (char *)nullptr, k2,
+        // and the fp32 GEMM reads hout.  (The kernel gets the whole flag array: it raises its own word and the GEMM's.)
+        const bool image = L.plan->front_writes_h_image;
+        FD_LAUNCH(L, "kp_front", k_kp_front_h2, grid, dim3(256), 0, io.mel, c->ws.kp_hB, image ? reinterpret_cast<char *>(c->ws.h_f16) : (char *)nullptr, k2,
                   (const float *)c->ws.noise, (const StepParams *)c->ws.params, io.sampler, B, T, gx_rows(T), c->ws.range_flag, lens);
-        run_if = c->ws.range_flag + 19;
-        name = "kp_front_fp32_fallback";
-        if (pipe == PIPE_F16_ONLY) return hipSuccess;
     }
-    KpFrontW kw;
-    for (int n = 0; n < fd::NBLK; ++n) {
-        kw.in_pack[n] = w.kp_in_pack[n]; kw.in_b[n] = w.blk[n].kp_in.b;
-        for (int l = 0; l < 6; ++l) { kw.res_pack[n][l] = w.kp_res_pack[n][l]; kw.res_b[n][l] = w.blk[n].kp_res[l].b; }
+    if (s.f32) {
+        KpFrontW kw;
+        for (int n = 0; n < fd::NBLK; ++n) {
+            kw.in_pack[n] = w.kp_in_pack[n]; kw.in_b[n] = w.blk[n].kp_in.b;
+            for (int l = 0; l < 6; ++l) { kw.res_pack[n][l] = w.kp_res_pack[n][l]; kw.res_b[n][l] = w.blk[n].kp_res[l].b; }
+        }
+        FD_LAUNCH(L, s.label("kp_front", "kp_front_fp32_fallback"), k_kp_front, grid, dim3(256), 0, io.mel, c->ws.kp_hB, kw, (const float *)c->ws.noise,
+                  (const StepParams *)c->ws.params, io.sampler, B, T, s.run_if, lens);
     }
-    FD_LAUNCH(L, name, k_kp_front, grid, dim3(256), 0, io.mel, c->ws.kp_hB, kw, (const float *)c->ws.noise,
-              (const StepParams *)c->ws.params, io.sampler, B, T, run_if, lens);
     return hipSuccess;
 }
 
@@ -1164,43 +1158,41 @@ hipError_t fast_kp_gemm(const Launch &L, int B, int T)
     // measured and did not pay: LABBOOK.md)
     fd_context *c = L.ctx;
     const DevWeights &w = c->w;
-    const StepMode &m = *L.mode;
-    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
-    const Pipe pipe = fd_pipe(m, m.gemm_f16 && w.gemm_f16_ok, 0);
-    const bool f16 = pipe != PIPE_F32_ONLY;
-    if (f16 && m.gemm_wino && w.gemm_w_ok) {
+    const int *lens = L.lens();
+    const GemmForm form = L.plan->gemm;
+    const Twin s = L.twin(fd::flags::GEMM);      // (the flag is raised by the producer of the image: the front, k_h_wino or k_h_split)
+    if (form == GEMM_WINO16 || form == GEMM_WINO32) {
         // Winograd F(2,3) over the frame axis: the transformed piece image from the front's fp32 h, then 2/3 of the direct form's matrix work
         const int P = gw_pairs(T);
         const GemmGrid g = gemm_grid(c, B, P / GW_PAIRS);
         FD_LAUNCH(L, "h_wino", k_h_wino, dim3((8 * P + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
-                  reinterpret_cast<char *>(c->ws.h_f16), c->ws.range_flag, B, T, P, lens);
-        const auto gemm_w = m.gemm_tile16 ? &k_kp_gemm_w<16> : &k_kp_gemm_w<32>;      // option gemm_tile
+                  reinterpret_cast<char *>(c->ws.h_f16), s.flag, B, T, P, lens);
+        const auto gemm_w = form == GEMM_WINO16 ? &k_kp_gemm_w<16> : &k_kp_gemm_w<32>;      // option gemm_tile
         FD_LAUNCH(L, "kp_gemm_f16x2", gemm_w, dim3(g.grid), dim3(256), 0,
                   reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[0]), reinterpret_cast<const float4 *>(w.gemm_w_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_w_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, P, g.chunks, g.items, lens);
-        if (pipe == PIPE_F16_ONLY) return hipSuccess;
-    } else if (f16) {
+                  (const int *)s.flag, B, T, P, g.chunks, g.items, lens);
+    } else if (form == GEMM_DIRECT) {
         const int R = gx_rows(T);
         const GemmGrid g = gemm_grid(c, B, (T + GX_CT * 32 - 1) / (GX_CT * 32));
-        if (!front_writes_h_image(m, w))      // (else the fp16-pipe predictor front wrote the image)
+        if (!L.plan->front_writes_h_image)      // (else the fp16-pipe predictor front wrote the image)
             FD_LAUNCH(L, "h_split", k_h_split, dim3((32 * R + 255) / 256, fd::NBLK * B), dim3(256), 0, (const float *)c->ws.kp_hB,
-                      reinterpret_cast<unsigned *>(c->ws.h_f16), c->ws.range_flag, B, T, R, lens);
+                      reinterpret_cast<unsigned *>(c->ws.h_f16), s.flag, B, T, R, lens);
         FD_LAUNCH(L, "kp_gemm_f16x2", k_kp_gemm_h2, dim3(g.grid), dim3(256), 0, reinterpret_cast<const char *>(c->ws.h_f16), c->ws.kpack,
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[0]), reinterpret_cast<const float4 *>(w.gemm_h2_pack[1]),
                   reinterpret_cast<const float4 *>(w.gemm_h2_pack[2]), w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2],
-                  (const int *)c->ws.range_flag, B, T, R, g.chunks, g.items, lens);
-        if (pipe == PIPE_F16_ONLY) return hipSuccess;
+                  (const int *)s.flag, B, T, R, g.chunks, g.items, lens);
     }
+    if (!s.f32) return hipSuccess;
     // fp32 matrix pipe: the whole job when the fp16 form is off, otherwise an early-exit launch that only works when
     // k_h_split found operands outside the fp16 range
     const int tiles_per_utt = (T + 31) / 32;
     const GemmGrid g = gemm_grid(c, B, (tiles_per_utt + GEMM_CT - 1) / GEMM_CT);
     const int chunk_tiles = (tiles_per_utt + g.chunks - 1) / g.chunks;     // balanced, <= GEMM_CT
-    FD_LAUNCH(L, f16 ? "kp_gemm_fp32_fallback" : "kp_gemm", k_kp_gemm, dim3(g.grid), dim3(256), 0, (const float *)c->ws.kp_hB, c->ws.kpack,
+    FD_LAUNCH(L, s.label("kp_gemm", "kp_gemm_fp32_fallback"), k_kp_gemm, dim3(g.grid), dim3(256), 0, (const float *)c->ws.kp_hB, c->ws.kpack,
               w.gemm_pack[0], w.gemm_pack[1], w.gemm_pack[2], w.gemm_bias[0], w.gemm_bias[1], w.gemm_bias[2], B, T, g.chunks,
-              chunk_tiles, g.items, f16 ? (const int *)c->ws.range_flag : (const int *)nullptr, lens);
+              chunk_tiles, g.items, s.run_if, lens);
     return hipSuccess;
 }
 

@@ -1140,51 +1140,40 @@ static hipError_t launch_lvc(const Launch &L, const StepIO &io, const char *name
                              float *x_out, int B, int T, bool up)
 {
     fd_context *c = L.ctx;
-    const StepMode &m = *L.mode;
     const DevWeights &w = c->w;
     constexpr int W = LvcCfg<HOP, DIL>::W;
     const int Ln = T * HOP;
-    const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
-    // block n's records; with a hoisted predictor (fd_internal.h) the batch behind kpack is hoist_np * B entries and this step's are
-    // the hoist_step-th B of them
-    const float *kp = c->ws.kpack + ((int64_t)n * m.hoist_np + io.hoist_step) * B * T * fd::KREC;
-    const int *run_if = nullptr;
-    if constexpr (HOP >= 64 && DIL == 1) {
-        if (up) {      // x_in = the block's input: the ConvTranspose runs inside the layer (the caller made sure both stages are fp16x2-only)
+    const int *lens = L.lens();
+    const float *kp = L.kpack(n, io, B, T);
+    const Twin s = L.twin(fd::flags::lvc(n, layer));
+    if constexpr (DIL == 1) {
+        if (up) {      // x_in = the block's input: the ConvTranspose runs inside the layer (StepPlan::fuse_up: both stages are fp16x2-only)
             constexpr int R = (HOP == 256) ? 4 : 8;
             FD_LAUNCH(L, HOP == 256 ? "lvc_up_h256" : "lvc_up_h64", (k_lvc_h2<HOP, 1, false, R>), dim3(((Ln + 255) / 256 + 7) / 8 * 8, B), dim3(256), 0, x_in, skip, x_out, kp, layer,
                       reinterpret_cast<const float4 *>(w.lvc_conv_h2[n][layer]), w.blk[n].convs[layer].w, w.blk[n].convs[layer].b,
-                      c->ws.range_flag + 1 + n * fd::LAYERS + layer, T, lens, (float *)nullptr, (const float4 *)nullptr,
-                      reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, c->ws.range_flag + 16 + n);
+                      s.flag, T, lens, (float *)nullptr, (const float4 *)nullptr,
+                      reinterpret_cast<const float4 *>(w.up_h2[n]), w.blk[n].up.b, c->ws.range_flag + fd::flags::convt(n));
             return hipSuccess;
         }
     }
-    if constexpr (HOP >= 64) {
-        const Pipe pipe = fd_pipe(m, m.lvc_f16 && w.lvc_f16_ok, 1 + n * fd::LAYERS + layer);
-        if (pipe != PIPE_F32_ONLY) {
-            int *flag = c->ws.range_flag + 1 + n * fd::LAYERS + layer;
-            // the last layer of the last block feeds final_conv only: fused unless someone wants to look at the block output
-            bool fused = false;
-            if constexpr (HOP == 256 && DIL == 27) {
-                fused = last_lvc_fuses_final(m, w);
-                if (fused)      // its own profile row: this variant never writes its 32 output channels
-                    FD_LAUNCH(L, "lvc_final_h256", (k_lvc_h2<HOP, DIL, true>), dim3(((Ln + 255) / 256 + 7) / 8 * 8, B), dim3(256), 0, x_in, skip, x_out, kp,
-                              layer, reinterpret_cast<const float4 *>(w.lvc_conv_h2[n][layer]), w.blk[n].convs[layer].w,
-                              w.blk[n].convs[layer].b, flag, T, lens, c->ws.eps_acc, reinterpret_cast<const float4 *>(w.final_fuse),
-                              (const float4 *)nullptr, (const float *)nullptr, (int *)nullptr);
-            }
-            if (!fused)
-                FD_LAUNCH(L, name, (k_lvc_h2<HOP, DIL, false>), dim3(((Ln + 255) / 256 + 7) / 8 * 8, B), dim3(256), 0, x_in, skip, x_out, kp,
-                          layer, reinterpret_cast<const float4 *>(w.lvc_conv_h2[n][layer]), w.blk[n].convs[layer].w,
-                          w.blk[n].convs[layer].b, flag, T, lens, (float *)nullptr, (const float4 *)nullptr,
-                          (const float4 *)nullptr, (const float *)nullptr, (int *)nullptr);
-            run_if = flag;
-            name = "lvc_fp32_fallback";
-            if (pipe == PIPE_F16_ONLY) return hipSuccess;
-        }
+    // the last layer of the last block feeds final_conv only: fused unless someone wants to look at the block output
+    bool fused = false;
+    if constexpr (HOP == 256 && DIL == 27) {
+        fused = L.plan->fuse_final;
+        if (fused)      // its own profile row: this variant never writes its 32 output channels
+            FD_LAUNCH(L, "lvc_final_h256", (k_lvc_h2<HOP, DIL, true>), dim3(((Ln + 255) / 256 + 7) / 8 * 8, B), dim3(256), 0, x_in, skip, x_out, kp,
+                      layer, reinterpret_cast<const float4 *>(w.lvc_conv_h2[n][layer]), w.blk[n].convs[layer].w,
+                      w.blk[n].convs[layer].b, s.flag, T, lens, c->ws.eps_acc, reinterpret_cast<const float4 *>(w.final_fuse),
+                      (const float4 *)nullptr, (const float *)nullptr, (int *)nullptr);
     }
-    FD_LAUNCH(L, name, (k_lvc_layer<HOP, DIL>), dim3((Ln + W - 1) / W, B), dim3(256), 0, x_in, skip, x_out, kp, layer,
-              w.lvc_conv_pack[n][layer], w.blk[n].convs[layer].w, w.blk[n].convs[layer].b, T, run_if, lens);
+    if (s.f16 && !fused)
+        FD_LAUNCH(L, name, (k_lvc_h2<HOP, DIL, false>), dim3(((Ln + 255) / 256 + 7) / 8 * 8, B), dim3(256), 0, x_in, skip, x_out, kp,
+                  layer, reinterpret_cast<const float4 *>(w.lvc_conv_h2[n][layer]), w.blk[n].convs[layer].w,
+                  w.blk[n].convs[layer].b, s.flag, T, lens, (float *)nullptr, (const float4 *)nullptr,
+                  (const float4 *)nullptr, (const float *)nullptr, (int *)nullptr);
+    if (s.f32)
+        FD_LAUNCH(L, s.label(name, "lvc_fp32_fallback"), (k_lvc_layer<HOP, DIL>), dim3((Ln + W - 1) / W, B), dim3(256), 0, x_in, skip, x_out, kp, layer,
+                  w.lvc_conv_pack[n][layer], w.blk[n].convs[layer].w, w.blk[n].convs[layer].b, T, s.run_if, lens);
     return hipSuccess;
 }
 
@@ -1199,23 +1188,20 @@ hipError_t fast_lvc_layer(const Launch &L, const StepIO &io, int n, int layer, c
     default: return launch_lvc<HOP_, 27>(L, io, NAME_ "_d27", n, layer, x_in, skip, x_out, B, T, up);                    \
     }
     if (n == 0) {
-        fd_context *c = L.ctx;
-        const StepMode &m = *L.mode;
-        const DevWeights &w = c->w;
+        const DevWeights &w = L.ctx->w;
         const int Ln = T * 8;
-        const int *lens = m.ragged ? c->ws.lens_dev : nullptr;
-        const float *kp = c->ws.kpack + (int64_t)io.hoist_step * B * T * fd::KREC;      // (block 0; hoisted predictor: this step's entries)
+        const int *lens = L.lens();
+        const float *kp = L.kpack(0, io, B, T);
         const dim3 grid(((Ln + 31) / 32 + 7) / 8 * 8, B);      // a multiple of 8: blockIdx.x % 8 is the XCD (lvc_tile_of_workgroup)
-        const Pipe pipe = fd_pipe(m, m.lvc_f16 && w.lvc_f16_ok && m.lvc_h8_mfma, 1 + layer);
-        int *flag = c->ws.range_flag + 1 + layer;
+        const Twin s = L.twin(fd::flags::lvc(0, layer));      // (option lvc_h8 = valu: fp32-only, k_lvc_h8 is the layer)
 #define FD_H8(DIL_, NAME_)                                                                                          \
-        if (pipe != PIPE_F32_ONLY)                                                                                   \
+        if (s.f16)                                                                                                   \
             FD_LAUNCH(L, NAME_, k_lvc_h8m<DIL_>, grid, dim3(256), 0, x_in, skip, x_out, kp, layer,                     \
-                      reinterpret_cast<const float4 *>(w.lvc_conv_h16[layer]), w.blk[0].convs[layer].w, w.blk[0].convs[layer].b, flag, T, \
+                      reinterpret_cast<const float4 *>(w.lvc_conv_h16[layer]), w.blk[0].convs[layer].w, w.blk[0].convs[layer].b, s.flag, T, \
                       lens);                                                                                 \
-        if (pipe != PIPE_F16_ONLY)                                                                                   \
-            FD_LAUNCH(L, pipe == PIPE_F32_ONLY ? NAME_ : "lvc_fp32_fallback", k_lvc_h8<DIL_>, grid, dim3(256), 0, x_in, skip, x_out, kp, layer, \
-                      w.blk[0].convs[layer].w, w.blk[0].convs[layer].b, T, lens, pipe == PIPE_F32_ONLY ? (const int *)nullptr : (const int *)flag)
+        if (s.f32)                                                                                                   \
+            FD_LAUNCH(L, s.label(NAME_, "lvc_fp32_fallback"), k_lvc_h8<DIL_>, grid, dim3(256), 0, x_in, skip, x_out, kp, layer, \
+                      w.blk[0].convs[layer].w, w.blk[0].convs[layer].b, T, lens, s.run_if)
         switch (layer) {
         case 0: FD_H8(1, "lvc_layer_h8_d1"); break;
         case 1: FD_H8(3, "lvc_layer_h8_d3"); break;

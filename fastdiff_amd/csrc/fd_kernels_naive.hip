@@ -2,8 +2,7 @@
 // base.yaml's shapes and the tuned workspace.  It exists to (a) bring the path up, (b) isolate a wrong fast kernel stage by stage on
 // the GPU (option "kernels.<stage>"="naive"), never as the shipped configuration.  The embed, update, Philox and epilogue kernels at
 // the bottom are shared by both modes.
-#include "fd_kernels.h"
-#include "fd_device.h"
+#include "fd_kernels_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // stage drivers (naive mode)
@@ -230,12 +229,7 @@ hipError_t naive_update(const Launch &L, float *x, const float *eps, int64_t n)
 __global__ void k_advance(StepParams *p, int *range_flags, int inc, int set_step)
 {
     if (threadIdx.x == 0) p->step_idx = inc ? p->step_idx + inc : set_step;
-    if (threadIdx.x < 32) {      // this step's flags become "previous step" (inc == 0: start of a call or of a redo, all cleared)
-        const int f = range_flags[threadIdx.x];
-        range_flags[32 + threadIdx.x] = inc ? f : 0;
-        range_flags[64 + threadIdx.x] = inc ? (range_flags[64 + threadIdx.x] | f) : 0;      // sticky over the call: what the host looks at
-        range_flags[threadIdx.x] = 0;
-    }
+    if (threadIdx.x < fd::flags::WORDS) fdk_fast::roll_range_flags(range_flags, threadIdx.x, inc);
 }
 
 hipError_t advance_step(const Launch &L)
